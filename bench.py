@@ -24,14 +24,21 @@ path's only exchange).  ``--config C4`` partitions the
 rank a full C3-sized slab instead.  ``python bench.py --gpus N`` launches its own
 ``torch.distributed.run`` when it is not already running under one.
 
-One JSON line on stdout (rank 0).  Besides the contract's keys it carries
+One JSON line on stdout (rank 0).  A plain run sets up, warms up, times --steps steps, writes
+the last step's outputs when ``--dump-outputs DIR`` is given (max_coa, max_norm_coa,
+max_coa_idx as DIR/<name>.npy, float64; the inputs are seeded, so two builds can be compared
+output for output) and prints the line: the contract's keys, the workload, and what the timed
+steps themselves tell about the stacking kernel (``kernel`` and
   roofline      : the dominant kernel (fused LDS-tiled float64 stack) against HBM with its
                   ALGORITHMIC bytes (table + onsets + outputs) -- by construction far below
                   1 %: the kernel is LDS-gather / VALU bound, not HBM bound (SURVEY.md
                   section 8d) -- plus ``lds_frac`` / ``fp64_valu_frac``, the ceilings that do
                   bind it, and ``adds_only_frac`` (the reference's S adds alone); ``traffic`` =
                   HBM bytes per launch from the newest stored PMC passes over this kernel and
-                  workload (profiles/rNN_pmc_traffic.json; null if none matches);
+                  workload (profiles/rNN_pmc_traffic.json; null if none matches)).
+Everything that takes runs of its own, or checks rather than measures, runs only with ``--full``
+(each leg still subject to its ``--no-*`` option):
+  events        : the in-bench check that the injected events are found where they were put;
   step_with_copies : the same steps fed from pinned host memory -- H2D of the onsets and D2H
                   of the three series inside the timed region, overlapped on HIP streams
                   (SURVEY.md section 8d's PCIe-inclusive step; never ``value``);
@@ -114,7 +121,24 @@ def parse():
                     help="single process: build and time the slab rank --emulate-rank of an "
                          "N-GPU partition would hold (no exchange); for measuring C4 on 1 GPU")
     ap.add_argument("--emulate-rank", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the in-bench event check, "
+                         "step_with_copies, screened_optin, tie_rule_optin, the locate-style volume "
+                         "legs, table_switch, roofline_materialised_full and cpu_baseline (each "
+                         "still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed -- "
+                         "max_coa, max_norm_coa, max_coa_idx -- as DIR/<name>.npy in float64")
     return ap.parse_args()
+
+
+def dump_outputs(directory, res):
+    """The last timed step's series as a caller of the detect path receives them; the flat node
+    index (int64 on the device) is exact in float64 for every grid here (< 2^53 nodes)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, series in zip(("max_coa", "max_norm_coa", "max_coa_idx"), res):
+        a = series.cpu().numpy() if hasattr(series, "cpu") else np.asarray(series)
+        np.save(os.path.join(directory, name + ".npy"), a.astype(np.float64))
 
 
 def cpu_baseline(case, budget_s):
@@ -451,22 +475,23 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- in-bench sanity: injected events are found where they were put ------------
+    # ---- in-bench sanity (--full): injected events are found where they were put ------------
     last = (args.warmup + args.steps - 1) % n_pool
     if spl > 1 and not streaming:                       # the last launch's last step
         last = (args.warmup + args.steps - spl + spl - 1) % n_pool
     if time_sharded:
         last = (args.warmup + rank + world * (args.steps - 1)) % n_pool
-    idx = res[2].cpu().numpy()
-    for (ijk, t_ev) in cases[last].event_nodes:
-        if part_world != world and not (x_range[0] <= ijk[0] < x_range[1]):
-            continue                                    # emulated slab: event lies elsewhere
-        found = np.unravel_index(int(idx[t_ev]), grid)
-        # on coarse grids (C2-C4) this is the event's node itself; on the 25 m Icequake-sized
-        # grid neighbouring nodes are within a sample of each other and the reference, too,
-        # lands one node off (tests/golden/c1_icequake_geometry.npz)
-        assert max(abs(int(a) - int(b)) for a, b in zip(found, ijk)) <= 2, \
-            f"event at sample {t_ev}: node {found} is not at {ijk}"
+    if args.full:
+        idx = res[2].cpu().numpy()
+        for (ijk, t_ev) in cases[last].event_nodes:
+            if part_world != world and not (x_range[0] <= ijk[0] < x_range[1]):
+                continue                                # emulated slab: event lies elsewhere
+            found = np.unravel_index(int(idx[t_ev]), grid)
+            # on coarse grids (C2-C4) this is the event's node itself; on the 25 m Icequake-sized
+            # grid neighbouring nodes are within a sample of each other and the reference, too,
+            # lands one node off (tests/golden/c1_icequake_geometry.npz)
+            assert max(abs(int(a) - int(b)) for a, b in zip(found, ijk)) <= 2, \
+                f"event at sample {t_ev}: node {found} is not at {ijk}"
 
     # where the imbalance is: every rank's average stacking-kernel time
     world_kernel_ms = [kern_ms / max(kern_calls, 1)]
@@ -479,6 +504,8 @@ def main():
         if use_dist:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
 
     n_norm = n_total                                    # what the engine normalises by
     if part_world != world:
@@ -593,7 +620,7 @@ def main():
     }
 
     # ---- the same steps fed from the host: H2D + detect + D2H inside the timed region ----
-    if world == 1 and not streaming and not args.no_copies:
+    if args.full and world == 1 and not streaming and not args.no_copies:
         from quakemigrate_amd.stream import StreamingDetector
 
         sd = StreamingDetector(eng, S, t_samples, case.fsmp, case.lsmp, case.available,
@@ -625,7 +652,7 @@ def main():
                     "timed region"}
 
     # ---- the opt-in screened detect on the same steps, beside the float64 engine --------
-    if not screened and world == 1 and not streaming and not args.no_screened:
+    if args.full and not screened and world == 1 and not streaming and not args.no_screened:
         sx = lib.Engine(local_rank, **dict(tunables, screen=1))
         sx.set_stream(torch.cuda.current_stream().cuda_stream)
         sx.load_lut(case.traveltimes, node_offset=x_range[0] * ny * nz)
@@ -669,7 +696,8 @@ def main():
         sx.close()
 
     # ---- the opt-in tie_rule = 1 (the reference's arg-max rule on near-ties) on the same steps ----
-    if not screened and world == 1 and not streaming and not args.no_screened and not tunables.get("tie_rule"):
+    if (args.full and not screened and world == 1 and not streaming and not args.no_screened
+            and not tunables.get("tie_rule")):
         tx = lib.Engine(local_rank, **dict(tunables, tie_rule=1))
         tx.set_stream(torch.cuda.current_stream().cuda_stream)
         tx.load_lut(case.traveltimes, node_offset=x_range[0] * ny * nz)
@@ -705,7 +733,7 @@ def main():
         tx.close()
 
     # ---- locate-style materialising variant on the same grid (HBM-write bound) ------
-    if not args.no_materialised and world == 1 and cfg_name == "C3" and not streaming:
+    if args.full and not args.no_materialised and world == 1 and cfg_name == "C3" and not streaming:
         ns_loc = 401                                    # 4 * marginal_window(2 s) * 50 Hz + 1
         on = onsets_dev[0][:, : case.fsmp + ns_loc + case.lsmp].contiguous()
         vol = torch.empty((n_local, ns_loc), dtype=torch.float64, device=dev)
@@ -780,7 +808,7 @@ def main():
         del vol
 
     # ---- a change of station availability: another table takes over (lut.py:529-537) --------------
-    if not args.no_table_switch and world == 1 and cfg_name == "C3" and not streaming and spl == 1:
+    if args.full and not args.no_table_switch and world == 1 and cfg_name == "C3" and not streaming and spl == 1:
         torch.cuda.synchronize()
         keep = [r for r in range(S) if r not in (3, S - 2)]        # a P and an S row drop out
         tt_b = torch.from_numpy(np.ascontiguousarray(case.traveltimes[..., keep])).to(dev)
@@ -835,12 +863,12 @@ def main():
         del tt_a, tt_b
 
     # ---- BASELINE configs[2] literally: the whole n_samples volume of the step written to HBM with its scan
-    # (SURVEY 8d figure 1 on the configuration itself: 196 GB at C3).  Part of the default line since round 6
-    # (VERDICT r05 item 3), skipped -- and said so -- where the GPU has not the memory free.
+    # (SURVEY 8d figure 1 on the configuration itself: 196 GB at C3).  Part of the --full line at C3 (and
+    # of any line with --materialise-full), skipped -- and said so -- where the GPU has not the memory free.
     full_bytes = 8.0 * n_local * ns
-    free_bytes = torch.cuda.mem_get_info(dev)[0] if world == 1 else 0
-    want_full = (args.materialise_full or (cfg_name == "C3" and not args.no_materialise_full)) and \
+    want_full = (args.materialise_full or (args.full and cfg_name == "C3" and not args.no_materialise_full)) and \
         world == 1 and not streaming and part_world == 1
+    free_bytes = torch.cuda.mem_get_info(dev)[0] if want_full else 0
     if want_full and free_bytes < full_bytes + (4 << 30):
         lib.release_cached_memory() if hasattr(lib, "release_cached_memory") else None
         torch.cuda.empty_cache()
@@ -877,7 +905,7 @@ def main():
             "workload": f"whole step materialised: {8.0 * n_local * ns / 1e9:.0f} GB volume + scan"}
         del vol
 
-    if not args.no_cpu_baseline and world == 1 and not streaming:
+    if args.full and not args.no_cpu_baseline and world == 1 and not streaming:
         result["cpu_baseline"] = cpu_baseline(case, args.cpu_seconds)
     else:
         result["cpu_baseline"] = None

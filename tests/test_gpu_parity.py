@@ -2101,8 +2101,9 @@ def test_bench_self_launch_two_ranks_prints_one_json_line(tmp_path):
 
     root = pathlib.Path(__file__).resolve().parents[1]
     env = dict(os.environ, QM_BENCH_ONE_DEVICE="1")
+    # (--full: the in-bench check that the injected events are found where they were put runs too)
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--config", "C2",
-                        "--steps", "2", "--warmup", "1"], env=env, capture_output=True, text=True,
+                        "--steps", "2", "--warmup", "1", "--full"], env=env, capture_output=True, text=True,
                        cwd=tmp_path, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -2117,6 +2118,44 @@ def test_bench_self_launch_two_ranks_prints_one_json_line(tmp_path):
     assert line["value"] > 0 and line["unit"] == "node-samples/s" and line["dtype"] == "f64"
     assert line["roofline"]["bound"] in ("lds", "fp64_valu") and 0 < line["roofline"]["frac"] < 1
     assert line["roofline"]["hbm_compulsory"]["frac"] < 0.05
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(lib, tmp_path):
+    """`python bench.py --steps N --warmup W --dump-outputs DIR`: one JSON line whose `steps` is N and whose
+    `ms_per_step` is the timed region over N; the legs of --full are not run; DIR holds the last timed step's
+    three series in float64, and they are what the engine computes for that timestep of the seeded workload."""
+    import json
+    import pathlib
+    import subprocess
+    import sys
+
+    root = pathlib.Path(__file__).resolve().parents[1]
+    out_dir = tmp_path / "dump"
+    steps, warmup = 4, 1
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--config", "C2",
+                        "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(out_dir)],
+                       capture_output=True, text=True, cwd=tmp_path, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0
+    assert line["value"] > 0 and line["unit"] == "node-samples/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and line["cpu_baseline"] is None
+    assert not {"step_with_copies", "screened_optin", "tie_rule_optin", "roofline_materialised",
+                "table_switch", "roofline_materialised_full"} & set(line)
+    got = {k: np.load(out_dir / f"{k}.npy") for k in ("max_coa", "max_norm_coa", "max_coa_idx")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    # the bench cycles three timesteps after one set-up step on the first: the last timed one is this
+    case = synth.make_case("C2", step=(warmup + steps - 1) % 3)
+    tt = synth.make_case("C2", step=0).traveltimes
+    eng = lib.Engine(0)
+    eng.load_lut(tt)
+    a, b, c = eng.detect(np.ascontiguousarray(np.log(np.clip(case.onsets, 0.01, np.inf))), case.fsmp,
+                         case.lsmp, case.available)
+    eng.close()
+    assert np.array_equal(got["max_coa_idx"], c.astype(np.float64))
+    assert np.array_equal(got["max_coa"], a) and np.array_equal(got["max_norm_coa"], b)
 
 
 def test_host_enqueue_budget_of_an_eight_way_sharded_step():

@@ -769,49 +769,72 @@ def test_headline_kernels_stay_in_registers(tmp_path):
 
 
 def _reference_binding_against(so_path):
-    """The reference's own quakemigrate/core/lib.py, imported unmodified, with `_load_cdll`
-    answering with `so_path` (the technique of oracle/make_golden.py: empty parent packages and
-    a pass-through `util.timeit` stand in for imports that file never executes here)."""
-    import importlib.util
-    import sys
+    """The binding the reference's own quakemigrate/core/lib.py makes, on `so_path`, restated from
+    the record of what that file sets (tests/golden/reference_binding.json, written by
+    oracle/make_golden_binding.py): every symbol it binds is looked up with the argtypes it sets,
+    and its three STA/LTA wrappers -- the header they build, the output buffer they hand over --
+    are callables here."""
+    import json
     import types
 
-    ref = pathlib.Path("/root/reference/quakemigrate/core/lib.py")
-    if not ref.exists():
-        pytest.skip("the reference tree is not on this box")
-    saved = {k: sys.modules.get(k) for k in ("quakemigrate", "quakemigrate.core",
-                                             "quakemigrate.util", "quakemigrate.core.libnames",
-                                             "quakemigrate.core.lib")}
-    qm = types.ModuleType("quakemigrate"); qm.__path__ = []
-    core = types.ModuleType("quakemigrate.core"); core.__path__ = []
-    util = types.ModuleType("quakemigrate.util"); util.timeit = lambda *a, **k: (lambda f: f)
-    ln = types.ModuleType("quakemigrate.core.libnames")
-    ln._load_cdll = lambda name: ctypes.CDLL(str(so_path))
-    qm.util = util
-    sys.modules.update({"quakemigrate": qm, "quakemigrate.core": core, "quakemigrate.util": util,
-                        "quakemigrate.core.libnames": ln})
-    try:
-        spec = importlib.util.spec_from_file_location("quakemigrate.core.lib", ref)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)                    # binds all five symbols (lib.py:24-283)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
-    return mod
+    import numpy.ctypeslib as clib
+
+    rec = json.loads((ROOT / "tests" / "golden" / "reference_binding.json").read_text())
+
+    def dtype(d):
+        return np.dtype(d if isinstance(d, str) else dict(d))
+
+    def ctype(t):
+        if "ndpointer" in t:
+            p = t["ndpointer"]
+            return clib.ndpointer(dtype=dtype(p["dtype"]), ndim=p["ndim"], shape=p["shape"],
+                                  flags=p["flags"])
+        c = getattr(ctypes, t["ctype"])
+        assert ctypes.sizeof(c) == t["size"], t
+        return c
+
+    qmlib = ctypes.CDLL(str(so_path))
+    for name, entry in rec["symbols"].items():
+        fn = getattr(qmlib, name)                       # a symbol the reference binds must be there
+        if entry["argtypes"] is not None:
+            fn.argtypes = [ctype(t) for t in entry["argtypes"]]
+        if "restype" in entry:
+            fn.restype = None if entry["restype"] is None else ctype(entry["restype"])
+
+    def wrapper(kind):
+        call = rec["stalta_calls"][kind]
+        head_t = dtype(call["header"]["dtype"])
+        init = call["output"]["initial_values"]
+        # the recorded call: header (len(signal), nsta, nlta), output pre-filled with one value
+        assert head_t.names == ("n", "nsta", "nlta") and len(init) == 1, call
+        assert call["header"]["values"] == [[len(call["signal"]["values"]), call["nsta"], call["nlta"]]]
+        assert call["output"]["length"] == len(call["signal"]["values"])
+
+        def fn(signal, nsta, nlta):
+            head = np.empty(1, dtype=head_t)
+            head[:] = (len(signal), nsta, nlta)
+            signal = np.ascontiguousarray(signal, dtype=np.dtype(call["signal"]["dtype"]))
+            onset = np.full(len(signal), init[0], dtype=np.dtype(call["output"]["dtype"]))
+            getattr(qmlib, f"{kind}_sta_lta")(signal, head, onset)
+            return onset
+        return fn
+
+    return types.SimpleNamespace(qmlib=qmlib, symbols=sorted(rec["symbols"]),
+                                 **{f"{k}_sta_lta": wrapper(k) for k in rec["stalta_calls"]})
 
 
 def test_reference_front_end_binds_the_drop_in_library(built):
     """copy qmlib<EXT_SUFFIX> over the reference's extension and its
-    unmodified core/lib.py imports -- every `qmlib.<symbol>.argtypes = ...` line finds its symbol
-    -- and the three STA/LTA entry points (host code in both libraries) give the reference's
-    vectors through the reference's own wrappers."""
+    unmodified core/lib.py binds it -- every `qmlib.<symbol>.argtypes = ...` line finds its symbol
+    (the argtypes as recorded from that file) -- and the three STA/LTA entry points (host code in
+    both libraries) give the reference's vectors when called the way the reference's own wrappers
+    call them."""
     import sysconfig
 
     alias = ROOT / "quakemigrate_amd" / "csrc" / ("qmlib" + sysconfig.get_config_var("EXT_SUFFIX"))
     ref_lib = _reference_binding_against(alias)
+    assert ref_lib.symbols == sorted(["migrate", "find_max_coa", "overlapping_sta_lta", "centred_sta_lta",
+                                      "recursive_sta_lta"])
     for name in ("migrate", "find_max_coa", "overlapping_sta_lta", "centred_sta_lta",
                  "recursive_sta_lta"):
         assert getattr(ref_lib.qmlib, name).argtypes is not None, name

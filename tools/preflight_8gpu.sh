@@ -34,22 +34,22 @@ python -m pytest tests -q -m gpu -x > "$OUT/pytest_gpu.log" 2>&1 || fail "pytest
 tail -1 "$OUT/pytest_gpu.log"
 python -c "import __graft_entry__ as g; g.smoke()" || fail "smoke"
 echo "== 2. N = 1 bench line (the reference point of the scaling curve)"
-python bench.py --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/bench_C3_n1.json" 2> "$OUT/bench_n1.err" || fail "bench N=1"
+python bench.py --full --gpus 1 --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/bench_C3_n1.json" 2> "$OUT/bench_n1.err" || fail "bench N=1"
 check "$OUT/bench_C3_n1.json" 1
 for n in 2 4 $N; do
   [ "$n" -gt "$N" ] && continue
   echo "== 3. C3 sharded over $n GPUs (strong scaling: the same grid, column partition, ONE packed all-gather per step)"
-  python bench.py --gpus $n --config C3 --steps 20 --warmup 3 > "$OUT/bench_C3_n$n.json" 2> "$OUT/bench_C3_n$n.err" || fail "bench C3 N=$n (see $OUT/bench_C3_n$n.err)"
+  python bench.py --full --gpus $n --config C3 --steps 20 --warmup 3 > "$OUT/bench_C3_n$n.json" 2> "$OUT/bench_C3_n$n.err" || fail "bench C3 N=$n (see $OUT/bench_C3_n$n.err)"
   check "$OUT/bench_C3_n$n.json" $n
 done
 echo "== 4. C4 (401x401x201 x 60 rows x 12000 samples) over $N GPUs -- BASELINE configs[3]"
-python bench.py --gpus $N --config C4 --steps 5 --warmup 1 > "$OUT/bench_C4_n$N.json" 2> "$OUT/bench_C4_n$N.err" || fail "bench C4 N=$N"
+python bench.py --full --gpus $N --config C4 --steps 5 --warmup 1 > "$OUT/bench_C4_n$N.json" 2> "$OUT/bench_C4_n$N.err" || fail "bench C4 N=$N"
 check "$OUT/bench_C4_n$N.json" $N
 echo "== 5. C5: the 24 h stream, timesteps round-robin over the ranks, no collective in the data path"
-python bench.py --gpus $N --config C5 --steps 90 --warmup 3 > "$OUT/bench_C5_n$N.json" 2> "$OUT/bench_C5_n$N.err" || fail "bench C5 N=$N"
+python bench.py --full --gpus $N --config C5 --steps 90 --warmup 3 > "$OUT/bench_C5_n$N.json" 2> "$OUT/bench_C5_n$N.err" || fail "bench C5 N=$N"
 check "$OUT/bench_C5_n$N.json" $N
 echo "== 6. the three-all-reduce form of the exchange and the plane partition give the same series"
-python bench.py --gpus $N --exchange allreduce --partition planes --steps 5 --warmup 1 > "$OUT/bench_C3_n${N}_allreduce.json" 2> "$OUT/bench_allreduce.err" || fail "bench allreduce"
+python bench.py --full --gpus $N --exchange allreduce --partition planes --steps 5 --warmup 1 > "$OUT/bench_C3_n${N}_allreduce.json" 2> "$OUT/bench_allreduce.err" || fail "bench allreduce"
 check "$OUT/bench_C3_n${N}_allreduce.json" $N
 echo "expected at N = 8 on C3 (from the one-GPU slab timings, DESIGN.md section 5): kernel ~5.9 ms per rank, "
 echo "step ~6.0-6.3 ms with the exchange (one 432 KB all-gather + a fold of 24 sets), i.e. ~7.2-7.5x of N = 1."

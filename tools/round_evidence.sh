@@ -41,18 +41,18 @@ if has suite; then
   python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -2 $OUT/smoke.log
 fi
 if has bench; then
-  python bench.py --steps 20 --warmup 3 > $OUT/bench_C3.json 2> $OUT/bench.err; tail -3 $OUT/bench.err
+  python bench.py --full --steps 20 --warmup 3 > $OUT/bench_C3.json 2> $OUT/bench.err; tail -3 $OUT/bench.err
   Q="--no-cpu-baseline --no-screened --no-copies --no-table-switch"
-  python bench.py --steps 20 --warmup 3 --engine '{"shift_wide": 0}' $Q --no-materialised > $OUT/bench_C3_round5_tiles.json 2>> $OUT/bench.err
-  python bench.py --steps 20 --warmup 3 --engine '{"shift_wide": 0, "shift_tail": 0}' $Q --no-materialised > $OUT/bench_C3_round3_tiles.json 2>> $OUT/bench.err
-  python bench.py --steps 20 --warmup 3 --engine '{"shift": 0}' $Q --no-materialised > $OUT/bench_C3_round2_kernels.json 2>> $OUT/bench.err
-  python bench.py --config C2 --steps 30 --warmup 3 --no-cpu-baseline --no-materialised > $OUT/bench_C2.json 2>> $OUT/bench.err
+  python bench.py --full --steps 20 --warmup 3 --engine '{"shift_wide": 0}' $Q --no-materialised > $OUT/bench_C3_round5_tiles.json 2>> $OUT/bench.err
+  python bench.py --full --steps 20 --warmup 3 --engine '{"shift_wide": 0, "shift_tail": 0}' $Q --no-materialised > $OUT/bench_C3_round3_tiles.json 2>> $OUT/bench.err
+  python bench.py --full --steps 20 --warmup 3 --engine '{"shift": 0}' $Q --no-materialised > $OUT/bench_C3_round2_kernels.json 2>> $OUT/bench.err
+  python bench.py --full --config C2 --steps 30 --warmup 3 --no-cpu-baseline --no-materialised > $OUT/bench_C2.json 2>> $OUT/bench.err
   for cfg in C1 E1 E2 E2F; do for k in 1 8; do
-    python bench.py --config $cfg --steps 400 --warmup 8 --steps-per-launch $k --no-cpu-baseline --no-materialised --no-screened --no-table-switch > $OUT/bench_${cfg}_k$k.json 2>> $OUT/bench.err
+    python bench.py --full --config $cfg --steps 400 --warmup 8 --steps-per-launch $k --no-cpu-baseline --no-materialised --no-screened --no-table-switch > $OUT/bench_${cfg}_k$k.json 2>> $OUT/bench.err
   done; done
-  python bench.py --config C4 --emulate-world 8 --emulate-rank 3 --steps 5 --warmup 1 --no-cpu-baseline --no-materialised > $OUT/bench_C4_slab3of8.json 2>> $OUT/bench.err
-  python bench.py --config C5 --steps 30 --warmup 3 > $OUT/bench_C5_stream.json 2>> $OUT/bench.err
-  python bench.py --config C5 --steps 720 --warmup 3 > $OUT/bench_C5_24h.json 2>> $OUT/bench.err
+  python bench.py --full --config C4 --emulate-world 8 --emulate-rank 3 --steps 5 --warmup 1 --no-cpu-baseline --no-materialised > $OUT/bench_C4_slab3of8.json 2>> $OUT/bench.err
+  python bench.py --full --config C5 --steps 30 --warmup 3 > $OUT/bench_C5_stream.json 2>> $OUT/bench.err
+  python bench.py --full --config C5 --steps 720 --warmup 3 > $OUT/bench_C5_24h.json 2>> $OUT/bench.err
   line $OUT/bench_*.json | tee $OUT/bench_lines.txt
   # tables of more than 64 rows (row blocks) on the C3 grid x 1536 samples, and a 401-sample volume on one
   { for r in 66 128 200; do python tools/ab.py --config C3 --case "{\"rows\": $r, \"n_samples\": 1536}" - | sed "s/^-/rows $r/"; done
@@ -60,15 +60,15 @@ if has bench; then
 fi
 if has ranks; then
   # N > 1 plumbing on one GPU (gloo rendezvous; RCCL refuses two ranks on one device): self-launch
-  QM_BENCH_ONE_DEVICE=1 python bench.py --gpus 2 --steps 5 --warmup 1 > $OUT/bench_C3_2ranks_one_gpu.json 2> $OUT/bench_2ranks.err; tail -c 300 $OUT/bench_C3_2ranks_one_gpu.json; tail -2 $OUT/bench_2ranks.err
-  QM_BENCH_ONE_DEVICE=1 python bench.py --gpus 2 --config C5 --steps 6 --warmup 1 > $OUT/bench_C5_2ranks_one_gpu.json 2>> $OUT/bench_2ranks.err
-  QM_BENCH_FORCE_DIST=1 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-screened --no-copies --no-materialised --no-table-switch > $OUT/bench_C3_one_rank_rccl.json 2>> $OUT/bench_2ranks.err; tail -c 300 $OUT/bench_C3_one_rank_rccl.json
+  QM_BENCH_ONE_DEVICE=1 python bench.py --full --gpus 2 --steps 5 --warmup 1 > $OUT/bench_C3_2ranks_one_gpu.json 2> $OUT/bench_2ranks.err; tail -c 300 $OUT/bench_C3_2ranks_one_gpu.json; tail -2 $OUT/bench_2ranks.err
+  QM_BENCH_ONE_DEVICE=1 python bench.py --full --gpus 2 --config C5 --steps 6 --warmup 1 > $OUT/bench_C5_2ranks_one_gpu.json 2>> $OUT/bench_2ranks.err
+  QM_BENCH_FORCE_DIST=1 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-screened --no-copies --no-materialised --no-table-switch > $OUT/bench_C3_one_rank_rccl.json 2>> $OUT/bench_2ranks.err; tail -c 300 $OUT/bench_C3_one_rank_rccl.json
   python tools/enqueue_budget.py --world 8 --rank 3 > $OUT/enqueue_C3_rank3of8.json 2> $OUT/enqueue.err; cat $OUT/enqueue_C3_rank3of8.json
 fi
 if has stats; then
   cd /tmp && export TMPDIR=/tmp
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o bench -- \
-      python $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-screened --no-table-switch --no-copies --no-materialised > $OUT/bench_C3_headline_only_under_rocprof.json 2> $OUT/prof.err
+      python $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-screened --no-table-switch --no-copies --no-materialised > $OUT/bench_C3_headline_only_under_rocprof.json 2> $OUT/prof.err
   find $OUT/prof -name "*kernel_stats.csv" -exec cp {} $OUT/bench_C3_headline_only_kernel_stats.csv \;
   head -6 $OUT/bench_C3_headline_only_kernel_stats.csv
   python -c "
