@@ -14,7 +14,8 @@
  * stack + exp + scan that never materialises the 4-D volume) that this
  * repository's own host side (quakemigrate_amd/) drives.  Part 3 is the
  * continuous detect sweep as a pipeline (pinned ring, copies overlapped with
- * compute) -- the loop of QuakeScan._continuous_compute around part 2's call.
+ * compute) -- the loop of QuakeScan._continuous_compute around part 2's call.  Part 4 are engine
+ * groups: one process driving the grid on several GPUs (or several parts of one).
  *
  * Conventions: every function of part 2 returns 0 on success, non-zero on
  * failure; qm_last_error() returns a thread-local message.  `*_on_device`
@@ -438,6 +439,61 @@ int qm_engine_last_kernel_ms(qm_engine *e, double *ms);
  * pair of HIP events (on the engine stream); this returns the summed duration
  * and the number of launches since the last call, and resets the log. */
 int qm_engine_kernel_log(qm_engine *e, double *total_ms, int32_t *n_calls);
+
+/* ------------------------------------------------------------------ part 4 */
+/* Engine groups: ONE process and ONE host thread drive a grid on several devices (csrc/qm_group.hip; DESIGN.md
+ * section 5), no collective library.  device_ids lists one PART per entry; ids may repeat ({0, 0}: two parts on
+ * GPU 0).  Entry 0 is the lead device: the fold of the parts' partials, the outputs' staging and the near-tie
+ * refinement's fold run there.  Below the handle each part holds one qm_engine per box of its share of the grid
+ * (at most three), on its device and stream, with the box's slice of the table and its node offset -- the layout
+ * of quakemigrate_amd/distributed.py's ColumnShardedDetector.  A step stages the log-onsets once into pinned
+ * memory (one H2D per part), enqueues every box's partial, moves each part's packed [3 boxes][3][n_samples]
+ * partials to the lead (hipMemcpyPeerAsync; a direct write on the lead's own device) ordered by events, folds
+ * them there over n_parts * 3 sets (as qm_engine_finalize_packed), and only then waits -- once.  tie_rule = 1
+ * adds the second exchange of qm_engine_tie_partial / _tie_fold.  Host in, host out; results are those of one
+ * engine over the whole table (max_coa and max_coa_idx bit for bit; max_norm_coa's sum over the nodes is formed
+ * in another order).  Not available on a group: screen = 1 (refused by qm_group_config), on-device serving,
+ * detect_batch and the qm_stream pipeline, device pointers.  Every call returns 0 / non-zero + qm_last_error(). */
+typedef struct qm_group qm_group;
+
+/* The partition, host code: part `part` of n_parts as up to three boxes (x0, x1, y0, y1, z0, z1), ascending in
+ * flat order, each a contiguous flat range starting at node (x0 * ny + y0) * nz + z0.  A 3-D grid is cut into
+ * balanced ranges of (x, y) columns (distributed.shard_columns / column_boxes, z0 = 0, z1 = nz); a flat table
+ * (nx = ny = 1: what the drop-in migrate() loads without QM_HIP_GRID) into balanced contiguous z-runs, one box
+ * (0, 1, 0, 1, z0, z1) each.  A part may be empty (*n_boxes = 0) when there are more parts than columns. */
+int qm_group_plan(int32_t nx, int32_t ny, int32_t nz, int32_t n_parts, int32_t part, int32_t *boxes /*[3][6]*/,
+                  int32_t *n_boxes);
+int qm_group_create(const int32_t *device_ids, int32_t n, qm_group **out);
+void qm_group_destroy(qm_group *g);
+/* a key of qm_engine_config to every engine of the group; qm_group_get: the engines' common value (fails if they
+ * disagree), or the group's own read-outs n_parts, n_nodes, n_rows, nx, ny, nz, lut_max */
+int qm_group_config(qm_group *g, const char *key, int64_t value);
+int qm_group_get(qm_group *g, const char *key, int64_t *value);
+/* host table i32 [nx][ny][nz][n_rows], sliced by the plan (flat tables: nx = ny = 1, nz = n_nodes) */
+int qm_group_load_lut(qm_group *g, const int32_t *host_table, int32_t nx, int32_t ny, int32_t nz, int32_t n_rows);
+/* qm_engine_table_select on every box engine; *resident = 1 only if every one has its slice resident */
+int qm_group_table_select(qm_group *g, uint64_t key, int32_t capacity, int32_t *resident);
+/* qm_engine_detect / _marginal / _migrate / _find_max_coa over the whole grid, host arrays: log_onsets f64
+ * [n_rows][t_samples], series [n_samples], coa_map f64 [n_nodes], map4d f64 [n_nodes][n_samples] (accumulate != 0:
+ * added on top of its content).  max_coa == NULL: no series.  find_max_coa: part p scans the balanced flat range p
+ * of the volume's nodes, the partials are folded on the lead. */
+int qm_group_detect(qm_group *g, const double *log_onsets, int32_t t_samples, int32_t fsmp, int32_t lsmp,
+                    int32_t available, double *max_coa, double *max_norm_coa, int64_t *max_coa_idx);
+int qm_group_marginal(qm_group *g, const double *log_onsets, int32_t t_samples, int32_t fsmp, int32_t lsmp,
+                      int32_t available, int32_t first_sample, int32_t end_sample, double *coa_map,
+                      double *max_coa, double *max_norm_coa, int64_t *max_coa_idx);
+int qm_group_migrate(qm_group *g, const double *log_onsets, int32_t t_samples, int32_t fsmp, int32_t lsmp,
+                     int32_t available, double *map4d, int accumulate, double *max_coa, double *max_norm_coa,
+                     int64_t *max_coa_idx);
+int qm_group_find_max_coa(qm_group *g, const double *map4d, int32_t n_samples, int64_t n_nodes, double *max_coa,
+                          double *max_norm_coa, int64_t *max_coa_idx);
+int qm_group_synchronize(qm_group *g);
+int qm_group_n_parts(qm_group *g, int32_t *n_parts);
+/* part `part`: its device, boxes as qm_group_plan, flat node range [node_range[0], node_range[1]) and the device
+ * time (ms) of its share of the last step, from behind its onsets' copy to its last kernel (-1: none yet).
+ * Any pointer may be NULL. */
+int qm_group_part_info(qm_group *g, int32_t part, int32_t *device, int32_t *boxes /*[3][6]*/, int32_t *n_boxes,
+                       int64_t *node_range /*[2]*/, double *last_ms);
 
 #ifdef __cplusplus
 }

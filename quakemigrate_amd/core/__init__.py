@@ -6,6 +6,7 @@
 
 from .lib import (  # noqa: F401
     Engine,
+    EngineGroup,
     QMHipError,
     centred_sta_lta,
     default_engine,

@@ -131,6 +131,25 @@ qmlib.qm_stream_pending.argtypes = [_vp, ctypes.POINTER(c_int32), ctypes.POINTER
 qmlib.qm_engine_last_kernel_ms.argtypes = [_vp, ctypes.POINTER(ctypes.c_double)]
 qmlib.qm_engine_kernel_log.argtypes = [_vp, ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(c_int32)]
+# ---- engine groups (include/qmhip.h part 4) -----------------------------------
+_i32p = ctypes.POINTER(c_int32)
+qmlib.qm_group_plan.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, _i32p, _i32p]
+qmlib.qm_group_create.argtypes = [_i32p, c_int32, ctypes.POINTER(_vp)]
+qmlib.qm_group_destroy.argtypes = [_vp]
+qmlib.qm_group_destroy.restype = None
+qmlib.qm_group_config.argtypes = [_vp, ctypes.c_char_p, c_int64]
+qmlib.qm_group_get.argtypes = [_vp, ctypes.c_char_p, ctypes.POINTER(c_int64)]
+qmlib.qm_group_load_lut.argtypes = [_vp, _vp, c_int32, c_int32, c_int32, c_int32]
+qmlib.qm_group_table_select.argtypes = [_vp, ctypes.c_uint64, c_int32, ctypes.POINTER(c_int32)]
+qmlib.qm_group_detect.argtypes = [_vp, _vp, c_int32, c_int32, c_int32, c_int32, _vp, _vp, _vp]
+qmlib.qm_group_marginal.argtypes = [_vp, _vp, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _vp, _vp,
+                                    _vp, _vp]
+qmlib.qm_group_migrate.argtypes = [_vp, _vp, c_int32, c_int32, c_int32, c_int32, _vp, ctypes.c_int, _vp, _vp, _vp]
+qmlib.qm_group_find_max_coa.argtypes = [_vp, _vp, c_int32, c_int64, _vp, _vp, _vp]
+qmlib.qm_group_synchronize.argtypes = [_vp]
+qmlib.qm_group_n_parts.argtypes = [_vp, _i32p]
+qmlib.qm_group_part_info.argtypes = [_vp, c_int32, _i32p, _i32p, _i32p, ctypes.POINTER(c_int64),
+                                     ctypes.POINTER(ctypes.c_double)]
 
 
 class QMHipError(RuntimeError):
@@ -634,6 +653,205 @@ class Engine:
                 f"{rows}:{self.n_rows}")
 
 
+def group_plan(nx, ny, nz, n_parts, part):
+    """Boxes ``(x0, x1, y0, y1, z0, z1)`` of part ``part`` of an engine group of ``n_parts`` over the grid
+    (``qm_group_plan``: the column partition of ``distributed.column_boxes``, or balanced z-runs of a flat
+    ``(1, 1, N)`` table).  Host code."""
+    boxes = (c_int32 * 18)()
+    n = c_int32()
+    _check(qmlib.qm_group_plan(int(nx), int(ny), int(nz), int(n_parts), int(part), boxes, ctypes.byref(n)))
+    return [tuple(int(v) for v in boxes[6 * k: 6 * k + 6]) for k in range(n.value)]
+
+
+def _host_f64(x, what, count=None):
+    if not isinstance(x, np.ndarray) or x.dtype != np.float64 or not x.flags["C_CONTIGUOUS"]:
+        raise TypeError(f"{what}: an engine group takes C-contiguous float64 host arrays")
+    if count is not None and x.size < count:
+        raise ValueError(f"{what}: array holds {x.size} elements, {count} needed")
+    return _host(x)
+
+
+class EngineGroup:
+    """
+    One process driving a grid on several GPUs (``include/qmhip.h`` part 4): ``devices`` lists one part per
+    entry, ids may repeat (``[0, 0]``: two parts on GPU 0); entry 0 is the lead device.  The surface of
+    :class:`Engine` that :class:`quakemigrate_amd.scan.MigrationScan`, :func:`migrate` and :func:`find_max_coa`
+    use, host arrays in and out.  ``locate_fits``, ``rbf_peak`` and ``onsets`` run on an :class:`Engine` of the
+    lead device.  Not available: ``screen = 1``, on-device serving, ``detect_batch`` / the continuous pipeline.
+    """
+
+    def __init__(self, devices, **config):
+        ids = [int(d) for d in devices]
+        arr = (c_int32 * max(len(ids), 1))(*ids)
+        h = _vp()
+        _check(qmlib.qm_group_create(arr, len(ids), ctypes.byref(h)))
+        self._h = h
+        self.devices = ids
+        self.device = ids[0]
+        self._finalizer = weakref.finalize(self, qmlib.qm_group_destroy, h)
+        self.lead = Engine(ids[0])
+        self.grid = None
+        self.n_rows = None
+        self.node_offset = 0
+        self.table_generation = 0
+        self.grids_generation = 0
+        for k, v in config.items():
+            self.config(k, v)
+
+    def close(self):
+        self._finalizer()
+        self.lead.close()
+
+    def config(self, key, value):
+        _check(qmlib.qm_group_config(self._h, key.encode(), int(value)))
+        if key != "screen":                 # (the lead's own engine runs the locate rows only)
+            self.lead.config(key, value)
+
+    def get(self, key):
+        v = c_int64()
+        _check(qmlib.qm_group_get(self._h, key.encode(), ctypes.byref(v)))
+        return int(v.value)
+
+    def synchronize(self):
+        _check(qmlib.qm_group_synchronize(self._h))
+
+    @property
+    def n_parts(self):
+        return len(self.devices)
+
+    def part_info(self, part):
+        """``dict(device, boxes, node_range, last_ms)`` of one part (``last_ms``: device time of its share of
+        the last step, -1 if none)."""
+        dev, n = c_int32(), c_int32()
+        boxes = (c_int32 * 18)()
+        rng = (c_int64 * 2)()
+        ms = ctypes.c_double()
+        _check(qmlib.qm_group_part_info(self._h, int(part), ctypes.byref(dev), boxes, ctypes.byref(n), rng,
+                                        ctypes.byref(ms)))
+        return {"device": int(dev.value),
+                "boxes": [tuple(int(v) for v in boxes[6 * k: 6 * k + 6]) for k in range(n.value)],
+                "node_range": (int(rng[0]), int(rng[1])), "last_ms": float(ms.value)}
+
+    # -- table --------------------------------------------------------------
+    def load_lut(self, traveltimes, node_offset=0, shape=None):
+        if int(node_offset) != 0:
+            raise ValueError("an engine group holds the whole grid (node_offset = 0)")
+        if not isinstance(traveltimes, np.ndarray) or traveltimes.dtype != np.int32 \
+                or not traveltimes.flags["C_CONTIGUOUS"]:
+            raise TypeError("an engine group loads a C-contiguous int32 host table")
+        shape = tuple(traveltimes.shape) if shape is None else tuple(shape)
+        if len(shape) != 4:
+            raise ValueError("traveltimes must have shape (nx, ny, nz, n_rows)")
+        nx, ny, nz, rows = (int(v) for v in shape)
+        _check(qmlib.qm_group_load_lut(self._h, _host(traveltimes), nx, ny, nz, rows))
+        self.grid = (nx, ny, nz)
+        self.n_rows = rows
+        self.table_generation += 1
+
+    def select_table(self, key, capacity=4):
+        """As :meth:`Engine.select_table`, on every box engine of the group."""
+        import hashlib
+
+        k64 = int.from_bytes(hashlib.blake2b(repr(key).encode(), digest_size=8).digest(), "little")
+        resident = c_int32()
+        _check(qmlib.qm_group_table_select(self._h, k64, int(capacity), ctypes.byref(resident)))
+        if resident.value:
+            self.grid = (self.get("nx"), self.get("ny"), self.get("nz"))
+            self.n_rows = self.get("n_rows")
+        else:
+            self.grid, self.n_rows = None, None
+        self.table_generation += 1
+        return bool(resident.value)
+
+    def set_traveltime_grids(self, grids):
+        raise ValueError("on-device table serving is not available on an engine group")
+
+    def serve(self, *args, **kwargs):
+        raise ValueError("on-device table serving is not available on an engine group")
+
+    @property
+    def lut_max(self):
+        return self.get("lut_max")
+
+    @property
+    def n_nodes(self):
+        return int(np.prod(self.grid))
+
+    # -- steps --------------------------------------------------------------
+    def _steps(self, log_onsets, fsmp, lsmp):
+        rows, t_samples = (int(v) for v in log_onsets.shape)
+        if self.n_rows is None:
+            raise QMHipError("no travel-time table resident: call load_lut first")
+        if rows != self.n_rows:
+            raise ValueError("Mismatch between number of stations for data and LUT, "
+                             f"{rows}:{self.n_rows}")
+        return _host_f64(log_onsets, "log_onsets"), t_samples, max(t_samples - int(fsmp) - int(lsmp), 0)
+
+    @staticmethod
+    def _series_ptrs(out, n):
+        if out is None:
+            return _vp(None), _vp(None), _vp(None)
+        a, b, c = out
+        if not isinstance(c, np.ndarray) or c.dtype != np.int64 or not c.flags["C_CONTIGUOUS"] or c.size < n:
+            raise TypeError("the index series must be a C-contiguous int64 host array")
+        return _host_f64(a, "max_coa", n), _host_f64(b, "max_norm_coa", n), _host(c)
+
+    def _total(self, n_nodes_total):
+        if n_nodes_total is not None and int(n_nodes_total) != self.n_nodes:
+            raise ValueError("an engine group normalises by its whole grid's node count")
+
+    def detect(self, log_onsets, fsmp, lsmp, available, n_nodes_total=None, out=None):
+        """Fused migrate + find_max_coa over the group (host arrays)."""
+        self._total(n_nodes_total)
+        po, t_samples, n = self._steps(log_onsets, fsmp, lsmp)
+        if out is None:
+            out = (np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int64))
+        pa, pb, pc = self._series_ptrs(out, n)
+        _check(qmlib.qm_group_detect(self._h, po, t_samples, int(fsmp), int(lsmp), int(available), pa, pb, pc))
+        return out
+
+    def marginal_map(self, log_onsets, fsmp, lsmp, available, first_sample, end_sample, out=None,
+                     scan_out=None, n_nodes_total=None):
+        """As :meth:`Engine.marginal_map`: the whole grid's map, each part's flat range at its offset."""
+        self._total(n_nodes_total)
+        po, t_samples, n = self._steps(log_onsets, fsmp, lsmp)
+        if out is None:
+            out = np.zeros(self.grid, dtype=np.float64)
+        pm = _host_f64(out, "out", self.n_nodes)
+        pa, pb, pc = self._series_ptrs(scan_out, n)
+        _check(qmlib.qm_group_marginal(self._h, po, t_samples, int(fsmp), int(lsmp), int(available),
+                                       int(first_sample), int(end_sample), pm, pa, pb, pc))
+        return out
+
+    def migrate(self, log_onsets, fsmp, lsmp, available, map4d, scan_out=None, accumulate=False,
+                n_nodes_total=None):
+        self._total(n_nodes_total)
+        po, t_samples, n = self._steps(log_onsets, fsmp, lsmp)
+        pm = _host_f64(map4d, "map4d", self.n_nodes * n)
+        pa, pb, pc = self._series_ptrs(scan_out, n)
+        _check(qmlib.qm_group_migrate(self._h, po, t_samples, int(fsmp), int(lsmp), int(available), pm,
+                                      1 if accumulate else 0, pa, pb, pc))
+        return map4d
+
+    def find_max_coa(self, map4d, n_samples, n_nodes, out=None):
+        if out is None:
+            out = (np.zeros(n_samples), np.zeros(n_samples), np.zeros(n_samples, dtype=np.int64))
+        pm = _host_f64(map4d, "map4d", int(n_samples) * int(n_nodes))
+        pa, pb, pc = self._series_ptrs(out, int(n_samples))
+        _check(qmlib.qm_group_find_max_coa(self._h, pm, int(n_samples), int(n_nodes), pa, pb, pc))
+        return out
+
+    # -- the rows next to the path: the lead device's engine ---------------------
+    def locate_fits(self, *args, **kwargs):
+        return self.lead.locate_fits(*args, **kwargs)
+
+    def rbf_peak(self, *args, **kwargs):
+        return self.lead.rbf_peak(*args, **kwargs)
+
+    def onsets(self, *args, **kwargs):
+        return self.lead.onsets(*args, **kwargs)
+
+
 def timeit(*args_, **kwargs_):
     """
     The reference's per-call wall-time log line (quakemigrate/util.py:651-669, applied at
@@ -679,11 +897,27 @@ def release_cached_memory():
     qmlib.qm_release_cached_memory()
 
 
+def _device_list():
+    """``QM_HIP_DEVICES`` ("0,1,2,3") as a list of ids, or None when it is unset or empty."""
+    import os
+
+    text = os.environ.get("QM_HIP_DEVICES", "").strip()
+    if not text:
+        return None
+    return [int(v) for v in text.replace(" ", "").split(",") if v != ""]
+
+
 def default_engine():
+    """The process-wide engine: an :class:`EngineGroup` when ``QM_HIP_DEVICES`` lists more than one id, else
+    an :class:`Engine` on ``$QM_HIP_DEVICE`` (default 0)."""
     if _default["engine"] is None:
         import os
 
-        _default["engine"] = Engine(int(os.environ.get("QM_HIP_DEVICE", "0")))
+        ids = _device_list()
+        if ids is not None and len(ids) > 1:
+            _default["engine"] = EngineGroup(ids)
+        else:
+            _default["engine"] = Engine(int(os.environ.get("QM_HIP_DEVICE", "0")))
     return _default["engine"]
 
 

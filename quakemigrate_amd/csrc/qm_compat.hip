@@ -91,6 +91,44 @@ static bool any_nonzero(const double *p, size_t n) {
 }
 }  // extern "C++"
 
+// QM_HIP_DEVICES=0,1,... with more than one id: the two symbols run on a process-wide engine group
+// (qm_group.hip) of those devices instead -- same table reuse, QM_HIP_GRID, NaN fill and status
+static qm_group *g_compat_group = nullptr;
+static bool g_group_checked = false;
+
+static bool compat_group_wanted(std::vector<int32_t> *ids) {
+    const char *list = getenv("QM_HIP_DEVICES");
+    if (!list) return false;
+    ids->clear();
+    for (const char *p = list; *p;) {
+        char *end = nullptr;
+        const long v = strtol(p, &end, 10);
+        if (end == p) break;
+        ids->push_back((int32_t)v);
+        p = end;
+        while (*p == ',' || *p == ' ') ++p;
+    }
+    return ids->size() > 1;
+}
+
+// the group, or NULL for the single compat engine; *rc != 0: it was wanted and could not be made
+static qm_group *compat_group(int *rc) {
+    *rc = 0;
+    if (g_compat_group || g_group_checked) return g_compat_group;
+    std::vector<int32_t> ids;
+    if (!compat_group_wanted(&ids)) {
+        g_group_checked = true;
+        return nullptr;
+    }
+    if (qm_group_create(ids.data(), (int32_t)ids.size(), &g_compat_group)) {
+        g_compat_group = nullptr;
+        *rc = 1;
+        return nullptr;
+    }
+    g_group_checked = true;
+    return g_compat_group;
+}
+
 static qm_engine *compat_engine() {
     if (!g_compat) {
         const char *dev = getenv("QM_HIP_DEVICE");
@@ -127,8 +165,14 @@ void migrate(double *onsets, int32_t *lookup_tables, double *map4d, int32_t fsmp
     auto poison = [&]() {
         for (size_t i = 0; i < total; ++i) map4d[i] = std::nan("");
     };
-    qm_engine *e = compat_engine();
-    if (!e) {
+    int group_rc = 0;
+    qm_group *grp = compat_group(&group_rc);
+    if (group_rc) {
+        compat_failed(1, "migrate/create");
+        return poison();
+    }
+    qm_engine *e = grp ? nullptr : compat_engine();
+    if (!grp && !e) {
         compat_failed(1, "migrate/create");
         return poison();
     }
@@ -158,18 +202,27 @@ void migrate(double *onsets, int32_t *lookup_tables, double *map4d, int32_t fsmp
     table_hash(lookup_tables, (size_t)n_nodes * n_stations, &h, &h2);
     const char *reup = getenv("QM_HIP_COMPAT_REUPLOAD");
     const bool force = reup && atoi(reup) != 0;
-    if (force || !(g_compat_table.valid && e->have_lut && g_compat_table.hash == h &&
+    if (force || !(g_compat_table.valid && (grp || e->have_lut) && g_compat_table.hash == h &&
                    g_compat_table.hash2 == h2 && g_compat_table.n_nodes == n_nodes &&
                    g_compat_table.n_rows == n_stations && g_compat_table.gx == gx &&
                    g_compat_table.gy == gy && g_compat_table.gz == gz)) {
         g_compat_table.valid = false;
-        e->cfg_bx = gx ? 0 : 1;
-        e->cfg_by = gx ? 0 : 1;
-        e->cfg_bz = gx ? 0 : 32;
-        if (compat_failed(qm_engine_load_lut(e, lookup_tables, 0, gx ? gx : 1, gx ? gy : 1,
-                                             gx ? gz : (int32_t)n_nodes, n_stations, 0),
-                          "migrate/load"))
-            return poison();
+        if (grp) {
+            // (a flat table: the plan's z-runs, bricked 1 x 1 x 32 like the single engine's)
+            int rc = qm_group_config(grp, "brick_x", gx ? 0 : 1) || qm_group_config(grp, "brick_y", gx ? 0 : 1) ||
+                     qm_group_config(grp, "brick_z", gx ? 0 : 32) ||
+                     qm_group_load_lut(grp, lookup_tables, gx ? gx : 1, gx ? gy : 1, gx ? gz : (int32_t)n_nodes,
+                                       n_stations);
+            if (compat_failed(rc, "migrate/load")) return poison();
+        } else {
+            e->cfg_bx = gx ? 0 : 1;
+            e->cfg_by = gx ? 0 : 1;
+            e->cfg_bz = gx ? 0 : 32;
+            if (compat_failed(qm_engine_load_lut(e, lookup_tables, 0, gx ? gx : 1, gx ? gy : 1,
+                                                 gx ? gz : (int32_t)n_nodes, n_stations, 0),
+                              "migrate/load"))
+                return poison();
+        }
         g_compat_table.hash = h;
         g_compat_table.hash2 = h2;
         g_compat_table.n_nodes = n_nodes;
@@ -182,10 +235,11 @@ void migrate(double *onsets, int32_t *lookup_tables, double *map4d, int32_t fsmp
     // check: the caller vouches for a zeroed map, as the reference's own binding passes)
     const char *zero = getenv("QM_HIP_ASSUME_ZERO_MAP");
     const int accumulate = (zero && atoi(zero) != 0) ? 0 : (any_nonzero(map4d, total) ? 1 : 0);
-    if (compat_failed(qm_engine_migrate(e, onsets, 0, fsmp + lsmp + n_samples, fsmp, lsmp,
-                                        available, n_nodes, map4d, 0, accumulate, nullptr, nullptr,
-                                        nullptr, 0), "migrate"))
-        poison();
+    const int rc = grp ? qm_group_migrate(grp, onsets, fsmp + lsmp + n_samples, fsmp, lsmp, available, map4d,
+                                          accumulate, nullptr, nullptr, nullptr)
+                       : qm_engine_migrate(e, onsets, 0, fsmp + lsmp + n_samples, fsmp, lsmp, available, n_nodes,
+                                           map4d, 0, accumulate, nullptr, nullptr, nullptr, 0);
+    if (compat_failed(rc, "migrate")) poison();
 }
 
 void find_max_coa(double *map4d, double *max_coa, double *max_norm_coa, int64_t *max_coa_idx,
@@ -193,11 +247,16 @@ void find_max_coa(double *map4d, double *max_coa, double *max_norm_coa, int64_t 
     (void)threads;
     std::lock_guard<std::mutex> lock(g_compat_mutex);
     g_compat_status = 0;
-    qm_engine *e = compat_engine();
-    if (!e || compat_failed(qm_engine_find_max_coa(e, map4d, 0, n_samples, n_nodes, max_coa,
-                                                   max_norm_coa, max_coa_idx, 0),
-                            "find_max_coa")) {
-        if (!e) compat_failed(1, "find_max_coa/create");
+    int group_rc = 0;
+    qm_group *grp = compat_group(&group_rc);
+    qm_engine *e = (grp || group_rc) ? nullptr : compat_engine();
+    const bool made = grp || e;
+    if (!made || compat_failed(grp ? qm_group_find_max_coa(grp, map4d, n_samples, n_nodes, max_coa, max_norm_coa,
+                                                           max_coa_idx)
+                                   : qm_engine_find_max_coa(e, map4d, 0, n_samples, n_nodes, max_coa,
+                                                            max_norm_coa, max_coa_idx, 0),
+                               "find_max_coa")) {
+        if (!made) compat_failed(1, "find_max_coa/create");
         for (int32_t i = 0; i < n_samples; ++i) {
             max_coa[i] = max_norm_coa[i] = std::nan("");
             max_coa_idx[i] = 0;

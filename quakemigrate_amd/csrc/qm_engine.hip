@@ -1309,3 +1309,71 @@ int qm_engine_last_kernel_ms(qm_engine *e, double *ms) {
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ partial-output forms (qm_group.hip)
+// The step entry points above, stopped before the final normalisation: this engine's partial (log2-domain
+// maximum or, for a scanned volume, the value itself; GLOBAL node index; sum) per sample written to p_max /
+// p_idx / p_sum on the device, as qm_engine_detect_partial writes it -- what the group folds across boxes.
+// Inputs and outputs are device memory on the engine's GPU; nothing waits.  p_max == NULL: no series.
+int marginal_partial(qm_engine *e, const double *d_on, int T, int fsmp, int lsmp, int available, int first,
+                     int end, double *d_map, double *p_max, int64_t *p_idx, double *p_sum) {
+    DeviceGuard guard(e->device);
+    int ns = 0, sets = 0;
+    if (check_step(e, T, fsmp, lsmp, available, &ns)) return 1;
+    if (first < 0 || end > ns || first >= end)
+        return fail("marginal window [%d, %d) outside the %d scanned samples", first, end, ns);
+    const bool want_scan = p_max != nullptr;
+    if (run_stack(e, d_on, T, fsmp, ns, available, 0, ns, nullptr, 0, 0, want_scan, &sets, true, first, end))
+        return 1;
+    hipLaunchKernelGGL(qm::marginal_reduce_kernel, dim3((unsigned)((e->n_nodes + 255) / 256)), dim3(256), 0,
+                       e->stream, e->d_marg.p, e->marg_tiles, e->n_nodes, d_map);
+    QM_HIP(hipGetLastError());
+    e->last_sets_own = want_scan;
+    if (want_scan && combine(e, e->d_pmax.p, e->d_pidx.p, e->d_psum.p, sets, ns, 0, e->node_offset, 0, p_max,
+                             p_sum, p_idx))
+        return 1;
+    return 0;
+}
+
+int migrate_partial(qm_engine *e, const double *d_on, int T, int fsmp, int lsmp, int available, double *d_vol,
+                    int accumulate, double *p_max, int64_t *p_idx, double *p_sum) {
+    DeviceGuard guard(e->device);
+    int ns = 0, sets = 0;
+    if (check_step(e, T, fsmp, lsmp, available, &ns)) return 1;
+    const bool want_scan = p_max != nullptr;
+    if (run_stack(e, d_on, T, fsmp, ns, available, 0, ns, d_vol, ns, accumulate, want_scan, &sets)) return 1;
+    e->last_sets_own = want_scan;
+    if (want_scan && combine(e, e->d_pmax.p, e->d_pidx.p, e->d_psum.p, sets, ns, 0, e->node_offset, 0, p_max,
+                             p_sum, p_idx))
+        return 1;
+    return 0;
+}
+
+// find_max_coa's scan over the n_nodes rows [node0, node0 + n_nodes) of a volume whose rows are d_vol's
+int scan_partial(qm_engine *e, const double *d_vol, int ns, int64_t n_nodes, int64_t node0, double *p_max,
+                 int64_t *p_idx, double *p_sum) {
+    DeviceGuard guard(e->device);
+    const int tiles = (ns + qm::kWave - 1) / qm::kWave;
+    const int groups = (tiles + qm::kScanWaves - 1) / qm::kScanWaves;
+    const int waves = (tiles + groups - 1) / groups;
+    const int xgroups = (tiles + waves - 1) / waves;
+    int64_t sets = std::max<int64_t>(1, ((int64_t)e->cfg_scan_waves * e->n_cu + tiles - 1) / tiles);
+    sets = std::min<int64_t>(sets, std::max<int64_t>(1, n_nodes / 256));
+    sets = std::min<int64_t>(sets, 65535);
+    const int64_t per = (n_nodes + sets - 1) / sets;
+    sets = (n_nodes + per - 1) / per;
+    const size_t need = (size_t)sets * ns;
+    if (e->d_pmax.ensure(need) || e->d_psum.ensure(need) || e->d_pidx.ensure(need)) return 1;
+    hipLaunchKernelGGL(qm::scan_volume_kernel, dim3(xgroups, (unsigned)sets), dim3(waves * qm::kWave), 0, e->stream,
+                       d_vol, (int64_t)ns, ns, n_nodes, per, e->d_pmax.p, e->d_pidx.p, e->d_psum.p);
+    QM_HIP(hipGetLastError());
+    return combine(e, e->d_pmax.p, e->d_pidx.p, e->d_psum.p, (int)sets, ns, 0, node0, 0, p_max, p_sum, p_idx);
+}
+
+// the fold of scan_partial's sets, packed [n_sets][3][ns] as for qm_engine_finalize_packed: find_max_coa's outputs
+int fold_scanned(qm_engine *e, const double *d_packed, int n_sets, int ns, int64_t n_nodes_total, double *o_max,
+                 double *o_norm, int64_t *o_idx) {
+    DeviceGuard guard(e->device);
+    return combine(e, d_packed, reinterpret_cast<const int64_t *>(d_packed + ns), d_packed + 2 * (int64_t)ns, n_sets,
+                   ns, 2, 0, n_nodes_total, o_max, o_norm, o_idx, nullptr, 3 * (int64_t)ns);
+}

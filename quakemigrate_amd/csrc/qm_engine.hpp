@@ -10,6 +10,7 @@
 //   qm_stream.hip    the continuous detect pipeline (pinned ring, copies overlapped with compute)
 //   qm_widen.hip     the rows next to the path: onset stage, locate fits, RBF peak
 //   qm_compat.hip    the five reference-signature symbols (qmlib.h:28-44)
+//   qm_group.hip     engine groups: one process driving the boxes of a column partition on several devices
 // Everything declared here lives in the library only (hidden visibility).
 #pragma once
 #include "../../include/qmhip.h"
@@ -370,6 +371,16 @@ int stage_out(qm_engine *e, int n, int out_on_device, double *max_coa, double *m
               int64_t *idx, OutStage *st);
 int fetch_out(qm_engine *e, int n, int out_on_device, const OutStage &st, double *max_coa,
               double *max_norm, int64_t *idx);
+// partial-output forms of marginal / migrate (device volume) / find_max_coa and the fold of scanned partials:
+// device in, device out, nothing waits (the engine group, qm_group.hip)
+int marginal_partial(qm_engine *e, const double *d_on, int T, int fsmp, int lsmp, int available, int first,
+                     int end, double *d_map, double *p_max, int64_t *p_idx, double *p_sum);
+int migrate_partial(qm_engine *e, const double *d_on, int T, int fsmp, int lsmp, int available, double *d_vol,
+                    int accumulate, double *p_max, int64_t *p_idx, double *p_sum);
+int scan_partial(qm_engine *e, const double *d_vol, int ns, int64_t n_nodes, int64_t node0, double *p_max,
+                 int64_t *p_idx, double *p_sum);
+int fold_scanned(qm_engine *e, const double *d_packed, int n_sets, int ns, int64_t n_nodes_total, double *o_max,
+                 double *o_norm, int64_t *o_idx);
 
 // ---- qm_stream.hip ------------------------------------------------------------------------------
 // the engine is going away: its pipelines give their buffers back and refuse further calls

@@ -201,6 +201,30 @@ def gather_planes(local, nx_total, group=None):
     return torch.cat([whole[r, : x1 - x0] for r, (x0, x1) in enumerate(sizes)], dim=0)
 
 
+def gather_flat_ranges(local, ranges, group=None):
+    """
+    All-gather of contiguous flat node ranges: ``local`` is this rank's 1-D piece of ``ranges[rank]``
+    (``(n0, n1)`` per rank, ascending and together ``[0, N)`` -- what :func:`shard_columns` times ``nz``
+    gives); returns the whole ``[N]`` map on every rank, each rank's range at its node offset -- the assembly the
+    engine group (csrc/qm_group.hip) does with copies.  Ranges differ in length, so every rank pads to the
+    longest and the padding is cut away after the exchange.
+    """
+    import torch.distributed as dist
+
+    world = dist.get_world_size(group)
+    longest = max(1, max(n1 - n0 for n0, n1 in ranges))
+    padded = torch.zeros(longest, dtype=local.dtype, device=local.device)
+    padded[: local.numel()] = local.reshape(-1)
+    whole = torch.empty((world, longest), dtype=local.dtype, device=local.device)
+    if local.is_cuda and _backend(group) == "gloo":      # no device all-gather in gloo
+        host = torch.empty(whole.numel(), dtype=whole.dtype)
+        dist.all_gather_into_tensor(host, padded.cpu(), group=group)
+        whole.view(-1).copy_(host)
+    else:
+        dist.all_gather_into_tensor(whole.view(-1), padded, group=group)
+    return torch.cat([whole[r, : n1 - n0] for r, (n0, n1) in enumerate(ranges)])
+
+
 class ShardedDetector:
     """
     One rank's share of a grid-sharded detect sweep.
@@ -400,3 +424,23 @@ class ColumnShardedDetector:
             all_gather_packed(self.tie_packed, self.tie_gathered, self.group)
             self.fold_engine.tie_fold(self.tie_gathered, self.world * MAX_BOXES, self.n_samples, out[2])
         return out
+
+    def marginal_map(self, log_onsets, fsmp, lsmp, available, first_sample, end_sample, grid_shape):
+        """
+        Locate without the volume on the column partition: every box marginalises its nodes
+        (``Engine.marginal_map``) into this rank's flat range, the ranges are gathered at their node offsets
+        (:func:`gather_flat_ranges`).  ``grid_shape`` = the whole grid's ``(nx, ny, nz)``; returns the whole map
+        on every rank (device tensor of that shape).
+        """
+        import torch.distributed as dist
+
+        nx, ny, nz = (int(v) for v in grid_shape)
+        self._bind_stream()
+        ranges = [tuple(c * nz for c in shard_columns(nx, ny, self.world, r)) for r in range(self.world)]
+        n0, n1 = ranges[dist.get_rank(self.group)]
+        local = torch.zeros(n1 - n0, dtype=torch.float64, device=self.device)
+        for eng in self.engines:
+            off = eng.node_offset - n0
+            eng.marginal_map(log_onsets, fsmp, lsmp, available, first_sample, end_sample,
+                             out=local[off: off + eng.n_nodes], n_nodes_total=self.n_nodes_total)
+        return gather_flat_ranges(local, ranges, self.group).view(nx, ny, nz)

@@ -116,8 +116,11 @@ class MigrationScan:
         ``run.stage`` of the reference (scan.py:641).
     scan_rate : int, optional
         Passed to ``event.mw_times`` in the locate stage (scan.py:646).
-    engine : quakemigrate_amd.core.Engine, optional
-        Defaults to the process-wide engine on ``$QM_HIP_DEVICE``.
+    engine : quakemigrate_amd.core.Engine or quakemigrate_amd.core.EngineGroup, optional
+        Defaults to the process-wide engine (``lib.default_engine``: a group when ``$QM_HIP_DEVICES``
+        lists several devices, else an engine on ``$QM_HIP_DEVICE``).  A group runs ``_compute``, the
+        locate calls and ``continuous_compute`` (timestep by timestep, without the pipeline); it takes
+        neither ``device_serving`` nor ``screen=True``.
     threads : int
         Accepted for signature compatibility; the GPU engine ignores it.
     device_serving : bool
@@ -156,6 +159,12 @@ class MigrationScan:
         # whenever the availability changes -- no per-timestep host stack / rint / upload.
         self.device_serving = bool(device_serving)
         self._grid_index = None
+        if isinstance(self.engine, lib.EngineGroup):
+            if self.device_serving:
+                raise ValueError("device_serving is not available on an engine group")
+            if self.screen:
+                raise ValueError("screen=True is not available on an engine group (the screened detect has "
+                                 "no partial form)")
 
     # -- table residency ------------------------------------------------------
     def _ensure_table(self, sampling_rate, availability):
@@ -386,6 +395,11 @@ class MigrationScan:
                                  f"{n_onsets}:{eng.n_rows}")
             if onsets.size < t_samples - lsmp:
                 raise ValueError("Data array smaller than coalescence array.")
+            if isinstance(eng, lib.EngineGroup):         # (a group: one timestep after the other, no pipeline)
+                a, b, c = eng.detect(onsets, fsmp, lsmp, avail)
+                sink.append(_shift(data.starttime, self.pre_pad), a, b, self.lut.index2coord(c, unravel=True), ucf)
+                rows.append(dict(onset_data.availability))
+                continue
             key = (self._resident_key, t_samples, fsmp, lsmp, avail)
             if key != state["key"]:                      # another table or window shape: a new pipeline
                 drain()
