@@ -197,7 +197,7 @@ int qm_engine_synchronize(qm_engine *e);
  * last_candidates, screen_brick_nodes; tie_refined_steps, tie_pairs and tie_overflow_samples (of the last
  * refined launch), tie_brick_rows (rows of per-brick maxima the last stacking launch left: 0 = it refined from
  * sets of bricks);
- * table_hits, table_misses, table_evictions, tables_parked, table_bytes, tables_parked_bytes. */
+ * table_hits, table_misses, table_evictions, tables_parked, table_bytes, tables_parked_bytes, table_digests. */
 int qm_engine_config(qm_engine *e, const char *key, int64_t value);
 int qm_engine_get(qm_engine *e, const char *key, int64_t *value);
 
@@ -234,6 +234,14 @@ int qm_engine_serve(qm_engine *e, double sampling_rate, const int32_t *rows, int
                     int32_t dfx, int32_t dfy, int32_t dfz, int64_t node_offset);
 /* copy the resident int32 table ([n_nodes][n_rows]) back to the host (tests, inspection) */
 int qm_engine_lut_download(qm_engine *e, int32_t *out);
+/* 64-bit digest of the resident int32 table ([n_nodes][n_rows] as qm_engine_lut_download returns it) mixed with
+ * nx, ny, nz, n_rows and node_offset; computed on the device, cached per table (a table brought back by
+ * qm_engine_table_select is not hashed again; qm_engine_get "table_digests" counts the passes).  With
+ * mix = the splitmix64 finalizer and i the flat element index: sum = SUM_i mix(mix(i) + (uint32)v_i) mod 2^64,
+ * then digest = sum; digest = mix(digest + f) for f in nx, ny, nz, n_rows, node_offset (as uint64).  One pass
+ * over the table; the order of the sum does not matter, so the value is exact and reproducible anywhere.
+ * What qm_stream_create_replicas compares. */
+int qm_engine_table_digest(qm_engine *e, uint64_t *digest);
 
 /* largest (clamped) delay in the resident table; callers must keep it <= lsmp */
 int qm_engine_lut_max(qm_engine *e, int32_t *max_delay);
@@ -430,6 +438,17 @@ int qm_stream_flush(qm_stream *s);
 int qm_stream_pop(qm_stream *s, int32_t n_steps, double *max_coa, double *max_norm_coa,
                   int64_t *max_coa_idx);
 int qm_stream_pending(qm_stream *s, int32_t *launched_not_popped, int32_t *pushed_not_launched);
+/* One pipeline over several engines that hold the SAME table (checked by digest): the continuous stream split by
+ * time, not by grid.  Launch j (K timesteps) runs on engine j mod n_engines, each engine with
+ * `depth` slots of its own; qm_stream_pop returns timesteps in push order.  Same qm_stream handle: push / flush /
+ * pop / pending / destroy work unchanged (push returns 2 when every slot of the engine next in turn holds
+ * un-popped results: all n_engines x depth launches are then un-popped, and popping the oldest one frees it).
+ * Refused: fewer than one engine, a NULL entry, the same engine twice (two engines on one device are fine), an
+ * engine without a table, tables of differing shape or node offset, differing digests.  Destroying an engine makes
+ * every call on the stream fail; qm_stream_destroy still frees it. */
+int qm_stream_create_replicas(qm_engine *const *engines, int32_t n_engines, int32_t t_samples, int32_t fsmp,
+                              int32_t lsmp, int32_t available, int64_t n_nodes_total, int32_t steps_per_launch,
+                              int32_t depth, qm_stream **out);
 
 /* Duration (ms, HIP events on the engine stream) of the stacking kernel(s) of
  * the most recent detect / migrate call; negative if none.  Synchronises. */
@@ -453,7 +472,8 @@ int qm_engine_kernel_log(qm_engine *e, double *total_ms, int32_t *n_calls);
  * adds the second exchange of qm_engine_tie_partial / _tie_fold.  Host in, host out; results are those of one
  * engine over the whole table (max_coa and max_coa_idx bit for bit; max_norm_coa's sum over the nodes is formed
  * in another order).  Not available on a group: screen = 1 (refused by qm_group_config), on-device serving,
- * detect_batch and the qm_stream pipeline, device pointers.  Every call returns 0 / non-zero + qm_last_error(). */
+ * detect_batch and the qm_stream pipeline (a continuous stream over several devices splits by time instead:
+ * qm_stream_create_replicas, part 3), device pointers.  Every call returns 0 / non-zero + qm_last_error(). */
 typedef struct qm_group qm_group;
 
 /* The partition, host code: part `part` of n_parts as up to three boxes (x0, x1, y0, y1, z0, z1), ascending in

@@ -7,6 +7,7 @@
 from .lib import (  # noqa: F401
     Engine,
     EngineGroup,
+    EngineReplicas,
     QMHipError,
     centred_sta_lta,
     default_engine,

@@ -80,6 +80,7 @@ qmlib.qm_engine_grids_set.argtypes = [_vp, c_int32, _vp, ctypes.c_int]
 qmlib.qm_engine_serve.argtypes = [_vp, ctypes.c_double, c_i32Pt, c_int32, c_int32, c_int32,
                                   c_int32, c_int64]
 qmlib.qm_engine_lut_download.argtypes = [_vp, c_i32Pt]
+qmlib.qm_engine_table_digest.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint64)]
 qmlib.qm_engine_detect.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32,
                                    c_int32, c_int32, c_int64, _vp, _vp, _vp,
                                    ctypes.c_int]
@@ -122,6 +123,8 @@ qmlib.qm_exp_correctly_rounded.restype = ctypes.c_double
 qmlib.qm_engine_exp_correctly_rounded.argtypes = [_vp, c_dPt, c_int64, c_dPt]
 qmlib.qm_stream_create.argtypes = [_vp, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32, c_int32,
                                    ctypes.POINTER(_vp)]
+qmlib.qm_stream_create_replicas.argtypes = [ctypes.POINTER(_vp), c_int32, c_int32, c_int32, c_int32, c_int32,
+                                            c_int64, c_int32, c_int32, ctypes.POINTER(_vp)]
 qmlib.qm_stream_destroy.argtypes = [_vp]
 qmlib.qm_stream_destroy.restype = None
 qmlib.qm_stream_push.argtypes = [_vp, _vp]
@@ -381,6 +384,13 @@ class Engine:
         out = np.empty(tuple(self.grid) + (self.n_rows,), dtype=np.int32)
         _check(qmlib.qm_engine_lut_download(self._h, out))
         return out
+
+    def table_digest(self):
+        """64-bit digest of the resident table and its shape, computed on the device once per table
+        (``qm_engine_table_digest``)."""
+        v = ctypes.c_uint64()
+        _check(qmlib.qm_engine_table_digest(self._h, ctypes.byref(v)))
+        return int(v.value)
 
     @property
     def lut_max(self):
@@ -842,6 +852,139 @@ class EngineGroup:
         return out
 
     # -- the rows next to the path: the lead device's engine ---------------------
+    def locate_fits(self, *args, **kwargs):
+        return self.lead.locate_fits(*args, **kwargs)
+
+    def rbf_peak(self, *args, **kwargs):
+        return self.lead.rbf_peak(*args, **kwargs)
+
+    def onsets(self, *args, **kwargs):
+        return self.lead.onsets(*args, **kwargs)
+
+
+class EngineReplicas:
+    """
+    One process driving a continuous stream on several GPUs by TIME: ``devices`` lists one
+    :class:`Engine` per entry, ids may repeat (``[0, 0]``: two engines on GPU 0); entry 0 is the lead.  Every
+    replica holds the whole table.  :class:`quakemigrate_amd.stream.StreamingDetector` runs one pipeline over all
+    of them (``qm_stream_create_replicas``: launch j on replica j mod n, results in push order), which is what
+    ``MigrationScan.continuous_compute`` uses; single calls (``detect``, ``migrate``, ``marginal_map``, the locate
+    rows) run on the lead and are an :class:`Engine`'s bit for bit.  Table operations and ``config`` go to every
+    replica.  For one large step over several GPUs use :class:`EngineGroup` instead.
+    """
+
+    def __init__(self, devices, **config):
+        ids = [int(d) for d in devices]
+        if not ids:
+            raise ValueError("EngineReplicas needs at least one device")
+        self.devices = ids
+        self.replicas = []
+        try:
+            for d in ids:
+                self.replicas.append(Engine(d))
+            for k, v in config.items():
+                self.config(k, v)
+        except BaseException:
+            self.close()
+            raise
+        self.table_generation = 0
+        self.grids_generation = 0
+
+    @property
+    def lead(self):
+        return self.replicas[0]
+
+    def close(self):
+        for r in self.replicas:
+            r.close()
+
+    def config(self, key, value):
+        for r in self.replicas:
+            r.config(key, value)
+
+    def get(self, key):
+        values = [r.get(key) for r in self.replicas]
+        if any(v != values[0] for v in values):
+            raise QMHipError(f"the replicas disagree on {key!r}: {values}")
+        return values[0]
+
+    def synchronize(self):
+        for r in self.replicas:
+            r.synchronize()
+
+    # -- table: every replica ----------------------------------------------------
+    def load_lut(self, traveltimes, node_offset=0, shape=None):
+        for r in self.replicas:
+            r.load_lut(traveltimes, node_offset=node_offset, shape=shape)
+        self.table_generation += 1
+
+    def select_table(self, key, capacity=4):
+        """As :meth:`Engine.select_table` on every replica; True only if every one has the table resident (else
+        the caller's ``load_lut`` / ``serve`` goes to all of them)."""
+        resident = [r.select_table(key, capacity) for r in self.replicas]
+        self.table_generation += 1
+        return all(resident)
+
+    def set_traveltime_grids(self, grids):
+        grids = list(grids)
+        for r in self.replicas:
+            r.set_traveltime_grids(grids)
+        self.grids_generation += 1
+        self.table_generation += 1
+
+    def serve(self, sampling_rate, rows, decimate=(1, 1, 1), node_offset=0):
+        for r in self.replicas:
+            r.serve(sampling_rate, rows, decimate=decimate, node_offset=node_offset)
+        self.table_generation += 1
+
+    def table_digest(self):
+        """The replicas' common table digest (:meth:`Engine.table_digest`); raises if one holds another table."""
+        digests = [r.table_digest() for r in self.replicas]
+        for i, d in enumerate(digests):
+            if d != digests[0]:
+                raise QMHipError(f"replica {i} holds another table than replica 0")
+        return digests[0]
+
+    def download_lut(self):
+        return self.lead.download_lut()
+
+    @property
+    def device(self):
+        return self.lead.device
+
+    @property
+    def grid(self):
+        return self.lead.grid
+
+    @property
+    def n_rows(self):
+        return self.lead.n_rows
+
+    @property
+    def node_offset(self):
+        return self.lead.node_offset
+
+    @property
+    def n_nodes(self):
+        return self.lead.n_nodes
+
+    @property
+    def lut_max(self):
+        return self.lead.lut_max
+
+    # -- single calls: the lead ----------------------------------------------------
+    def detect(self, *args, **kwargs):
+        return self.lead.detect(*args, **kwargs)
+
+    def migrate(self, *args, **kwargs):
+        return self.lead.migrate(*args, **kwargs)
+
+    def marginal_map(self, *args, **kwargs):
+        return self.lead.marginal_map(*args, **kwargs)
+
+    def find_max_coa(self, *args, **kwargs):
+        return self.lead.find_max_coa(*args, **kwargs)
+
     def locate_fits(self, *args, **kwargs):
         return self.lead.locate_fits(*args, **kwargs)
 

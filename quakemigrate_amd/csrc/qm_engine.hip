@@ -723,7 +723,7 @@ void qm_engine_destroy(qm_engine *e) {
     for (TableSlot &slot : e->slots) slot.state.release_all();
     e->d_grids.release(); e->d_rows.release(); e->d_served.release();
     e->d_sig.release(); e->d_sta.release(); e->d_lta.release(); e->d_raw.release();
-    e->d_onset_meta.release(); e->d_scalar.release();
+    e->d_onset_meta.release(); e->d_scalar.release(); e->d_digest.release();
     e->d_onsets.release(); e->d_pmax.release(); e->d_psum.release(); e->d_out_a.release();
     e->d_chunk.release(); e->d_marg.release(); e->d_marg_out.release(); e->d_pidx.release();
     e->d_fit_a.release(); e->d_fit_b.release(); e->d_fit_c.release(); e->d_fit_part.release();
@@ -926,6 +926,7 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     else if (k == "table_hits") *v = e->table_hits;
     else if (k == "table_misses") *v = e->table_misses;
     else if (k == "table_evictions") *v = e->table_evictions;
+    else if (k == "table_digests") *v = e->table_digests;
     else if (k == "tables_parked") {
         *v = 0;
         for (const TableSlot &sl : e->slots) *v += sl.used ? 1 : 0;

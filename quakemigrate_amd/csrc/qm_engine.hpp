@@ -7,7 +7,8 @@
 //   qm_engine.hip    engine handle, tunables, the stacking launches and the step entry points
 //                    (detect / detect_batch / partial / finalize / migrate / marginal / find_max_coa)
 //   qm_screen.hip    the opt-in screened detect's launch sequence
-//   qm_stream.hip    the continuous detect pipeline (pinned ring, copies overlapped with compute)
+//   qm_stream.hip    the continuous detect pipeline (pinned ring, copies overlapped with compute), also over
+//                    several engines that hold the same table (replicas: launches round-robin)
 //   qm_widen.hip     the rows next to the path: onset stage, locate fits, RBF peak
 //   qm_compat.hip    the five reference-signature symbols (qmlib.h:28-44)
 //   qm_group.hip     engine groups: one process driving the boxes of a column partition on several devices
@@ -139,6 +140,8 @@ struct TableState {
     bool have_lut = false;
     uint64_t serial = 0;            // identity of the loaded table (process-unique; travels with the state
                                     // through qm_engine_table_select): what a qm_stream checks before a launch
+    uint64_t digest = 0;            // qm_engine_table_digest of this table, valid while digest_serial == serial
+    uint64_t digest_serial = 0;     // (computed once per table; travels with the state like the serial)
     qm::GridDesc g{};
     int64_t n_nodes = 0;
     int64_t node_offset = 0;
@@ -213,6 +216,8 @@ struct qm_engine : TableState {
     uint64_t cur_key = 0, table_clock = 0;
     bool cur_keyed = false;
     int64_t table_hits = 0, table_misses = 0, table_evictions = 0;
+    int64_t table_digests = 0;          // digest kernels run (qm_engine_table_digest: once per table)
+    DevBuf<unsigned long long> d_digest;    // ... their sum
 
     // tunables
     int cfg_bx = 0, cfg_by = 0, cfg_bz = 0;      // 0 = choose the brick shape per table

@@ -51,6 +51,16 @@ struct qm_stream {
     int64_t launched_steps = 0, popped_steps = 0, launches = 0;
     unsigned long long *h_stamp = nullptr;   // ("stream_stamps") pinned [2][4096]
     bool pulled = false;                // the last launch's inputs were pulled by a kernel (no copy command)
+    // A stream over replicas (qm_stream_create_replicas) holds no slots of its own: one ordinary stream per
+    // engine (a LANE, registered on that engine like any other stream) and the launches in push order.  Launch j
+    // goes to lane j mod n; the entry points dispatch to the replicas_* functions below.
+    std::vector<qm_stream *> lanes;
+    struct Launch {
+        int lane = 0;
+        int left = 0;                   // steps not yet popped
+    };
+    std::deque<Launch> launched;        // oldest first
+    int cur = 0;                        // the lane being filled
 };
 
 namespace {
@@ -187,6 +197,70 @@ int launch_slot(qm_stream *s) {
     return 0;
 }
 
+// ---- replicas: one pipeline over several engines that hold the same table -----------------------------------
+// Launches go round the lanes in push order, so a lane's next slot is in flight only when all n x depth launches
+// are un-popped -- and then the oldest launch is on that lane: "pop the oldest launch, push again" still frees it.
+
+int replicas_alive(const qm_stream *s, const char *what) {
+    for (const qm_stream *lane : s->lanes)
+        if (alive(lane, what)) return 1;
+    return 0;
+}
+
+// the current lane launched `steps` timesteps (a push that filled its slot, or a flush): record them, next lane
+void replicas_launched(qm_stream *s, int64_t steps) {
+    s->launched.push_back({s->cur, (int)steps});
+    s->cur = (s->cur + 1) % (int)s->lanes.size();
+}
+
+int replicas_flush(qm_stream *s) {
+    if (replicas_alive(s, "qm_stream_flush")) return 1;
+    qm_stream *lane = s->lanes[s->cur];
+    const int64_t before = lane->launched_steps;
+    if (qm_stream_flush(lane)) return 1;
+    if (lane->launched_steps != before) replicas_launched(s, lane->launched_steps - before);
+    return 0;
+}
+
+int replicas_push(qm_stream *s, const double *log_onsets) {
+    if (replicas_alive(s, "qm_stream_push")) return 1;
+    // (a full slot whose launch failed -- the table changed under the stream -- goes out first, as on one engine;
+    // then this timestep goes to the next lane, not behind it on the same one)
+    if (s->lanes[s->cur]->fill_n >= s->lanes[s->cur]->K && replicas_flush(s)) return 1;
+    qm_stream *lane = s->lanes[s->cur];
+    const int64_t before = lane->launched_steps;
+    const int rc = qm_stream_push(lane, log_onsets);
+    if (lane->launched_steps != before) replicas_launched(s, lane->launched_steps - before);
+    return rc;
+}
+
+int replicas_pending(const qm_stream *s, int64_t *launched_not_popped) {
+    int64_t n = 0;
+    for (const qm_stream *lane : s->lanes) n += lane->launched_steps - lane->popped_steps;
+    *launched_not_popped = n;
+    return s->lanes[s->cur]->fill_n;
+}
+
+int replicas_pop(qm_stream *s, int32_t n_steps, double *max_coa, double *max_norm_coa, int64_t *max_coa_idx) {
+    if (replicas_alive(s, "qm_stream_pop")) return 1;
+    int64_t waiting = 0;
+    const int filling = replicas_pending(s, &waiting);
+    if (n_steps < 0 || n_steps > waiting)
+        return fail("qm_stream_pop: %d steps asked for, %lld launched and not yet popped (%d pushed into "
+                    "a launch that has not gone out: qm_stream_flush)", n_steps, (long long)waiting, filling);
+    const size_t ns = (size_t)s->lanes[0]->ns;
+    for (int k = 0; k < n_steps;) {
+        qm_stream::Launch &l = s->launched.front();
+        const int take = std::min(n_steps - k, l.left);
+        if (qm_stream_pop(s->lanes[l.lane], take, max_coa + k * ns, max_norm_coa + k * ns, max_coa_idx + k * ns))
+            return 1;
+        k += take;
+        l.left -= take;
+        if (l.left == 0) s->launched.pop_front();
+    }
+    return 0;
+}
+
 }  // namespace
 
 void streams_orphan(qm_engine *e) {
@@ -240,8 +314,52 @@ int qm_stream_create(qm_engine *e, int32_t t_samples, int32_t fsmp, int32_t lsmp
     return 0;
 }
 
+int qm_stream_create_replicas(qm_engine *const *engines, int32_t n_engines, int32_t t_samples, int32_t fsmp,
+                              int32_t lsmp, int32_t available, int64_t n_nodes_total, int32_t steps_per_launch,
+                              int32_t depth, qm_stream **out) {
+    if (!engines || !out) return fail("qm_stream_create_replicas: NULL argument");
+    *out = nullptr;
+    if (n_engines < 1) return fail("qm_stream_create_replicas: at least one engine is needed (got %d)", n_engines);
+    for (int r = 0; r < n_engines; ++r) {
+        if (!engines[r]) return fail("qm_stream_create_replicas: replica %d is NULL", r);
+        for (int q = 0; q < r; ++q)
+            if (engines[q] == engines[r])
+                return fail("qm_stream_create_replicas: replicas %d and %d are the same engine (two engines on one "
+                            "device are fine, one engine twice is not)", q, r);
+        if (!engines[r]->have_lut) return fail("qm_stream_create_replicas: replica %d holds no travel-time table", r);
+    }
+    const qm_engine *lead = engines[0];
+    uint64_t d0 = 0;
+    if (qm_engine_table_digest(engines[0], &d0)) return 1;
+    for (int r = 1; r < n_engines; ++r) {
+        const qm_engine *e = engines[r];
+        if (e->g.n_rows != lead->g.n_rows || e->g.nx != lead->g.nx || e->g.ny != lead->g.ny || e->g.nz != lead->g.nz ||
+            e->node_offset != lead->node_offset)
+            return fail("qm_stream_create_replicas: replica %d holds a table of another shape (%d x %d x %d nodes, "
+                        "%d rows, node offset %lld) than replica 0 (%d x %d x %d, %d rows, node offset %lld)", r,
+                        e->g.nx, e->g.ny, e->g.nz, e->g.n_rows, (long long)e->node_offset, lead->g.nx, lead->g.ny,
+                        lead->g.nz, lead->g.n_rows, (long long)lead->node_offset);
+        uint64_t d = 0;
+        if (qm_engine_table_digest(engines[r], &d)) return 1;
+        if (d != d0) return fail("qm_stream_create_replicas: replica %d holds another table than replica 0", r);
+    }
+    qm_stream *s = new qm_stream();
+    for (int r = 0; r < n_engines; ++r) {
+        qm_stream *lane = nullptr;
+        if (qm_stream_create(engines[r], t_samples, fsmp, lsmp, available, n_nodes_total, steps_per_launch, depth,
+                             &lane)) {
+            qm_stream_destroy(s);
+            return 1;
+        }
+        s->lanes.push_back(lane);
+    }
+    *out = s;
+    return 0;
+}
+
 void qm_stream_destroy(qm_stream *s) {
     if (!s) return;
+    for (qm_stream *lane : s->lanes) qm_stream_destroy(lane);   // (a replicated stream: its lanes, orphaned or not)
     if (s->e) {                                         // (else: orphaned by qm_engine_destroy)
         DeviceGuard guard(s->e->device);
         release_stream(s);
@@ -253,6 +371,7 @@ void qm_stream_destroy(qm_stream *s) {
 
 int qm_stream_push(qm_stream *s, const double *log_onsets) {
     if (!log_onsets) return fail("qm_stream_push: NULL argument");
+    if (s && !s->lanes.empty()) return replicas_push(s, log_onsets);
     if (alive(s, "qm_stream_push")) return 1;
     DeviceGuard guard(s->e->device);
     // A full slot whose launch FAILED (the table changed under the stream, no memory, a refused step) is still
@@ -272,6 +391,7 @@ int qm_stream_push(qm_stream *s, const double *log_onsets) {
 }
 
 int qm_stream_flush(qm_stream *s) {
+    if (s && !s->lanes.empty()) return replicas_flush(s);
     if (alive(s, "qm_stream_flush")) return 1;
     if (s->fill_n == 0) return 0;
     DeviceGuard guard(s->e->device);
@@ -281,6 +401,7 @@ int qm_stream_flush(qm_stream *s) {
 int qm_stream_pop(qm_stream *s, int32_t n_steps, double *max_coa, double *max_norm_coa,
                   int64_t *max_coa_idx) {
     if (!max_coa || !max_norm_coa || !max_coa_idx) return fail("qm_stream_pop: NULL argument");
+    if (s && !s->lanes.empty()) return replicas_pop(s, n_steps, max_coa, max_norm_coa, max_coa_idx);
     if (alive(s, "qm_stream_pop")) return 1;
     if (n_steps < 0 || n_steps > s->launched_steps - s->popped_steps)
         return fail("qm_stream_pop: %d steps asked for, %lld launched and not yet popped (%d pushed into "
@@ -308,6 +429,14 @@ int qm_stream_pop(qm_stream *s, int32_t n_steps, double *max_coa, double *max_no
 }
 
 int qm_stream_pending(qm_stream *s, int32_t *launched_not_popped, int32_t *pushed_not_launched) {
+    if (s && !s->lanes.empty()) {
+        if (replicas_alive(s, "qm_stream_pending")) return 1;
+        int64_t waiting = 0;
+        const int filling = replicas_pending(s, &waiting);
+        if (launched_not_popped) *launched_not_popped = (int32_t)waiting;
+        if (pushed_not_launched) *pushed_not_launched = filling;
+        return 0;
+    }
     if (alive(s, "qm_stream_pending")) return 1;
     if (launched_not_popped) *launched_not_popped = (int32_t)(s->launched_steps - s->popped_steps);
     if (pushed_not_launched) *pushed_not_launched = s->fill_n;

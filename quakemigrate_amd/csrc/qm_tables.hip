@@ -3,7 +3,8 @@
 // tables the stacking kernels build from it on first use (round-2 window offsets, the paired layout,
 // the shift-reuse layout with its record stream, the screening sweep's offsets), tables parked under a
 // key while another availability's table is worked on (qm_engine_table_select), and on-device serving
-// of the int32 table from float64 travel-time grids (qm_engine_serve; lut.py:502-538, :102-140).
+// of the int32 table from float64 travel-time grids (qm_engine_serve; lut.py:502-538, :102-140), and the table's
+// device digest (qm_engine_table_digest).
 #define QM_TU_TABLES 1
 #include "qm_engine.hpp"
 
@@ -504,6 +505,47 @@ int ensure_screen_tables(qm_engine *e, const ScreenPlan &plan) {
     return 0;
 }
 
+// ---- the table's digest (qm_engine_table_digest) ---------------------------------------------------
+// sum over the flat elements i of mix(mix(i) + (uint32)v_i) mod 2^64, mix = the splitmix64 finalizer.  A sum
+// of wrapping integers does not depend on the order it is formed in: any grid of any shape gives the same
+// value, and NumPy restates it exactly (tests/test_replicas_gpu.py).
+namespace {
+
+__device__ __host__ inline uint64_t splitmix64_mix(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+__device__ inline uint64_t digest_term(uint64_t i, int32_t v) {
+    return splitmix64_mix(splitmix64_mix(i) + (uint64_t)(uint32_t)v);
+}
+
+// one pass over the table, 16 bytes per lane per load; per-lane sums, a wavefront reduction, one 64-bit
+// atomicAdd per workgroup into *sum (zeroed before the launch)
+__global__ __launch_bounds__(256) void table_digest_kernel(const int32_t *__restrict__ lut, size_t n,
+                                                           unsigned long long *sum) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n4 = n / 4;
+    const int4 *lut4 = reinterpret_cast<const int4 *>(lut);
+    uint64_t acc = 0;
+    for (size_t q = tid; q < n4; q += stride) {
+        const int4 v = lut4[q];
+        const uint64_t i = 4 * (uint64_t)q;
+        acc += digest_term(i, v.x) + digest_term(i + 1, v.y) + digest_term(i + 2, v.z) + digest_term(i + 3, v.w);
+    }
+    for (size_t i = 4 * n4 + tid; i < n; i += stride) acc += digest_term(i, lut[i]);
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    __shared__ uint64_t wave_sum[4];
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        atomicAdd(sum, (unsigned long long)(wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3]));
+}
+
+}  // namespace
+
 extern "C" {
 
 int qm_engine_load_lut(qm_engine *e, const int32_t *lut, int lut_on_device, int32_t nx,
@@ -803,6 +845,32 @@ int qm_engine_lut_download(qm_engine *e, int32_t *out) {
     DeviceGuard guard(e->device);
     QM_HIP(copy_back(out, e->d_lut.p, (size_t)e->n_nodes * e->g.n_rows * sizeof(int32_t), e->stream));
     QM_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+int qm_engine_table_digest(qm_engine *e, uint64_t *digest) {
+    if (!e || !digest) return fail("qm_engine_table_digest: NULL argument");
+    if (!e->have_lut) return fail("qm_engine_table_digest: no travel-time table resident");
+    if (e->digest_serial != e->serial) {
+        DeviceGuard guard(e->device);
+        const size_t n = (size_t)e->n_nodes * e->g.n_rows;
+        if (e->d_digest.ensure(1)) return 1;
+        QM_HIP(hipMemsetAsync(e->d_digest.p, 0, sizeof(unsigned long long), e->stream));
+        const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>(4 * (size_t)e->n_cu, (n / 4 + 255) / 256));
+        hipLaunchKernelGGL(table_digest_kernel, dim3(blocks), dim3(256), 0, e->stream, e->d_lut.p, n, e->d_digest.p);
+        QM_HIP(hipGetLastError());
+        unsigned long long sum = 0;
+        QM_HIP(copy_back(&sum, e->d_digest.p, sizeof(sum), e->stream));
+        QM_HIP(hipStreamSynchronize(e->stream));
+        // the shape fields, folded in on the host in this order
+        uint64_t h = sum;
+        for (int64_t f : {(int64_t)e->g.nx, (int64_t)e->g.ny, (int64_t)e->g.nz, (int64_t)e->g.n_rows, e->node_offset})
+            h = splitmix64_mix(h + (uint64_t)f);
+        e->digest = h;
+        e->digest_serial = e->serial;
+        ++e->table_digests;
+    }
+    *digest = e->digest;
     return 0;
 }
 

@@ -116,11 +116,13 @@ class MigrationScan:
         ``run.stage`` of the reference (scan.py:641).
     scan_rate : int, optional
         Passed to ``event.mw_times`` in the locate stage (scan.py:646).
-    engine : quakemigrate_amd.core.Engine or quakemigrate_amd.core.EngineGroup, optional
+    engine : quakemigrate_amd.core.Engine, EngineGroup or EngineReplicas, optional
         Defaults to the process-wide engine (``lib.default_engine``: a group when ``$QM_HIP_DEVICES``
         lists several devices, else an engine on ``$QM_HIP_DEVICE``).  A group runs ``_compute``, the
         locate calls and ``continuous_compute`` (timestep by timestep, without the pipeline); it takes
-        neither ``device_serving`` nor ``screen=True``.
+        neither ``device_serving`` nor ``screen=True``.  Replicas run ``_compute`` and the locate calls
+        on their lead and ``continuous_compute`` as one pipeline over all of them (timesteps split
+        round-robin by launch); they take everything an Engine takes.
     threads : int
         Accepted for signature compatibility; the GPU engine ignores it.
     device_serving : bool
@@ -395,7 +397,9 @@ class MigrationScan:
                                  f"{n_onsets}:{eng.n_rows}")
             if onsets.size < t_samples - lsmp:
                 raise ValueError("Data array smaller than coalescence array.")
-            if isinstance(eng, lib.EngineGroup):         # (a group: one timestep after the other, no pipeline)
+            # (an Engine or EngineReplicas goes through the native pipeline below -- over every replica for the
+            # latter; a group: one timestep after the other, no pipeline)
+            if isinstance(eng, lib.EngineGroup):
                 a, b, c = eng.detect(onsets, fsmp, lsmp, avail)
                 sink.append(_shift(data.starttime, self.pre_pad), a, b, self.lut.index2coord(c, unravel=True), ucf)
                 rows.append(dict(onset_data.availability))

@@ -28,12 +28,15 @@ class StreamingDetector:
     """
     Parameters
     ----------
-    engine : quakemigrate_amd.core.Engine with the travel-time table resident.
+    engine : quakemigrate_amd.core.Engine with the travel-time table resident, or a
+        quakemigrate_amd.core.EngineReplicas whose replicas all hold it: then ONE pipeline runs over
+        every replica (``qm_stream_create_replicas``: launch j on replica j mod n, results in push
+        order, bit for bit an Engine's).
     n_rows, t_samples : shape of every onset window (rows x samples, float64, already
         ``log(clip(., 0.01))``).
     fsmp, lsmp, available : as in ``Engine.detect``.
     n_nodes_total : node count of the full grid (normalisation).
-    depth : slots of the ring = launches that may be in flight or un-popped (>= 2).
+    depth : slots of the ring = launches that may be in flight or un-popped (>= 2); per replica.
     steps_per_launch : timesteps stacked by ONE launch (``qm_engine_detect_batch``).  Timesteps are
         independent given their onsets, so K of them can share a launch: on the grids the
         reference's examples use (1e4 - 3e5 nodes) one timestep is a few workgroup rounds and a
@@ -57,8 +60,14 @@ class StreamingDetector:
         self.k = max(1, int(steps_per_launch))
         total = engine.n_nodes if n_nodes_total is None else int(n_nodes_total)
         h = ctypes.c_void_p()
-        _lib._check(_qm.qm_stream_create(engine._h, self.t_samples, self.fsmp, self.lsmp,
-                                         self.available, total, self.k, self.depth, ctypes.byref(h)))
+        if isinstance(engine, _lib.EngineReplicas):
+            handles = (ctypes.c_void_p * len(engine.replicas))(*[r._h.value for r in engine.replicas])
+            _lib._check(_qm.qm_stream_create_replicas(handles, len(engine.replicas), self.t_samples, self.fsmp,
+                                                      self.lsmp, self.available, total, self.k, self.depth,
+                                                      ctypes.byref(h)))
+        else:
+            _lib._check(_qm.qm_stream_create(engine._h, self.t_samples, self.fsmp, self.lsmp,
+                                             self.available, total, self.k, self.depth, ctypes.byref(h)))
         self._h = h
         import weakref
 
