@@ -262,45 +262,47 @@ int auto_groups(const qm_engine *e, int ntiles, int units, int blocks_per_cu, in
 }
 
 // Stack samples [sample0, sample0+n_chunk) of the scan.  Partials (if want_scan) land in
-// e->d_pmax/d_pidx/d_psum as [*n_sets][n_chunk].
-int run_stack(qm_engine *e, const double *d_onsets, int T, int fsmp, int n_samples,
-              int available, int sample0, int n_chunk, double *volume, int64_t vol_stride,
-              int accumulate, bool want_scan, int *n_sets, bool marginal, int m0, int m1,
-              const int32_t *run_if, int n_steps, int64_t step_stride, bool *batched) {
-    // n_steps > 1: that many timesteps in ONE launch (fused detect only) -- onset arrays step_stride
-    // doubles apart, partial sets [*n_sets][n_steps * n_chunk].  Not every kernel can (row blocks, the
-    // 12-wave shape): *batched = false then, nothing is launched and the caller goes step by step.
-    // marginal: per-tile sums over the samples [m0, m1) land in e->d_marg as [*n_tiles][n_nodes]
-    // (e->marg_tiles: the kernels differ in their tile length)
+// e->d_pmax/d_pidx/d_psum as [sets][n_steps * n_chunk].
+StackResult run_stack(qm_engine *e, const StackLaunch &s) {
+    // n_steps > 1: that many timesteps in ONE launch (fused detect only).  Not every kernel can: batched =
+    // false then.  marginal: per-tile sums over the samples [first, end) land in e->d_marg as
+    // [e->marg_tiles][n_nodes] (the kernels differ in their tile length)
+    const auto *vol = std::get_if<StackLaunch::Volume>(&s.kind);
+    const auto *marg = std::get_if<StackLaunch::Marginal>(&s.kind);
+    double *const volume = vol ? vol->p : nullptr;
+    const int64_t vol_stride = vol ? vol->stride : 0;
+    const int accumulate = vol ? vol->accumulate : 0;
+    const bool marginal = marg != nullptr, want_scan = s.want_scan;
+    const int n_chunk = s.n_chunk;
     const int J = run_j(e, n_chunk);
     if (plan_wide(e, J)) return 1;
     const int KT = qm::kWave * J;
     qm::StackArgs a{};
     a.g = e->g;
-    a.onsets = d_onsets;
+    a.onsets = s.onsets;
     a.lut = e->d_lut.p;
     a.rel = e->d_rel.p;
     a.brick_meta = e->d_bmeta.p;
     a.brick_total = e->d_btotal.p;
-    a.T = T;
-    a.fsmp = fsmp;
-    a.n_samples = n_samples;
-    a.sample0 = sample0;
+    a.T = s.T;
+    a.fsmp = s.fsmp;
+    a.n_samples = s.n_samples;
+    a.sample0 = s.sample0;
     a.n_chunk = n_chunk;
     a.ntiles = (n_chunk + KT - 1) / KT;
     a.cap_doubles = lds_cap_doubles(e);
     // coa = exp(stack/available) = 2^(stack * log2(e)/available)
-    a.z_scale = 1.4426950408889634074 / (double)available;
+    a.z_scale = 1.4426950408889634074 / (double)s.available;
     a.volume = volume;
     a.vol_stride = vol_stride;
     a.accumulate = accumulate;
     a.want_scan = want_scan ? 1 : 0;
     a.set0 = 0;
     a.marginal = nullptr;
-    a.m0 = m0;
-    a.m1 = m1;
+    a.m0 = marg ? marg->first : 0;
+    a.m1 = marg ? marg->end : 0;
     a.n_nodes = e->n_nodes;
-    a.run_if = run_if;
+    a.run_if = s.run_if;
 
     // ---- the shift-reuse kernel (qm_shift.hpp): the fused detect's default where the table fits
     bool shift = shift_wanted(e, n_chunk, !accumulate && (volume || marginal || want_scan),
@@ -370,13 +372,13 @@ int run_stack(qm_engine *e, const double *d_onsets, int T, int fsmp, int n_sampl
         a.ntiles = (n_chunk + PKT - 1) / PKT;
         a.cap_doubles = kPairLdsBytes / 8;
     }
-    if (n_steps > 1) {
-        const bool ok = !volume && !marginal && !accumulate && run_if == nullptr && want_scan &&
-                        (!shift || (L->nblk == 1 && L->nw != qm::kShiftWaves3 && !(L->wide && L->direct)));
-        if (batched) *batched = ok;
-        if (!ok) return batched ? 0 : fail("run_stack: this launch cannot hold several timesteps");
-        a.n_steps = n_steps;
-        a.step_stride = step_stride;
+    StackResult r;
+    if (s.n_steps > 1) {
+        r.batched = !volume && !marginal && !accumulate && s.run_if == nullptr && want_scan &&
+                    (!shift || (L->nblk == 1 && L->nw != qm::kShiftWaves3 && !(L->wide && L->direct)));
+        if (!r.batched) return r;
+        a.n_steps = s.n_steps;
+        a.step_stride = s.step_stride;
     }
     const int steps = a.n_steps > 1 ? a.n_steps : 1;
     a.part_stride = (int64_t)steps * n_chunk;
@@ -461,7 +463,7 @@ int run_stack(qm_engine *e, const double *d_onsets, int T, int fsmp, int n_sampl
     a.part_max = e->d_pmax.p;
     a.part_idx = e->d_pidx.p;
     a.part_sum = e->d_psum.p;
-    *n_sets = sets;
+    r.sets = sets;
     e->last_sets = sets;
     e->last_scan_n = steps * n_chunk;
     e->last_g = a.g;
@@ -474,7 +476,7 @@ int run_stack(qm_engine *e, const double *d_onsets, int T, int fsmp, int n_sampl
 
     // a conditional launch (the fallback of a screened step) is not part of the timing log: it
     // returns at once unless the step has to be redone
-    const bool logged = run_if == nullptr;
+    const bool logged = s.run_if == nullptr;
     hipEvent_t ev_begin = e->ev0, ev_end = e->ev1;
     if (e->log_timing && logged) {
         if (e->ev_used + 2 > e->ev_log.size()) {
@@ -514,64 +516,110 @@ int run_stack(qm_engine *e, const double *d_onsets, int T, int fsmp, int n_sampl
         QM_HIP(hipEventRecord(ev_end, e->stream));
         e->timed = !e->log_timing;
     }
-    return 0;
+    return r;
 }
 
-int combine(qm_engine *e, const double *pmax, const int64_t *pidx, const double *psum, int sets,
-            int n, int mode, int64_t node_offset, int64_t n_nodes_total, double *o_max,
-            double *o_second, int64_t *o_idx, const int32_t *run_if, int64_t set_stride) {
+SetView engine_sets(const qm_engine *e, int n_sets, int n) {
+    return {e->d_pmax.p, e->d_pidx.p, e->d_psum.p, n_sets, n, n};
+}
+
+SetView packed_sets(const double *d_packed, int n_sets, int n) {
+    return {d_packed, reinterpret_cast<const int64_t *>(d_packed + n), d_packed + 2 * (int64_t)n, n_sets, n,
+            3 * (int64_t)n};
+}
+
+OutSeries packed_set(double *d_packed, int n) {
+    return {d_packed, d_packed + 2 * (int64_t)n, reinterpret_cast<int64_t *>(d_packed + n)};
+}
+
+int combine(qm_engine *e, const SetView &in, CombineMode mode, int64_t node_offset, int64_t n_nodes_total,
+            const OutSeries &out, const int32_t *run_if) {
     // (tie_rule = 1 with a row of maxima per brick: the fold of the workgroups' own sets also leaves the largest z)
     double *o_z = nullptr;
-    if (e->cfg_tie_rule && e->last_brick_rows > 0 && pmax == e->d_pmax.p && run_if == nullptr) {
-        if (e->d_tie_zext.ensure(n)) return 1;
+    if (e->cfg_tie_rule && e->last_brick_rows > 0 && in.max == e->d_pmax.p && run_if == nullptr) {
+        if (e->d_tie_zext.ensure(in.n)) return 1;
         o_z = e->d_tie_zext.p;
     }
-    hipLaunchKernelGGL(qm::combine_kernel, dim3((n + qm::kWave - 1) / qm::kWave),
+    hipLaunchKernelGGL(qm::combine_kernel, dim3((in.n + qm::kWave - 1) / qm::kWave),
                        dim3(qm::kCombineWaves * qm::kWave), 0,
-                       e->stream, pmax, pidx, psum, sets, n, set_stride > 0 ? set_stride : (int64_t)n,
-                       mode, node_offset, (double)n_nodes_total, o_max, o_second, o_idx, run_if, o_z);
+                       e->stream, in.max, in.idx, in.sum, in.n_sets, in.n, in.stride, (int)mode, node_offset,
+                       (double)n_nodes_total, out.max, out.second, out.idx, run_if, o_z);
     QM_HIP(hipGetLastError());
     return 0;
 }
 
+StackResult stack_fold(qm_engine *e, const StackLaunch &s, CombineMode mode, int64_t n_nodes_total,
+                       const OutSeries &out) {
+    const StackResult r = run_stack(e, s);
+    if (r.rc || !r.batched) return r;
+    if (const auto *m = std::get_if<StackLaunch::Marginal>(&s.kind)) {
+        hipLaunchKernelGGL(qm::marginal_reduce_kernel, dim3((unsigned)((e->n_nodes + 255) / 256)), dim3(256), 0,
+                           e->stream, e->d_marg.p, e->marg_tiles, e->n_nodes, m->map);
+        QM_HIP(hipGetLastError());
+    }
+    if (!s.want_scan) return r;
+    const OutSeries o = out.at(s.sample0);
+    if (combine(e, engine_sets(e, r.sets, s.n_chunk * s.n_steps), mode, e->node_offset, n_nodes_total, o,
+                s.run_if))
+        return 1;
+    // (the reference's rule on near-ties: final series of this engine's own nodes only -- the partial
+    // sets of a sharded detect leave the engine before anyone knows the global maximum -- and not on the
+    // screened step's fallback)
+    if (mode == kCombineFinal && e->cfg_tie_rule && s.run_if == nullptr && refine_ties(e, s, o.idx, nullptr, nullptr))
+        return 1;
+    return r;
+}
+
 // Detect-type stacking of the whole scan plus the combine of its partial sets into the three
-// output series (mode as combine_kernel).  With screening: the screened result is combined first;
+// output series.  With screening: the screened result is combined first;
 // then the float64 kernel and its combine are enqueued conditionally on the step's flag word, so a
 // step that could not be screened (too many candidate cells, non-finite onsets) is redone on the
 // device without the host ever waiting -- those launches return at once otherwise.
-int detect_core(qm_engine *e, const double *d_on, int T, int fsmp, int ns, int available, int mode,
-                int64_t n_nodes_total, double *o_max, double *o_second, int64_t *o_idx) {
+int detect_core(qm_engine *e, const double *d_on, int T, int fsmp, int ns, int available, CombineMode mode,
+                int64_t n_nodes_total, const OutSeries &out) {
     int sets = 0;
     bool screened = false;
     if (run_screen(e, d_on, T, fsmp, ns, available, &sets, &screened)) return 1;
-    const int32_t *run_if = nullptr;
+    StackLaunch s(d_on, T, fsmp, ns, available);
     if (screened) {
-        if (combine(e, e->d_pmax.p, e->d_pidx.p, e->d_psum.p, sets, ns, mode, e->node_offset,
-                    n_nodes_total, o_max, o_second, o_idx))
-            return 1;
-        run_if = e->d_flags.p;
+        if (combine(e, engine_sets(e, sets, ns), mode, e->node_offset, n_nodes_total, out, nullptr)) return 1;
+        s.run_if = e->d_flags.p;
     }
-    if (run_stack(e, d_on, T, fsmp, ns, available, 0, ns, nullptr, 0, 0, true, &sets, false, 0, 0,
-                  run_if))
-        return 1;
+    if (stack_fold(e, s, mode, n_nodes_total, out).rc) return 1;
     e->last_sets_own = !screened;                       // (d_pmax holds the float64 launch's sets for certain)
-    if (combine(e, e->d_pmax.p, e->d_pidx.p, e->d_psum.p, sets, ns, mode, e->node_offset,
-                n_nodes_total, o_max, o_second, o_idx, run_if))
-        return 1;
-    // (the reference's rule on near-ties: final series of this engine's own nodes only -- the partial
-    // sets of a sharded detect leave the engine before anyone knows the global maximum)
-    if (e->cfg_tie_rule && mode == 1 && !screened)
-        return refine_ties(e, d_on, T, fsmp, available, 0, ns, sets, o_idx);
     return 0;
 }
 
-// tie_rule = 1 (qm_ties.hpp): the index series of the launch whose partial sets lie in d_pmax, refined.
-// n_steps > 1: the launch held several timesteps (sets [sets][n_steps * n_chunk], step k's onsets step_stride
-// doubles behind step 0's).  zext / o_key: a sharded detect's engine -- its sets against the grid's maxima, the
-// outcome exported (tie_export_kernel) instead of applied.
-int refine_ties(qm_engine *e, const double *d_on, int T, int fsmp, int available, int sample0,
-                int n_chunk, int sets, int64_t *o_idx, int n_steps, int64_t step_stride,
-                const double *zext, unsigned long long *o_key) {
+int scan_fold(qm_engine *e, const double *vol, int64_t stride, int ns, int64_t n_nodes, int64_t node0,
+              CombineMode mode, const OutSeries &out) {
+    // a workgroup = up to 16 adjacent tiles (one wavefront each); ~cfg_scan_waves wavefronts
+    // per CU in total; at least 256 nodes per chunk
+    const int tiles = (ns + qm::kWave - 1) / qm::kWave;
+    const int groups = (tiles + qm::kScanWaves - 1) / qm::kScanWaves;
+    const int waves = (tiles + groups - 1) / groups;          // per workgroup, balanced
+    const int xgroups = (tiles + waves - 1) / waves;
+    int64_t sets = std::max<int64_t>(1, ((int64_t)e->cfg_scan_waves * e->n_cu + tiles - 1) / tiles);
+    sets = std::min<int64_t>(sets, std::max<int64_t>(1, n_nodes / 256));
+    sets = std::min<int64_t>(sets, 65535);
+    const int64_t per = (n_nodes + sets - 1) / sets;
+    sets = (n_nodes + per - 1) / per;
+    const size_t need = (size_t)sets * ns;
+    if (e->d_pmax.ensure(need) || e->d_psum.ensure(need) || e->d_pidx.ensure(need)) return 1;
+    hipLaunchKernelGGL(qm::scan_volume_kernel, dim3(xgroups, (unsigned)sets), dim3(waves * qm::kWave), 0, e->stream,
+                       vol, stride, ns, n_nodes, per, e->d_pmax.p, e->d_pidx.p, e->d_psum.p);
+    QM_HIP(hipGetLastError());
+    // (a partial has no normalisation: n_nodes_total only matters for the values' series)
+    return combine(e, engine_sets(e, (int)sets, ns), mode, node0, mode == kCombinePartial ? 0 : n_nodes, out,
+                   nullptr);
+}
+
+// tie_rule = 1 (qm_ties.hpp): the index series o_idx of `launch`, whose partial sets lie in d_pmax (as the
+// last_* fields describe them), refined.  n_steps > 1: the launch held several timesteps.  zext / o_key:
+// a sharded detect's engine -- its sets against the grid's maxima, the outcome exported (tie_export_kernel)
+// instead of applied.
+int refine_ties(qm_engine *e, const StackLaunch &launch, int64_t *o_idx, const double *zext,
+                unsigned long long *o_key) {
+    const int n_steps = launch.n_steps, n_chunk = launch.n_chunk, sets = e->last_sets;
     const int n = n_chunk * std::max(1, n_steps);
     if (n > INT32_MAX / (2 * qm::kTieMaxSets)) return fail("tie_rule: %d samples in one launch are too many", n);
     const int max_pairs = qm::kTieMaxSets * n;
@@ -602,13 +650,13 @@ int refine_ties(qm_engine *e, const double *d_on, int T, int fsmp, int available
     e->tie_counts_pending = true;
     qm::TieArgs a{};
     a.g = e->last_g;
-    a.onsets = d_on;
+    a.onsets = launch.onsets;
     a.lut = e->d_lut.p;
-    a.T = T; a.fsmp = fsmp; a.sample0 = sample0; a.n_chunk = n;
+    a.T = launch.T; a.fsmp = launch.fsmp; a.sample0 = launch.sample0; a.n_chunk = n;
     a.ns_step = n_steps > 1 ? n_chunk : 0;
-    a.step_stride = step_stride;
-    a.z_scale = 1.4426950408889634074 / (double)available;
-    a.recip = 1.0 / (double)available;
+    a.step_stride = launch.step_stride;
+    a.z_scale = 1.4426950408889634074 / (double)launch.available;
+    a.recip = 1.0 / (double)launch.available;
     a.groups_lds = e->last_groups_lds;
     a.groups_direct = e->last_groups_direct;
     a.brick_rows = rows;
@@ -636,7 +684,7 @@ int refine_ties(qm_engine *e, const double *d_on, int T, int fsmp, int available
                            e->node_offset, o_key, o_idx);
     else
         hipLaunchKernelGGL(qm::tie_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, s,
-                           (const int32_t *)e->d_tie_imin.p, n, e->node_offset, o_idx + sample0);
+                           (const int32_t *)e->d_tie_imin.p, n, e->node_offset, o_idx);
     QM_HIP(hipGetLastError());
     return 0;
 }
@@ -668,27 +716,38 @@ int stage_onsets(qm_engine *e, const double *onsets, int on_device, int T, const
     return 0;
 }
 
-int stage_out(qm_engine *e, int n, int out_on_device, double *max_coa, double *max_norm,
-              int64_t *idx, OutStage *st) {
+int stage_out(qm_engine *e, int n, int out_on_device, const OutSeries &user, OutSeries *st) {
     if (out_on_device) {
-        *st = OutStage{max_coa, max_norm, idx};
+        *st = user;
         return 0;
     }
     // (the three series back to back in ONE buffer: they travel to the host as one copy, fetch_out)
     if (e->d_out_a.ensure(3 * (size_t)n)) return 1;
-    *st = OutStage{e->d_out_a.p, e->d_out_a.p + n, reinterpret_cast<int64_t *>(e->d_out_a.p + 2 * (size_t)n)};
+    *st = OutSeries{e->d_out_a.p, e->d_out_a.p + n, reinterpret_cast<int64_t *>(e->d_out_a.p + 2 * (size_t)n)};
     return 0;
 }
 
-int fetch_out(qm_engine *e, int n, int out_on_device, const OutStage &st, double *max_coa,
-              double *max_norm, int64_t *idx) {
+int fetch_out(qm_engine *e, int n, int out_on_device, const OutSeries &st, const OutSeries &user) {
     if (out_on_device) return 0;
     // one DMA of the packed [3][n] buffer, three CPU copies out of the pinned half (round 4: three
     // DMAs with a wait each -- two round trips more per host-array call)
-    void *dst[3] = {max_coa, max_norm, idx};
-    QM_HIP(copy_back_pieces(dst, st.a, 3, (size_t)n * sizeof(double), e->stream));
+    void *dst[3] = {user.max, user.second, user.idx};
+    QM_HIP(copy_back_pieces(dst, st.max, 3, (size_t)n * sizeof(double), e->stream));
     return 0;
 }
+
+namespace {
+
+// qm_engine_finalize / _finalize_packed: the final series of partial sets, on host or device
+int finalize_sets(qm_engine *e, const SetView &in, int64_t n_nodes_total, const OutSeries &user, int out_on_device) {
+    DeviceGuard guard(e->device);
+    OutSeries st;
+    if (stage_out(e, in.n, out_on_device, user, &st) || combine(e, in, kCombineFinal, 0, n_nodes_total, st, nullptr))
+        return 1;
+    return fetch_out(e, in.n, out_on_device, st, user);
+}
+
+}  // namespace
 
 // ------------------------------------------------------------------------------- C ABI
 extern "C" {
@@ -973,10 +1032,11 @@ int qm_engine_detect_partial(qm_engine *e, const double *log_onsets, int onsets_
         return fail("qm_engine_detect_partial: NULL argument");
     DeviceGuard guard(e->device);
     int ns = 0;
-    if (check_step(e, T, fsmp, lsmp, available, &ns)) return 1;
     const double *d_on = nullptr;
-    if (stage_onsets(e, log_onsets, onsets_on_device, T, &d_on)) return 1;
-    return detect_core(e, d_on, T, fsmp, ns, available, 0, 0, d_part_max, d_part_sum, d_part_idx);
+    if (check_step(e, T, fsmp, lsmp, available, &ns) || stage_onsets(e, log_onsets, onsets_on_device, T, &d_on))
+        return 1;
+    return detect_core(e, d_on, T, fsmp, ns, available, kCombinePartial, 0,
+                       OutSeries{d_part_max, d_part_sum, d_part_idx});
 }
 
 int qm_engine_finalize(qm_engine *e, const double *d_part_max, const int64_t *d_part_idx,
@@ -987,13 +1047,8 @@ int qm_engine_finalize(qm_engine *e, const double *d_part_max, const int64_t *d_
         !max_coa_idx)
         return fail("qm_engine_finalize: NULL argument");
     if (n_sets < 1 || n_samples < 1) return fail("qm_engine_finalize: empty input");
-    DeviceGuard guard(e->device);
-    OutStage st;
-    if (stage_out(e, n_samples, out_on_device, max_coa, max_norm_coa, max_coa_idx, &st)) return 1;
-    if (combine(e, d_part_max, d_part_idx, d_part_sum, n_sets, n_samples, 1, 0, n_nodes_total,
-                st.a, st.b, st.i))
-        return 1;
-    return fetch_out(e, n_samples, out_on_device, st, max_coa, max_norm_coa, max_coa_idx);
+    return finalize_sets(e, SetView{d_part_max, d_part_idx, d_part_sum, n_sets, n_samples, n_samples},
+                         n_nodes_total, OutSeries{max_coa, max_norm_coa, max_coa_idx}, out_on_device);
 }
 
 int qm_engine_finalize_packed(qm_engine *e, const double *d_packed, int32_t n_sets,
@@ -1002,15 +1057,8 @@ int qm_engine_finalize_packed(qm_engine *e, const double *d_packed, int32_t n_se
     if (!e || !d_packed || !max_coa || !max_norm_coa || !max_coa_idx)
         return fail("qm_engine_finalize_packed: NULL argument");
     if (n_sets < 1 || n_samples < 1) return fail("qm_engine_finalize_packed: empty input");
-    DeviceGuard guard(e->device);
-    OutStage st;
-    if (stage_out(e, n_samples, out_on_device, max_coa, max_norm_coa, max_coa_idx, &st)) return 1;
-    // set s = rows [s][0] (maxima), [s][1] (indices, int64 bits), [s][2] (sums) of [n_sets][3][n]
-    if (combine(e, d_packed, reinterpret_cast<const int64_t *>(d_packed + n_samples),
-                d_packed + 2 * (int64_t)n_samples, n_sets, n_samples, 1, 0, n_nodes_total, st.a,
-                st.b, st.i, nullptr, 3 * (int64_t)n_samples))
-        return 1;
-    return fetch_out(e, n_samples, out_on_device, st, max_coa, max_norm_coa, max_coa_idx);
+    return finalize_sets(e, packed_sets(d_packed, n_sets, n_samples), n_nodes_total,
+                         OutSeries{max_coa, max_norm_coa, max_coa_idx}, out_on_device);
 }
 
 int qm_engine_detect(qm_engine *e, const double *log_onsets, int onsets_on_device, int32_t T,
@@ -1021,13 +1069,14 @@ int qm_engine_detect(qm_engine *e, const double *log_onsets, int onsets_on_devic
         return fail("qm_engine_detect: NULL argument");
     DeviceGuard guard(e->device);
     int ns = 0;
-    if (check_step(e, T, fsmp, lsmp, available, &ns)) return 1;
     const double *d_on = nullptr;
-    if (stage_onsets(e, log_onsets, onsets_on_device, T, &d_on)) return 1;
-    OutStage st;
-    if (stage_out(e, ns, out_on_device, max_coa, max_norm_coa, max_coa_idx, &st)) return 1;
-    if (detect_core(e, d_on, T, fsmp, ns, available, 1, n_nodes_total, st.a, st.b, st.i)) return 1;
-    return fetch_out(e, ns, out_on_device, st, max_coa, max_norm_coa, max_coa_idx);
+    const OutSeries user{max_coa, max_norm_coa, max_coa_idx};
+    OutSeries st;
+    if (check_step(e, T, fsmp, lsmp, available, &ns) || stage_onsets(e, log_onsets, onsets_on_device, T, &d_on) ||
+        stage_out(e, ns, out_on_device, user, &st))
+        return 1;
+    if (detect_core(e, d_on, T, fsmp, ns, available, kCombineFinal, n_nodes_total, st)) return 1;
+    return fetch_out(e, ns, out_on_device, st, user);
 }
 
 int qm_engine_detect_batch(qm_engine *e, const double *log_onsets, int onsets_on_device,
@@ -1049,30 +1098,27 @@ int qm_engine_detect_batch(qm_engine *e, const double *log_onsets, int onsets_on
         d_on = e->d_onsets.p;
     }
     const int n_all = n_steps * ns;
-    OutStage st;
-    if (stage_out(e, n_all, out_on_device, max_coa, max_norm_coa, max_coa_idx, &st)) return 1;
+    const OutSeries user{max_coa, max_norm_coa, max_coa_idx};
+    OutSeries st;
+    if (stage_out(e, n_all, out_on_device, user, &st)) return 1;
     bool batched = false;
-    int sets = 0;
     if (n_steps > 1 && !e->cfg_screen) {
-        if (run_stack(e, d_on, T, fsmp, ns, available, 0, ns, nullptr, 0, 0, true, &sets, false, 0, 0,
-                      nullptr, n_steps, (int64_t)per_step, &batched))
-            return 1;
-        // partial sets [sets][n_steps * ns] -> the steps' series back to back
-        if (batched && combine(e, e->d_pmax.p, e->d_pidx.p, e->d_psum.p, sets, n_all, 1, e->node_offset,
-                               n_nodes_total, st.a, st.b, st.i))
-            return 1;
-        // (tie_rule = 1 keeps the step axis: the refinement reads the launch's sets with sample t = step * ns + ...)
-        if (batched && e->cfg_tie_rule &&
-            refine_ties(e, d_on, T, fsmp, available, 0, ns, sets, st.i, n_steps, (int64_t)per_step))
-            return 1;
+        // partial sets [sets][n_steps * ns] -> the steps' series back to back (tie_rule = 1 keeps the step
+        // axis: the refinement reads the launch's sets with sample t = step * ns + ...)
+        StackLaunch s(d_on, T, fsmp, ns, available);
+        s.n_steps = n_steps;
+        s.step_stride = (int64_t)per_step;
+        const StackResult r = stack_fold(e, s, kCombineFinal, n_nodes_total, st);
+        if (r.rc) return 1;
+        batched = r.batched;
     }
     if (!batched)                                       // step by step (a single step, the screened
         for (int k = 0; k < n_steps; ++k)               // detect, kernels without the step axis)
-            if (detect_core(e, d_on + (size_t)k * per_step, T, fsmp, ns, available, 1, n_nodes_total,
-                            st.a + (size_t)k * ns, st.b + (size_t)k * ns, st.i + (size_t)k * ns))
+            if (detect_core(e, d_on + (size_t)k * per_step, T, fsmp, ns, available, kCombineFinal, n_nodes_total,
+                            st.at((int64_t)k * ns)))
                 return 1;
     e->last_batched = batched ? n_steps : 1;
-    return fetch_out(e, n_all, out_on_device, st, max_coa, max_norm_coa, max_coa_idx);
+    return fetch_out(e, n_all, out_on_device, st, user);
 }
 
 // tie_rule = 1 on a sharded detect (qm_ties.hpp, tie_export_kernel / tie_fold_kernel): after the exchange of
@@ -1097,9 +1143,8 @@ int qm_engine_tie_partial(qm_engine *e, const double *log_onsets, int onsets_on_
     hipLaunchKernelGGL(qm::tie_zmax_kernel, dim3((ns + 255) / 256), dim3(256), 0, e->stream, d_packed, (int)n_sets,
                        ns, 3 * (int64_t)ns, e->d_tie_zgrid.p);
     QM_HIP(hipGetLastError());
-    return refine_ties(e, d_on, T, fsmp, available, 0, ns, e->last_sets,
-                       reinterpret_cast<int64_t *>(d_tie_packed + ns), 1, 0, e->d_tie_zgrid.p,
-                       reinterpret_cast<unsigned long long *>(d_tie_packed));
+    return refine_ties(e, StackLaunch(d_on, T, fsmp, ns, available), reinterpret_cast<int64_t *>(d_tie_packed + ns),
+                       e->d_tie_zgrid.p, reinterpret_cast<unsigned long long *>(d_tie_packed));
 }
 
 // ... and folds the gathered outcomes [n_sets][2][n_samples] into the index series (device, in place).
@@ -1124,24 +1169,18 @@ int qm_engine_migrate(qm_engine *e, const double *log_onsets, int onsets_on_devi
     if (want_scan && (!max_norm_coa || !max_coa_idx))
         return fail("qm_engine_migrate: all three scan outputs or none");
     DeviceGuard guard(e->device);
-    int ns = 0, sets = 0;
-    if (check_step(e, T, fsmp, lsmp, available, &ns)) return 1;
+    int ns = 0;
     const double *d_on = nullptr;
-    if (stage_onsets(e, log_onsets, onsets_on_device, T, &d_on)) return 1;
-    OutStage st{nullptr, nullptr, nullptr};
-    if (want_scan &&
-        stage_out(e, ns, out_on_device, max_coa, max_norm_coa, max_coa_idx, &st))
+    const OutSeries user{max_coa, max_norm_coa, max_coa_idx};
+    OutSeries st;
+    if (check_step(e, T, fsmp, lsmp, available, &ns) || stage_onsets(e, log_onsets, onsets_on_device, T, &d_on) ||
+        (want_scan && stage_out(e, ns, out_on_device, user, &st)))
         return 1;
-
+    StackLaunch s(d_on, T, fsmp, ns, available);
+    s.want_scan = want_scan;
     if (map_on_device) {
-        if (run_stack(e, d_on, T, fsmp, ns, available, 0, ns, map4d, ns, accumulate, want_scan,
-                      &sets))
-            return 1;
-        if (want_scan && combine(e, e->d_pmax.p, e->d_pidx.p, e->d_psum.p, sets, ns, 1,
-                                 e->node_offset, n_nodes_total, st.a, st.b, st.i))
-            return 1;
-        if (want_scan && e->cfg_tie_rule && refine_ties(e, d_on, T, fsmp, available, 0, ns, sets, st.i))
-            return 1;
+        s.kind = StackLaunch::Volume{map4d, ns, accumulate};
+        if (stack_fold(e, s, kCombineFinal, n_nodes_total, st).rc) return 1;
     } else {
         // host volume: stream it through a device chunk buffer, time-chunk by time-chunk
         const int KT = qm::kWave * eff_j(e);
@@ -1155,21 +1194,16 @@ int qm_engine_migrate(qm_engine *e, const double *log_onsets, int onsets_on_devi
                 QM_HIP(copy_in_2d(e->d_chunk.p, nk * sizeof(double), map4d + k0,
                                         (size_t)ns * sizeof(double), nk * sizeof(double),
                                         e->n_nodes, e->stream));
-            if (run_stack(e, d_on, T, fsmp, ns, available, k0, nk, e->d_chunk.p, nk, accumulate,
-                          want_scan, &sets))
-                return 1;
-            if (want_scan && combine(e, e->d_pmax.p, e->d_pidx.p, e->d_psum.p, sets, nk, 1,
-                                     e->node_offset, n_nodes_total, st.a + k0, st.b + k0,
-                                     st.i + k0))
-                return 1;
-            if (want_scan && e->cfg_tie_rule && refine_ties(e, d_on, T, fsmp, available, k0, nk, sets, st.i))
-                return 1;
+            s.sample0 = k0;
+            s.n_chunk = nk;
+            s.kind = StackLaunch::Volume{e->d_chunk.p, nk, accumulate};
+            if (stack_fold(e, s, kCombineFinal, n_nodes_total, st).rc) return 1;
             QM_HIP(copy_back_2d(map4d + k0, (size_t)ns * sizeof(double), e->d_chunk.p,
                                     nk * sizeof(double), nk * sizeof(double), e->n_nodes, e->stream));
             QM_HIP(hipStreamSynchronize(e->stream));
         }
     }
-    if (want_scan) return fetch_out(e, ns, out_on_device, st, max_coa, max_norm_coa, max_coa_idx);
+    if (want_scan) return fetch_out(e, ns, out_on_device, st, user);
     if (!map_on_device) QM_HIP(hipStreamSynchronize(e->stream));
     return 0;
 }
@@ -1184,37 +1218,31 @@ int qm_engine_marginal(qm_engine *e, const double *log_onsets, int onsets_on_dev
     if (want_scan && (!max_norm_coa || !max_coa_idx))
         return fail("qm_engine_marginal: all three scan outputs or none");
     DeviceGuard guard(e->device);
-    int ns = 0, sets = 0;
+    int ns = 0;
     if (check_step(e, T, fsmp, lsmp, available, &ns)) return 1;
     if (first_sample < 0 || end_sample > ns || first_sample >= end_sample)
         return fail("marginal window [%d, %d) outside the %d scanned samples", first_sample,
                     end_sample, ns);
     const double *d_on = nullptr;
-    if (stage_onsets(e, log_onsets, onsets_on_device, T, &d_on)) return 1;
-    OutStage st{nullptr, nullptr, nullptr};
-    if (want_scan && stage_out(e, ns, out_on_device, max_coa, max_norm_coa, max_coa_idx, &st))
+    const OutSeries user{max_coa, max_norm_coa, max_coa_idx};
+    OutSeries st;
+    if (stage_onsets(e, log_onsets, onsets_on_device, T, &d_on) ||
+        (want_scan && stage_out(e, ns, out_on_device, user, &st)))
         return 1;
     double *d_map = coa_map;
     if (!map_on_device) {
         if (e->d_marg_out.ensure((size_t)e->n_nodes)) return 1;
         d_map = e->d_marg_out.p;
     }
-    if (run_stack(e, d_on, T, fsmp, ns, available, 0, ns, nullptr, 0, 0, want_scan, &sets, true,
-                  first_sample, end_sample))
-        return 1;
-    hipLaunchKernelGGL(qm::marginal_reduce_kernel, dim3((unsigned)((e->n_nodes + 255) / 256)),
-                       dim3(256), 0, e->stream, e->d_marg.p, e->marg_tiles, e->n_nodes, d_map);
-    QM_HIP(hipGetLastError());
-    if (want_scan && combine(e, e->d_pmax.p, e->d_pidx.p, e->d_psum.p, sets, ns, 1,
-                             e->node_offset, n_nodes_total, st.a, st.b, st.i))
-        return 1;
-    if (want_scan && e->cfg_tie_rule && refine_ties(e, d_on, T, fsmp, available, 0, ns, sets, st.i))
-        return 1;
+    StackLaunch s(d_on, T, fsmp, ns, available);
+    s.want_scan = want_scan;
+    s.kind = StackLaunch::Marginal{first_sample, end_sample, d_map};
+    if (stack_fold(e, s, kCombineFinal, n_nodes_total, st).rc) return 1;
     if (!map_on_device) {
         QM_HIP(copy_back(coa_map, d_map, (size_t)e->n_nodes * sizeof(double), e->stream));
         QM_HIP(hipStreamSynchronize(e->stream));
     }
-    if (want_scan) return fetch_out(e, ns, out_on_device, st, max_coa, max_norm_coa, max_coa_idx);
+    if (want_scan) return fetch_out(e, ns, out_on_device, st, user);
     return 0;
 }
 
@@ -1225,31 +1253,11 @@ int qm_engine_find_max_coa(qm_engine *e, const double *map4d, int map_on_device,
         return fail("qm_engine_find_max_coa: NULL argument");
     if (n_samples < 1 || n_nodes < 1) return fail("qm_engine_find_max_coa: empty volume");
     DeviceGuard guard(e->device);
-    OutStage st;
-    if (stage_out(e, n_samples, out_on_device, max_coa, max_norm_coa, max_coa_idx, &st)) return 1;
-    auto scan = [&](const double *vol, int64_t stride, int nk, int k0) -> int {
-        // a workgroup = up to 16 adjacent tiles (one wavefront each); ~cfg_scan_waves wavefronts
-        // per CU in total; at least 256 nodes per chunk
-        const int tiles = (nk + qm::kWave - 1) / qm::kWave;
-        const int groups = (tiles + qm::kScanWaves - 1) / qm::kScanWaves;
-        const int waves = (tiles + groups - 1) / groups;          // per workgroup, balanced
-        const int xgroups = (tiles + waves - 1) / waves;
-        int64_t sets = std::max<int64_t>(1, ((int64_t)e->cfg_scan_waves * e->n_cu + tiles - 1) / tiles);
-        sets = std::min<int64_t>(sets, std::max<int64_t>(1, n_nodes / 256));
-        sets = std::min<int64_t>(sets, 65535);
-        const int64_t per = (n_nodes + sets - 1) / sets;
-        sets = (n_nodes + per - 1) / per;
-        const size_t need = (size_t)sets * nk;
-        if (e->d_pmax.ensure(need) || e->d_psum.ensure(need) || e->d_pidx.ensure(need)) return 1;
-        hipLaunchKernelGGL(qm::scan_volume_kernel, dim3(xgroups, (unsigned)sets),
-                           dim3(waves * qm::kWave), 0, e->stream, vol, stride, nk, n_nodes, per,
-                           e->d_pmax.p, e->d_pidx.p, e->d_psum.p);
-        QM_HIP(hipGetLastError());
-        return combine(e, e->d_pmax.p, e->d_pidx.p, e->d_psum.p, (int)sets, nk, 2, 0, n_nodes,
-                       st.a + k0, st.b + k0, st.i + k0);
-    };
+    const OutSeries user{max_coa, max_norm_coa, max_coa_idx};
+    OutSeries st;
+    if (stage_out(e, n_samples, out_on_device, user, &st)) return 1;
     if (map_on_device) {
-        if (scan(map4d, n_samples, n_samples, 0)) return 1;
+        if (scan_fold(e, map4d, n_samples, n_samples, n_nodes, 0, kCombineValues, st)) return 1;
     } else {
         int64_t chunk = std::max<int64_t>(1, e->cfg_chunk_bytes / (8 * n_nodes));
         chunk = std::min<int64_t>(chunk, n_samples);
@@ -1259,11 +1267,11 @@ int qm_engine_find_max_coa(qm_engine *e, const double *map4d, int map_on_device,
             QM_HIP(copy_in_2d(e->d_chunk.p, nk * sizeof(double), map4d + k0,
                                     (size_t)n_samples * sizeof(double), nk * sizeof(double),
                                     n_nodes, e->stream));
-            if (scan(e->d_chunk.p, nk, nk, k0)) return 1;
+            if (scan_fold(e, e->d_chunk.p, nk, nk, n_nodes, 0, kCombineValues, st.at(k0))) return 1;
             QM_HIP(hipStreamSynchronize(e->stream));
         }
     }
-    return fetch_out(e, n_samples, out_on_device, st, max_coa, max_norm_coa, max_coa_idx);
+    return fetch_out(e, n_samples, out_on_device, st, user);
 }
 
 double qm_exp_correctly_rounded(double x) { return qm::exp_correctly_rounded(x); }
@@ -1310,71 +1318,3 @@ int qm_engine_last_kernel_ms(qm_engine *e, double *ms) {
 }
 
 }  // extern "C"
-
-// ------------------------------------------------------------------ partial-output forms (qm_group.hip)
-// The step entry points above, stopped before the final normalisation: this engine's partial (log2-domain
-// maximum or, for a scanned volume, the value itself; GLOBAL node index; sum) per sample written to p_max /
-// p_idx / p_sum on the device, as qm_engine_detect_partial writes it -- what the group folds across boxes.
-// Inputs and outputs are device memory on the engine's GPU; nothing waits.  p_max == NULL: no series.
-int marginal_partial(qm_engine *e, const double *d_on, int T, int fsmp, int lsmp, int available, int first,
-                     int end, double *d_map, double *p_max, int64_t *p_idx, double *p_sum) {
-    DeviceGuard guard(e->device);
-    int ns = 0, sets = 0;
-    if (check_step(e, T, fsmp, lsmp, available, &ns)) return 1;
-    if (first < 0 || end > ns || first >= end)
-        return fail("marginal window [%d, %d) outside the %d scanned samples", first, end, ns);
-    const bool want_scan = p_max != nullptr;
-    if (run_stack(e, d_on, T, fsmp, ns, available, 0, ns, nullptr, 0, 0, want_scan, &sets, true, first, end))
-        return 1;
-    hipLaunchKernelGGL(qm::marginal_reduce_kernel, dim3((unsigned)((e->n_nodes + 255) / 256)), dim3(256), 0,
-                       e->stream, e->d_marg.p, e->marg_tiles, e->n_nodes, d_map);
-    QM_HIP(hipGetLastError());
-    e->last_sets_own = want_scan;
-    if (want_scan && combine(e, e->d_pmax.p, e->d_pidx.p, e->d_psum.p, sets, ns, 0, e->node_offset, 0, p_max,
-                             p_sum, p_idx))
-        return 1;
-    return 0;
-}
-
-int migrate_partial(qm_engine *e, const double *d_on, int T, int fsmp, int lsmp, int available, double *d_vol,
-                    int accumulate, double *p_max, int64_t *p_idx, double *p_sum) {
-    DeviceGuard guard(e->device);
-    int ns = 0, sets = 0;
-    if (check_step(e, T, fsmp, lsmp, available, &ns)) return 1;
-    const bool want_scan = p_max != nullptr;
-    if (run_stack(e, d_on, T, fsmp, ns, available, 0, ns, d_vol, ns, accumulate, want_scan, &sets)) return 1;
-    e->last_sets_own = want_scan;
-    if (want_scan && combine(e, e->d_pmax.p, e->d_pidx.p, e->d_psum.p, sets, ns, 0, e->node_offset, 0, p_max,
-                             p_sum, p_idx))
-        return 1;
-    return 0;
-}
-
-// find_max_coa's scan over the n_nodes rows [node0, node0 + n_nodes) of a volume whose rows are d_vol's
-int scan_partial(qm_engine *e, const double *d_vol, int ns, int64_t n_nodes, int64_t node0, double *p_max,
-                 int64_t *p_idx, double *p_sum) {
-    DeviceGuard guard(e->device);
-    const int tiles = (ns + qm::kWave - 1) / qm::kWave;
-    const int groups = (tiles + qm::kScanWaves - 1) / qm::kScanWaves;
-    const int waves = (tiles + groups - 1) / groups;
-    const int xgroups = (tiles + waves - 1) / waves;
-    int64_t sets = std::max<int64_t>(1, ((int64_t)e->cfg_scan_waves * e->n_cu + tiles - 1) / tiles);
-    sets = std::min<int64_t>(sets, std::max<int64_t>(1, n_nodes / 256));
-    sets = std::min<int64_t>(sets, 65535);
-    const int64_t per = (n_nodes + sets - 1) / sets;
-    sets = (n_nodes + per - 1) / per;
-    const size_t need = (size_t)sets * ns;
-    if (e->d_pmax.ensure(need) || e->d_psum.ensure(need) || e->d_pidx.ensure(need)) return 1;
-    hipLaunchKernelGGL(qm::scan_volume_kernel, dim3(xgroups, (unsigned)sets), dim3(waves * qm::kWave), 0, e->stream,
-                       d_vol, (int64_t)ns, ns, n_nodes, per, e->d_pmax.p, e->d_pidx.p, e->d_psum.p);
-    QM_HIP(hipGetLastError());
-    return combine(e, e->d_pmax.p, e->d_pidx.p, e->d_psum.p, (int)sets, ns, 0, node0, 0, p_max, p_sum, p_idx);
-}
-
-// the fold of scan_partial's sets, packed [n_sets][3][ns] as for qm_engine_finalize_packed: find_max_coa's outputs
-int fold_scanned(qm_engine *e, const double *d_packed, int n_sets, int ns, int64_t n_nodes_total, double *o_max,
-                 double *o_norm, int64_t *o_idx) {
-    DeviceGuard guard(e->device);
-    return combine(e, d_packed, reinterpret_cast<const int64_t *>(d_packed + ns), d_packed + 2 * (int64_t)ns, n_sets,
-                   ns, 2, 0, n_nodes_total, o_max, o_norm, o_idx, nullptr, 3 * (int64_t)ns);
-}

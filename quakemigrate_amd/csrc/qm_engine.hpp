@@ -4,8 +4,9 @@
 //   qm_tables.hip    everything derived from ONE travel-time table: load, layout search, the kernels'
 //                    derived tables (round-2 offsets, paired, shift-reuse, screening), parked tables,
 //                    on-device serving
-//   qm_engine.hip    engine handle, tunables, the stacking launches and the step entry points
-//                    (detect / detect_batch / partial / finalize / migrate / marginal / find_max_coa)
+//   qm_engine.hip    engine handle, tunables, the stacking launches, one core per launch kind and the step
+//                    entry points around them (detect / detect_batch / partial / finalize / migrate / marginal /
+//                    find_max_coa)
 //   qm_screen.hip    the opt-in screened detect's launch sequence
 //   qm_stream.hip    the continuous detect pipeline (pinned ring, copies overlapped with compute), also over
 //                    several engines that hold the same table (replicas: launches round-robin)
@@ -28,6 +29,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <variant>
 #include <vector>
 
 #include "qm_kernels.hpp"
@@ -335,10 +337,64 @@ struct ScreenPlan {
     int threads() const { return big ? 1024 : 512; }
 };
 
-// where the kernels write the three series; copies back afterwards if the caller is on host
-struct OutStage {
-    double *a, *b;
-    int64_t *i;
+// combine_kernel's modes (qm_kernels.hpp)
+enum CombineMode : int {
+    kCombinePartial = 0,            // one combined partial: log2-domain maximum, sum, index + node offset
+    kCombineFinal = 1,              // the final series from log2-domain partials
+    kCombineValues = 2,             // the final series from partials that hold coalescence values (volume scan)
+};
+
+// The three series a combine writes, in this order everywhere: maxima, second (max_norm for the final
+// series, the sum for a partial), indices.  at(k): the same series from sample k on.
+struct OutSeries {
+    double *max = nullptr, *second = nullptr;
+    int64_t *idx = nullptr;
+    OutSeries at(int64_t k) const { return {max + k, second + k, idx + k}; }
+};
+
+// Partial sets as combine reads them: n samples per set, set s from element s * stride of each array
+struct SetView {
+    const double *max = nullptr;
+    const int64_t *idx = nullptr;
+    const double *sum = nullptr;
+    int n_sets = 0, n = 0;
+    int64_t stride = 0;
+};
+
+// One stacking launch (run_stack): samples [sample0, sample0 + n_chunk) of a scan of n_samples over the
+// onsets (rows of T samples, fsmp before the scan), and what it leaves besides the partial sets.
+struct StackLaunch {
+    struct Detect {};
+    struct Volume {                         // [n_nodes][stride] rows of the launch's samples
+        double *p = nullptr;
+        int64_t stride = 0;
+        int accumulate = 0;                 // 1: added to (the reference's +=), 0: overwritten
+    };
+    struct Marginal {                       // per node, the sum over the scan's samples [first, end)
+        int first = 0, end = 0;
+        double *map = nullptr;
+    };
+    const double *onsets = nullptr;
+    int T = 0, fsmp = 0, n_samples = 0, available = 0;
+    int sample0 = 0, n_chunk = 0;
+    std::variant<Detect, Volume, Marginal> kind;
+    bool want_scan = true;                  // partial sets for the three series
+    const int32_t *run_if = nullptr;        // returns at once unless *run_if (the screened step's fallback)
+    int n_steps = 1;                        // that many timesteps in ONE launch (fused detect only), their
+    int64_t step_stride = 0;                // ... onsets step_stride doubles apart
+
+    // a detect of the whole scan, one timestep
+    StackLaunch(const double *on, int T_, int fsmp_, int ns, int avail)
+        : onsets(on), T(T_), fsmp(fsmp_), n_samples(ns), available(avail), n_chunk(ns) {}
+};
+
+// What run_stack reports.  rc != 0: it failed (qm_last_error).  batched = false: the launch cannot hold
+// its n_steps timesteps (row blocks, the 12-wave shape) -- nothing was launched, the caller goes step by step.
+struct StackResult {
+    int rc = 0;
+    int sets = 0;                           // partial sets in d_pmax / d_pidx / d_psum: [sets][n_steps * n_chunk]
+    bool batched = true;
+    StackResult(int rc_ = 0) : rc(rc_) {}   // (from an int: `return fail(...)` as everywhere else)
 };
 
 // ---- qm_tables.hip ------------------------------------------------------------------------------
@@ -356,36 +412,34 @@ int ensure_screen_tables(qm_engine *e, const ScreenPlan &plan);
 
 // ---- qm_engine.hip ------------------------------------------------------------------------------
 int auto_groups(const qm_engine *e, int ntiles, int units, int blocks_per_cu, int rounds = 0);
-int run_stack(qm_engine *e, const double *d_onsets, int T, int fsmp, int n_samples, int available,
-              int sample0, int n_chunk, double *volume, int64_t vol_stride, int accumulate,
-              bool want_scan, int *n_sets, bool marginal = false, int m0 = 0, int m1 = 0,
-              const int32_t *run_if = nullptr, int n_steps = 1, int64_t step_stride = 0,
-              bool *batched = nullptr);
-int combine(qm_engine *e, const double *pmax, const int64_t *pidx, const double *psum, int sets,
-            int n, int mode, int64_t node_offset, int64_t n_nodes_total, double *o_max,
-            double *o_second, int64_t *o_idx, const int32_t *run_if = nullptr,
-            int64_t set_stride = 0);
-int refine_ties(qm_engine *e, const double *d_on, int T, int fsmp, int available, int sample0,
-                int n_chunk, int sets, int64_t *o_idx, int n_steps = 1, int64_t step_stride = 0,
-                const double *zext = nullptr, unsigned long long *o_key = nullptr);
-int detect_core(qm_engine *e, const double *d_on, int T, int fsmp, int ns, int available, int mode,
-                int64_t n_nodes_total, double *o_max, double *o_second, int64_t *o_idx);
+StackResult run_stack(qm_engine *e, const StackLaunch &s);
+// the sets the last stacking launch or volume scan left: [n_sets][n] in d_pmax / d_pidx / d_psum
+SetView engine_sets(const qm_engine *e, int n_sets, int n);
+// n_sets packed sets [n_sets][3][n]: rows maxima, index bits, sums (the layout of the exchange across devices)
+SetView packed_sets(const double *d_packed, int n_sets, int n);
+OutSeries packed_set(double *d_packed, int n);      // ... one of them, as a combine in partial mode writes it
+int combine(qm_engine *e, const SetView &in, CombineMode mode, int64_t node_offset, int64_t n_nodes_total,
+            const OutSeries &out, const int32_t *run_if);
+int refine_ties(qm_engine *e, const StackLaunch &s, int64_t *o_idx, const double *zext,
+                unsigned long long *o_key);
+// The cores of the step calls: device in, device out, nothing waits.  The public calls wrap them in the
+// argument checks and the staging of host arrays; the engine group (qm_group.hip) calls them in partial mode.
+//   stack_fold:  one stacking launch, the marginal map (a marginal launch), the combine of its sets into `out`
+//                from s.sample0 on (want_scan) and, final series only, the near-tie refinement
+//   scan_fold:   find_max_coa's scan of the n_nodes rows [node0, node0 + n_nodes) of a volume, combined
+//   detect_core: a detect step, screened or float64
+StackResult stack_fold(qm_engine *e, const StackLaunch &s, CombineMode mode, int64_t n_nodes_total,
+                       const OutSeries &out);
+int scan_fold(qm_engine *e, const double *vol, int64_t stride, int ns, int64_t n_nodes, int64_t node0,
+              CombineMode mode, const OutSeries &out);
+int detect_core(qm_engine *e, const double *d_on, int T, int fsmp, int ns, int available, CombineMode mode,
+                int64_t n_nodes_total, const OutSeries &out);
 int check_step(qm_engine *e, int T, int fsmp, int lsmp, int available, int *n_samples);
 int stage_onsets(qm_engine *e, const double *onsets, int on_device, int T, const double **out);
-int stage_out(qm_engine *e, int n, int out_on_device, double *max_coa, double *max_norm,
-              int64_t *idx, OutStage *st);
-int fetch_out(qm_engine *e, int n, int out_on_device, const OutStage &st, double *max_coa,
-              double *max_norm, int64_t *idx);
-// partial-output forms of marginal / migrate (device volume) / find_max_coa and the fold of scanned partials:
-// device in, device out, nothing waits (the engine group, qm_group.hip)
-int marginal_partial(qm_engine *e, const double *d_on, int T, int fsmp, int lsmp, int available, int first,
-                     int end, double *d_map, double *p_max, int64_t *p_idx, double *p_sum);
-int migrate_partial(qm_engine *e, const double *d_on, int T, int fsmp, int lsmp, int available, double *d_vol,
-                    int accumulate, double *p_max, int64_t *p_idx, double *p_sum);
-int scan_partial(qm_engine *e, const double *d_vol, int ns, int64_t n_nodes, int64_t node0, double *p_max,
-                 int64_t *p_idx, double *p_sum);
-int fold_scanned(qm_engine *e, const double *d_packed, int n_sets, int ns, int64_t n_nodes_total, double *o_max,
-                 double *o_norm, int64_t *o_idx);
+// where the kernels write the caller's three series (on host: the engine's packed [3][n] buffer) ...
+int stage_out(qm_engine *e, int n, int out_on_device, const OutSeries &user, OutSeries *st);
+// ... and their copy back to the caller
+int fetch_out(qm_engine *e, int n, int out_on_device, const OutSeries &st, const OutSeries &user);
 
 // ---- qm_stream.hip ------------------------------------------------------------------------------
 // the engine is going away: its pipelines give their buffers back and refuse further calls

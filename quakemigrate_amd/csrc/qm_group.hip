@@ -538,11 +538,16 @@ int qm_group_marginal(qm_group *g, const double *log_onsets, int32_t T, int32_t 
             if (q.d_map.ensure((size_t)(q.node1 - q.node0))) return failed(g);
         }
         for (int k = 0; k < q.n_boxes; ++k) {
-            double *pk = q.pack + k * 3 * (int64_t)ns;
-            double *map = q.d_map.p + (q.eng[k]->node_offset - q.node0);
-            if (marginal_partial(q.eng[k], q.d_on.p, T, fsmp, lsmp, available, first_sample, end_sample, map,
-                                 want_scan ? pk : nullptr, reinterpret_cast<int64_t *>(pk + ns), pk + 2 * ns))
+            qm_engine *e = q.eng[k];
+            DeviceGuard guard(e->device);
+            StackLaunch s(q.d_on.p, T, fsmp, ns, available);
+            s.want_scan = want_scan;
+            s.kind = StackLaunch::Marginal{first_sample, end_sample, q.d_map.p + (e->node_offset - q.node0)};
+            int ns_k = 0;
+            if (check_step(e, T, fsmp, lsmp, available, &ns_k) ||
+                stack_fold(e, s, kCombinePartial, 0, packed_set(q.pack + k * 3 * (int64_t)ns, ns)).rc)
                 return failed(g);
+            e->last_sets_own = want_scan;
         }
     }
     if (want_scan && exchange(g, T, fsmp, lsmp, available, ns)) return failed(g);
@@ -582,11 +587,16 @@ int qm_group_migrate(qm_group *g, const double *log_onsets, int32_t T, int32_t f
             }
         }
         for (int k = 0; k < q.n_boxes; ++k) {
-            double *pk = q.pack + k * 3 * (int64_t)ns;
-            double *vol = q.d_vol.p + (q.eng[k]->node_offset - q.node0) * ns;
-            if (migrate_partial(q.eng[k], q.d_on.p, T, fsmp, lsmp, available, vol, accumulate,
-                                want_scan ? pk : nullptr, reinterpret_cast<int64_t *>(pk + ns), pk + 2 * ns))
+            qm_engine *e = q.eng[k];
+            DeviceGuard guard(e->device);
+            StackLaunch s(q.d_on.p, T, fsmp, ns, available);
+            s.want_scan = want_scan;
+            s.kind = StackLaunch::Volume{q.d_vol.p + (e->node_offset - q.node0) * ns, ns, accumulate};
+            int ns_k = 0;
+            if (check_step(e, T, fsmp, lsmp, available, &ns_k) ||
+                stack_fold(e, s, kCombinePartial, 0, packed_set(q.pack + k * 3 * (int64_t)ns, ns)).rc)
                 return failed(g);
+            e->last_sets_own = want_scan;
         }
     }
     if (want_scan && exchange(g, T, fsmp, lsmp, available, ns)) return failed(g);
@@ -623,8 +633,7 @@ int qm_group_find_max_coa(qm_group *g, const double *map4d, int32_t n_samples, i
                 return failed(g);
             }
             QM_HIP(hipEventRecord(q.ev_t0, q.stream));
-            if (scan_partial(q.eng[0], q.d_vol.p, ns, n1 - n0, n0, q.fpack, reinterpret_cast<int64_t *>(q.fpack + ns),
-                             q.fpack + 2 * ns))
+            if (scan_fold(q.eng[0], q.d_vol.p, ns, ns, n1 - n0, n0, kCombinePartial, packed_set(q.fpack, ns)))
                 return failed(g);
             QM_HIP(hipEventRecord(q.ev_t1, q.stream));
             q.timed = true;
@@ -632,9 +641,13 @@ int qm_group_find_max_coa(qm_group *g, const double *map4d, int32_t n_samples, i
         if (to_lead(g, q, g->d_fgather.p + (size_t)p * 3 * ns, q.fpack, 3 * (size_t)ns)) return failed(g);
     }
     double *o = g->d_out.p;
-    if (fold_scanned(g->lead, g->d_fgather.p, P, ns, n_nodes, o, o + ns, reinterpret_cast<int64_t *>(o + 2 * (size_t)ns)) ||
-        fetch_series(g, ns, max_coa, max_norm_coa, max_coa_idx))
-        return failed(g);
+    {
+        DeviceGuard lead(g->lead_dev);
+        if (combine(g->lead, packed_sets(g->d_fgather.p, P, ns), kCombineValues, 0, n_nodes,
+                    OutSeries{o, o + ns, reinterpret_cast<int64_t *>(o + 2 * (size_t)ns)}, nullptr))
+            return failed(g);
+    }
+    if (fetch_series(g, ns, max_coa, max_norm_coa, max_coa_idx)) return failed(g);
     return 0;
 }
 
