@@ -128,7 +128,11 @@ int qm_engine_synchronize(qm_engine *e);
  *                                                (migratelib.c:98-105 as its scalar-libm build computes it);
  *                                                final series of detect / detect_batch (the step axis kept) /
  *                                                migrate / marginal, and sharded detects through
- *                                                qm_engine_tie_partial / _tie_fold; values unchanged.  Device
+ *                                                qm_engine_tie_partial / _tie_fold; values unchanged.  REFUSED
+ *                                                together with screen = 1 by every detect call (detect,
+ *                                                detect_batch, detect_partial, the stream): an error naming the
+ *                                                two keys, nothing is computed -- the screened detect has no
+ *                                                refinement; migrate / marginal of such an engine refine.  Device
  *                                                memory: 8 bytes per brick (512-1024 nodes) and scanned sample
  *                                                besides the partial sets (C3: 227 MB per timestep of a launch)
  * tie_sets              0 / 1 [1]                (measurements) 1: with tie_rule = 1 the shift-reuse fused detect
@@ -308,7 +312,10 @@ int qm_engine_finalize_packed(qm_engine *e, const double *d_packed, int32_t n_se
  * qm_engine_tie_fold takes the gathered [n_sets][2][n_samples] and overwrites, in the device series
  * d_max_coa_idx [n_samples], every sample some rank refined: largest exp, lowest index among the ranks reaching
  * it (what the reference's loop over ascending flat indices returns).  Samples nobody refined keep the default
- * rule's index.  Both calls only enqueue. */
+ * rule's index.  Both calls only enqueue.  qm_engine_tie_partial is refused (an error that asks for
+ * qm_engine_detect_partial first) unless that detect_partial was the engine's LAST launch: any other stacking
+ * launch, qm_engine_find_max_coa, qm_engine_load_lut / _serve or qm_engine_table_select in between overwrites or
+ * re-describes the sets it would read. */
 int qm_engine_tie_partial(qm_engine *e, const double *log_onsets, int onsets_on_device,
                           int32_t t_samples, int32_t fsmp, int32_t lsmp, int32_t available,
                           const double *d_packed, int32_t n_sets, double *d_tie_packed);
@@ -491,7 +498,11 @@ int qm_group_config(qm_group *g, const char *key, int64_t value);
 int qm_group_get(qm_group *g, const char *key, int64_t *value);
 /* host table i32 [nx][ny][nz][n_rows], sliced by the plan (flat tables: nx = ny = 1, nz = n_nodes) */
 int qm_group_load_lut(qm_group *g, const int32_t *host_table, int32_t nx, int32_t ny, int32_t nz, int32_t n_rows);
-/* qm_engine_table_select on every box engine; *resident = 1 only if every one has its slice resident */
+/* qm_engine_table_select on every box engine; *resident = 1 only if every one has its slice resident.  The box
+ * engines park and evict on their own, and one that has a box for only some of the grids' shapes has parked fewer
+ * tables than the others: with a small capacity the group can therefore MISS a table that a single engine given the
+ * same calls would still hold (never the reverse) -- the caller loads it again, a rebuild, never another table.  A
+ * load after such a miss leaves every box engine's table known under the key. */
 int qm_group_table_select(qm_group *g, uint64_t key, int32_t capacity, int32_t *resident);
 /* qm_engine_detect / _marginal / _migrate / _find_max_coa over the whole grid, host arrays: log_onsets f64
  * [n_rows][t_samples], series [n_samples], coa_map f64 [n_nodes], map4d f64 [n_nodes][n_samples] (accumulate != 0:

@@ -92,7 +92,7 @@ def log_onsets(onsets: np.ndarray) -> np.ndarray:
 
 
 def _migrate_with(fns, onsets, traveltimes, first_idx, last_idx, available,
-                  threads, prelogged=False):
+                  threads, prelogged=False, initial=None):
     lon = np.ascontiguousarray(onsets if prelogged else log_onsets(onsets))
     *grid, n_luts = traveltimes.shape
     n_onsets, t_samples = lon.shape
@@ -104,6 +104,8 @@ def _migrate_with(fns, onsets, traveltimes, first_idx, last_idx, available,
     if lon.size < n_samples + first_idx:
         raise ValueError("Data array smaller than coalescence array.")
     map4d = np.zeros(tuple(grid) + (n_samples,), dtype=np.float64)
+    if initial is not None:         # the volume's content joins the stack (migratelib.c:57 '+='), then the exp
+        map4d[...] = np.asarray(initial, dtype=np.float64).reshape(map4d.shape)
     fns["stack"](lon, np.ascontiguousarray(traveltimes), map4d, first_idx,
                  last_idx, n_samples, n_onsets, int(available),
                  int(np.prod(grid)), int(threads))
@@ -122,9 +124,10 @@ def _scan_with(fns, map4d, threads):
 
 
 def c_migrate(onsets, traveltimes, first_idx, last_idx, available, threads=1,
-              prelogged=False):
+              prelogged=False, initial=None):
+    """``initial``: what the volume holds before the call (the reference accumulates on top of it)."""
     return _migrate_with(_port(), onsets, traveltimes, first_idx, last_idx,
-                         available, threads, prelogged)
+                         available, threads, prelogged, initial)
 
 
 def c_find_max_coa(map4d, threads=1):

@@ -446,6 +446,9 @@ StackResult run_stack(qm_engine *e, const StackLaunch &s) {
                                           : auto_groups(e, a.ntiles, units, 2048 / threads);
     }
     const int sets = groups_lds + groups_direct;
+    // (from here on d_pmax and the last_* fields describe THIS launch: whatever a detect left for
+    // qm_engine_tie_partial is gone -- detect_core and the group's partial launches say so again)
+    e->last_sets_own = false;
     if (want_scan) {
         const size_t need = (size_t)sets * steps * n_chunk;
         if (e->d_pmax.ensure(need) || e->d_psum.ensure(need) || e->d_pidx.ensure(need)) return 1;
@@ -579,6 +582,13 @@ int detect_core(qm_engine *e, const double *d_on, int T, int fsmp, int ns, int a
                 int64_t n_nodes_total, const OutSeries &out) {
     int sets = 0;
     bool screened = false;
+    // (the screened sweep leaves no float64 sets to refine near-ties from, and its conditional fallback cannot be
+    // followed by a refinement nobody waits for: the two opt-ins exclude each other on the detect calls)
+    e->last_sets_own = false;                           // (the screened sweep writes d_pmax as well; a refused
+                                                        // call is no detect_partial either)
+    if (e->cfg_screen && e->cfg_tie_rule)
+        return fail("detect: the config keys screen = 1 and tie_rule = 1 cannot be combined (the screened detect "
+                    "has no near-tie refinement): set one of them to 0");
     if (run_screen(e, d_on, T, fsmp, ns, available, &sets, &screened)) return 1;
     StackLaunch s(d_on, T, fsmp, ns, available);
     if (screened) {
@@ -586,7 +596,10 @@ int detect_core(qm_engine *e, const double *d_on, int T, int fsmp, int ns, int a
         s.run_if = e->d_flags.p;
     }
     if (stack_fold(e, s, mode, n_nodes_total, out).rc) return 1;
-    e->last_sets_own = !screened;                       // (d_pmax holds the float64 launch's sets for certain)
+    // (d_pmax holds the float64 launch's sets for certain -- and they are those of a detect_partial, the only call
+    // qm_engine_tie_partial follows: a final detect of other onsets at the same sample count is refused like any
+    // other launch in between)
+    e->last_sets_own = !screened && mode == kCombinePartial;
     return 0;
 }
 
@@ -604,6 +617,7 @@ int scan_fold(qm_engine *e, const double *vol, int64_t stride, int ns, int64_t n
     const int64_t per = (n_nodes + sets - 1) / sets;
     sets = (n_nodes + per - 1) / per;
     const size_t need = (size_t)sets * ns;
+    e->last_sets_own = false;                           // (a volume's sets overwrite a detect's: qm_engine_tie_partial)
     if (e->d_pmax.ensure(need) || e->d_psum.ensure(need) || e->d_pidx.ensure(need)) return 1;
     hipLaunchKernelGGL(qm::scan_volume_kernel, dim3(xgroups, (unsigned)sets), dim3(waves * qm::kWave), 0, e->stream,
                        vol, stride, ns, n_nodes, per, e->d_pmax.p, e->d_pidx.p, e->d_psum.p);
@@ -1135,7 +1149,8 @@ int qm_engine_tie_partial(qm_engine *e, const double *log_onsets, int onsets_on_
     if (!e->cfg_tie_rule) return fail("qm_engine_tie_partial: the engine was not configured with tie_rule = 1");
     if (e->last_scan_n != ns || e->last_sets < 1 || !e->last_sets_own)
         return fail("qm_engine_tie_partial: no partial sets of a float64 detect of %d samples on this engine "
-                    "(call qm_engine_detect_partial for the step first; the screened sweep leaves none)", ns);
+                    "(call qm_engine_detect_partial for the step first, with no other launch, volume scan or "
+                    "table change in between; the screened sweep leaves none)", ns);
     const double *d_on = nullptr;
     if (stage_onsets(e, log_onsets, onsets_on_device, T, &d_on)) return 1;
     // the grid's largest z per sample: the fold of the gathered maxima (rows [s][0] of [n_sets][3][ns])

@@ -404,6 +404,7 @@ int eff_j(const qm_engine *e);
 int run_j(const qm_engine *e, int n_chunk);
 int plan_wide(qm_engine *e, int J);
 int pair_jp(const qm_engine *e, int n_chunk, bool volume);
+void table_set_key(qm_engine *e, uint64_t key);     // the resident table is known under `key` (engine groups)
 int ensure_pair_tables(qm_engine *e, int jp);
 int ensure_shift_tables(qm_engine *e, ShiftLayout &L);
 bool screen_plan_feasible(const qm_engine *e, int S, const ScreenPlan &p);

@@ -437,6 +437,8 @@ int qm_group_load_lut(qm_group *g, const int32_t *host_table, int32_t nx, int32_
     if (nx < 1 || ny < 1 || nz < 1 || n_rows < 1)
         return fail("qm_group_load_lut: bad shape (%d, %d, %d, %d)", nx, ny, nz, n_rows);
     const bool same_grid = g->nx == nx && g->ny == ny && g->nz == nz;
+    const bool after_miss = g->miss;
+    const uint64_t miss_key = g->miss_key;
     if (g->miss) {                                     // (loaded after a select miss: known under its key)
         g->miss = false;
         bool seen = false;
@@ -461,6 +463,11 @@ int qm_group_load_lut(qm_group *g, const int32_t *host_table, int32_t nx, int32_
                 g->have_lut = false;
                 return 1;
             }
+            // The GROUP's select missed as soon as one box engine had lost the table; an engine that still had its
+            // box parked brought it back, and this load on top of it would take its key away (qm_engine_load_lut: a
+            // load onto a resident table is a foreign one) -- that engine would never park the table again, and the
+            // group would rebuild it at every later select although the cache has room.
+            if (after_miss) table_set_key(q.eng[k], miss_key);
         }
     return 0;
 }

@@ -562,6 +562,7 @@ int qm_engine_load_lut(qm_engine *e, const int32_t *lut, int lut_on_device, int3
     // "resident" and stack through a foreign table.
     if (e->have_lut) e->cur_keyed = false;
     e->have_lut = false;
+    e->last_sets_own = false;                           // (the sets of a detect on the former table: qm_engine_tie_partial)
     const size_t lut_elems = (size_t)n_nodes * n_rows;
     if (e->d_lut.ensure(lut_elems) || e->d_scalar.ensure(4)) return 1;
     if (lut_on_device)
@@ -704,6 +705,18 @@ int qm_engine_load_lut(qm_engine *e, const int32_t *lut, int lut_on_device, int3
     return plan_wide(e, eff_j(e));
 }
 
+}  // extern "C"
+
+// The resident table is the one known under `key`, whatever qm_engine_load_lut made of the engine's key when it
+// loaded it (a load onto a resident table un-keys it: above).  For a caller that knows better -- the engine group,
+// whose select missed as a whole while this engine had the table back (qm_group_load_lut).
+void table_set_key(qm_engine *e, uint64_t key) {
+    e->cur_key = key;
+    e->cur_keyed = true;
+}
+
+extern "C" {
+
 int qm_engine_table_select(qm_engine *e, uint64_t key, int32_t capacity, int32_t *resident) {
     if (!e || !resident) return fail("qm_engine_table_select: NULL argument");
     if (capacity < 0 || capacity > 64) return fail("qm_engine_table_select: capacity must be in 0..64");
@@ -714,6 +727,7 @@ int qm_engine_table_select(qm_engine *e, uint64_t key, int32_t capacity, int32_t
         return 0;
     }
     DeviceGuard guard(e->device);
+    e->last_sets_own = false;                           // (another table from here on: qm_engine_tie_partial)
     TableState &cur = *e;
     const bool park = e->have_lut && e->cur_keyed && capacity > 0;
     // Is the requested table parked?  Then it trades places with the current one in ITS slot -- looked
