@@ -13,7 +13,12 @@ against the oracle's restatement of the reference's exp rule.  Round 6: three tr
 samples, and half of all trials ask for the WIDE tiles (six samples per lane) wherever the scan holds one.
 On a mismatch the trial's diagnosis is printed before the assertion (which kernel, which nodes and
 samples, whether a second run moves): the round-4 GPU-sharing study started from these lines.
-usage: fuzz_shift.py [trials] [seed]      (QM_FUZZ_ONLY=trial [QM_FUZZ_REPEAT=n]: that trial of the seed only)"""
+With a third argument `noise` the trial's table is replaced by one of the BOUNDED-NOISE family (tests/shift_layout.py):
+tt[..., r] = c_r + U{0..m_r} per node, m_r <= 20 (18 where the trial may take wide tiles) -- the whole 24-double register
+window is consumed and no brick leaves for the direct kernel, which the distance-like tables above never reach (ordinary
+rows stay below offset 16, steep ones overflow).  That family draws from a generator of its own, so that a (seed, trial)
+pair replays the same trial with and without it.
+usage: fuzz_shift.py [trials] [seed] [noise]      (QM_FUZZ_ONLY=trial [QM_FUZZ_REPEAT=n]: that trial of the seed only)"""
 import os
 import sys
 
@@ -24,7 +29,11 @@ from oracle import qm_oracle  # noqa: E402
 from quakemigrate_amd.core import lib  # noqa: E402
 
 trials = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+rng = np.random.default_rng(seed)
+noise = len(sys.argv) > 3 and sys.argv[3] == "noise"
+if len(sys.argv) > 3 and not noise:
+    sys.exit(__doc__)
 used = wide = blocks = six = 0
 repeat = int(os.environ.get("QM_FUZZ_REPEAT", "1"))    # (with QM_FUZZ_ONLY: the trial's engine sequence this many times)
 for trial in range(trials):
@@ -61,6 +70,14 @@ for trial in range(trials):
                shift_wide=int(rng.choice([1, 1, 0, -1])),
                # (... on row blocks: beyond 64 rows by itself, in a third of the trials whatever the row count)
                shift_wide_rows=int(rng.choice([1, 1, 2])))
+    if noise:                           # (its own generator: the trial's other draws are those of a run without it)
+        nrng = np.random.default_rng([seed, trial, 0x5817])
+        top = 18 if cfg["shift_wide"] != 0 and ns >= 384 else 20
+        m_r = np.where(nrng.random(S) < 0.6, top, nrng.integers(0, top + 1, size=S))
+        c_r = nrng.integers(0, max(1, lsmp - top), size=S)
+        tt = (c_r + nrng.integers(0, m_r + 1, size=grid + (S,))).astype(np.int32)
+        if trial % 3 == 0:
+            tt[(tt <= 1) & (nrng.random(tt.shape) < 0.5)] = -3
     if os.environ.get("QM_FUZZ_ONLY") and trial != int(os.environ["QM_FUZZ_ONLY"]):
         # (replay one trial of a seed: the random stream has to advance as in the full run, including
         # the draws the skipped checks would have made)
