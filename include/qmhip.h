@@ -186,6 +186,10 @@ int qm_engine_synchronize(qm_engine *e);
  *                                                stream instead of copied by a command on a second stream: -1 =
  *                                                slots of <= 1 MB (example-sized grids, few steps per launch), 1 =
  *                                                always, 0 = never; same results
+ * -- the pre-processing stage --
+ * preproc_skew          0 / 1 [1]                the band-pass recurrence with section s on lane s, one sample behind
+ *                                                lane s - 1 (critical path T + n_sections); 0 = every section on one
+ *                                                lane (T x n_sections): the in-device cross-check; same bits
  * -- measurement --
  * stream_stamps         0 / 1 [0]                qm_stream: a one-thread kernel before and behind every launch stores
  *                                                the GPU's clock; busy time per launch and the gaps between launches
@@ -403,6 +407,29 @@ int qm_engine_onsets(qm_engine *e, const double *signals, int signals_on_device,
                      int position, int32_t taper_pad, double min_onset_value,
                      double *raw_onsets, double *log_onsets, int out_on_device);
 
+/* Pre-processing on the device -- the step upstream of the onset stage: what STALTAOnset.calculate_onsets does to
+ * every component trace before the STA/LTA (stalta.py:137-211, :353-489) for gap-free traces of the full timespan
+ * (the reference's default, full_timespan = True, allow_gaps = False; resampling, gappy traces and the envelope
+ * transforms stay with the caller).  Per trace, one workgroup:
+ *   1. detrend = 1: the least-squares line over t = 0..T-1 is subtracted in its centred form,
+ *      y = x - (mean(x) + slope (t - mean(t))), slope = sum (t - mean t)(x - mean x) / sum (t - mean t)^2,
+ *      then the mean of y (the reference detrends "linear", then "constant").  The sums are fixed-order
+ *      reductions: the same bits in every run.
+ *   2. y[k] *= taper_left[k] (k < n_left), y[T - n_right + k] *= taper_right[k] (k < n_right): the weights are the
+ *      caller's (a 5 % cosine taper in the reference); either length may be 0.
+ *   3. the cascade of n_sections second-order sections sos[trace_filter[i]] ([n_filters][n_sections][6] as SciPy
+ *      lays them out: b0 b1 b2 a0 a1 a2, a0 == 1), direct form II transposed from a zero state, in the operation
+ *      order of scipy.signal.sosfilt and without contraction: its bits.  zero_phase = 1: the same filter again over
+ *      the reversed result, reversed back (the reference's zerophase band-pass).
+ * signals / filtered: f64 [n_traces][t_samples], host or device (filtered may be signals on the device).
+ * Refused: n_sections outside 1..8, a trace_filter entry outside [0, n_filters), n_left + n_right > t_samples,
+ * a section whose a0 is not 1. */
+int qm_engine_preprocess(qm_engine *e, const double *signals, int signals_on_device, int32_t n_traces,
+                         int32_t t_samples, const int32_t *trace_filter, const double *sos, int32_t n_filters,
+                         int32_t n_sections, int detrend, const double *taper_left, int32_t n_left,
+                         const double *taper_right, int32_t n_right, int zero_phase, double *filtered,
+                         int out_on_device);
+
 /* exp(x) rounded to nearest from a double-double evaluation (csrc/qm_ties.hpp): the function the
  * opt-in arg-max rule "tie_rule" = 1 compares near-tied nodes on (the reference exponentiates, then
  * compares: migratelib.c:60-62, :98-105).  Host code, exported for the tests that pin it. */
@@ -445,6 +472,24 @@ int qm_stream_flush(qm_stream *s);
 int qm_stream_pop(qm_stream *s, int32_t n_steps, double *max_coa, double *max_norm_coa,
                   int64_t *max_coa_idx);
 int qm_stream_pending(qm_stream *s, int32_t *launched_not_popped, int32_t *pushed_not_launched);
+/* Waveforms in: with an onset stage the stream takes a timestep's resampled component traces (host f64
+ * [n_traces][t_samples]) through qm_stream_push_signals instead of its log-onsets, and a slot's launch becomes
+ * pull or copy of the signals -> qm_engine_preprocess's kernel (zero-phase) over the slot's (step, trace)s ->
+ * qm_engine_onsets' kernels over its (step, trace)s and (step, row)s -> the fused detect: every timestep's bits are
+ * those of the three staged calls.  The arguments are those of qm_engine_preprocess and qm_engine_onsets (n_rows is
+ * the resident table's); every array is copied to the device here, so no launch waits on a host buffer.
+ * qm_stream_set_onset_stage is called once, before the first push.  A stream takes signals or log-onsets, never both:
+ * refused are a second stage, a stage after a push, qm_stream_push_signals without a stage, qm_stream_push after
+ * qm_stream_push_signals and the reverse, a trace_row entry out of range or a row without a trace, and what
+ * qm_engine_preprocess refuses.  Over replicas the stage and the pushes go lane by lane like everything else.
+ * qm_stream_push_signals returns what qm_stream_push returns; flush / pop / pending are unchanged. */
+int qm_stream_set_onset_stage(qm_stream *s, int32_t n_traces, const int32_t *trace_row,
+                              const int32_t *trace_filter, const double *sos, int32_t n_filters,
+                              int32_t n_sections, int detrend, const double *taper_left,
+                              int32_t n_left, const double *taper_right, int32_t n_right,
+                              const int32_t *nsta, const int32_t *nlta, int transform, int position,
+                              int32_t taper_pad, double min_onset_value);
+int qm_stream_push_signals(qm_stream *s, const double *signals);
 /* One pipeline over several engines that hold the SAME table (checked by digest): the continuous stream split by
  * time, not by grid.  Launch j (K timesteps) runs on engine j mod n_engines, each engine with
  * `depth` slots of its own; qm_stream_pop returns timesteps in push order.  Same qm_stream handle: push / flush /

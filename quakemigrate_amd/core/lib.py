@@ -114,6 +114,9 @@ qmlib.qm_engine_rbf_peak.argtypes = [_vp, ctypes.POINTER(ctypes.c_double), c_int
 qmlib.qm_engine_onsets.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32, c_i32Pt, c_int32,
                                    c_i32Pt, c_i32Pt, ctypes.c_int, ctypes.c_int, c_int32,
                                    ctypes.c_double, _vp, _vp, ctypes.c_int]
+qmlib.qm_engine_preprocess.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32, c_i32Pt, c_dPt, c_int32, c_int32,
+                                       ctypes.c_int, c_dPt, c_int32, c_dPt, c_int32, ctypes.c_int, _vp,
+                                       ctypes.c_int]
 qmlib.qm_engine_find_max_coa.argtypes = [_vp, _vp, ctypes.c_int, c_int32,
                                          c_int64, _vp, _vp, _vp, ctypes.c_int]
 qmlib.qm_exp2f_max_error.argtypes = [_vp, ctypes.c_float, ctypes.c_float,
@@ -128,6 +131,10 @@ qmlib.qm_stream_create_replicas.argtypes = [ctypes.POINTER(_vp), c_int32, c_int3
 qmlib.qm_stream_destroy.argtypes = [_vp]
 qmlib.qm_stream_destroy.restype = None
 qmlib.qm_stream_push.argtypes = [_vp, _vp]
+qmlib.qm_stream_push_signals.argtypes = [_vp, _vp]
+qmlib.qm_stream_set_onset_stage.argtypes = [_vp, c_int32, c_i32Pt, c_i32Pt, c_dPt, c_int32, c_int32, ctypes.c_int,
+                                            c_dPt, c_int32, c_dPt, c_int32, c_i32Pt, c_i32Pt, ctypes.c_int,
+                                            ctypes.c_int, c_int32, ctypes.c_double]
 qmlib.qm_stream_flush.argtypes = [_vp]
 qmlib.qm_stream_pop.argtypes = [_vp, c_int32, _vp, _vp, _vp]
 qmlib.qm_stream_pending.argtypes = [_vp, ctypes.POINTER(c_int32), ctypes.POINTER(c_int32)]
@@ -644,6 +651,38 @@ class Engine:
             int(taper_pad), float(min_onset_value), pr, pl, dev_o))
         return raw_out, log_out
 
+    def preprocess(self, signals, trace_filter, sos, taper=(None, None), detrend=True, zero_phase=True,
+                   out=None):
+        """
+        Pre-processing on the GPU, the step before :meth:`onsets` (what ``STALTAOnset.calculate_onsets`` does to
+        every gap-free, full-timespan component trace before the STA/LTA, stalta.py:137-211, :353-489): linear
+        detrend and demean, taper, band-pass as a cascade of second-order sections -- forward, and with
+        ``zero_phase`` backward as well.  The filter's bits are ``scipy.signal.sosfilt``'s.
+
+        ``signals`` (n_traces, T), host or device like :meth:`onsets`; ``trace_filter`` (n_traces,) picks each
+        trace's filter out of ``sos`` (n_filters, n_sections, 6), SciPy's layout with ``a0 == 1``
+        (:func:`quakemigrate_amd.preprocess.butter_bandpass_sos`); ``taper = (left, right)``: the weights of
+        the first and last samples (:func:`quakemigrate_amd.preprocess.cosine_taper_sides`), either may be
+        ``None``.  Returns the filtered traces (``out``, host or device, or a new host array).
+        """
+        n_traces, t_samples = (int(v) for v in signals.shape)
+        trace_filter = np.ascontiguousarray(trace_filter, dtype=np.int32)
+        sos = np.ascontiguousarray(sos, dtype=np.float64)
+        if trace_filter.shape != (n_traces,):
+            raise ValueError(f"trace_filter of shape {trace_filter.shape} for {n_traces} traces")
+        if sos.ndim != 3 or sos.shape[2] != 6:
+            raise ValueError(f"sos of shape {sos.shape}: (n_filters, n_sections, 6) expected")
+        left, right = (np.ascontiguousarray([] if w is None else w, dtype=np.float64).reshape(-1) for w in taper)
+        ps, dev_s = self._ptr(signals, np.float64)
+        if out is None:
+            out = np.zeros((n_traces, t_samples))
+        po, dev_o = self._ptr(out, np.float64, n_traces * t_samples)
+        _check(qmlib.qm_engine_preprocess(
+            self._h, ps, dev_s, n_traces, t_samples, trace_filter, sos.reshape(-1), int(sos.shape[0]),
+            int(sos.shape[1]), 1 if detrend else 0, left, len(left), right, len(right), 1 if zero_phase else 0,
+            po, dev_o))
+        return out
+
     def find_max_coa(self, map4d, n_samples, n_nodes, out=None):
         if out is None:
             out = (np.zeros(n_samples), np.zeros(n_samples),
@@ -993,6 +1032,9 @@ class EngineReplicas:
 
     def onsets(self, *args, **kwargs):
         return self.lead.onsets(*args, **kwargs)
+
+    def preprocess(self, *args, **kwargs):
+        return self.lead.preprocess(*args, **kwargs)
 
 
 def timeit(*args_, **kwargs_):

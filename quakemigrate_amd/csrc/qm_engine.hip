@@ -796,6 +796,7 @@ void qm_engine_destroy(qm_engine *e) {
     for (TableSlot &slot : e->slots) slot.state.release_all();
     e->d_grids.release(); e->d_rows.release(); e->d_served.release();
     e->d_sig.release(); e->d_sta.release(); e->d_lta.release(); e->d_raw.release();
+    e->d_pre_coef.release(); e->d_pre_out.release(); e->d_pre_meta.release();
     e->d_onset_meta.release(); e->d_scalar.release(); e->d_digest.release();
     e->d_onsets.release(); e->d_pmax.release(); e->d_psum.release(); e->d_out_a.release();
     e->d_chunk.release(); e->d_marg.release(); e->d_marg_out.release(); e->d_pidx.release();
@@ -926,6 +927,8 @@ int qm_engine_config(qm_engine *e, const char *key, int64_t v) {
         e->cfg_stream_pull = (int)v;
     } else if (k == "stream_stamps") {
         e->cfg_stream_stamps = v ? 1 : 0;
+    } else if (k == "preproc_skew") {
+        e->cfg_preproc_skew = v ? 1 : 0;
     } else if (k == "log_timing") {
         e->log_timing = v != 0;
         e->ev_used = 0;
@@ -982,6 +985,7 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     else if (k == "tie_rule") *v = e->cfg_tie_rule;
     else if (k == "tie_sets") *v = e->cfg_tie_sets;
     else if (k == "stream_pull") *v = e->cfg_stream_pull;
+    else if (k == "preproc_skew") *v = e->cfg_preproc_skew;
     else if (k == "tie_brick_rows") *v = e->last_brick_rows;
 
     else if (k == "tie_refined_steps") *v = e->tie_refined_steps;

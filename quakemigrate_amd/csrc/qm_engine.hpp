@@ -11,6 +11,7 @@
 //   qm_stream.hip    the continuous detect pipeline (pinned ring, copies overlapped with compute), also over
 //                    several engines that hold the same table (replicas: launches round-robin)
 //   qm_widen.hip     the rows next to the path: onset stage, locate fits, RBF peak
+//   qm_preproc.hip   the row before the onset stage: detrend, taper, zero-phase band-pass of the component traces
 //   qm_compat.hip    the five reference-signature symbols (qmlib.h:28-44)
 //   qm_group.hip     engine groups: one process driving the boxes of a column partition on several devices
 // Everything declared here lives in the library only (hidden visibility).
@@ -38,6 +39,7 @@
 #include "qm_pair.hpp"
 #include "qm_shift.hpp"
 #include "qm_ties.hpp"
+#include "qm_preproc.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -255,6 +257,8 @@ struct qm_engine : TableState {
     int cfg_stream_pull = -1;               // qm_stream: a slot's pinned inputs pulled by a kernel on the engine's stream
                                             // instead of a copy command on another (-1: slots of <= 1 MB, 0, 1)
     int cfg_stream_stamps = 0;              // qm_stream, measurement: GPU-clock stamps around every launch (stderr digest)
+    int cfg_preproc_skew = 1;               // pre-processing filter: 1 section s on lane s, one sample behind lane s - 1
+                                            // (qm_preproc.hpp); 0: every section on one lane (the cross-check)
     int cfg_tie_rule = 0;                   // 0: largest float64 sum, lowest index among equal ones (default);
                                             // 1: the reference's rule on near-ties (qm_ties.hpp)
     int cfg_tie_sets = 1;                   // ... refined from a partial set PER BRICK where the stacking kernel has
@@ -299,6 +303,9 @@ struct qm_engine : TableState {
     // onset stage scratch
     DevBuf<double> d_sig, d_sta, d_lta, d_raw;
     DevBuf<int32_t> d_onset_meta;
+    // pre-processing stage scratch: coefficients and taper weights, the traces' filters, the filtered traces
+    DevBuf<double> d_pre_coef, d_pre_out;
+    DevBuf<int32_t> d_pre_meta;
 
     // scratch
     DevBuf<double> d_onsets, d_pmax, d_psum, d_out_a, d_chunk, d_marg, d_marg_out;
@@ -445,6 +452,18 @@ int fetch_out(qm_engine *e, int n, int out_on_device, const OutSeries &st, const
 // ---- qm_stream.hip ------------------------------------------------------------------------------
 // the engine is going away: its pipelines give their buffers back and refuse further calls
 void streams_orphan(qm_engine *e);
+
+// ---- qm_widen.hip -------------------------------------------------------------------------------
+// the two onset kernels on the engine's stream: enqueue only
+int launch_onset_stage(qm_engine *e, const qm::OnsetArgs &a);
+
+// ---- qm_preproc.hip -----------------------------------------------------------------------------
+// what qm_engine_preprocess and qm_stream_set_onset_stage refuse (host arrays)
+int check_preproc(const char *what, int32_t n_traces, int32_t t_samples, const int32_t *trace_filter,
+                  const double *sos, int32_t n_filters, int32_t n_sections, const double *taper_left, int32_t n_left,
+                  const double *taper_right, int32_t n_right);
+// the pre-processing kernel over n_traces traces on the engine's stream: enqueue only
+int launch_preproc_stage(qm_engine *e, const qm::PreprocArgs &a, int64_t n_traces);
 
 // ---- qm_screen.hip ------------------------------------------------------------------------------
 constexpr int kFlagRing = 1024;

@@ -14,6 +14,11 @@
 //   engine's stream : ONE fused-detect launch for the slot's K steps (qm_engine_detect_batch); its
 //                     combine kernel writes the results, packed as [3][K x n_samples] float64, STRAIGHT
 //                     into the slot's pinned host buffer (a few KB per timestep; no D2H command)
+//   -- or, with an onset stage (qm_stream_set_onset_stage), WAVEFORMS cross the bus instead of log-onsets:
+//   caller's thread : qm_stream_push_signals   CPU copy of a step's resampled component traces, pinned
+//   engine's stream : pull or copy as above, then the pre-processing kernel (detrend, taper, zero-phase band-pass;
+//                     qm_preproc.hpp) over the slot's (step, trace)s, the two onset kernels over its (step, trace)s and
+//                     (step, row)s -- their output IS the slot's device log-onsets -- and the fused detect as above
 //   caller's thread : qm_stream_pop    waits for the launch's event, CPU copy of a step's three series
 //
 // Round 4 drove a pipeline like this from Python (three D2H copies, three events and NumPy staging per
@@ -37,6 +42,8 @@ struct qm_stream {
     struct Slot {
         double *h_on = nullptr;         // pinned [K][n_rows][T]
         double *d_on = nullptr;         // device, the same
+        double *h_sig = nullptr;        // onset stage: pinned [K][n_traces][T] component traces
+        double *d_sig = nullptr;        // ... device, the same; filtered in place
         double *h_out = nullptr;        // pinned [3][K * ns]: max_coa, max_norm_coa, indices (int64 bits) --
                                         // written by the kernels themselves
         hipEvent_t copied = nullptr;    // the inputs are on the device
@@ -51,6 +58,18 @@ struct qm_stream {
     int64_t launched_steps = 0, popped_steps = 0, launches = 0;
     unsigned long long *h_stamp = nullptr;   // ("stream_stamps") pinned [2][4096]
     bool pulled = false;                // the last launch's inputs were pulled by a kernel (no copy command)
+    // Onset stage (qm_stream_set_onset_stage): the slot's log-onsets are made on the device from pushed signals.
+    // Everything the kernels read is on the device from set-up on, replicated over the K steps of a launch:
+    // (step, trace) is the kernels' trace, (step, row) their row.
+    enum Feed { kNothingYet = 0, kLogOnsets = 1, kSignals = 2 };
+    int feed = kNothingYet;             // what the pushes carry: one kind per stream
+    bool staged = false;
+    int n_traces = 0;
+    qm::PreprocArgs pre{};              // in / out: per slot
+    qm::OnsetArgs on{};                 // signals / logged, n_traces / n_rows: per slot and launch
+    double *d_coef = nullptr;           // sos, taper_left, taper_right
+    double *d_sta = nullptr, *d_lta = nullptr;  // [K][n_traces][T] scratch of the onset kernels
+    int32_t *d_meta = nullptr;          // trace_filter [K][n_traces], trace_row the same, nsta [K][n_rows], nlta
     // A stream over replicas (qm_stream_create_replicas) holds no slots of its own: one ordinary stream per
     // engine (a LANE, registered on that engine like any other stream) and the launches in push order.  Launch j
     // goes to lane j mod n; the entry points dispatch to the replicas_* functions below.
@@ -87,6 +106,7 @@ __global__ __launch_bounds__(256) void pull_kernel(const pull2 *__restrict__ src
 __global__ void stamp_kernel(unsigned long long *slot) { *slot = wall_clock64(); }
 
 size_t step_in(const qm_stream *s) { return (size_t)s->n_rows * s->T; }
+size_t step_sig(const qm_stream *s) { return (size_t)s->n_traces * s->T; }
 
 int alive(const qm_stream *s, const char *what) {
     if (!s) return fail("%s: NULL argument", what);
@@ -97,7 +117,9 @@ int alive(const qm_stream *s, const char *what) {
 void free_slot(qm_stream::Slot &sl) {
     if (sl.h_on) (void)hipHostFree(sl.h_on);
     if (sl.h_out) (void)hipHostFree(sl.h_out);
+    if (sl.h_sig) (void)hipHostFree(sl.h_sig);
     if (sl.d_on) pool_free(sl.d_on);
+    if (sl.d_sig) pool_free(sl.d_sig);
     for (hipEvent_t ev : {sl.copied, sl.done})
         if (ev) (void)hipEventDestroy(ev);
     sl = qm_stream::Slot{};
@@ -129,6 +151,12 @@ void release_stream(qm_stream *s) {
     {
         PoolReleaseScope one_wait;
         for (qm_stream::Slot &sl : s->slots) free_slot(sl);
+        if (s->d_coef) pool_free(s->d_coef);
+        if (s->d_sta) pool_free(s->d_sta);
+        if (s->d_lta) pool_free(s->d_lta);
+        if (s->d_meta) pool_free(s->d_meta);
+        s->d_coef = s->d_sta = s->d_lta = nullptr;
+        s->d_meta = nullptr;
     }
     if (s->copy_stream) park_stream(s->e->device, s->copy_stream);
     s->copy_stream = nullptr;
@@ -148,7 +176,10 @@ int launch_slot(qm_stream *s) {
                     (unsigned long long)(e->have_lut ? e->serial : 0), e->have_lut ? e->g.n_rows : 0,
                     (unsigned long long)s->table_serial, s->n_rows);
     const size_t kns = (size_t)s->K * s->ns;
-    const size_t words = (size_t)n * step_in(s);
+    const bool signals = s->feed == qm_stream::kSignals;
+    const size_t words = (size_t)n * (signals ? step_sig(s) : step_in(s));
+    const double *h_in = signals ? sl.h_sig : sl.h_on;
+    double *d_in = signals ? sl.d_sig : sl.d_on;
     const bool pull = e->cfg_stream_pull > 0 || (e->cfg_stream_pull < 0 && words * sizeof(double) <= kPullBytes);
     // ("stream_stamps" = 1, measurement: the GPU's clock before and behind every launch -- two one-thread kernels;
     // the digest goes to stderr when the stream is destroyed.  What found round 6's one-off stall: tools/diag_stream.py)
@@ -163,17 +194,31 @@ int launch_slot(qm_stream *s) {
     if (pull) {
         const unsigned blocks = (unsigned)std::min<size_t>(4 * (size_t)e->n_cu, (words / 2 + 255) / 256 + 1);
         hipLaunchKernelGGL(pull_kernel, dim3(blocks), dim3(256), 0, e->stream,
-                           reinterpret_cast<const pull2 *>(sl.h_on), reinterpret_cast<pull2 *>(sl.d_on),
-                           words / 2, (const double *)sl.h_on, sl.d_on, words);
+                           reinterpret_cast<const pull2 *>(h_in), reinterpret_cast<pull2 *>(d_in),
+                           words / 2, h_in, d_in, words);
         QM_HIP(hipGetLastError());
     } else {
         if (!s->copy_stream && acquire_stream(e->device, &s->copy_stream) != hipSuccess)
             return fail("qm_stream: no HIP stream for the input copies");
-        QM_HIP(hipMemcpyAsync(sl.d_on, sl.h_on, words * sizeof(double), hipMemcpyHostToDevice, s->copy_stream));
+        QM_HIP(hipMemcpyAsync(d_in, h_in, words * sizeof(double), hipMemcpyHostToDevice, s->copy_stream));
         QM_HIP(hipEventRecord(sl.copied, s->copy_stream));
         QM_HIP(hipStreamWaitEvent(e->stream, sl.copied, 0));
     }
     s->pulled = pull;
+    if (signals) {
+        // waveforms -> log-onsets, all on the engine's stream: the n steps' traces filtered in place, then the onset
+        // kernels with (step, trace) as their trace and (step, row) as their row, straight into the slot's d_on
+        qm::PreprocArgs p = s->pre;
+        p.in = p.out = sl.d_sig;
+        p.skew = e->cfg_preproc_skew;
+        if (launch_preproc_stage(e, p, (int64_t)n * s->n_traces)) return 1;
+        qm::OnsetArgs o = s->on;
+        o.signals = sl.d_sig;
+        o.logged = sl.d_on;
+        o.n_traces = n * s->n_traces;
+        o.n_rows = n * s->n_rows;
+        if (launch_onset_stage(e, o)) return 1;
+    }
     // The results are a few KB per timestep: the combine kernel writes them STRAIGHT into the slot's
     // pinned host buffer (pinned memory is device-accessible under one address; the event behind the
     // launch makes them visible to the host) -- no D2H copy command, no third stream.  (With a copy on a
@@ -222,14 +267,14 @@ int replicas_flush(qm_stream *s) {
     return 0;
 }
 
-int replicas_push(qm_stream *s, const double *log_onsets) {
-    if (replicas_alive(s, "qm_stream_push")) return 1;
+int replicas_push(qm_stream *s, const double *step, bool signals) {
+    if (replicas_alive(s, signals ? "qm_stream_push_signals" : "qm_stream_push")) return 1;
     // (a full slot whose launch failed -- the table changed under the stream -- goes out first, as on one engine;
     // then this timestep goes to the next lane, not behind it on the same one)
     if (s->lanes[s->cur]->fill_n >= s->lanes[s->cur]->K && replicas_flush(s)) return 1;
     qm_stream *lane = s->lanes[s->cur];
     const int64_t before = lane->launched_steps;
-    const int rc = qm_stream_push(lane, log_onsets);
+    const int rc = signals ? qm_stream_push_signals(lane, step) : qm_stream_push(lane, step);
     if (lane->launched_steps != before) replicas_launched(s, lane->launched_steps - before);
     return rc;
 }
@@ -369,10 +414,21 @@ void qm_stream_destroy(qm_stream *s) {
     delete s;
 }
 
-int qm_stream_push(qm_stream *s, const double *log_onsets) {
-    if (!log_onsets) return fail("qm_stream_push: NULL argument");
-    if (s && !s->lanes.empty()) return replicas_push(s, log_onsets);
-    if (alive(s, "qm_stream_push")) return 1;
+// a timestep into the slot being filled: log-onsets, or (an onset stage) signals -- one kind per stream
+static int push_step(qm_stream *s, const double *step, int feed, const char *what) {
+    if (!step || !s) return fail("%s: NULL argument", what);
+    const bool replicated = !s->lanes.empty();          // (the kind of input is the whole stream's, not a lane's)
+    if (!replicated && alive(s, what)) return 1;
+    if (feed == qm_stream::kSignals && !s->staged)
+        return fail("qm_stream_push_signals: the stream has no onset stage (qm_stream_set_onset_stage)");
+    if (s->feed != qm_stream::kNothingYet && s->feed != feed)
+        return fail("%s: this stream takes %s: one stream, one kind of input", what,
+                    s->feed == qm_stream::kSignals ? "signals (qm_stream_push_signals)" : "log-onsets (qm_stream_push)");
+    if (replicated) {
+        const int rc = replicas_push(s, step, feed == qm_stream::kSignals);
+        if (rc == 0) s->feed = feed;
+        return rc;
+    }
     DeviceGuard guard(s->e->device);
     // A full slot whose launch FAILED (the table changed under the stream, no memory, a refused step) is still
     // waiting to go out: it goes first, or this call fails as that one did -- never a copy past the slot's
@@ -381,13 +437,109 @@ int qm_stream_push(qm_stream *s, const double *log_onsets) {
     if (s->fill_n >= s->K && launch_slot(s)) return 1;
     qm_stream::Slot &sl = s->slots[s->fill_slot];
     if (s->fill_n == 0 && sl.in_flight) {
-        (void)fail("qm_stream_push: all %d slots hold results that have not been popped", s->depth);
+        (void)fail("%s: all %d slots hold results that have not been popped", what, s->depth);
         return 2;
     }
+    s->feed = feed;
     // (the slot's previous H2D has finished: its launch's results were popped)
-    host_copy(sl.h_on + (size_t)s->fill_n * step_in(s), log_onsets, step_in(s) * sizeof(double));
+    if (feed == qm_stream::kSignals)
+        host_copy(sl.h_sig + (size_t)s->fill_n * step_sig(s), step, step_sig(s) * sizeof(double));
+    else
+        host_copy(sl.h_on + (size_t)s->fill_n * step_in(s), step, step_in(s) * sizeof(double));
     if (++s->fill_n < s->K) return 0;
     return launch_slot(s);
+}
+
+int qm_stream_push(qm_stream *s, const double *log_onsets) {
+    return push_step(s, log_onsets, qm_stream::kLogOnsets, "qm_stream_push");
+}
+
+int qm_stream_push_signals(qm_stream *s, const double *signals) {
+    return push_step(s, signals, qm_stream::kSignals, "qm_stream_push_signals");
+}
+
+int qm_stream_set_onset_stage(qm_stream *s, int32_t n_traces, const int32_t *trace_row, const int32_t *trace_filter,
+                              const double *sos, int32_t n_filters, int32_t n_sections, int detrend,
+                              const double *taper_left, int32_t n_left, const double *taper_right, int32_t n_right,
+                              const int32_t *nsta, const int32_t *nlta, int transform, int position,
+                              int32_t taper_pad, double min_onset_value) {
+    const char *what = "qm_stream_set_onset_stage";
+    if (!s || !trace_row || !nsta || !nlta) return fail("%s: NULL argument", what);
+    if (s->staged) return fail("%s: the stream has its onset stage already (it is set once)", what);
+    if (s->feed != qm_stream::kNothingYet || s->fill_n > 0 || s->launched_steps > 0)
+        return fail("%s: the stage is set before the first push", what);
+    if (!s->lanes.empty()) {
+        for (qm_stream *lane : s->lanes)
+            if (qm_stream_set_onset_stage(lane, n_traces, trace_row, trace_filter, sos, n_filters, n_sections, detrend,
+                                          taper_left, n_left, taper_right, n_right, nsta, nlta, transform, position,
+                                          taper_pad, min_onset_value))
+                return 1;
+        s->staged = true;
+        return 0;
+    }
+    if (alive(s, what)) return 1;
+    if (check_preproc(what, n_traces, s->T, trace_filter, sos, n_filters, n_sections, taper_left, n_left, taper_right,
+                      n_right))
+        return 1;
+    if (transform != 0 && transform != 1) return fail("transform must be 0 (energy) or 1 (abs)");
+    if (position < 0 || position > 2) return fail("position must be 0 (classic), 1 (centred) or 2 (recursive)");
+    const int n_rows = s->n_rows, K = s->K;
+    std::vector<int> per_row(n_rows, 0);
+    for (int i = 0; i < n_traces; ++i) {
+        if (trace_row[i] < 0 || trace_row[i] >= n_rows) return fail("%s: trace %d: row out of range", what, i);
+        ++per_row[trace_row[i]];
+    }
+    for (int r = 0; r < n_rows; ++r)
+        if (per_row[r] == 0) return fail("%s: onset row %d has no trace", what, r);
+    if ((int64_t)K * n_traces * s->T >= INT32_MAX || (int64_t)K * n_rows * s->T >= INT32_MAX)
+        return fail("%s: too many samples per launch", what);
+    qm_engine *e = s->e;
+    DeviceGuard guard(e->device);
+    // host images: everything K times, the rows of step k behind those of step k - 1
+    const size_t n_coef = (size_t)n_filters * n_sections * 6;
+    std::vector<double> coef(sos, sos + n_coef);
+    coef.insert(coef.end(), taper_left, taper_left + n_left);
+    coef.insert(coef.end(), taper_right, taper_right + n_right);
+    std::vector<int32_t> meta;
+    for (int k = 0; k < K; ++k) meta.insert(meta.end(), trace_filter, trace_filter + n_traces);
+    for (int k = 0; k < K; ++k)
+        for (int i = 0; i < n_traces; ++i) meta.push_back(k * n_rows + trace_row[i]);
+    for (int k = 0; k < K; ++k) meta.insert(meta.end(), nsta, nsta + n_rows);
+    for (int k = 0; k < K; ++k) meta.insert(meta.end(), nlta, nlta + n_rows);
+    s->n_traces = n_traces;
+    const size_t sig_bytes = (size_t)K * step_sig(s) * sizeof(double);
+    hipError_t r = pool_alloc(reinterpret_cast<void **>(&s->d_coef), coef.size() * sizeof(double));
+    if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&s->d_meta), meta.size() * sizeof(int32_t));
+    if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&s->d_sta), sig_bytes);
+    if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&s->d_lta), sig_bytes);
+    for (qm_stream::Slot &sl : s->slots) {
+        if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&sl.h_sig), sig_bytes, hipHostMallocDefault);
+        if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&sl.d_sig), sig_bytes);
+    }
+    if (r != hipSuccess)                                // (what was allocated goes back with the stream)
+        return fail("%s: %s (%d steps of %zu bytes per slot, %d slots)", what, hipGetErrorString(r), K,
+                    step_sig(s) * sizeof(double), s->depth);
+    QM_HIP(copy_in(s->d_coef, coef.data(), coef.size() * sizeof(double), e->stream));
+    QM_HIP(copy_in(s->d_meta, meta.data(), meta.size() * sizeof(int32_t), e->stream));
+    const size_t kt = (size_t)K * n_traces, kr = (size_t)K * n_rows;
+    s->pre = qm::PreprocArgs{};
+    s->pre.trace_filter = s->d_meta;
+    s->pre.sos = s->d_coef;
+    s->pre.taper_left = s->d_coef + n_coef;
+    s->pre.taper_right = s->d_coef + n_coef + n_left;
+    s->pre.T = s->T; s->pre.n_sections = n_sections; s->pre.n_left = n_left; s->pre.n_right = n_right;
+    s->pre.detrend = detrend ? 1 : 0; s->pre.zero_phase = 1;
+    s->on = qm::OnsetArgs{};
+    s->on.trace_row = s->d_meta + kt;
+    s->on.nsta = s->d_meta + 2 * kt;
+    s->on.nlta = s->d_meta + 2 * kt + kr;
+    s->on.sta = s->d_sta;
+    s->on.lta = s->d_lta;
+    s->on.T = s->T;
+    s->on.transform = transform; s->on.position = position; s->on.taper_pad = taper_pad;
+    s->on.min_onset_value = min_onset_value;
+    s->staged = true;
+    return 0;
 }
 
 int qm_stream_flush(qm_stream *s) {

@@ -43,6 +43,21 @@ int axis_taps(int n, double sgm, bool mirror, qm::Taps *t) {
 
 }  // namespace
 
+int launch_onset_stage(qm_engine *e, const qm::OnsetArgs &a) {
+    // one workgroup per trace; the transformed trace lives in LDS if it fits (20 480 samples)
+    const size_t lds = (size_t)a.T * sizeof(double);
+    const int in_lds = lds <= 160 * 1024 ? 1 : 0;
+    if (in_lds)
+        QM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&qm::stalta_sums_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(qm::stalta_sums_kernel, dim3(a.n_traces), dim3(256), in_lds ? lds : 0, e->stream, a, in_lds);
+    QM_HIP(hipGetLastError());
+    const size_t out = (size_t)a.n_rows * a.T;
+    hipLaunchKernelGGL(qm::onset_rows_kernel, dim3((unsigned)((out + 255) / 256)), dim3(256), 0, e->stream, a);
+    QM_HIP(hipGetLastError());
+    return 0;
+}
+
 extern "C" {
 
 int qm_engine_onsets(qm_engine *e, const double *signals, int signals_on_device,
@@ -100,20 +115,7 @@ int qm_engine_onsets(qm_engine *e, const double *signals, int signals_on_device,
     }
     a.raw = d_raw;
     a.logged = d_log;
-    {
-        // one workgroup per trace; the transformed trace lives in LDS if it fits (20 480 samples)
-        const size_t lds = (size_t)t_samples * sizeof(double);
-        const int in_lds = lds <= 160 * 1024 ? 1 : 0;
-        if (in_lds)
-            QM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&qm::stalta_sums_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(qm::stalta_sums_kernel, dim3(n_traces), dim3(256), in_lds ? lds : 0,
-                           e->stream, a, in_lds);
-        QM_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(qm::onset_rows_kernel, dim3((unsigned)((out + 255) / 256)), dim3(256), 0,
-                       e->stream, a);
-    QM_HIP(hipGetLastError());
+    if (launch_onset_stage(e, a)) return 1;
     if (!out_on_device) {
         QM_HIP(copy_back(log_onsets, d_log, out * sizeof(double), e->stream));
         if (raw_onsets)

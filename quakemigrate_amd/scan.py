@@ -301,6 +301,19 @@ class MigrationScan:
         pre-processes the next timestep; results reach the sink in timestep order.  A change of
         station availability (another served table) or a data gap drains the pipeline first.
 
+        Waveforms in: an onset plugin that offers ``device_stage(data) -> (signals, OnsetStage, onset_data)`` has
+        its detrend, taper, zero-phase band-pass and STA/LTA run on the GPU inside the pipeline's launch
+        (``StreamingDetector(..., onset_stage=...)``, ``qm_stream_push_signals``) instead of on the host per
+        timestep: ``signals`` are the resampled, not yet filtered, full-timespan traces of the available rows in
+        availability order, (n_traces, T) float64; the stage (``quakemigrate_amd.preprocess.OnsetStage``) names
+        their filters, windows and row layout.  The device stage covers gap-free traces of the full timespan only
+        (the reference's default, ``full_timespan=True, allow_gaps=False``): gappy traces (their second taper and
+        tiny-float padding, stalta.py:442-461), resampling and the ``env`` transforms stay on the host plugin
+        path -- ``device_stage`` returns ``None`` for a timestep it cannot describe and ``calculate_onsets`` is
+        called for it.  The new path is used on an ``Engine`` or ``EngineReplicas`` only; a group, and a plugin
+        without ``device_stage``, run as before.  A changed stage (other windows, filters or layout) makes a new
+        pipeline, as a changed table does.
+
         ``steps_per_launch``: None = 8 on grids of up to a million nodes (where one timestep is a
         fraction of a millisecond and a launch's fixed costs show: x1.04-1.09 of the resident step
         instead of x1.3-1.4), else 1; results do not depend on it.
@@ -370,9 +383,18 @@ class MigrationScan:
             w_beg = _shift(_shift(starttime, timestep * i), -self.pre_pad)
             w_end = _shift(_shift(starttime, timestep * (i + 1) - 1 / scan_rate), self.post_pad)
             logging.debug(f" Processing : {w_beg}-{w_end} ".center(110, "~"))
+            device_stage = getattr(self.onset, "device_stage", None)
+            if not callable(device_stage) or not isinstance(self.engine, (lib.Engine, lib.EngineReplicas)):
+                device_stage = None
             try:
                 data = archive.read_waveform_data(w_beg, w_end)
-                onsets, onset_data = self.onset.calculate_onsets(data)
+                staged = device_stage(data) if device_stage is not None else None
+                if staged is not None:                   # waveforms in: the onsets are made in the launch
+                    signals, stage, onset_data = staged
+                    onsets = None
+                else:
+                    stage = None
+                    onsets, onset_data = self.onset.calculate_onsets(data)
             except Exception as e:  # noqa: BLE001
                 if not _is_no_data(e):
                     raise
@@ -390,12 +412,19 @@ class MigrationScan:
             fsmp = time2sample(self.pre_pad, onset_data.sampling_rate)
             lsmp = time2sample(self.post_pad, onset_data.sampling_rate)
             avail = int(np.sum([value for _, value in onset_data.availability.items()]))
-            onsets = np.ascontiguousarray(np.log(np.clip(onsets, 0.01, np.inf)))      # lib.py:93-94
-            n_onsets, t_samples = onsets.shape
+            if stage is not None:
+                signals = np.ascontiguousarray(signals, dtype=np.float64)
+                if signals.ndim != 2 or signals.shape[0] != stage.n_traces:
+                    raise ValueError(f"device_stage: signals of shape {signals.shape} for a stage of "
+                                     f"{stage.n_traces} traces")
+                n_onsets, t_samples = stage.n_rows, signals.shape[1]
+            else:
+                onsets = np.ascontiguousarray(np.log(np.clip(onsets, 0.01, np.inf)))      # lib.py:93-94
+                n_onsets, t_samples = onsets.shape
             if n_onsets != eng.n_rows:
                 raise ValueError("Mismatch between number of stations for data and LUT, "
                                  f"{n_onsets}:{eng.n_rows}")
-            if onsets.size < t_samples - lsmp:
+            if n_onsets * t_samples < t_samples - lsmp:
                 raise ValueError("Data array smaller than coalescence array.")
             # (an Engine or EngineReplicas goes through the native pipeline below -- over every replica for the
             # latter; a group: one timestep after the other, no pipeline)
@@ -404,17 +433,19 @@ class MigrationScan:
                 sink.append(_shift(data.starttime, self.pre_pad), a, b, self.lut.index2coord(c, unravel=True), ucf)
                 rows.append(dict(onset_data.availability))
                 continue
-            key = (self._resident_key, t_samples, fsmp, lsmp, avail)
-            if key != state["key"]:                      # another table or window shape: a new pipeline
+            key = (self._resident_key, t_samples, fsmp, lsmp, avail, stage)
+            if key != state["key"]:                      # another table, window shape or onset stage: a new pipeline
                 drain()
                 if state["stream"] is not None:
                     state["stream"].close()
                 k = steps_per_launch if steps_per_launch else (8 if eng.n_nodes <= 1_000_000 else 1)
                 state["stream"] = StreamingDetector(eng, n_onsets, t_samples, fsmp, lsmp, avail,
-                                                    depth=depth, steps_per_launch=k)
+                                                    depth=depth, steps_per_launch=k, onset_stage=stage,
+                                                    sampling_rate=onset_data.sampling_rate)
                 state["key"] = key
             stream = state["stream"]
-            while not stream.push(onsets):
+            push, window = (stream.push, onsets) if stage is None else (stream.push_signals, signals)
+            while not push(window):
                 emit(min(stream.k, stream.pending()[0]))
             pending.append((_shift(data.starttime, self.pre_pad), onset_data))
             rows.append(dict(onset_data.availability))

@@ -43,10 +43,16 @@ class StreamingDetector:
         fraction of a millisecond, and K steps per launch are what fills the GPU and amortises the
         launch, the combine and the copies' latencies.  Results are identical step for step.
     device : accepted for compatibility with round 4's signature; the engine's device is used.
+    onset_stage : ``None`` -- the windows are log-onsets (``push``) -- or the stage that makes them on the device
+        from resampled component traces (``push_signals``): a :class:`quakemigrate_amd.preprocess.OnsetStage`
+        (then ``sampling_rate`` is needed) or the dict its ``arrays(t_samples, sampling_rate)`` returns.  A slot's
+        launch is then pre-processing (detrend, taper, zero-phase band-pass) -> onsets -> fused detect, every
+        timestep's bits those of ``Engine.detect(Engine.onsets(Engine.preprocess(x)))``.  A stream takes one kind
+        of window, never both.
     """
 
     def __init__(self, engine, n_rows, t_samples, fsmp, lsmp, available, n_nodes_total=None,
-                 depth=2, device=None, steps_per_launch=1):
+                 depth=2, device=None, steps_per_launch=1, onset_stage=None, sampling_rate=None):
         if engine.n_rows is None:
             raise _lib.QMHipError("no travel-time table resident: call load_lut first")
         if int(n_rows) != engine.n_rows:
@@ -72,6 +78,34 @@ class StreamingDetector:
         import weakref
 
         self._finalizer = weakref.finalize(self, _qm.qm_stream_destroy, h)
+        self.n_traces = None
+        if onset_stage is not None:
+            self.set_onset_stage(onset_stage, sampling_rate)
+
+    def set_onset_stage(self, onset_stage, sampling_rate=None):
+        """Once, before the first push (``qm_stream_set_onset_stage``)."""
+        if hasattr(onset_stage, "arrays"):
+            if sampling_rate is None:
+                raise ValueError("an OnsetStage needs the sampling_rate of the windows")
+            onset_stage = onset_stage.arrays(self.t_samples, sampling_rate)
+        a = onset_stage
+        i32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)     # noqa: E731
+        f64 = lambda x: np.ascontiguousarray(x, dtype=np.float64)   # noqa: E731
+        trace_row, trace_filter = i32(a["trace_row"]), i32(a["trace_filter"])
+        nsta, nlta = i32(a["nsta"]), i32(a["nlta"])
+        sos = f64(a["sos"])
+        left, right = f64(a["taper_left"]).reshape(-1), f64(a["taper_right"]).reshape(-1)
+        if sos.ndim != 3 or sos.shape[2] != 6:
+            raise ValueError(f"sos of shape {sos.shape}: (n_filters, n_sections, 6) expected")
+        if trace_filter.shape != trace_row.shape or trace_row.ndim != 1:
+            raise ValueError("trace_row and trace_filter: one entry per trace each")
+        if nsta.shape != (self.n_rows,) or nlta.shape != (self.n_rows,):
+            raise ValueError(f"nsta / nlta: one entry per onset row ({self.n_rows}) each")
+        _lib._check(_qm.qm_stream_set_onset_stage(
+            self._h, len(trace_row), trace_row, trace_filter, sos.reshape(-1), int(sos.shape[0]), int(sos.shape[1]),
+            int(a.get("detrend", 1)), left, len(left), right, len(right), nsta, nlta, int(a["transform"]),
+            int(a["position"]), int(a["taper_pad"]), float(a["min_onset_value"])))
+        self.n_traces = len(trace_row)
 
     def close(self):
         self._finalizer()
@@ -84,6 +118,18 @@ class StreamingDetector:
         if w.shape != (self.n_rows, self.t_samples):
             raise ValueError(f"window of shape {w.shape}, the stream takes {(self.n_rows, self.t_samples)}")
         rc = _qm.qm_stream_push(self._h, w.ctypes.data_as(ctypes.c_void_p))
+        if rc == 2:
+            return False
+        _lib._check(rc)
+        return True
+
+    def push_signals(self, window):
+        """One timestep's resampled component traces (n_traces, t_samples) into a pipeline with an onset stage;
+        returns like :meth:`push`."""
+        w = np.ascontiguousarray(window, dtype=np.float64)
+        if self.n_traces is not None and w.shape != (self.n_traces, self.t_samples):
+            raise ValueError(f"window of shape {w.shape}, the stage takes {(self.n_traces, self.t_samples)}")
+        rc = _qm.qm_stream_push_signals(self._h, w.ctypes.data_as(ctypes.c_void_p))
         if rc == 2:
             return False
         _lib._check(rc)
@@ -111,8 +157,8 @@ class StreamingDetector:
     # -- the loop -----------------------------------------------------------------------
     def run(self, windows, on_result=None):
         """
-        ``windows``: iterable of float64 arrays (n_rows, t_samples), one per timestep, already
-        logged.  Returns a list of ``(max_coa, max_norm_coa, max_coa_idx)`` NumPy triples (or
+        ``windows``: iterable of float64 arrays, one per timestep: (n_rows, t_samples), already logged --
+        or, on a stream with an onset stage, (n_traces, t_samples) resampled component traces.  Returns a list of ``(max_coa, max_norm_coa, max_coa_idx)`` NumPy triples (or
         calls ``on_result(step, triple)`` and returns the number of steps).
         """
         results = []
@@ -129,8 +175,9 @@ class StreamingDetector:
                     on_result(step, triple)
                 step += 1
 
+        push = self.push if self.n_traces is None else self.push_signals
         for w in windows:
-            while not self.push(w):
+            while not push(w):
                 take(min(self.k, self.pending()[0]))     # the oldest launch's timesteps
         self.flush()
         left = self.pending()[0]

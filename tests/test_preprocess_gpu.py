@@ -1,0 +1,434 @@
+# -*- coding: utf-8 -*-
+"""
+The pre-processing stage on the GPU (qm_engine_preprocess, qm_stream_set_onset_stage / qm_stream_push_signals,
+MigrationScan.continuous_compute's device stage) against its NumPy restatement, tests/preprocess_ref.py.
+
+Inputs are seeded Gaussian noise of amplitude ~1e3 on a ramp and an offset (no dead traces).  The filter alone is
+held to the restatement's bits -- which are scipy.signal.sosfilt's (tests/test_preprocess_host.py); the whole stage
+to a bound derived from the detrend sums' rounding and the filter's l1 gain.
+"""
+
+import numpy as np
+import pytest
+
+import preprocess_ref as pr
+
+pytestmark = pytest.mark.gpu
+
+LDS_SAMPLES = 20480
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from quakemigrate_amd.core import lib as _lib
+
+    if _lib.qmlib.qm_device_count() < 1:
+        pytest.fail("no HIP device visible")
+    return _lib
+
+
+@pytest.fixture(scope="module")
+def engine(lib):
+    eng = lib.Engine(0)
+    yield eng
+    eng.close()
+
+
+def stable_sos(seed, n_filters, n_sections):
+    """Random stable sections, a0 == 1: complex pole pairs of radius 0.5-0.95, arbitrary zeros, gains near 1."""
+    rng = np.random.default_rng(seed)
+    r = rng.uniform(0.5, 0.95, size=(n_filters, n_sections))
+    th = rng.uniform(0.2, 2.9, size=(n_filters, n_sections))
+    sos = np.empty((n_filters, n_sections, 6))
+    sos[..., :3] = rng.uniform(-1.0, 1.0, size=(n_filters, n_sections, 3))
+    sos[..., 3] = 1.0
+    sos[..., 4] = -2.0 * r * np.cos(th)
+    sos[..., 5] = r * r
+    return sos
+
+
+TRACE_FILTER = np.array([0, 1, 0, 1, 0], dtype=np.int32)        # 5 traces, 2 filters, no filter's traces adjacent
+
+
+# -- 1. the filter alone, bit for bit ------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_sections", [1, 2, 4, 8])
+def test_filter_alone_is_the_restatement_bit_for_bit(engine, n_sections):
+    sos = stable_sos(n_sections, 2, n_sections)
+    try:
+        for T in (1, 2, 63, 64, 65, 301, 2049):
+            x = pr.noisy_traces(1000 * n_sections + T, 5, T)
+            for zero_phase in (False, True):
+                want = pr.preprocess(x, TRACE_FILTER, sos, detrend_on=False, zero_phase=zero_phase)
+                got = {}
+                for skew in (1, 0):
+                    engine.config("preproc_skew", skew)
+                    got[skew] = engine.preprocess(x, TRACE_FILTER, sos, detrend=False, zero_phase=zero_phase)
+                    assert np.array_equal(got[skew], want), (T, zero_phase, skew,
+                                                             float(np.max(np.abs(got[skew] - want))))
+                assert got[0].tobytes() == got[1].tobytes(), (T, zero_phase)
+    finally:
+        engine.config("preproc_skew", 1)
+
+
+def test_filter_of_a_trace_above_the_lds_limit(engine):
+    T = LDS_SAMPLES + 1
+    sos = stable_sos(77, 2, 2)
+    x = pr.noisy_traces(77, 2, T)
+    tf = np.array([1, 0], dtype=np.int32)
+    want = pr.preprocess(x, tf, sos, detrend_on=False, zero_phase=True)
+    try:
+        for skew in (1, 0):
+            engine.config("preproc_skew", skew)
+            got = engine.preprocess(x, tf, sos, detrend=False, zero_phase=True)
+            assert np.array_equal(got, want), (skew, float(np.max(np.abs(got - want))))
+    finally:
+        engine.config("preproc_skew", 1)
+
+
+# -- 2. the whole stage --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("T", [301, 2049])
+def test_whole_stage_against_the_restatement(engine, T):
+    """
+    Tolerance ||h||_1^2 * 4 T 2^-53 max|x| with h the restated forward filter's response to a unit impulse over T
+    samples: the detrend's sums carry at most T eps relative error in any order, and a linear filter (run twice)
+    amplifies a perturbation of its input by at most its l1 gain (squared).  The figures are printed before they are
+    asserted.
+    Observed maximum on an MI355X: not measured yet (each case prints its figure: run with ``-s``).
+    """
+    pytest.importorskip("scipy.signal")
+    from quakemigrate_amd.preprocess import butter_bandpass_sos
+
+    sos = np.stack([butter_bandpass_sos(2.0, 16.0, 50, 2), butter_bandpass_sos(2.0, 12.0, 50, 2)])
+    gain = max(pr.impulse_l1(sos[f], T) for f in range(2)) ** 2
+    x = pr.noisy_traces(T, 5, T)
+    t = np.arange(T, dtype=np.float64)
+    x[2] = 0.75 * t - 4321.0                                     # a pure ramp plus offset
+    tol = gain * 4 * T * 2.0 ** -53 * np.max(np.abs(x))
+    rng = np.random.default_rng(T)
+    for m in (0, 15, T // 2):
+        left, right = np.sort(rng.uniform(0, 1, m)), np.sort(rng.uniform(0, 1, m))[::-1].copy()
+        want = pr.preprocess(x, TRACE_FILTER, sos, left, right, detrend_on=True, zero_phase=True)
+        got = engine.preprocess(x, TRACE_FILTER, sos, taper=(left, right), detrend=True, zero_phase=True)
+        err = float(np.max(np.abs(got - want)))
+        ramp = float(np.max(np.abs(got[2])))
+        print(f"T = {T}, taper {m}: max |device - restatement| = {err:.3e}, ramp residue {ramp:.3e}, "
+              f"tolerance {tol:.3e} (l1 gain squared {gain:.3f})")
+        assert err <= tol
+        assert ramp <= tol
+
+
+# -- 3. device-resident in and out, scratch reuse --------------------------------------------------------------------
+def test_device_resident_equals_host_and_a_reused_engine_equals_a_fresh_one(lib, engine):
+    import torch
+
+    sos = stable_sos(5, 2, 3)
+    shapes = [(5, 301), (5, 2049), (5, 64)]                     # growing, then shrinking: the scratch is reused
+    left, right = np.linspace(0, 1, 15, endpoint=False), np.linspace(1, 0, 15, endpoint=False)
+    for k, (n, T) in enumerate(shapes):
+        x = pr.noisy_traces(31 + k, n, T)
+        host = engine.preprocess(x, TRACE_FILTER, sos, taper=(left, right))
+        d_in = torch.from_numpy(x).to(f"cuda:{engine.device}")
+        d_out = torch.empty_like(d_in)
+        engine.preprocess(d_in, TRACE_FILTER, sos, taper=(left, right), out=d_out)
+        engine.synchronize()
+        assert np.array_equal(d_out.cpu().numpy(), host), (n, T)
+        fresh = lib.Engine(engine.device)
+        try:
+            assert np.array_equal(fresh.preprocess(x, TRACE_FILTER, sos, taper=(left, right)), host), (n, T)
+        finally:
+            fresh.close()
+
+
+# -- 4. the pipeline equals the staged calls ---------------------------------------------------------------------------
+N_STEPS = 7
+TRACE_ROW = np.array([0, 1, 2, 3, 3, 4, 4, 5, 5], dtype=np.int32)       # 6 rows (3 P, 3 S), 9 traces
+TRACE_PHASE = tuple("PPPSSSSSS")
+
+
+def _stage(T, rate=50):
+    from quakemigrate_amd.preprocess import OnsetStage
+
+    stage = OnsetStage(filters={"P": (2.0, 16.0, 2), "S": (2.0, 12.0, 2)},
+                       sta_lta_windows={"P": (0.2, 1.0), "S": (0.3, 1.5)}, trace_row=TRACE_ROW,
+                       trace_phase=TRACE_PHASE, row_phase=tuple("PPPSSS"), taper_pad=20)
+    return stage, stage.arrays(T, rate)
+
+
+def _signals(case, steps):
+    """Component traces whose bursts follow the case's arrivals: noise ~1e3 on a ramp and an offset."""
+    T = case.onsets.shape[1]
+    out = []
+    for k in range(steps):
+        x = pr.noisy_traces(900 + k, len(TRACE_ROW), T)
+        rng = np.random.default_rng(70 + k)
+        for i, row in enumerate(TRACE_ROW):
+            peak = int(np.argmax(case.onsets[row]))
+            n = min(40, T - peak)
+            x[i, peak:peak + n] += 2e4 * rng.standard_normal(n) * np.exp(-np.arange(n) / 12.0)
+        out.append(x)
+    return out
+
+
+def _staged(engine, a, case, x):
+    T = x.shape[1]
+    f = engine.preprocess(x, a["trace_filter"], a["sos"], taper=(a["taper_left"], a["taper_right"]))
+    _, logged = engine.onsets(f, a["trace_row"], a["nsta"], a["nlta"], transform="energy", position="classic",
+                              taper_pad=a["taper_pad"], min_onset_value=a["min_onset_value"])
+    return engine.detect(logged, case.fsmp, case.lsmp, case.available)
+
+
+@pytest.fixture(scope="module", params=["C3", "C2"], ids=["coherent", "incoherent"])
+def pipeline_case(request, lib):
+    from quakemigrate_amd import synth
+
+    case = synth.make_case(request.param, step=1, grid=(16, 16, 16), rows=6, n_samples=120)
+    T = case.onsets.shape[1]
+    stage, a = _stage(T)
+    signals = _signals(case, N_STEPS)
+    eng = lib.Engine(0)
+    eng.load_lut(case.traveltimes)
+    want = [tuple(np.array(s) for s in _staged(eng, a, case, x)) for x in signals]
+    eng.close()
+    return case, stage, signals, want
+
+
+@pytest.mark.parametrize("replicas", [False, True], ids=["engine", "replicas"])
+@pytest.mark.parametrize("K", [1, 2, 5])
+def test_pipeline_equals_the_staged_calls(lib, pipeline_case, K, replicas):
+    from quakemigrate_amd.stream import StreamingDetector
+
+    case, stage, signals, want = pipeline_case
+    T = case.onsets.shape[1]
+    eng = lib.EngineReplicas([0, 0]) if replicas else lib.Engine(0)
+    try:
+        eng.load_lut(case.traveltimes)
+        if K == 2:
+            eng.config("stream_pull", 0)                        # (slots this small are pulled: the copy stream as well)
+        det = StreamingDetector(eng, 6, T, case.fsmp, case.lsmp, case.available, depth=2, steps_per_launch=K,
+                                onset_stage=stage, sampling_rate=50)
+        got = det.run(signals)                                  # (7 steps: the last slot goes out partly filled)
+        det.close()
+    finally:
+        eng.close()
+    assert len(got) == N_STEPS
+    for step, (g, w) in enumerate(zip(got, want)):
+        for name, gs, ws in zip(("max_coa", "max_norm_coa", "max_coa_idx"), g, w):
+            assert np.array_equal(gs, ws), (step, name)
+    assert np.ptp(want[0][0]) > 0                               # (not a flat series)
+
+
+# -- 5. refusals --------------------------------------------------------------------------------------------------------
+def test_refusals_are_errors(lib, pipeline_case):
+    from quakemigrate_amd.stream import StreamingDetector
+
+    case, stage, signals, _ = pipeline_case
+    T = case.onsets.shape[1]
+    _, a = _stage(T)
+    eng = lib.Engine(0)
+    try:
+        eng.load_lut(case.traveltimes)
+        logged = np.log(np.clip(case.onsets, 0.01, np.inf))
+
+        def detector(**kw):
+            return StreamingDetector(eng, 6, T, case.fsmp, case.lsmp, case.available, depth=2, steps_per_launch=2,
+                                     **kw)
+
+        det = detector(onset_stage=a)                           # signals first, then log-onsets
+        assert det.push_signals(signals[0])
+        with pytest.raises(lib.QMHipError, match="one kind of input"):
+            det.push(logged)
+        with pytest.raises(lib.QMHipError, match="already"):    # the stage twice
+            det.set_onset_stage(a)
+        det.close()
+
+        det = detector(onset_stage=a)                           # log-onsets first, then signals
+        assert det.push(logged)
+        with pytest.raises(lib.QMHipError, match="one kind of input"):
+            det.push_signals(signals[0])
+        det.close()
+
+        det = detector()                                        # no stage
+        with pytest.raises(lib.QMHipError, match="no onset stage"):
+            det.push_signals(signals[0])
+        assert det.push(logged)
+        with pytest.raises(lib.QMHipError, match="before the first push"):
+            det.set_onset_stage(a)
+        det.flush()
+        det.pop(1)
+        det.close()
+
+        det = detector()
+        orphan = dict(a, trace_row=np.where(a["trace_row"] == 2, 1, a["trace_row"]).astype(np.int32))
+        with pytest.raises(lib.QMHipError, match="row 2 has no trace"):
+            det.set_onset_stage(orphan)
+        nine = dict(a, sos=stable_sos(9, 2, 9))
+        with pytest.raises(lib.QMHipError, match="n_sections"):
+            det.set_onset_stage(nine)
+        det.set_onset_stage(a)                                  # (a refused stage leaves the stream usable)
+        assert det.push_signals(signals[0])
+        det.flush()
+        det.pop(1)
+        det.close()
+
+        reps = lib.EngineReplicas([0, 0])                       # the kind of input is the stream's, not a lane's
+        try:
+            reps.load_lut(case.traveltimes)
+            det = StreamingDetector(reps, 6, T, case.fsmp, case.lsmp, case.available, depth=2, steps_per_launch=1,
+                                    onset_stage=a)
+            assert det.push_signals(signals[0])                 # (launched on lane 0; lane 1 is next)
+            with pytest.raises(lib.QMHipError, match="one kind of input"):
+                det.push(logged)
+            with pytest.raises(lib.QMHipError, match="already"):
+                det.set_onset_stage(a)
+            det.pop(1)
+            det.close()
+        finally:
+            reps.close()
+
+        x = signals[0]
+        with pytest.raises(lib.QMHipError, match="n_sections"):
+            eng.preprocess(x, a["trace_filter"], stable_sos(9, 2, 9))
+        with pytest.raises(lib.QMHipError, match="out of range"):
+            eng.preprocess(x, np.full(len(x), 2, dtype=np.int32), a["sos"])
+        with pytest.raises(lib.QMHipError, match="tapers cover"):
+            eng.preprocess(x, a["trace_filter"], a["sos"], taper=(np.ones(T // 2 + 1), np.ones(T // 2 + 1)))
+        bad = a["sos"].copy()
+        bad[1, 0, 3] = 2.0
+        with pytest.raises(lib.QMHipError, match="a0"):
+            eng.preprocess(x, a["trace_filter"], bad)
+    finally:
+        eng.close()
+
+
+# -- 6. continuous_compute: the device stage against the host plugin path ----------------------------------------------
+RATE = 50
+PRE_PAD, TIMESTEP = 2.0, 3.0
+CC_STEPS = 5
+
+
+class _Data:
+    def __init__(self, starttime, signals):
+        self.starttime, self.signals = starttime, signals
+
+
+class _OnsetData:
+    def __init__(self, availability):
+        self.sampling_rate, self.availability = RATE, availability
+
+
+class _Archive:
+    """Gap-free component traces per window: noise ~1e3 on a ramp and an offset, and one event per timestep whose
+    bursts follow the table's arrivals at a node of that timestep."""
+
+    def __init__(self, case, post_pad):
+        self.case, self.post_pad = case, post_pad
+        self.tt = case.traveltimes.reshape(-1, case.traveltimes.shape[-1])
+
+    def read_waveform_data(self, w_beg, w_end):
+        T = int(round((w_end - w_beg) * RATE)) + 1
+        step = int(round((w_beg + PRE_PAD) / TIMESTEP))
+        x = pr.noisy_traces(4000 + step, len(TRACE_ROW), T)
+        rng = np.random.default_rng(5000 + step)
+        node = int(rng.integers(0, self.tt.shape[0]))
+        t0 = int(PRE_PAD * RATE) + int(rng.integers(20, int(TIMESTEP * RATE) - 20))
+        for i, row in enumerate(TRACE_ROW):
+            at = t0 + int(self.tt[node, row])
+            n = min(50, T - at)
+            x[i, at:at + n] += 3e4 * rng.standard_normal(n) * np.exp(-np.arange(n) / 15.0)
+        return _Data(w_beg, x)
+
+
+class _HostPlugin:
+    """calculate_onsets on the host: the restated pre-processing, then the oracle's onset stage."""
+
+    def __init__(self, stage, T):
+        self.stage, self.a = stage, stage.arrays(T, RATE)
+        self.availability = {f"ST{r % 3}_{'PS'[r // 3]}": 1 for r in range(6)}
+        self.raw = []
+
+    def calculate_onsets(self, data):
+        from oracle import qm_oracle
+
+        a = self.a
+        f = pr.preprocess(data.signals, a["trace_filter"], a["sos"], a["taper_left"], a["taper_right"])
+        raw, _ = qm_oracle.np_onset_stage(f, a["trace_row"], a["nsta"], a["nlta"], transform="energy",
+                                          position="classic", taper_pad=a["taper_pad"],
+                                          min_onset_value=a["min_onset_value"])
+        self.raw.append(raw)
+        return raw, _OnsetData(self.availability)
+
+
+class _DevicePlugin(_HostPlugin):
+    def device_stage(self, data):
+        return data.signals, self.stage, _OnsetData(self.availability)
+
+
+class _Lut:
+    def __init__(self, case):
+        self.case = case
+
+    def serve_traveltimes(self, sampling_rate, availability):
+        return self.case.traveltimes
+
+    def index2coord(self, idx, unravel=True):
+        return np.column_stack(np.unravel_index(np.asarray(idx), self.case.grid))
+
+
+class _Sink:
+    written = False
+
+    def __init__(self):
+        self.steps = []
+
+    def append(self, time, max_coa, max_coa_n, coord, ucf):
+        self.steps.append((time, np.array(max_coa), np.array(max_coa_n), np.array(coord)))
+
+    def empty(self, *args):
+        raise AssertionError("no timestep of this archive is empty")
+
+    def write(self):
+        self.written = True
+
+
+def test_continuous_compute_device_stage_equals_the_host_plugin_path(lib, oracle):
+    """
+    Values within the project's 1e-6 relative contract; node indices equal on every sample where the host path's two
+    largest node values differ by more than 1e-9 relative -- at most 1 % of the samples may lie under that gap
+    (asserted on the host path alone, computed with the oracle from the host plugin's onsets).
+    """
+    pytest.importorskip("scipy.signal")
+    from quakemigrate_amd import synth
+    from quakemigrate_amd.scan import MigrationScan
+
+    case = synth.make_case("C3", step=2, grid=(16, 16, 16), rows=6, n_samples=int(TIMESTEP * RATE))
+    fsmp, lsmp = int(PRE_PAD * RATE), case.lsmp
+    post_pad = lsmp / RATE
+    T = fsmp + int(TIMESTEP * RATE) + lsmp
+    stage, _ = _stage(T, RATE)
+    stage = __import__("dataclasses").replace(stage, taper_pad=10)
+    runs = {}
+    for name, plugin in (("host", _HostPlugin(stage, T)), ("device", _DevicePlugin(stage, T))):
+        eng = lib.Engine(0)
+        try:
+            sink = _Sink()
+            scan = MigrationScan(_Lut(case), plugin, PRE_PAD, post_pad, engine=eng)
+            rows = scan.continuous_compute(_Archive(case, post_pad), 0.0, CC_STEPS, TIMESTEP, RATE, sink,
+                                           steps_per_launch=2, depth=2)
+        finally:
+            eng.close()
+        assert len(rows) == CC_STEPS and len(sink.steps) == CC_STEPS and sink.written
+        runs[name] = (sink.steps, plugin)
+    assert len(runs["host"][1].raw) == CC_STEPS and not runs["device"][1].raw      # (the device run made no host onsets)
+    under = total = 0
+    for step, (h, d) in enumerate(zip(runs["host"][0], runs["device"][0])):
+        assert h[0] == d[0]
+        np.testing.assert_allclose(d[1], h[1], rtol=1e-6)
+        np.testing.assert_allclose(d[2], h[2], rtol=1e-6)
+        vol = oracle.c_migrate(runs["host"][1].raw[step], case.traveltimes, fsmp, lsmp, 6, threads=4)
+        top = np.partition(vol.reshape(-1, vol.shape[-1]), -2, axis=0)[-2:]
+        clear = (top[1] - top[0]) > 1e-9 * top[1]
+        under += int(np.sum(~clear))
+        total += clear.size
+        assert np.array_equal(d[3][clear], h[3][clear]), step
+    print(f"samples under the 1e-9 gap on the host path: {under} of {total}")
+    assert under <= 0.01 * total
