@@ -8,9 +8,10 @@ time of the maximum as the origin time, drops the event if its trigger time is n
 marginal_window``, trims the map to that window, marginalises it over time and fits three locations.
 ``MigrationScan(stage="locate").locate_compute`` is that loop with the same plugin objects and the same
 rules -- without the 4-D map: one fused detect launch over the event's window fixes the origin time, one
-marginal-map launch sums the window inside the stacking kernel.  Picking, magnitudes and the event files
-remain the reference's (``on_event`` is where they would be called).  Everything here is synthetic and
-obspy-free.
+marginal-map launch sums the window inside the stacking kernel.  With a ``picker`` the phase picks follow on the
+engine too (``quakemigrate_amd.picks.DevicePicker`` for the reference's ``GaussianPicker``: one launch over the
+event's onset rows).  Magnitudes and the event files remain the reference's (``on_event`` is where they would be
+called).  Everything here is synthetic and obspy-free.
 
 Run:  python examples/locate_events.py
 """
@@ -25,13 +26,15 @@ ROOT = pathlib.Path(__file__).resolve().parent.parent
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
-from quakemigrate_amd import scan, synth  # noqa: E402
+from quakemigrate_amd import picks, scan, synth  # noqa: E402
 
 
-def run(grid=(36, 32, 20), rows=12, rate=50, marginal_window=1.0, n_events=5):
+def run(grid=(36, 32, 20), rows=12, rate=50, marginal_window=1.0, n_events=5, with_picker=True,
+        on_event=None):
     """``n_events`` synthetic events, one per trigger, each somewhere inside a 12-s record; the trigger
     times are what a detect run would hand over: within a fraction of the marginal window of the truth.
-    (The third record ends too early for its event's window: the archive raises, the event is dropped.)"""
+    (The third record ends too early for its event's window: the archive raises, the event is dropped.)
+    ``with_picker=False`` stops after the location fits; ``on_event`` is handed to ``locate_compute``."""
     mw, spacing = marginal_window, 0.5
     n_win = int(4 * mw * rate) + 1
     cases = [synth.make_case("C3", step=10 + s, grid=grid, rows=rows, n_samples=600, n_events=1,
@@ -66,12 +69,31 @@ def run(grid=(36, 32, 20), rows=12, rate=50, marginal_window=1.0, n_events=5):
         sampling_rate = rate
         availability = dict.fromkeys(keys, 1)
 
+        def __init__(self, starttime):
+            self.starttime = starttime
+
     class Onset:
-        def calculate_onsets(self, data):
-            return data.onsets, OnsetData()
+        taper_pad = 10                                      # samples of either end a taper would have touched
+
+        def calculate_onsets(self, data, timespan=None):
+            onsets = data.onsets
+            if timespan:                                    # the picker's call: un-logged, taper windows set to 1
+                onsets = onsets.copy()
+                onsets[:, :self.taper_pad] = 1.0
+                onsets[:, onsets.shape[1] - self.taper_pad:] = 1.0
+            return onsets, OnsetData(data.starttime)
+
+        def gaussian_halfwidth(self, phase):                # samples (the reference: half a short-term window)
+            return 5.0 if phase == "P" else 7.5
 
     class Lut:
         node_spacing = np.array([spacing] * 3)
+        fraction_tt = 0.1
+
+        def traveltime_to(self, phase, ijk, station):       # homogeneous velocities: no interpolation needed
+            row = keys.index(f"{station}_{phase}")
+            xyz = np.asarray(ijk, dtype=np.float64) * spacing
+            return np.array([np.sqrt(((c0.stations[row] - xyz) ** 2).sum()) / c0.velocities[row]])
 
         def serve_traveltimes(self, sampling_rate, availability):
             return c0.traveltimes
@@ -80,7 +102,8 @@ def run(grid=(36, 32, 20), rows=12, rate=50, marginal_window=1.0, n_events=5):
             return np.stack(np.unravel_index(idx, grid), axis=-1) * spacing
 
     s = scan.MigrationScan(Lut(), Onset(), pre, post, stage="locate", scan_rate=rate)
-    located = s.locate_compute(Archive(), triggers, mw)
+    located = s.locate_compute(Archive(), triggers, mw, on_event=on_event,
+                               picker=picks.DevicePicker(s.onset) if with_picker else None)
     assert all(r["max_coa"].shape[0] <= n_win for r in located)
     return located, truth, record_start, rate
 
@@ -94,3 +117,10 @@ if __name__ == "__main__":
         print(f"{r['uid']}: origin sample {origin:.0f} (truth {t0}), spline node {np.round(r['fits'].spline, 2)}, "
               f"gaussian {np.round(r['fits'].gaussian, 2)} (truth {node}), "
               f"marginal window {r['last_sample'] - r['first_sample']} samples")
+        p = r["picks"]
+        for i in range(len(p["Station"])):
+            made = (f"pick {(p['PickTime'][i] - start).total_seconds():.3f} s +/- {p['PickError'][i]:.3f} s, SNR "
+                    f"{p['SNR'][i]:.1f}, residual {p['Residual'][i]:+.3f} s" if p["status"][i] == 0
+                    else f"no pick (status {p['status'][i]})")
+            print(f"    {p['Station'][i]} {p['Phase'][i]}: modelled "
+                  f"{(p['ModelledTime'][i] - start).total_seconds():.3f} s, {made}")

@@ -205,7 +205,8 @@ int qm_engine_synchronize(qm_engine *e);
  * last_candidates, screen_brick_nodes; tie_refined_steps, tie_pairs and tie_overflow_samples (of the last
  * refined launch), tie_brick_rows (rows of per-brick maxima the last stacking launch left: 0 = it refined from
  * sets of bricks);
- * table_hits, table_misses, table_evictions, tables_parked, table_bytes, tables_parked_bytes, table_digests. */
+ * table_hits, table_misses, table_evictions, tables_parked, table_bytes, tables_parked_bytes, table_digests;
+ * pick_lds_samples (the longest onset row qm_engine_pick_phases takes: row and selection keys live in LDS). */
 int qm_engine_config(qm_engine *e, const char *key, int64_t value);
 int qm_engine_get(qm_engine *e, const char *key, int64_t *value);
 
@@ -430,6 +431,40 @@ int qm_engine_preprocess(qm_engine *e, const double *signals, int signals_on_dev
                          const double *taper_right, int32_t n_right, int zero_phase, double *filtered,
                          int out_on_device);
 
+/* Phase picks on the device -- the step after the location: what GaussianPicker.pick_phases does to every onset row
+ * (one station x phase) of a located event (quakemigrate/signal/pickers/gaussian.py:319-560).  One launch, one
+ * workgroup per row; onsets: f64 [n_rows][t_samples], the UN-LOGGED onset functions (qm_engine_onsets' raw_onsets
+ * with the taper windows set to 1), host or device; every other array is a host array.  Per row:
+ *   1. noise set: the samples that lie in no window [lo, hi) of any row with the same row_group (the phases of one
+ *      station mask each other, gaussian.py:341-343) and whose value is > 1 (the taper pads are 1).
+ *   2. threshold_mode 0: med = median(noise), mad = 1.4826 median(|noise - med|), threshold = med + mad *
+ *      mad_multiplier -- exact selection, NumPy's operation order, no contraction: NumPy's bits; an empty noise set
+ *      gives NaN and no pick.  threshold_mode 1: thresholds_in[row] as given (the percentile method, by the caller).
+ *   3. peak (_find_peak): the FIRST maximum of [lo, hi) and the maximal run of consecutive samples > threshold
+ *      around it; the fit range [f0, f1) is the run padded by one sample on each side.
+ *   4. fit of a exp(-(x - b)^2 / (2 c^2)) to (k / sampling_rate, onsets[k]), k in [f0, f1), from p0 = [max y,
+ *      (f0 + argmax y) / rate, halfwidth[row] / rate] (halfwidth in samples): Levenberg-Marquardt on the 3x3 normal
+ *      equations, analytic Jacobian, damping mu D^2 with D the running maximum of the Jacobian's column norms, a step
+ *      accepted when the gain ratio rho exceeds 1e-4, mu *= max(1/3, 1 - (2 rho - 1)^3) then, mu *= nu, nu *= 2
+ *      otherwise (mu = 1e-3, nu = 2 at the start), until every |dp_i| <= 1e-13 (|p_i| + 1e-13), at most 200
+ *      iterations.  All sums are fixed-order reductions: a call gives the same bits every time.
+ *   5. the pick stands if lo < b sampling_rate < hi (strict, gaussian.py:459).
+ * picks [n_rows][8]: 0 threshold, 1 a (SNR), 2 b (s from the row's first sample), 3 |c| (pick error, s),
+ * 4 c as fitted, 5 f0, 6 f1, 7 iterations.  Columns 1-4 are -1 unless status == 0; 5-6 are -1 for status 1, 2, 6.
+ * status [n_rows]: 0 picked, 1 nothing above the threshold, 2 peak of one sample, 3 fit range leaves the trace
+ * (the reference makes no pick there either: it fails at the trace's start and curve_fit refuses the ragged arrays
+ * at its end), 4 not converged, 5 mean outside the window, 6 non-finite input (threshold NaN; a deviation: the
+ * reference's result there is an accident of np.argmax on NaN).
+ * Rows of several events may share a call: row_group distinct per event and station.
+ * Refused, with the outputs untouched: a NULL argument, n_rows < 1, t_samples < 1 or above "pick_lds_samples", a
+ * window with lo < 0, hi > t_samples or lo > hi, sampling_rate <= 0, a threshold_mode other than 0 / 1,
+ * threshold_mode 1 without thresholds_in.  qm_engine_last_kernel_ms reports the launch. */
+int qm_engine_pick_phases(qm_engine *e, const double *onsets, int onsets_on_device, int32_t n_rows,
+                          int32_t t_samples, const int32_t *windows /*[n_rows][3]: lo, arrival, hi*/,
+                          const int32_t *row_group, double sampling_rate, const double *halfwidth,
+                          int threshold_mode, double mad_multiplier, const double *thresholds_in,
+                          double *picks, int32_t *status);
+
 /* exp(x) rounded to nearest from a double-double evaluation (csrc/qm_ties.hpp): the function the
  * opt-in arg-max rule "tie_rule" = 1 compares near-tied nodes on (the reference exponentiates, then
  * compares: migratelib.c:60-62, :98-105).  Host code, exported for the tests that pin it. */
@@ -503,7 +538,8 @@ int qm_stream_create_replicas(qm_engine *const *engines, int32_t n_engines, int3
                               int32_t depth, qm_stream **out);
 
 /* Duration (ms, HIP events on the engine stream) of the stacking kernel(s) of
- * the most recent detect / migrate call; negative if none.  Synchronises. */
+ * the most recent detect / migrate call, or of the pick kernel of a more recent
+ * qm_engine_pick_phases; negative if none.  Synchronises. */
 int qm_engine_last_kernel_ms(qm_engine *e, double *ms);
 
 /* With config "log_timing" = 1 every stacking launch is bracketed by its own

@@ -117,6 +117,8 @@ qmlib.qm_engine_onsets.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32, c_i
 qmlib.qm_engine_preprocess.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32, c_i32Pt, c_dPt, c_int32, c_int32,
                                        ctypes.c_int, c_dPt, c_int32, c_dPt, c_int32, ctypes.c_int, _vp,
                                        ctypes.c_int]
+qmlib.qm_engine_pick_phases.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32, _vp, _vp, ctypes.c_double, _vp,
+                                        ctypes.c_int, ctypes.c_double, _vp, _vp, _vp]
 qmlib.qm_engine_find_max_coa.argtypes = [_vp, _vp, ctypes.c_int, c_int32,
                                          c_int64, _vp, _vp, _vp, ctypes.c_int]
 qmlib.qm_exp2f_max_error.argtypes = [_vp, ctypes.c_float, ctypes.c_float,
@@ -683,6 +685,40 @@ class Engine:
             po, dev_o))
         return out
 
+    def pick_phases(self, onsets, windows, row_group, sampling_rate, halfwidth, threshold_mode=0,
+                    mad_multiplier=8.0, thresholds=None):
+        """
+        Phase picks on the GPU, the step after the location (``GaussianPicker``'s threshold, peak and Gaussian fit
+        per onset row, gaussian.py:319-560; include/qmhip.h: ``qm_engine_pick_phases``).  ``onsets`` (n_rows, T):
+        the un-logged onset functions, host array or device tensor like :meth:`preprocess`; ``windows``
+        (n_rows, 3) int32 ``[lo, arrival, hi]`` (:func:`quakemigrate_amd.picks.pick_windows`); ``row_group``
+        (n_rows,): the rows of one station share a value; ``halfwidth`` (n_rows,) in samples.
+        ``threshold_mode`` 0: median + ``mad_multiplier`` x MAD of the row outside its station's windows; 1: the
+        given ``thresholds`` (n_rows,).  Returns ``(picks (n_rows, 8) float64, status (n_rows,) int32)``: columns
+        threshold, a, b (s), |c| (s), c, f0, f1, iterations; status 0 is a pick.
+        """
+        n_rows, t_samples = (int(v) for v in onsets.shape)
+        po, dev = self._ptr(onsets, np.float64, n_rows * t_samples)
+        windows = np.ascontiguousarray(windows, dtype=np.int32)
+        row_group = np.ascontiguousarray(row_group, dtype=np.int32)
+        halfwidth = np.ascontiguousarray(halfwidth, dtype=np.float64)
+        if windows.shape != (n_rows, 3):
+            raise ValueError(f"windows of shape {windows.shape} for {n_rows} rows: (n_rows, 3) expected")
+        for name, a in (("row_group", row_group), ("halfwidth", halfwidth)):
+            if a.shape != (n_rows,):
+                raise ValueError(f"{name} of shape {a.shape} for {n_rows} rows")
+        pt = _vp(None)
+        if thresholds is not None:
+            thresholds = np.ascontiguousarray(thresholds, dtype=np.float64)
+            if thresholds.shape != (n_rows,):
+                raise ValueError(f"thresholds of shape {thresholds.shape} for {n_rows} rows")
+            pt = _host(thresholds)
+        picks, status = np.zeros((n_rows, 8)), np.zeros(n_rows, dtype=np.int32)
+        _check(qmlib.qm_engine_pick_phases(
+            self._h, po, dev, n_rows, t_samples, _host(windows), _host(row_group), float(sampling_rate),
+            _host(halfwidth), int(threshold_mode), float(mad_multiplier), pt, _host(picks), _host(status)))
+        return picks, status
+
     def find_max_coa(self, map4d, n_samples, n_nodes, out=None):
         if out is None:
             out = (np.zeros(n_samples), np.zeros(n_samples),
@@ -1035,6 +1071,9 @@ class EngineReplicas:
 
     def preprocess(self, *args, **kwargs):
         return self.lead.preprocess(*args, **kwargs)
+
+    def pick_phases(self, *args, **kwargs):
+        return self.lead.pick_phases(*args, **kwargs)
 
 
 def timeit(*args_, **kwargs_):

@@ -797,6 +797,7 @@ void qm_engine_destroy(qm_engine *e) {
     e->d_grids.release(); e->d_rows.release(); e->d_served.release();
     e->d_sig.release(); e->d_sta.release(); e->d_lta.release(); e->d_raw.release();
     e->d_pre_coef.release(); e->d_pre_out.release(); e->d_pre_meta.release();
+    e->d_pick_val.release(); e->d_pick_meta.release();
     e->d_onset_meta.release(); e->d_scalar.release(); e->d_digest.release();
     e->d_onsets.release(); e->d_pmax.release(); e->d_psum.release(); e->d_out_a.release();
     e->d_chunk.release(); e->d_marg.release(); e->d_marg_out.release(); e->d_pidx.release();
@@ -986,6 +987,7 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     else if (k == "tie_sets") *v = e->cfg_tie_sets;
     else if (k == "stream_pull") *v = e->cfg_stream_pull;
     else if (k == "preproc_skew") *v = e->cfg_preproc_skew;
+    else if (k == "pick_lds_samples") *v = qm::kPicksLdsSamples;
     else if (k == "tie_brick_rows") *v = e->last_brick_rows;
 
     else if (k == "tie_refined_steps") *v = e->tie_refined_steps;

@@ -12,6 +12,7 @@
 //                    several engines that hold the same table (replicas: launches round-robin)
 //   qm_widen.hip     the rows next to the path: onset stage, locate fits, RBF peak
 //   qm_preproc.hip   the row before the onset stage: detrend, taper, zero-phase band-pass of the component traces
+//   qm_picks.hip     the row after the location: phase picks, a Gaussian fitted to every onset row of an event
 //   qm_compat.hip    the five reference-signature symbols (qmlib.h:28-44)
 //   qm_group.hip     engine groups: one process driving the boxes of a column partition on several devices
 // Everything declared here lives in the library only (hidden visibility).
@@ -40,6 +41,7 @@
 #include "qm_shift.hpp"
 #include "qm_ties.hpp"
 #include "qm_preproc.hpp"
+#include "qm_picks.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -306,6 +308,9 @@ struct qm_engine : TableState {
     // pre-processing stage scratch: coefficients and taper weights, the traces' filters, the filtered traces
     DevBuf<double> d_pre_coef, d_pre_out;
     DevBuf<int32_t> d_pre_meta;
+    // phase-pick stage scratch: half-widths, thresholds and picks; windows, groups and status
+    DevBuf<double> d_pick_val;
+    DevBuf<int32_t> d_pick_meta;
 
     // scratch
     DevBuf<double> d_onsets, d_pmax, d_psum, d_out_a, d_chunk, d_marg, d_marg_out;

@@ -451,7 +451,8 @@ class MigrationScan:
             rows.append(dict(onset_data.availability))
         drain()
 
-    def locate_compute(self, archive, triggers, marginal_window, sgm=0.8, cov_thresh=0.90, on_event=None):
+    def locate_compute(self, archive, triggers, marginal_window, sgm=0.8, cov_thresh=0.90, on_event=None,
+                       picker=None):
         """
         ``QuakeScan._locate_events``' loop around the path (reference scan.py:472-545), up to and including
         ``_calculate_location``: per triggered event read ``trigger_time -/+ (2 * marginal_window + pad)``
@@ -476,6 +477,12 @@ class MigrationScan:
         (time stamp of the first trimmed sample), ``first_sample, last_sample`` (trimmed series, inclusive,
         in scanned samples), ``max_coa, max_coa_n, coord`` (trimmed), ``coa_map`` (normalised), ``fits``
         (:class:`locate.LocationFits`), ``onset_data``.
+
+        ``picker`` (:class:`quakemigrate_amd.picks.DevicePicker`): the reference's next step, ``pick_phases``
+        (pickers/gaussian.py:115-243), on the engine as well.  The onsets are computed again un-logged, with the
+        taper windows set to 1 (``onset.calculate_onsets(data, timespan=4 * marginal_window)``, gaussian.py:142-144),
+        the hypocentre is the spline location, the traveltimes are ``lut.traveltime_to(phase, ijk, station)`` per
+        row, and the result gets ``"picks"`` (the picker's table) before ``on_event`` sees it.
         """
         from quakemigrate_amd import locate
 
@@ -545,10 +552,26 @@ class MigrationScan:
                 "coord": self.lut.index2coord(series[2][sel], unravel=True),
                 "coa_map": coa_map, "fits": fits, "onset_data": onset_data,
             }
+            if picker is not None:
+                result["picks"] = self._pick_phases(picker, eng, data, onset_data, result, mw)
             results.append(result)
             if on_event is not None:
                 on_event(result)
         return results
+
+    def _pick_phases(self, picker, eng, data, onset_data, result, mw):
+        """The located event's picks: one launch over its onset rows (``DevicePicker.pick``)."""
+        raw_onsets, raw_data = self.onset.calculate_onsets(data, timespan=4 * mw)      # gaussian.py:142-144
+        raw_onsets = np.ascontiguousarray(raw_onsets, dtype=np.float64)
+        keys = [key for key, available in raw_data.availability.items() if available]
+        ijk = np.asarray(result["fits"].spline, dtype=np.float64)
+        traveltimes = []
+        for key in keys:
+            station, _, phase = key.rpartition("_")
+            traveltimes.append(float(np.ravel(self.lut.traveltime_to(phase, ijk, station))[0]))
+        return picker.pick(eng, raw_onsets, keys, getattr(raw_data, "starttime", data.starttime),
+                           raw_data.sampling_rate, result["otime"], mw, traveltimes,
+                           fraction_tt=getattr(self.lut, "fraction_tt", None))
 
     def marginal_coalescence(self, data, first_sample, end_sample):
         """
