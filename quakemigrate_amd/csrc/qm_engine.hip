@@ -9,6 +9,10 @@
 
 namespace {
 
+// The launch_*_path functions below are handed, in a.g / a.brick_list / a.n_list, the bricks of the layout the
+// launch runs on and those of them that do not fit its LDS kernel (run_stack): the LDS launch runs without a
+// list, the direct launch on that one.
+
 qm::LaunchShape stack_shape(const qm_engine *e, const qm::StackArgs &a, int groups, int threads,
                             size_t lds) {
     // the grid is padded to a multiple of 8 groups (XCD-aware workgroup -> (tile, group) map)
@@ -30,6 +34,8 @@ int launch_direct(qm_engine *e, const qm::StackArgs &a, int J, bool volume, int 
 template <int J, bool VOLUME>
 int launch_stack_j(qm_engine *e, qm::StackArgs &a, int groups_lds, int groups_direct,
                    bool use_lds, bool use_direct) {
+    const int32_t *const list = a.brick_list;
+    const int n_list = a.n_list;
     const int KT = qm::kWave * J;
     const int threads = e->cfg_waves * qm::kWave;
     const size_t publish_bytes = (size_t)3 * e->cfg_waves * KT * sizeof(double);
@@ -80,8 +86,8 @@ int launch_stack_j(qm_engine *e, qm::StackArgs &a, int groups_lds, int groups_di
             a.brick_list = nullptr;
             a.n_list = e->g.nbricks;
         } else {
-            a.brick_list = e->d_wide.p;
-            a.n_list = e->n_wide;
+            a.brick_list = list;
+            a.n_list = n_list;
         }
         if (launch_direct(e, a, J, VOLUME, groups_direct, threads, publish_bytes)) return 1;
         a.set0 += groups_direct;
@@ -96,6 +102,8 @@ using qm::pair_jp_of;
 template <int JP, bool VOLUME>
 int launch_pair_path(qm_engine *e, qm::StackArgs &a, int groups_lds, int groups_direct,
                      bool use_lds, bool use_direct) {
+    const int32_t *const list = a.brick_list;
+    const int n_list = a.n_list;
     if (use_lds) {
         a.ngroups = groups_lds;
         a.brick_list = nullptr;
@@ -116,8 +124,8 @@ int launch_pair_path(qm_engine *e, qm::StackArgs &a, int groups_lds, int groups_
         const int threads = 1024;
         const size_t publish_bytes = (size_t)3 * (threads / qm::kWave) * qm::kWave * J * sizeof(double);
         a.ngroups = groups_direct;
-        a.brick_list = e->d_pwide.p;
-        a.n_list = e->n_pwide;
+        a.brick_list = list;
+        a.n_list = n_list;
         if (launch_direct(e, a, J, VOLUME, groups_direct, threads, publish_bytes)) return 1;
         a.set0 += groups_direct;
     }
@@ -171,6 +179,8 @@ void shift_wide_tiles(const qm_engine *e, int n_chunk, bool only_wide, qm::Stack
 
 int launch_shift_path(qm_engine *e, const ShiftLayout &L, qm::StackArgs &a, int groups_lds, int groups_direct,
                       bool use_lds, bool use_direct, int mode) {
+    const int32_t *const list = a.brick_list;
+    const int n_list = a.n_list;
     const bool volume = mode != qm::kShiftDetect;        // (the direct kernel's VOLUME covers the map too)
     if (use_lds) {
         a.ngroups = groups_lds;
@@ -229,8 +239,8 @@ int launch_shift_path(qm_engine *e, const ShiftLayout &L, qm::StackArgs &a, int 
         const int threads = 512;
         const size_t publish_bytes = (size_t)3 * (threads / qm::kWave) * qm::kShiftKT * sizeof(double);
         a.ngroups = groups_direct;
-        a.brick_list = L.list.p;
-        a.n_list = L.n_list;
+        a.brick_list = list;
+        a.n_list = n_list;
         a.tail_spl = 0;                                // (its own whole tiles of 256 samples, clamped)
         a.brick_max = nullptr;
         a.wide_tiles = 0;
@@ -277,13 +287,20 @@ StackResult run_stack(qm_engine *e, const StackLaunch &s) {
     const int J = run_j(e, n_chunk);
     if (plan_wide(e, J)) return 1;
     const int KT = qm::kWave * J;
+    // The bricks the launch runs on, those of them that go to the direct kernel and the LDS kernel's tables are those
+    // of ONE layout: the round-2 kernels' unless the shift-reuse or the paired kernel takes the launch below
     qm::StackArgs a{};
-    a.g = e->g;
+    auto run_on = [&a](const BrickLayout &layout) {
+        a.g = layout.g;
+        a.brick_list = layout.list.p;
+        a.n_list = layout.n_list;
+        a.rel = layout.rel.p;
+        a.brick_meta = layout.meta.p;
+        a.brick_total = layout.total.p;
+    };
+    run_on(e->r2());
     a.onsets = s.onsets;
     a.lut = e->d_lut.p;
-    a.rel = e->d_rel.p;
-    a.brick_meta = e->d_bmeta.p;
-    a.brick_total = e->d_btotal.p;
     a.T = s.T;
     a.fsmp = s.fsmp;
     a.n_samples = s.n_samples;
@@ -345,7 +362,7 @@ StackResult run_stack(qm_engine *e, const StackLaunch &s) {
             shift = false;
     }
     if (shift) {
-        a.g = L->g;
+        run_on(*L);                                     // (its tables travel in ShiftArgs: launch_shift_path)
         a.rel = nullptr;
         a.brick_meta = nullptr;
         a.brick_total = nullptr;
@@ -361,14 +378,11 @@ StackResult run_stack(qm_engine *e, const StackLaunch &s) {
     if (jp > 0) {
         if (!pair_built(e->g.n_rows)) jp = 0;
         else if (ensure_pair_tables(e, jp) != 0) return 1;   // a HIP failure while building the tables
-        else if (!e->pair_ok) jp = 0;                         // the layout does not fit this table
+        else if (!e->pair.ok) jp = 0;                         // the layout does not fit this table
     }
     if (jp > 0) {
         const int PKT = 128 * jp;
-        a.g = e->pg;
-        a.rel = e->d_prel.p;
-        a.brick_meta = e->d_pmeta.p;
-        a.brick_total = e->d_ptotal.p;
+        run_on(e->pair);
         a.ntiles = (n_chunk + PKT - 1) / PKT;
         a.cap_doubles = kPairLdsBytes / 8;
     }
@@ -384,15 +398,14 @@ StackResult run_stack(qm_engine *e, const StackLaunch &s) {
     a.part_stride = (int64_t)steps * n_chunk;
     if (!shift && jp == 0) {                            // the round-2 kernels' own offsets
         if (ensure_rel(e)) return 1;
-        a.rel = e->d_rel.p;
+        a.rel = e->r2().rel.p;
     }
     if (marginal) {
         if (e->d_marg.ensure((size_t)a.ntiles * e->n_nodes)) return 1;
         a.marginal = e->d_marg.p;
         e->marg_tiles = a.ntiles;
     }
-    const int n_wide_now = shift ? L->n_list : jp > 0 ? e->n_pwide : e->n_wide;
-    const int nbricks_now = shift ? L->g.nbricks : jp > 0 ? e->pg.nbricks : e->g.nbricks;
+    const int n_wide_now = a.n_list, nbricks_now = a.g.nbricks;
     const bool use_direct = e->cfg_force_direct || n_wide_now > 0;
     const bool use_lds = !e->cfg_force_direct && n_wide_now < nbricks_now;
     const int threads = shift ? 512 : jp > 0 ? 1024 : e->cfg_waves * qm::kWave;   // (direct launch)
@@ -473,8 +486,7 @@ StackResult run_stack(qm_engine *e, const StackLaunch &s) {
     e->last_groups_lds = groups_lds;
     e->last_brick_rows = brick_rows;
     e->last_groups_direct = groups_direct;
-    e->last_list = !use_direct || e->cfg_force_direct ? nullptr
-                   : shift ? L->list.p : jp > 0 ? e->d_pwide.p : e->d_wide.p;
+    e->last_list = !use_direct || e->cfg_force_direct ? nullptr : a.brick_list;
     e->last_n_list = !use_direct ? 0 : e->cfg_force_direct ? nbricks_now : n_wide_now;
 
     // a conditional launch (the fallback of a screened step) is not part of the timing log: it
@@ -888,11 +900,11 @@ int qm_engine_config(qm_engine *e, const char *key, int64_t v) {
         if (v != 0 && v != qm::kShiftWaves && v != qm::kShiftWaves8 && v != qm::kShiftWaves3)
             return fail("shift_waves must be 0 (automatic), 4, 8 or 12");
         e->cfg_shift_waves = (int)v;
-        e->sh.built = false;
+        e->sh.invalidate();
     } else if (k == "shift_rows_direct") {
         if (v < 0 || v > 2) return fail("shift_rows_direct must be 0, 1 or 2");
         e->cfg_shift_rows_direct = (int)v;
-        e->sh.built = false;
+        e->sh.invalidate();
     } else if (k == "shift_tail") {
         e->cfg_shift_tail = v ? 1 : 0;
     } else if (k == "shift_wide") {
@@ -901,7 +913,7 @@ int qm_engine_config(qm_engine *e, const char *key, int64_t v) {
     } else if (k == "shift_wide_rows") {
         if (v < 0 || v > 2) return fail("shift_wide_rows must be 0 (never), 1 (where all rows do not fit) or 2 (always)");
         e->cfg_shift_wide_rows = (int)v;
-        e->shw.built = false;
+        e->shw.invalidate();
     } else if (k == "tie_rule") {
         if (v != 0 && v != 1) return fail("tie_rule must be 0 (largest sum) or 1 (the reference's exp rule)");
         e->cfg_tie_rule = (int)v;
@@ -915,14 +927,14 @@ int qm_engine_config(qm_engine *e, const char *key, int64_t v) {
     } else if (k == "screen_pairs") {
         if (v != 0 && v != 1 && v != 2 && v != 4) return fail("screen_pairs must be 0, 1, 2 or 4");
         e->cfg_screen_pairs = (int)v;
-        e->screen_kt = 0;
+        e->screen.invalidate();
     } else if (k == "screen_brick16") {
         e->cfg_screen_brick16 = v ? 1 : 0;
-        e->screen_kt = 0;
+        e->screen.invalidate();
     } else if (k == "screen_big") {
         if (v < -1 || v > 1) return fail("screen_big must be -1 (automatic), 0 or 1");
         e->cfg_screen_big = (int)v;
-        e->screen_kt = 0;
+        e->screen.invalidate();
     } else if (k == "stream_pull") {
         if (v < -1 || v > 1) return fail("stream_pull must be -1 (slots of <= 1 MB), 0 (never) or 1 (always)");
         e->cfg_stream_pull = (int)v;
@@ -963,7 +975,7 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     }
     else if (k == "screen_pairs") *v = e->last_plan_jp;
     else if (k == "screen_big") *v = e->last_plan_big;
-    else if (k == "screen_brick_nodes") *v = e->sg.brick_nodes;
+    else if (k == "screen_brick_nodes") *v = e->screen.g.brick_nodes;
     else if (k == "last_kernel") *v = e->last_kernel;
     else if (k == "last_kernel_j") *v = e->last_j;
     else if (k == "shift") *v = e->cfg_shift;
@@ -1021,20 +1033,21 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     else if (k == "shift_operands_per_add_x1000")   // 8-byte LDS operands fetched per add (x 1000)
         *v = e->sh.ok && e->sh.group_rows > 0
                  ? (e->sh.quads * 4 * 1000) / (e->sh.group_rows * 32) : 0;
-    else if (k == "pair_brick_nodes") *v = e->pair_kt ? e->pg.brick_nodes : 0;
-    else if (k == "pair_wide_bricks") *v = e->pair_kt ? e->n_pwide : 0;
-    else if (k == "pair_tile") *v = e->pair_ok ? e->pair_kt : 0;
+    else if (k == "pair_brick_nodes") *v = e->pair.kt ? e->pair.g.brick_nodes : 0;
+    else if (k == "pair_wide_bricks") *v = e->pair.kt ? e->pair.n_list : 0;
+    else if (k == "pair_tile") *v = e->pair.ok ? e->pair.kt : 0;
     else if (k == "n_bricks") *v = e->g.nbricks;
     else if (k == "n_wide_bricks") {
         if (e->have_lut) {
             DeviceGuard guard(e->device);
             if (plan_wide(e, eff_j(e))) return 1;
         }
-        *v = e->n_wide;
+        *v = e->r2().n_list;
     } else if (k == "mean_span") {                     // mean delay span per (brick, row), samples
         int64_t sum = 0;
-        for (int32_t t : e->h_btotal) sum += t;
-        *v = e->h_btotal.empty() ? 0 : sum / ((int64_t)e->h_btotal.size() * std::max(1, e->g.n_rows));
+        const std::vector<int32_t> &totals = e->r2().h_total;
+        for (int32_t t : totals) sum += t;
+        *v = totals.empty() ? 0 : sum / ((int64_t)totals.size() * std::max(1, e->g.n_rows));
     } else if (k == "n_cu") *v = e->n_cu;
     else if (k == "n_nodes") *v = e->n_nodes;
     else if (k == "n_rows") *v = e->g.n_rows;

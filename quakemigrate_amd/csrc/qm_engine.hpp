@@ -103,17 +103,49 @@ struct DevBuf {
     }
 };
 
+// The bricks of one kernel family over a table: brick grid, per-(brick, row) window records (`raw`: before the
+// prefix pass, where the family keeps them), the bricks' totals, the bricks whose windows do NOT fit the family's LDS
+// budget (the direct kernel takes them) and the 16-bit window offsets.  What a layout was built for -- its key --
+// stands beside it in the family's struct, with an invalidate() that voids the key and keeps grid and buffers.
+// invalidate() voids the RESIDENT table's layout only: a table parked at that moment (qm_engine_table_select) keeps
+// the layout it built under the former configuration and runs on it when it is selected back.
+struct BrickLayout {
+    qm::GridDesc g{};
+    DevBuf<int32_t> raw, meta, total, list;
+    DevBuf<uint16_t> rel;
+    int n_list = 0;
+    void release() {
+        PoolReleaseScope one_wait;
+        raw.release(); meta.release(); total.release(); list.release(); rel.release();
+    }
+    size_t device_bytes() const { return (raw.n + meta.n + total.n + list.n) * 4 + rel.n * 2; }
+};
+struct Round2Layout : BrickLayout {     // the round-2 kernels' (chunked, exact-row-count), on the table's own grid
+    bool rel_built = false;             // `rel` holds this table's offsets (built on first use)
+    std::vector<int32_t> h_total;       // the totals on the host: `list` is planned from them ...
+    int plan_j = -1, plan_cap = -1;     // ... for these samples per lane and this LDS budget (plan_wide)
+    void invalidate() { plan_j = -1; }
+};
+struct PairLayout : BrickLayout {       // the paired (16-byte operand) float64 kernel's (qm_pair.hpp): own brick grid
+    int kt = 0;                         // tile length the paired tables were built for
+    bool ok = false;                    // ... and whether (almost) every brick fits
+    void invalidate() { kt = 0; }
+};
+struct ScreenLayout : BrickLayout {     // the float32 screening sweep's (qm_screen.hpp): own brick grid,
+    int kt = 0, wb = 0;                 // staggered-copy offset table; what the screening table was built for
+    void invalidate() { kt = 0; }
+};
+
 // One shift-reuse layout of a table (qm_shift.hpp): brick grid with even brick dimensions, the row-window
 // records of every brick, which bricks fit, the record stream dealt over the workgroup's wavefronts.  A table
 // has up to two: `sh`, what rounds 3-5 built (256-sample tiles; any launch kind), and -- round 6 -- `shw` for
 // the fused detect where WIDE tiles fit: the 8-wave shape on its own brick grid, with a second set of records
 // and a second stream for the 384-sample tiles beside those of the 256-sample and tail tiles behind them.
-struct ShiftLayout {
+struct ShiftLayout : BrickLayout {          // (list: the bricks that do not fit -- direct kernel; rel stays empty)
     int nw = 0;                             // workgroup shape the tables were built for
-    qm::GridDesc g{};
-    DevBuf<int32_t> raw, meta, total, fit, list;   // list: the bricks that do not fit (direct kernel)
+    DevBuf<int32_t> fit;
     DevBuf<uint32_t> stream;
-    int n_list = 0, rows2 = 0;
+    int rows2 = 0;
     int nblk = 1, sb = 0;                   // row blocks (tables of more than 64 rows): blocks, rows per block
     int stage_slots = 0, stage_reach = 0;   // ... largest row window (slots), furthest sample it holds
     bool direct = false;                    // ... staged by LDS-direct loads (stack_shift_rows2_kernel)
@@ -126,13 +158,14 @@ struct ShiftLayout {
     DevBuf<uint32_t> wstream;
     int64_t wquads = 0;                     // quads fetched by the wide tiles' windows (per 48 adds, not 32)
 
+    void invalidate() { built = false; }
     void release() {
         PoolReleaseScope one_wait;
-        raw.release(); meta.release(); total.release(); fit.release(); list.release(); stream.release();
-        wmeta.release(); wtotal.release(); wstream.release();
+        BrickLayout::release();
+        fit.release(); stream.release(); wmeta.release(); wtotal.release(); wstream.release();
     }
-    size_t device_words() const {
-        return raw.n + meta.n + total.n + fit.n + list.n + stream.n + wmeta.n + wtotal.n + wstream.n;
+    size_t device_bytes() const {
+        return BrickLayout::device_bytes() + (fit.n + stream.n + wmeta.n + wtotal.n + wstream.n) * 4;
     }
 };
 
@@ -142,56 +175,43 @@ struct ShiftLayout {
 // inherits; qm_engine_table_select parks it in a slot and brings another one in (a swap of pointers:
 // no device work), so that a change of station availability -- a different served table,
 // lut.py:529-537 -- costs a rebuild only the first time that table is seen.
-struct TableState {
+// (The round-2 layout is a base, not a member like the others: its grid is the table's shape as well and is read
+// all over the engine as e->g.  Where the layout is meant, r2() says so.)
+struct TableState : Round2Layout {
     bool have_lut = false;
     uint64_t serial = 0;            // identity of the loaded table (process-unique; travels with the state
                                     // through qm_engine_table_select): what a qm_stream checks before a launch
     uint64_t digest = 0;            // qm_engine_table_digest of this table, valid while digest_serial == serial
     uint64_t digest_serial = 0;     // (computed once per table; travels with the state like the serial)
-    qm::GridDesc g{};
     int64_t n_nodes = 0;
     int64_t node_offset = 0;
     int32_t lut_max = 0;
     int n_rows_hint = 0;            // row count the automatic choice is based on
     int auto_j = 0;                 // samples per lane picked by the table's layout search (> 64 rows)
     int tab_waves = 0, tab_lds_bytes = 0;   // workgroup shape the layout search picked (0: none yet)
-    DevBuf<int32_t> d_lut, d_bmeta, d_btotal, d_wide;
-    DevBuf<uint16_t> d_rel;
-    bool rel_built = false;         // d_rel holds this table's offsets (built on first use)
-    std::vector<int32_t> h_btotal;
-    int n_wide = 0;
-    int plan_j = -1, plan_cap = -1;
+    DevBuf<int32_t> d_lut;
 
-    // float32 screening (qm_screen.hpp): staggered-copy offset table
-    DevBuf<int32_t> d_smeta, d_smeta_raw, d_stotal, d_swide;
-    qm::GridDesc sg{};                      // the sweep's own brick grid
-    DevBuf<uint16_t> d_srel;
-    int n_swide = 0;
-    int screen_kt = 0, screen_wb = 0;       // what the screening table was built for
-
-    // paired (16-byte operand) layout of the float64 kernel (qm_pair.hpp): own brick grid
-    qm::GridDesc pg{};
-    DevBuf<int32_t> d_pmeta, d_pmeta_raw, d_ptotal, d_pwide;
-    DevBuf<uint16_t> d_prel;
-    int n_pwide = 0;
-    int pair_kt = 0;                        // tile length the paired tables were built for
-    bool pair_ok = false;                   // ... and whether (almost) every brick fits
-
+    Round2Layout &r2() { return *this; }
+    const Round2Layout &r2() const { return *this; }
+    PairLayout pair;
+    ScreenLayout screen;
     // shift-reuse layouts (qm_shift.hpp): own brick grids, row-window slots, record streams
     ShiftLayout sh, shw;
 
+    // another table's values are coming in: every layout's key is void, and the shift-reuse layouts' read-outs
+    // report nothing until they are rebuilt.  Grids and buffers stay (qm_engine_load_lut reuses the allocations).
+    void invalidate_derived() {
+        r2().invalidate(); screen.invalidate(); pair.invalidate(); sh.invalidate(); shw.invalidate();
+        sh.ok = shw.ok = false;
+    }
     void release_all() {
         PoolReleaseScope one_wait;
-        d_lut.release(); d_bmeta.release(); d_btotal.release(); d_wide.release(); d_rel.release();
-        d_smeta.release(); d_smeta_raw.release(); d_stotal.release(); d_swide.release(); d_srel.release();
-        d_pmeta.release(); d_pmeta_raw.release(); d_ptotal.release(); d_pwide.release(); d_prel.release();
-        sh.release(); shw.release();
+        d_lut.release();
+        r2().release(); pair.release(); screen.release(); sh.release(); shw.release();
     }
     size_t device_bytes() const {
-        return (d_lut.n + d_bmeta.n + d_btotal.n + d_wide.n + d_smeta.n + d_smeta_raw.n + d_stotal.n +
-                d_swide.n + d_pmeta.n + d_pmeta_raw.n + d_ptotal.n + d_pwide.n + sh.device_words() +
-                shw.device_words()) * 4 +
-               (d_rel.n + d_srel.n + d_prel.n) * 2;
+        return d_lut.n * 4 + r2().device_bytes() + pair.device_bytes() + screen.device_bytes() +
+               sh.device_bytes() + shw.device_bytes();
     }
 };
 

@@ -59,7 +59,8 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
     if (ensure_screen_tables(e, plan)) return 1;
     e->last_plan_jp = plan.jp;
     e->last_plan_big = plan.big ? 1 : 0;
-    const qm::GridDesc &g = e->sg;
+    const ScreenLayout &L = e->screen;                  // the sweep's bricks, those that do not fit: direct kernel
+    const qm::GridDesc &g = L.g;
     if (!e->h_flags)
         QM_HIP(hipHostMalloc(reinterpret_cast<void **>(&e->h_flags),
                              2 * kFlagRing * sizeof(int32_t), hipHostMallocDefault));
@@ -67,15 +68,15 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
     const int ntiles = (ns + KT - 1) / KT;
     const int64_t ns_pad = (int64_t)ntiles * KT;
     const int S = g.n_rows;
-    const int n_fit = g.nbricks - e->n_swide;
+    const int n_fit = g.nbricks - L.n_list;
     if (n_fit < 2) return 0;                            // a single cell: nothing to screen
     const int groups = n_fit > 0 ? (e->cfg_groups > 0 ? std::min(e->cfg_groups, g.nbricks)
                                                        : auto_groups(e, ntiles, g.nbricks, plan.big ? 1 : 2))
                                  : 0;
     const int groups_direct =
-        e->n_swide > 0 ? (e->cfg_groups > 0 ? std::min(e->cfg_groups, e->n_swide)
-                                            : auto_groups(e, (ns + 63) / 64, e->n_swide, 4))
-                       : 0;
+        L.n_list > 0 ? (e->cfg_groups > 0 ? std::min(e->cfg_groups, L.n_list)
+                                          : auto_groups(e, (ns + 63) / 64, L.n_list, 4))
+                     : 0;
     const int sets = groups_direct + 1;
     constexpr int kGroupsPerBlock = 32;
     if (e->d_onq.ensure((size_t)S * T) || e->d_rowmax.ensure(S) || e->d_sparams.ensure(4) ||
@@ -116,9 +117,9 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
     qm::ScreenArgs a{};
     a.g = g;
     a.onsets_q = e->d_onq.p;
-    a.rel = e->d_srel.p;
-    a.brick_meta = e->d_smeta.p;
-    a.brick_total = e->d_stotal.p;
+    a.rel = L.rel.p;
+    a.brick_meta = L.meta.p;
+    a.brick_total = L.total.p;
     a.T = T;
     a.fsmp = fsmp;
     a.n_samples = ns;
@@ -159,8 +160,8 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
         d.part_max = e->d_pmax.p;
         d.part_idx = e->d_pidx.p;
         d.part_sum = e->d_psum.p;
-        d.brick_list = e->d_swide.p;
-        d.n_list = e->n_swide;
+        d.brick_list = L.list.p;
+        d.n_list = L.n_list;
         d.n_nodes = e->n_nodes;
         const size_t publish_bytes = (size_t)3 * 8 * 64 * sizeof(double);
         bool built = false;

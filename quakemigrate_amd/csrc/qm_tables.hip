@@ -10,16 +10,33 @@
 
 int lds_cap_doubles(const qm_engine *e) { return e->cfg_lds_bytes / 8; }
 
+// `g` cut into bricks of (at most) bx x by x bz nodes: bricks per axis, their number, nodes per brick.  The brick is
+// clamped to the grid -- `even`: to the grid's extents rounded up to even numbers, as the brick's own dimensions
+// are (the shift-reuse kernels walk 2x2x2 node groups).
+static qm::GridDesc rebrick(const qm::GridDesc &g, int bx, int by, int bz, bool even = false) {
+    auto clamp = [even](int b, int n) { return even ? std::min(b + (b & 1), n + (n & 1)) : std::min(b, n); };
+    qm::GridDesc r = g;
+    r.bx = clamp(bx, g.nx);
+    r.by = clamp(by, g.ny);
+    r.bz = clamp(bz, g.nz);
+    r.nbx = (g.nx + r.bx - 1) / r.bx;
+    r.nby = (g.ny + r.by - 1) / r.by;
+    r.nbz = (g.nz + r.bz - 1) / r.bz;
+    r.nbricks = r.nbx * r.nby * r.nbz;                  // (never more bricks than nodes: fewer than 2^31)
+    r.brick_nodes = r.bx * r.by * r.bz;
+    return r;
+}
+
 // 16-bit window offsets of the round-2 stacking kernels (brick_rel_kernel), on first use per table
 int ensure_rel(qm_engine *e) {
-    if (e->rel_built) return 0;
-    const qm::GridDesc &g = e->g;
-    if (e->d_rel.ensure((size_t)g.nbricks * g.brick_nodes * g.row_pad)) return 1;
+    Round2Layout &R = e->r2();
+    if (R.rel_built) return 0;
+    const qm::GridDesc &g = R.g;
+    if (R.rel.ensure((size_t)g.nbricks * g.brick_nodes * g.row_pad)) return 1;
     hipLaunchKernelGGL(qm::brick_rel_kernel, dim3(g.nbricks), dim3(256), 0, e->stream, g,
-                       e->d_lut.p, reinterpret_cast<const int4 *>(e->d_bmeta.p), e->d_btotal.p,
-                       e->d_rel.p);
+                       e->d_lut.p, reinterpret_cast<const int4 *>(R.meta.p), R.total.p, R.rel.p);
     QM_HIP(hipGetLastError());
-    e->rel_built = true;
+    R.rel_built = true;
     return 0;
 }
 
@@ -58,21 +75,22 @@ int run_j(const qm_engine *e, int n_chunk) {
 
 // bricks whose windows do not fit the LDS budget for tile length 64*J
 int plan_wide(qm_engine *e, int J) {
+    Round2Layout &R = e->r2();
     const int KT = qm::kWave * J;
     const int cap = lds_cap_doubles(e);
-    if (e->plan_j == J && e->plan_cap == cap) return 0;
+    if (R.plan_j == J && R.plan_cap == cap) return 0;
     std::vector<int32_t> wide;
-    for (int b = 0; b < e->g.nbricks; ++b) {
-        if (!qm::brick_fits(e->h_btotal[b], e->g.n_rows, KT, cap)) wide.push_back(b);
+    for (int b = 0; b < R.g.nbricks; ++b) {
+        if (!qm::brick_fits(R.h_total[b], R.g.n_rows, KT, cap)) wide.push_back(b);
     }
-    e->n_wide = (int)wide.size();
-    if (e->n_wide) {
-        if (e->d_wide.ensure(wide.size())) return 1;
-        QM_HIP(copy_in(e->d_wide.p, wide.data(), wide.size() * sizeof(int32_t), e->stream));
+    R.n_list = (int)wide.size();
+    if (R.n_list) {
+        if (R.list.ensure(wide.size())) return 1;
+        QM_HIP(copy_in(R.list.p, wide.data(), wide.size() * sizeof(int32_t), e->stream));
         QM_HIP(hipStreamSynchronize(e->stream));
     }
-    e->plan_j = J;
-    e->plan_cap = cap;
+    R.plan_j = J;
+    R.plan_cap = cap;
     return 0;
 }
 
@@ -96,67 +114,78 @@ int pair_jp(const qm_engine *e, int n_chunk, bool volume) {
     return (jp > 0 && run_j(e, n_chunk) == eff_j(e) && qm::kWave * eff_j(e) >= 128 * jp) ? jp : 0;
 }
 
-// Own brick grid (e->pg): the largest brick shape whose two staggered window copies fit 160 KB
-// for (almost) every brick; per-brick (min, span2, prefix) records and the 16-bit offset table.
-int ensure_pair_tables(qm_engine *e, int jp) {
-    const int KT = 128 * jp;
-    if (e->pair_kt == KT) return 0;
-    static const int kShapes[][3] = {{8, 8, 8}, {4, 8, 8}, {4, 4, 8}, {4, 4, 4},
-                                     {2, 4, 4}, {2, 2, 4}, {2, 2, 2}, {1, 1, 2}, {1, 1, 1}};
+// The brick grid of a layout that has its own (paired, screened): the largest of `shapes` (from index `first` on;
+// the configured brick shape, if there is one, as the table's own grid has it) whose windows fit `budget` at tile
+// length KT for (almost) every brick.  Leaves in L the grid, the per-brick (min, span2, prefix) records, the list
+// of the bricks that do not fit and -- where want_rel(grid, bricks that do not fit) says so -- the 16-bit offset
+// table rel_kernel builds.
+using BrickFits = bool (*)(int64_t total, int n_rows, int kt, int budget);
+using BrickRelKernel = void (*)(qm::GridDesc, const int32_t *, const int4 *, const int32_t *, int, int, uint16_t *);
+
+template <typename WantRel>
+static int search_bricks(qm_engine *e, BrickLayout &L, const int (*shapes)[3], int first, int n_shapes,
+                         BrickFits fits, int KT, int budget, BrickRelKernel rel_kernel, WantRel want_rel) {
     const bool fixed = e->cfg_bx > 0;
-    const int n_shapes = fixed ? 1 : (int)(sizeof(kShapes) / sizeof(kShapes[0]));
+    if (fixed) first = 0, n_shapes = 1;
     qm::GridDesc g = e->g;
     std::vector<int32_t> total, wide;
-    for (int s = 0; s < n_shapes; ++s) {
-        g = e->g;
-        if (!fixed) {
-            g.bx = std::min(kShapes[s][0], g.nx);
-            g.by = std::min(kShapes[s][1], g.ny);
-            g.bz = std::min(kShapes[s][2], g.nz);
-            g.nbx = (g.nx + g.bx - 1) / g.bx;
-            g.nby = (g.ny + g.by - 1) / g.by;
-            g.nbz = (g.nz + g.bz - 1) / g.bz;
-            g.nbricks = g.nbx * g.nby * g.nbz;
-            g.brick_nodes = g.bx * g.by * g.bz;
-        }
+    for (int s = first; s < std::max(n_shapes, first + 1); ++s) {
+        g = fixed ? e->g : rebrick(e->g, shapes[s][0], shapes[s][1], shapes[s][2]);
         const size_t br = (size_t)g.nbricks * g.n_rows;
-        if (e->d_pmeta_raw.ensure(4 * br) || e->d_pmeta.ensure(4 * br) ||
-            e->d_ptotal.ensure(g.nbricks) || e->d_scalar.ensure(4))
+        if (L.raw.ensure(4 * br) || L.meta.ensure(4 * br) || L.total.ensure(g.nbricks) || e->d_scalar.ensure(4))
             return 1;
         QM_HIP(hipMemsetAsync(e->d_scalar.p, 0, 4 * sizeof(int32_t), e->stream));
         hipLaunchKernelGGL(qm::brick_minmax_kernel, dim3(g.nbricks), dim3(64), 0, e->stream, g,
-                           e->d_lut.p, reinterpret_cast<int4 *>(e->d_pmeta_raw.p), e->d_scalar.p);
+                           e->d_lut.p, reinterpret_cast<int4 *>(L.raw.p), e->d_scalar.p);
         hipLaunchKernelGGL(qm::screen_prefix_kernel, dim3((g.nbricks + 255) / 256), dim3(256), 0,
-                           e->stream, g, reinterpret_cast<const int4 *>(e->d_pmeta_raw.p),
-                           reinterpret_cast<int4 *>(e->d_pmeta.p), e->d_ptotal.p);
+                           e->stream, g, reinterpret_cast<const int4 *>(L.raw.p),
+                           reinterpret_cast<int4 *>(L.meta.p), L.total.p);
         QM_HIP(hipGetLastError());
         total.resize(g.nbricks);
-        QM_HIP(copy_back(total.data(), e->d_ptotal.p, (size_t)g.nbricks * sizeof(int32_t), e->stream));
+        QM_HIP(copy_back(total.data(), L.total.p, (size_t)g.nbricks * sizeof(int32_t), e->stream));
         QM_HIP(hipStreamSynchronize(e->stream));
         wide.clear();
         for (int b = 0; b < g.nbricks; ++b)
-            if (!qm::pair_fits(total[b], g.n_rows, KT, kPairLdsBytes)) wide.push_back(b);
+            if (!fits(total[b], g.n_rows, KT, budget)) wide.push_back(b);
         if ((int64_t)wide.size() * 200 <= g.nbricks) break;    // <= 0.5 % on the slow path
     }
-    e->n_pwide = (int)wide.size();
-    // an incoherent table (every shape leaves bricks that do not fit): the chunked kernels, whose
-    // single-copy windows are half the size, take it
-    // (with an explicit brick shape: whatever fits is paired, the rest goes to the direct kernel)
-    e->pair_ok = fixed ? (int)wide.size() < g.nbricks : (int64_t)wide.size() * 200 <= g.nbricks;
-    if (e->n_pwide) {
-        if (e->d_pwide.ensure(wide.size())) return 1;
-        QM_HIP(copy_in(e->d_pwide.p, wide.data(), wide.size() * sizeof(int32_t), e->stream));
+    L.n_list = (int)wide.size();
+    const bool rel = want_rel(g, L.n_list);
+    if (L.n_list) {
+        if (L.list.ensure(wide.size())) return 1;
+        QM_HIP(copy_in(L.list.p, wide.data(), wide.size() * sizeof(int32_t), e->stream));
     }
-    if (e->pair_ok) {
-        if (e->d_prel.ensure((size_t)g.nbricks * g.brick_nodes * g.row_pad)) return 1;
-        hipLaunchKernelGGL(qm::pair_rel_kernel, dim3(g.nbricks), dim3(256), 0, e->stream, g,
-                           e->d_lut.p, reinterpret_cast<const int4 *>(e->d_pmeta.p), e->d_ptotal.p,
-                           KT, kPairLdsBytes, e->d_prel.p);
+    if (rel) {
+        if (L.rel.ensure((size_t)g.nbricks * g.brick_nodes * g.row_pad)) return 1;
+        hipLaunchKernelGGL(rel_kernel, dim3(g.nbricks), dim3(256), 0, e->stream, g, e->d_lut.p,
+                           reinterpret_cast<const int4 *>(L.meta.p), L.total.p, KT, budget, L.rel.p);
         QM_HIP(hipGetLastError());
     }
     QM_HIP(hipStreamSynchronize(e->stream));           // `wide` is a stack-lifetime buffer
-    e->pg = g;
-    e->pair_kt = KT;
+    L.g = g;
+    return 0;
+}
+
+// Own brick grid (e->pair.g): the largest brick shape whose two staggered window copies fit 160 KB
+// for (almost) every brick; per-brick (min, span2, prefix) records and the 16-bit offset table.
+int ensure_pair_tables(qm_engine *e, int jp) {
+    PairLayout &P = e->pair;
+    const int KT = 128 * jp;
+    if (P.kt == KT) return 0;
+    static const int kShapes[][3] = {{8, 8, 8}, {4, 8, 8}, {4, 4, 8}, {4, 4, 4},
+                                     {2, 4, 4}, {2, 2, 4}, {2, 2, 2}, {1, 1, 2}, {1, 1, 1}};
+    // an incoherent table (every shape leaves bricks that do not fit): the chunked kernels, whose
+    // single-copy windows are half the size, take it
+    // (with an explicit brick shape: whatever fits is paired, the rest goes to the direct kernel)
+    // -- the offsets are built only for a table that is paired
+    auto paired = [&](const qm::GridDesc &g, int n_list) {
+        P.ok = e->cfg_bx > 0 ? n_list < g.nbricks : (int64_t)n_list * 200 <= g.nbricks;
+        return P.ok;
+    };
+    if (search_bricks(e, P, kShapes, 0, (int)(sizeof(kShapes) / sizeof(kShapes[0])), qm::pair_fits, KT,
+                      kPairLdsBytes, qm::pair_rel_kernel, paired))
+        return 1;
+    P.kt = KT;
     return 0;
 }
 
@@ -287,22 +316,14 @@ static int build_shift_tables(qm_engine *e, ShiftLayout &L, bool wide, bool wide
     qm::GridDesc g = e->g;
     std::vector<int32_t> fit, fitw, list;
     bool ok = false;
-    auto even_up = [](int v) { return v + (v & 1); };
     for (int cand = 0; cand < n_candidates && !ok; ++cand) {
     nw = candidates[cand];
     const int (*kShapes)[3] = blocks ? (quad ? kShapesBlocks4 : kShapesBlocks) : wide ? kShapesWide
                               : nw == qm::kShiftWaves3 ? kShapes12 : nw == qm::kShiftWaves8 ? kShapes8 : shapes4;
     const int n_try = kShapes == shapes4 ? n_shapes : std::min(n_shapes, 5);
     for (int s = 0; s < n_try; ++s) {
-        g = e->g;
-        g.bx = std::min(even_up(fixed ? e->cfg_bx : kShapes[s][0]), even_up(g.nx));
-        g.by = std::min(even_up(fixed ? e->cfg_by : kShapes[s][1]), even_up(g.ny));
-        g.bz = std::min(even_up(fixed ? e->cfg_bz : kShapes[s][2]), even_up(g.nz));
-        g.nbx = (g.nx + g.bx - 1) / g.bx;
-        g.nby = (g.ny + g.by - 1) / g.by;
-        g.nbz = (g.nz + g.bz - 1) / g.bz;
-        g.nbricks = g.nbx * g.nby * g.nbz;
-        g.brick_nodes = g.bx * g.by * g.bz;
+        g = fixed ? rebrick(e->g, e->cfg_bx, e->cfg_by, e->cfg_bz, true)
+                  : rebrick(e->g, kShapes[s][0], kShapes[s][1], kShapes[s][2], true);
         const size_t br = (size_t)g.nbricks * S;
         const size_t nvb = (size_t)g.nbricks * nblk;               // (brick, row block) pairs
         // (meta: + 4 KB of slack -- the row-block loops prefetch that much metadata ahead)
@@ -444,64 +465,21 @@ ScreenPlan screen_plan(const qm_engine *e, int S, int n_samples) {
     return best;
 }
 
-// The sweep has its own brick grid (e->sg): its LDS budget and window layout differ from the
+// The sweep has its own brick grid (e->screen.g): its LDS budget and window layout differ from the
 // float64 kernel's, so the largest brick shape whose windows fit is chosen for it separately.
 int ensure_screen_tables(qm_engine *e, const ScreenPlan &plan) {
+    ScreenLayout &L = e->screen;
     const int KT = plan.kt();
     const int wb = plan.window_bytes(e);
-    if (e->screen_kt == KT && e->screen_wb == wb) return 0;
+    if (L.kt == KT && L.wb == wb) return 0;
     static const int kShapes[][3] = {{16, 8, 8}, {8, 8, 8}, {4, 8, 8}, {4, 4, 8}, {4, 4, 4},
                                      {2, 4, 4},  {2, 2, 4}, {2, 2, 2}, {1, 1, 2}, {1, 1, 1}};
-    const bool fixed = e->cfg_bx > 0;
-    const int n_shapes = fixed ? 1 : (int)(sizeof(kShapes) / sizeof(kShapes[0]));
-    const int first = fixed ? 0 : (e->cfg_screen_brick16 ? 0 : 1);
-    qm::GridDesc g = e->g;
-    std::vector<int32_t> total, wide;
-    for (int s = first; s < std::max(n_shapes, first + 1); ++s) {
-        g = e->g;
-        if (!fixed) {
-            g.bx = std::min(kShapes[s][0], g.nx);
-            g.by = std::min(kShapes[s][1], g.ny);
-            g.bz = std::min(kShapes[s][2], g.nz);
-            g.nbx = (g.nx + g.bx - 1) / g.bx;
-            g.nby = (g.ny + g.by - 1) / g.by;
-            g.nbz = (g.nz + g.bz - 1) / g.bz;
-            g.nbricks = g.nbx * g.nby * g.nbz;
-            g.brick_nodes = g.bx * g.by * g.bz;
-        }
-        const size_t br = (size_t)g.nbricks * g.n_rows;
-        if (e->d_smeta_raw.ensure(4 * br) || e->d_smeta.ensure(4 * br) ||
-            e->d_stotal.ensure(g.nbricks) || e->d_scalar.ensure(4))
-            return 1;
-        QM_HIP(hipMemsetAsync(e->d_scalar.p, 0, 4 * sizeof(int32_t), e->stream));
-        hipLaunchKernelGGL(qm::brick_minmax_kernel, dim3(g.nbricks), dim3(64), 0, e->stream, g,
-                           e->d_lut.p, reinterpret_cast<int4 *>(e->d_smeta_raw.p), e->d_scalar.p);
-        hipLaunchKernelGGL(qm::screen_prefix_kernel, dim3((g.nbricks + 255) / 256), dim3(256), 0,
-                           e->stream, g, reinterpret_cast<const int4 *>(e->d_smeta_raw.p),
-                           reinterpret_cast<int4 *>(e->d_smeta.p), e->d_stotal.p);
-        QM_HIP(hipGetLastError());
-        total.resize(g.nbricks);
-        QM_HIP(copy_back(total.data(), e->d_stotal.p, (size_t)g.nbricks * sizeof(int32_t), e->stream));
-        QM_HIP(hipStreamSynchronize(e->stream));
-        wide.clear();
-        for (int b = 0; b < g.nbricks; ++b)
-            if (!qm::screen_fits(total[b], g.n_rows, KT, wb)) wide.push_back(b);
-        if ((int64_t)wide.size() * 200 <= g.nbricks) break;    // <= 0.5 % on the slow path
-    }
-    e->n_swide = (int)wide.size();
-    if (e->n_swide) {
-        if (e->d_swide.ensure(wide.size())) return 1;
-        QM_HIP(copy_in(e->d_swide.p, wide.data(), wide.size() * sizeof(int32_t), e->stream));
-    }
-    if (e->d_srel.ensure((size_t)g.nbricks * g.brick_nodes * g.row_pad)) return 1;
-    hipLaunchKernelGGL(qm::screen_rel_kernel, dim3(g.nbricks), dim3(256), 0, e->stream, g,
-                       e->d_lut.p, reinterpret_cast<const int4 *>(e->d_smeta.p), e->d_stotal.p, KT,
-                       wb, e->d_srel.p);
-    QM_HIP(hipGetLastError());
-    QM_HIP(hipStreamSynchronize(e->stream));           // `wide` is a stack-lifetime buffer
-    e->sg = g;
-    e->screen_kt = KT;
-    e->screen_wb = wb;
+    if (search_bricks(e, L, kShapes, e->cfg_screen_brick16 ? 0 : 1, (int)(sizeof(kShapes) / sizeof(kShapes[0])),
+                      qm::screen_fits, KT, wb, qm::screen_rel_kernel,
+                      [](const qm::GridDesc &, int) { return true; }))   // (the offsets: always)
+        return 1;
+    L.kt = KT;
+    L.wb = wb;
     return 0;
 }
 
@@ -584,45 +562,37 @@ int qm_engine_load_lut(qm_engine *e, const int32_t *lut, int lut_on_device, int3
     // the table's largest delay); whether a shape's windows fit depends on the tile length and the
     // LDS budget and is decided on the host from the cached totals -- the layout search below asks
     // for up to seven (tile length, budget) pairs, which used to cost as many passes and host
-    // round trips per load.  `on_device`: the shape whose records d_bmeta / d_btotal hold.
+    // round trips per load.  `on_device`: the shape whose records R.meta / R.total hold.
+    Round2Layout &R = e->r2();
+    qm::GridDesc table{};                               // the table's shape, no bricks yet
+    table.nx = nx; table.ny = ny; table.nz = nz;
+    table.n_rows = n_rows; table.row_pad = (n_rows + 7) / 8 * 8;
     std::vector<std::vector<int32_t>> totals(n_shapes);
     std::vector<qm::GridDesc> shapes(n_shapes);
     int on_device = -1;
     auto measure = [&](int s) -> int {
         qm::GridDesc &gs = shapes[s];
-        gs = qm::GridDesc{};
-        gs.nx = nx; gs.ny = ny; gs.nz = nz;
-        gs.bx = std::min(e->cfg_bx > 0 ? e->cfg_bx : kShapes[s][0], (int)nx);
-        gs.by = std::min(e->cfg_bx > 0 ? e->cfg_by : kShapes[s][1], (int)ny);
-        gs.bz = std::min(e->cfg_bx > 0 ? e->cfg_bz : kShapes[s][2], (int)nz);
-        gs.nbx = (nx + gs.bx - 1) / gs.bx;
-        gs.nby = (ny + gs.by - 1) / gs.by;
-        gs.nbz = (nz + gs.bz - 1) / gs.bz;
-        const int64_t nbricks = (int64_t)gs.nbx * gs.nby * gs.nbz;
-        if (nbricks >= INT32_MAX) return fail("too many bricks");
-        gs.nbricks = (int)nbricks;
-        gs.brick_nodes = gs.bx * gs.by * gs.bz;
-        gs.n_rows = n_rows;
-        gs.row_pad = (n_rows + 7) / 8 * 8;
-        const size_t br = (size_t)nbricks * n_rows;
-        if (e->d_bmeta.ensure(4 * br) || e->d_btotal.ensure(nbricks)) return 1;
+        gs = e->cfg_bx > 0 ? rebrick(table, e->cfg_bx, e->cfg_by, e->cfg_bz)
+                           : rebrick(table, kShapes[s][0], kShapes[s][1], kShapes[s][2]);
+        const size_t nbricks = gs.nbricks;
+        const size_t br = nbricks * n_rows;
+        if (R.meta.ensure(4 * br) || R.total.ensure(nbricks)) return 1;
         QM_HIP(hipMemsetAsync(e->d_scalar.p, 0, 4 * sizeof(int32_t), e->stream));
         hipLaunchKernelGGL(qm::brick_minmax_kernel, dim3(gs.nbricks), dim3(64), 0, e->stream, gs,
-                           e->d_lut.p, reinterpret_cast<int4 *>(e->d_bmeta.p), e->d_scalar.p);
+                           e->d_lut.p, reinterpret_cast<int4 *>(R.meta.p), e->d_scalar.p);
         QM_HIP(hipGetLastError());
         hipLaunchKernelGGL(qm::brick_prefix_kernel, dim3((gs.nbricks + 255) / 256), dim3(256),
-                           0, e->stream, gs, reinterpret_cast<int4 *>(e->d_bmeta.p),
-                           e->d_btotal.p);
+                           0, e->stream, gs, reinterpret_cast<int4 *>(R.meta.p), R.total.p);
         QM_HIP(hipGetLastError());
         totals[s].resize(nbricks);
-        QM_HIP(copy_back(totals[s].data(), e->d_btotal.p, nbricks * sizeof(int32_t), e->stream));
+        QM_HIP(copy_back(totals[s].data(), R.total.p, nbricks * sizeof(int32_t), e->stream));
         QM_HIP(copy_back(&e->lut_max, e->d_scalar.p, sizeof(int32_t), e->stream));
         QM_HIP(hipStreamSynchronize(e->stream));
         on_device = s;
         return 0;
     };
     // largest candidate shape whose windows fit for tile length 64 * J under the current budget
-    // (result: g and e->h_btotal; `chosen` = its index)
+    // (result: g and R.h_total; `chosen` = its index)
     int chosen = 0;
     auto search = [&](int J) -> int {
         const int KT = qm::kWave * J;
@@ -683,22 +653,18 @@ int qm_engine_load_lut(qm_engine *e, const int32_t *lut, int lut_on_device, int3
     if (search(eff_j(e))) return 1;
     if (on_device != chosen && measure(chosen)) return 1;   // the chosen shape's records on the device
     g = shapes[chosen];
-    e->h_btotal = totals[chosen];
+    R.h_total = totals[chosen];
     // (the window-offset table of the round-2 kernels -- 2 bytes per table entry padded to 8 rows --
     // is built when one of them first runs: ensure_rel; tables the shift-reuse kernel takes never
     // need it)
-    e->rel_built = false;
+    R.rel_built = false;
     QM_HIP(hipStreamSynchronize(e->stream));
-    e->g = g;
+    R.g = g;
     e->n_nodes = n_nodes;
     e->node_offset = node_offset;
     e->tab_waves = e->cfg_waves;                        // (what the layout search left in the tunables)
     e->tab_lds_bytes = e->cfg_lds_bytes;
-    e->plan_j = -1;
-    e->screen_kt = 0;
-    e->pair_kt = 0;
-    e->sh.built = e->sh.ok = false;
-    e->shw.built = e->shw.ok = false;
+    e->invalidate_derived();
     e->have_lut = true;
     static std::atomic<uint64_t> next_serial{1};
     e->serial = next_serial.fetch_add(1);
@@ -778,11 +744,7 @@ int qm_engine_table_select(qm_engine *e, uint64_t key, int32_t capacity, int32_t
     } else if (e->have_lut) {
         // nothing may be parked: keep the buffers for the next table (load_lut reuses allocations)
         e->have_lut = false;
-        e->sh.built = e->sh.ok = false;
-        e->shw.built = e->shw.ok = false;
-        e->pair_kt = 0;
-        e->screen_kt = 0;
-        e->plan_j = -1;
+        e->invalidate_derived();
     }
     e->cur_key = key;
     e->cur_keyed = true;

@@ -12,7 +12,8 @@ first launch that takes them and parked with their table, and whose ``last_*`` f
   launch at scan lengths across every tile boundary, stream changes and pool releases.  Every distinct request is
   also evaluated ONCE on a fresh engine of the flavour (make, load, one call, close), that result is held to the CPU
   oracle at the suite's bounds (the tie_rule = 1 index series to oracle.np_argmax_exp_rule on every sample), and at every step the long-lived engine's outputs -- the three series, every stored
-  volume value, the marginal map, the partial sets, the read-outs of the launch -- must be ``np.array_equal`` to it.
+  volume value, the marginal map, the partial sets, the read-outs of the launch and of the brick layout it ran on
+  (``LAYOUT_KEYS``) -- must be ``np.array_equal`` to it.
 * ``test_walk_with_a_poisoned_pool``: the ``engine`` and ``tie_rule`` walks, shorter, in a child process each with
   ``QM_HIP_POOL_POISON=1`` (every block the device pool hands out starts as 0xFF bytes).
 * ``test_tie_partial_after_an_intervening_call`` and ``test_screen_and_tie_rule_exclude_each_other``: the two
@@ -171,10 +172,29 @@ def _get(lib, eng, key):
         return str(e)                   # a function of the launch as well)
 
 
+# The layout the launch ran on, by the stacking kernel's family (last_kernel): brick size and the bricks that do not
+# fit it.  Only the family the launch TOOK: a long-lived engine legitimately still holds an older layout in the others.
+LAYOUT_KEYS = {
+    0: ("n_bricks", "n_wide_bricks"),                                   # round-2 kernels: chunked ...
+    1: ("n_bricks", "n_wide_bricks"),                                   # ... and exact-row-count
+    2: ("pair_tile", "pair_brick_nodes", "pair_wide_bricks"),           # paired
+    3: ("shift_brick_nodes", "shift_wide_bricks"),                      # shift-reuse, 256-sample tiles
+    "wide": ("shift_wide_brick_nodes", "shift_wide_direct_bricks"),     # shift-reuse with wide tiles in front
+}
+SCREEN_LAYOUT_KEYS = ("screen_brick_nodes", "screen_pairs")
+
+
+def _swept_steps(lib, eng):
+    """Detect steps that went through the screening sweep so far, screened or redone in float64."""
+    return _get(lib, eng, "screened_steps") + _get(lib, eng, "fallback_steps")
+
+
 def _run(lib, eng, req):
     """One request on ``eng`` (its table is resident): a dict of everything the call wrote, outputs pre-filled with
     NaN / -1, and the launch's read-outs."""
     out = {}
+    sweeps = req.kind in ("detect", "detect_batch", "detect_partial") and _get(lib, eng, "screen") == 1
+    swept = _swept_steps(lib, eng) if sweeps else 0
     if req.kind == "find_max_coa":
         series = _nan_series(req.ns)
         eng.find_max_coa(sp.fmc_volume(req.ns), req.ns, sp.FMC_NODES, out=series)
@@ -234,6 +254,14 @@ def _run(lib, eng, req):
         read.update({k: _get(lib, eng, k) for k in ("shift_wide_tiles", "shift_tail_spl")})
     if req.kind == "detect_batch":
         read["steps_per_launch"] = _get(lib, eng, "steps_per_launch")
+    # ... and of the layout it ran on: a table that comes back from parking, or is loaded over another, has the
+    # layout a fresh engine builds (a group whose box engines disagree on the family: as before, the text alone)
+    family = read["last_kernel"]
+    if family == 3 and read["shift_wide_tiles"] != 0:
+        family = "wide" if isinstance(read["shift_wide_tiles"], int) else None
+    read.update({k: _get(lib, eng, k) for k in LAYOUT_KEYS.get(family, ())})
+    if sweeps and _swept_steps(lib, eng) > swept:
+        read.update({k: _get(lib, eng, k) for k in SCREEN_LAYOUT_KEYS})
     out["readouts"] = read
     return out
 
