@@ -205,6 +205,10 @@ int qm_engine_synchronize(qm_engine *e);
  * last_candidates, screen_brick_nodes; tie_refined_steps, tie_pairs and tie_overflow_samples (of the last
  * refined launch), tie_brick_rows (rows of per-brick maxima the last stacking launch left: 0 = it refined from
  * sets of bricks);
+ * The read-outs of a launch -- last_kernel, last_kernel_j, shift_waves, shift_lazy, shift_tail_spl, shift_wide_tiles,
+ * tie_brick_rows -- describe the LAST stacking launch, whatever its family: after a launch that is not shift-reuse
+ * shift_lazy, shift_tail_spl and shift_wide_tiles are 0 (shift_waves: the resident table's 256-sample layout's),
+ * after a launch of the direct kernel alone (force_direct, every brick too wide) last_kernel and last_kernel_j are 0.
  * table_hits, table_misses, table_evictions, tables_parked, table_bytes, tables_parked_bytes, table_digests;
  * pick_lds_samples (the longest onset row qm_engine_pick_phases takes: row and selection keys live in LDS). */
 int qm_engine_config(qm_engine *e, const char *key, int64_t value);

@@ -9,127 +9,13 @@
 
 namespace {
 
-// The launch_*_path functions below are handed, in a.g / a.brick_list / a.n_list, the bricks of the layout the
-// launch runs on and those of them that do not fit its LDS kernel (run_stack): the LDS launch runs without a
-// list, the direct launch on that one.
+using qm::kPairLdsBytes;
 
-qm::LaunchShape stack_shape(const qm_engine *e, const qm::StackArgs &a, int groups, int threads,
-                            size_t lds) {
+qm::LaunchShape stack_shape(const qm_engine *e, const qm::StackArgs &a, int threads, size_t lds) {
     // the grid is padded to a multiple of 8 groups (XCD-aware workgroup -> (tile, group) map)
     // (several timesteps per launch: the tile axis runs over (step, tile))
     const int steps = a.n_steps > 1 ? a.n_steps : 1;
-    return {(unsigned)(steps * a.ntiles * ((groups + 7) / 8 * 8)), threads, lds, e->stream};
-}
-
-int launch_direct(qm_engine *e, const qm::StackArgs &a, int J, bool volume, int groups,
-                  int threads, size_t publish_bytes) {
-    const qm::LaunchShape shape = stack_shape(e, a, groups, threads, publish_bytes);
-    bool built = false;
-    if (volume) QM_TABLE(qm::launch_direct_volume(J, a, shape, &built));
-    else QM_TABLE(qm::launch_direct_detect(J, a, shape, &built));
-    if (!built) return fail("no direct stacking kernel for %d samples per lane", J);
-    return 0;
-}
-
-template <int J, bool VOLUME>
-int launch_stack_j(qm_engine *e, qm::StackArgs &a, int groups_lds, int groups_direct,
-                   bool use_lds, bool use_direct) {
-    const int32_t *const list = a.brick_list;
-    const int n_list = a.n_list;
-    const int KT = qm::kWave * J;
-    const int threads = e->cfg_waves * qm::kWave;
-    const size_t publish_bytes = (size_t)3 * e->cfg_waves * KT * sizeof(double);
-    if (use_lds) {
-        const size_t lds = std::max((size_t)e->cfg_lds_bytes, publish_bytes);
-        a.ngroups = groups_lds;
-        a.brick_list = nullptr;
-        a.n_list = 0;
-        const qm::LaunchShape shape = stack_shape(e, a, groups_lds, threads, lds);
-        const int S = e->g.n_rows;
-        bool exact = false;
-        // the exact-row-count kernels: fused detect and the marginalised map for up to 64 rows,
-        // volume-writing for 33-64 rows (up to 32 the paired kernel writes volumes), when the
-        // launch uses the table width's own samples per lane
-        if (e->cfg_exact && !e->cfg_generic && !a.accumulate && qm::exact_built(S, J)) {
-            const bool j4_wide = J == 4 && S > 40;     // the second variant of 41-64 rows
-            if (a.marginal != nullptr) {
-                if (S <= 32) QM_TABLE(qm::launch_exact_marginal_1_32(S, a, shape, &exact));
-                else if (!j4_wide) QM_TABLE(qm::launch_exact_marginal_33_64(S, a, shape, &exact));
-                else QM_TABLE(qm::launch_exact_marginal_j4_41_64(S, a, shape, &exact));
-            } else if (!VOLUME) {
-                if (S <= 32) QM_TABLE(qm::launch_exact_detect_1_32(S, a, shape, &exact));
-                else if (!j4_wide) QM_TABLE(qm::launch_exact_detect_33_64(S, a, shape, &exact));
-                else QM_TABLE(qm::launch_exact_detect_j4_41_64(S, a, shape, &exact));
-            } else if (S > qm::kPairMaxRows) {
-                if (!j4_wide) QM_TABLE(qm::launch_exact_volume_33_64(S, a, shape, &exact));
-                else QM_TABLE(qm::launch_exact_volume_j4_41_64(S, a, shape, &exact));
-            }
-        }
-        e->last_kernel = exact ? 1 : 0;
-        e->last_j = J;
-        // Variants specialised on the number of 8-row offset chunks (whole-node offset prefetch;
-        // detect: software-pipelined node loop) for up to 64 table rows; otherwise, and for the
-        // reference's accumulate-into-volume semantics, the generic kernel.
-        if (!exact) {
-            int nch = (e->cfg_generic || a.accumulate) ? 0 : e->g.row_pad / 8;
-            if (nch > 8) nch = 0;
-            bool built = false;
-            if (VOLUME) QM_TABLE(qm::launch_chunked_volume(J, nch, a, shape, &built));
-            else QM_TABLE(qm::launch_chunked_detect(J, nch, a, shape, &built));
-            if (!built) return fail("no chunked stacking kernel for %d samples per lane", J);
-        }
-        a.set0 += groups_lds;
-    }
-    if (use_direct) {
-        a.ngroups = groups_direct;
-        if (e->cfg_force_direct) {
-            a.brick_list = nullptr;
-            a.n_list = e->g.nbricks;
-        } else {
-            a.brick_list = list;
-            a.n_list = n_list;
-        }
-        if (launch_direct(e, a, J, VOLUME, groups_direct, threads, publish_bytes)) return 1;
-        a.set0 += groups_direct;
-    }
-    return 0;
-}
-
-using qm::kPairLdsBytes;
-using qm::pair_jp_of;
-
-// LDS launch over the bricks that fit the paired layout + direct launch over those that do not
-template <int JP, bool VOLUME>
-int launch_pair_path(qm_engine *e, qm::StackArgs &a, int groups_lds, int groups_direct,
-                     bool use_lds, bool use_direct) {
-    const int32_t *const list = a.brick_list;
-    const int n_list = a.n_list;
-    if (use_lds) {
-        a.ngroups = groups_lds;
-        a.brick_list = nullptr;
-        a.n_list = 0;
-        bool done = false;
-        const qm::LaunchShape shape = stack_shape(e, a, a.ngroups, 1024, kPairLdsBytes);
-        if (pair_jp_of(e->g.n_rows) == JP) {
-            if (VOLUME) QM_TABLE(qm::launch_pair_volume(e->g.n_rows, a, shape, &done));
-            else QM_TABLE(qm::launch_pair_detect(e->g.n_rows, a, shape, &done));
-        }
-        if (!done) return fail("no paired kernel built for %d rows", e->g.n_rows);
-        e->last_kernel = 2;
-        e->last_j = 2 * JP;
-        a.set0 += groups_lds;
-    }
-    if (use_direct) {
-        constexpr int J = 2 * JP;                      // same tile length: 64 * J = 128 * JP
-        const int threads = 1024;
-        const size_t publish_bytes = (size_t)3 * (threads / qm::kWave) * qm::kWave * J * sizeof(double);
-        a.ngroups = groups_direct;
-        a.brick_list = list;
-        a.n_list = n_list;
-        if (launch_direct(e, a, J, VOLUME, groups_direct, threads, publish_bytes)) return 1;
-        a.set0 += groups_direct;
-    }
-    return 0;
+    return {(unsigned)(steps * a.ntiles * ((a.ngroups + 7) / 8 * 8)), threads, lds, e->stream};
 }
 
 bool pair_built(int S) { return S >= 1 && S <= qm::kPairMaxRows; }
@@ -163,92 +49,18 @@ int shift_tail_spl(const qm_engine *e, int rest) {
 // Tiles of a fused detect on the wide layout: 384-sample tiles in front; what the scan leaves beyond them runs
 // as ONE tail tile (<= 192 samples), ONE 256-sample tile pulled back over its predecessor (<= 256), or one more
 // wide tile pulled back (qm_shift.hpp: shift_work).
-void shift_wide_tiles(const qm_engine *e, int n_chunk, bool only_wide, qm::StackArgs &a) {
+void shift_wide_tiles(const qm_engine *e, int n_chunk, bool only_wide, StackPlan &p) {
     int wide = n_chunk / qm::kShiftWideKT;
     const int rest = n_chunk - wide * qm::kShiftWideKT;
-    a.tail_spl = 0;
+    p.tail_spl = 0;
     int behind = 0;
     if (rest > qm::kShiftKT || (only_wide && rest > 0)) ++wide;      // (row blocks: no other tile kinds)
     else if (rest > 0) {
-        a.tail_spl = shift_tail_spl(e, rest);
+        p.tail_spl = shift_tail_spl(e, rest);
         behind = 1;
     }
-    a.wide_tiles = wide;
-    a.ntiles = wide + behind;
-}
-
-int launch_shift_path(qm_engine *e, const ShiftLayout &L, qm::StackArgs &a, int groups_lds, int groups_direct,
-                      bool use_lds, bool use_direct, int mode) {
-    const int32_t *const list = a.brick_list;
-    const int n_list = a.n_list;
-    const bool volume = mode != qm::kShiftDetect;        // (the direct kernel's VOLUME covers the map too)
-    if (use_lds) {
-        a.ngroups = groups_lds;
-        a.brick_list = nullptr;
-        a.n_list = 0;
-        qm::ShiftArgs s{};
-        s.a = a;
-        s.smeta = reinterpret_cast<const int4 *>(L.meta.p);
-        s.stotal = L.total.p;
-        s.sfit = L.fit.p;
-        s.stream = reinterpret_cast<const char *>(L.stream.p);
-        s.wmeta = reinterpret_cast<const int4 *>(L.wmeta.p);
-        s.wtotal = L.wtotal.p;
-        s.wstream = reinterpret_cast<const char *>(L.wstream.p);
-        s.rows2 = L.rows2;
-        s.nw = L.nw;
-        s.nblk = L.nblk;
-        s.sb = L.sb;
-        s.stage_slots = L.stage_slots;
-        s.stage_reach = L.stage_reach;
-        // groups a wavefront sees before its running maximum is reset: bricks per workgroup x
-        // groups per (brick, wavefront)
-        // (brick maxima, tie_rule = 1: the wide tiles' loop raises them itself -- the running maximum lives as long
-        // as ever --, the other tiles fold and reset it after every brick)
-        const bool per_brick = a.brick_max && a.wide_tiles == 0;
-        const int64_t life = (per_brick ? 1 : (int64_t)L.g.nbricks / std::max(1, a.ngroups)) *
-                             std::max(1, L.g.brick_nodes / 8 / L.nw);
-        s.lazy = e->cfg_shift_lazy >= 0 ? e->cfg_shift_lazy : (life >= qm::kShiftLazyGroups ? 1 : 0);
-        if (L.nblk > 1 && !L.direct) s.lazy = 0;    // (the register-staged form: eager only)
-        e->shift_lazy_last = s.lazy;
-        e->shift_tail_last = a.tail_spl;
-        e->shift_wide_last = a.wide_tiles;
-        const qm::LaunchShape shape = stack_shape(e, a, a.ngroups, L.nw * qm::kWave,
-                                                  qm::shift_lds_bytes(L.nw));
-        const bool rows = L.nblk > 1, big = L.nw == qm::kShiftWaves8;
-        if (L.wide && L.direct) QM_TABLE(qm::launch_shift_wide_rows(s, shape));   // (also a single block)
-        else if (rows && L.quad && mode == qm::kShiftVolume) QM_TABLE(qm::launch_shift_rows4_volume(s, shape));
-        else if (rows && L.quad) QM_TABLE(qm::launch_shift_rows4(s, shape));
-        else if (rows && L.direct && mode == qm::kShiftVolume) QM_TABLE(qm::launch_shift_rows2_volume(s, shape));
-        else if (rows && L.direct) QM_TABLE(qm::launch_shift_rows2(s, shape));
-        else if (rows) QM_TABLE(qm::launch_shift_rows8(s, shape));
-        else if (mode == qm::kShiftMarginal && big) QM_TABLE(qm::launch_shift_marginal8(s, shape));
-        else if (mode == qm::kShiftMarginal) QM_TABLE(qm::launch_shift_marginal(s, shape));
-        else if (mode == qm::kShiftVolume && big) QM_TABLE(qm::launch_shift_volume8(s, shape));
-        else if (mode == qm::kShiftVolume) QM_TABLE(qm::launch_shift_volume(s, shape));
-        else if (L.nw == qm::kShiftWaves3) QM_TABLE(qm::launch_shift_detect3(s, shape));
-        else if (a.brick_max && big) QM_TABLE(qm::launch_shift_detect8_sets(s, shape));
-        else if (a.brick_max) QM_TABLE(qm::launch_shift_detect_sets(s, shape));
-        else if (big) QM_TABLE(qm::launch_shift_detect8(s, shape));
-        else QM_TABLE(qm::launch_shift_detect(s, shape));
-        e->last_kernel = 3;
-        e->last_j = a.wide_tiles > 0 ? qm::kShiftWideSpl : 4;
-        a.set0 += groups_lds;
-    }
-    if (use_direct) {
-        const int threads = 512;
-        const size_t publish_bytes = (size_t)3 * (threads / qm::kWave) * qm::kShiftKT * sizeof(double);
-        a.ngroups = groups_direct;
-        a.brick_list = list;
-        a.n_list = n_list;
-        a.tail_spl = 0;                                // (its own whole tiles of 256 samples, clamped)
-        a.brick_max = nullptr;
-        a.wide_tiles = 0;
-        a.ntiles = (a.n_chunk + qm::kShiftKT - 1) / qm::kShiftKT;
-        if (launch_direct(e, a, 4, volume, groups_direct, threads, publish_bytes)) return 1;
-        a.set0 += groups_direct;
-    }
-    return 0;
+    p.wide_tiles = wide;
+    p.ntiles = wide + behind;
 }
 
 }  // namespace
@@ -271,60 +83,31 @@ int auto_groups(const qm_engine *e, int ntiles, int units, int blocks_per_cu, in
     return (int)want;
 }
 
-// Stack samples [sample0, sample0+n_chunk) of the scan.  Partials (if want_scan) land in
-// e->d_pmax/d_pidx/d_psum as [sets][n_steps * n_chunk].
-StackResult run_stack(qm_engine *e, const StackLaunch &s) {
-    // n_steps > 1: that many timesteps in ONE launch (fused detect only).  Not every kernel can: batched =
-    // false then.  marginal: per-tile sums over the samples [first, end) land in e->d_marg as
-    // [e->marg_tiles][n_nodes] (the kernels differ in their tile length)
+namespace {
+
+// Everything that is decided about the stacking launch `s`, into *out: kernel family, layout, tiles, group counts,
+// what its partial sets will stand for.  Builds the family's tables on first use (device work); launches no stacking
+// kernel and leaves e->last alone.  out->batched = false: the launch cannot hold its n_steps timesteps.
+int plan_stack(qm_engine *e, const StackLaunch &s, StackPlan *out) {
+    StackPlan p;
     const auto *vol = std::get_if<StackLaunch::Volume>(&s.kind);
-    const auto *marg = std::get_if<StackLaunch::Marginal>(&s.kind);
-    double *const volume = vol ? vol->p : nullptr;
+    const bool volume = vol && vol->p, marginal = std::holds_alternative<StackLaunch::Marginal>(s.kind);
     const int64_t vol_stride = vol ? vol->stride : 0;
     const int accumulate = vol ? vol->accumulate : 0;
-    const bool marginal = marg != nullptr, want_scan = s.want_scan;
+    const bool want_scan = s.want_scan;
     const int n_chunk = s.n_chunk;
     const int J = run_j(e, n_chunk);
     if (plan_wide(e, J)) return 1;
     const int KT = qm::kWave * J;
     // The bricks the launch runs on, those of them that go to the direct kernel and the LDS kernel's tables are those
     // of ONE layout: the round-2 kernels' unless the shift-reuse or the paired kernel takes the launch below
-    qm::StackArgs a{};
-    auto run_on = [&a](const BrickLayout &layout) {
-        a.g = layout.g;
-        a.brick_list = layout.list.p;
-        a.n_list = layout.n_list;
-        a.rel = layout.rel.p;
-        a.brick_meta = layout.meta.p;
-        a.brick_total = layout.total.p;
-    };
-    run_on(e->r2());
-    a.onsets = s.onsets;
-    a.lut = e->d_lut.p;
-    a.T = s.T;
-    a.fsmp = s.fsmp;
-    a.n_samples = s.n_samples;
-    a.sample0 = s.sample0;
-    a.n_chunk = n_chunk;
-    a.ntiles = (n_chunk + KT - 1) / KT;
-    a.cap_doubles = lds_cap_doubles(e);
-    // coa = exp(stack/available) = 2^(stack * log2(e)/available)
-    a.z_scale = 1.4426950408889634074 / (double)s.available;
-    a.volume = volume;
-    a.vol_stride = vol_stride;
-    a.accumulate = accumulate;
-    a.want_scan = want_scan ? 1 : 0;
-    a.set0 = 0;
-    a.marginal = nullptr;
-    a.m0 = marg ? marg->first : 0;
-    a.m1 = marg ? marg->end : 0;
-    a.n_nodes = e->n_nodes;
-    a.run_if = s.run_if;
+    p.layout = &e->r2();
+    p.ntiles = (n_chunk + KT - 1) / KT;
+    p.cap_doubles = lds_cap_doubles(e);
 
     // ---- the shift-reuse kernel (qm_shift.hpp): the fused detect's default where the table fits
-    bool shift = shift_wanted(e, n_chunk, !accumulate && (volume || marginal || want_scan),
-                              volume != nullptr, vol_stride);
-    const int shift_mode = marginal ? qm::kShiftMarginal : volume ? qm::kShiftVolume : qm::kShiftDetect;
+    bool shift = shift_wanted(e, n_chunk, !accumulate && (volume || marginal || want_scan), volume, vol_stride);
+    p.shift_mode = marginal ? qm::kShiftMarginal : volume ? qm::kShiftVolume : qm::kShiftDetect;
     // Round 6: the fused detect of a scan that holds at least one 384-sample tile runs on the WIDE layout where
     // the table has one (ShiftLayout, qm_engine.hpp): its own brick grid, the 8-wave shape
     // (automatic: only where one timestep is at least eight rounds of one-brick workgroups over the CUs and holds
@@ -332,10 +115,10 @@ StackResult run_stack(qm_engine *e, const StackLaunch &s) {
     // the other, C3's 401-sample locate window 5.4 against 4.0: one wide tile and a short tail tile side by side
     // leave the CUs with the short one idle; the count is the single step's, so that a step's bits do not depend
     // on how many share its launch)
-    ShiftLayout *L = &e->sh;
+    const ShiftLayout *L = &e->sh;
     const int64_t wide_work = (int64_t)((e->g.nx + 7) / 8) * ((e->g.ny + 7) / 8) * ((e->g.nz + 15) / 16) *
                               ((n_chunk + qm::kShiftWideKT - 1) / qm::kShiftWideKT);
-    if (shift && shift_mode == qm::kShiftDetect && e->cfg_shift_wide != 0 && n_chunk >= qm::kShiftWideKT &&
+    if (shift && p.shift_mode == qm::kShiftDetect && e->cfg_shift_wide != 0 && n_chunk >= qm::kShiftWideKT &&
         // (tie_rule = 1 WITHOUT a row of maxima per brick -- tie_sets = 0, round 5's form -- re-stacks one set of bricks per
         // sample: the wide layout's few long workgroups would publish sets of tens of thousands of nodes)
         (e->cfg_shift_wide == 1 || (wide_work >= 8 * (int64_t)e->n_cu && n_chunk >= 4 * qm::kShiftWideKT &&
@@ -351,30 +134,26 @@ StackResult run_stack(qm_engine *e, const StackLaunch &s) {
         if (ensure_shift_tables(e, e->sh)) return 1;
         // the 12-wave shape and the register-staged row blocks are built for the fused detect only,
         // row blocks have no marginal-map flavour; none of the three has tail tiles
-        const bool plain = e->sh.nblk == 1 && e->sh.nw != qm::kShiftWaves3;
-        shift = e->sh.ok && (plain || (shift_mode == qm::kShiftDetect) ||
-                                (shift_mode == qm::kShiftVolume && e->sh.nblk > 1 && e->sh.direct));
-        a.tail_spl = (shift && plain) ? shift_tail_spl(e, n_chunk) : 0;
+        shift = L->ok && (L->plain() || (p.shift_mode == qm::kShiftDetect) ||
+                          (p.shift_mode == qm::kShiftVolume && L->nblk > 1 && L->direct));
+        p.tail_spl = (shift && L->plain()) ? shift_tail_spl(e, n_chunk) : 0;
         // a last tile that is pulled back needs a whole tile of scan (and the detect flavours of the
         // kernels without tail tiles keep their former lower bound)
-        if (shift && a.tail_spl == 0 && n_chunk % qm::kShiftKT != 0 &&
-            (shift_mode == qm::kShiftDetect ? n_chunk < 192 : n_chunk < qm::kShiftKT))
+        if (shift && p.tail_spl == 0 && n_chunk % qm::kShiftKT != 0 &&
+            (p.shift_mode == qm::kShiftDetect ? n_chunk < 192 : n_chunk < qm::kShiftKT))
             shift = false;
     }
     if (shift) {
-        run_on(*L);                                     // (its tables travel in ShiftArgs: launch_shift_path)
-        a.rel = nullptr;
-        a.brick_meta = nullptr;
-        a.brick_total = nullptr;
-        a.ntiles = (n_chunk + qm::kShiftKT - 1) / qm::kShiftKT;
-        a.cap_doubles = qm::kShiftLdsBytes / 8;
-        if (wide) shift_wide_tiles(e, n_chunk, L->direct, a);        // (direct: the wide layout's row-block form)
+        p.layout = p.shift = L;                         // (its tables travel in ShiftArgs: launch_shift_lds)
+        p.ntiles = (n_chunk + qm::kShiftKT - 1) / qm::kShiftKT;
+        p.cap_doubles = qm::kShiftLdsBytes / 8;
+        if (wide) shift_wide_tiles(e, n_chunk, L->direct, p);        // (direct: the wide layout's row-block form)
     } else {
-        a.tail_spl = 0;
+        p.tail_spl = 0;
     }
     // ---- the paired (16-byte operand) kernel where it applies and the shift-reuse kernel does not
     // take the launch: own brick grid and tables (built only then)
-    int jp = (shift || accumulate || marginal) ? 0 : pair_jp(e, n_chunk, volume != nullptr);
+    int jp = (shift || accumulate || marginal) ? 0 : pair_jp(e, n_chunk, volume);
     if (jp > 0) {
         if (!pair_built(e->g.n_rows)) jp = 0;
         else if (ensure_pair_tables(e, jp) != 0) return 1;   // a HIP failure while building the tables
@@ -382,38 +161,36 @@ StackResult run_stack(qm_engine *e, const StackLaunch &s) {
     }
     if (jp > 0) {
         const int PKT = 128 * jp;
-        run_on(e->pair);
-        a.ntiles = (n_chunk + PKT - 1) / PKT;
-        a.cap_doubles = kPairLdsBytes / 8;
+        p.layout = &e->pair;
+        p.ntiles = (n_chunk + PKT - 1) / PKT;
+        p.cap_doubles = kPairLdsBytes / 8;
     }
-    StackResult r;
     if (s.n_steps > 1) {
-        r.batched = !volume && !marginal && !accumulate && s.run_if == nullptr && want_scan &&
-                    (!shift || (L->nblk == 1 && L->nw != qm::kShiftWaves3 && !(L->wide && L->direct)));
-        if (!r.batched) return r;
-        a.n_steps = s.n_steps;
-        a.step_stride = s.step_stride;
+        p.batched = !volume && !marginal && !accumulate && s.run_if == nullptr && want_scan && (!shift || L->plain());
+        if (!p.batched) {
+            *out = p;
+            return 0;
+        }
+        p.steps = s.n_steps;
     }
-    const int steps = a.n_steps > 1 ? a.n_steps : 1;
-    a.part_stride = (int64_t)steps * n_chunk;
     if (!shift && jp == 0) {                            // the round-2 kernels' own offsets
+        if (J != 1 && J != 2 && J != 4) return fail("samples_per_lane must be 1, 2 or 4 (got %d)", J);
         if (ensure_rel(e)) return 1;
-        a.rel = e->r2().rel.p;
     }
-    if (marginal) {
-        if (e->d_marg.ensure((size_t)a.ntiles * e->n_nodes)) return 1;
-        a.marginal = e->d_marg.p;
-        e->marg_tiles = a.ntiles;
-    }
-    const int n_wide_now = a.n_list, nbricks_now = a.g.nbricks;
-    const bool use_direct = e->cfg_force_direct || n_wide_now > 0;
-    const bool use_lds = !e->cfg_force_direct && n_wide_now < nbricks_now;
-    const int threads = shift ? 512 : jp > 0 ? 1024 : e->cfg_waves * qm::kWave;   // (direct launch)
+    if (marginal) p.marg_tiles = p.ntiles;
+    const int n_wide_now = p.layout->n_list, nbricks_now = p.layout->g.nbricks;
+    p.use_direct = e->cfg_force_direct || n_wide_now > 0;
+    p.use_lds = !e->cfg_force_direct && n_wide_now < nbricks_now;
+    // the direct launch: the LDS kernel's tile length (64 * J = 128 * JP; the shift-reuse launch's bricks on whole
+    // 256-sample tiles of their own, clamped), the wavefronts' publish area
+    p.direct_j = shift ? 4 : jp > 0 ? 2 * jp : J;
+    p.direct_threads = shift ? 512 : jp > 0 ? 1024 : e->cfg_waves * qm::kWave;
+    p.direct_publish = (size_t)3 * (p.direct_threads / qm::kWave) * qm::kWave * p.direct_j * sizeof(double);
+    const int threads = p.direct_threads;
     const int lds_blocks_per_cu =
         shift ? (L->nw == qm::kShiftWaves ? 2 : 1) : jp > 0 ? 1
                : std::max(1, std::min(160 * 1024 / std::max(1, e->cfg_lds_bytes), 2048 / threads));
-    int groups_lds = 0, groups_direct = 0, brick_rows = 0;
-    if (use_lds) {
+    if (p.use_lds) {
         // (several timesteps per launch: the group count is the single step's -- the groups are the
         // order in which a sample's coalescence is summed over the nodes, and a step's result must
         // not depend on how many steps share its launch; the extra steps only make the grid longer)
@@ -430,107 +207,291 @@ StackResult run_stack(qm_engine *e, const StackLaunch &s) {
         if (shift && (wide || (L->nw == qm::kShiftWaves8 && L->nblk == 1)) && !e->user_rounds) {
             double best = 1e300;
             for (int r = 1; r <= e->cfg_rounds; ++r) {
-                const int g = auto_groups(e, a.ntiles, nbricks_now, lds_blocks_per_cu, r);
-                const double busy = (double)a.ntiles * g / ((double)r * e->n_cu * lds_blocks_per_cu);
+                const int g = auto_groups(e, p.ntiles, nbricks_now, lds_blocks_per_cu, r);
+                const double busy = (double)p.ntiles * g / ((double)r * e->n_cu * lds_blocks_per_cu);
                 const double cost = (1.0 - std::min(1.0, busy)) + 0.002 * r;
                 if (cost < best - 1e-9) { best = cost; rounds = r; }
             }
         }
         // (tie_rule = 1 stacks one SET of bricks again per sample, qm_ties.hpp: eight times as many,
         // smaller sets -- the refinement's cost falls with the set size, the stacking launch loses ~1 %)
-        groups_lds = e->cfg_groups > 0 ? std::min(e->cfg_groups, nbricks_now)
-                                       : auto_groups(e, a.ntiles, nbricks_now, lds_blocks_per_cu, rounds);
+        p.groups_lds = e->cfg_groups > 0 ? std::min(e->cfg_groups, nbricks_now)
+                                         : auto_groups(e, p.ntiles, nbricks_now, lds_blocks_per_cu, rounds);
         // Round 6: the shift-reuse fused detect leaves the largest z PER BRICK and sample beside its workgroups'
         // partial sets (StackArgs::brick_max): the refinement stacks one brick per sample, the launch keeps its
         // group count -- and its bits
-        brick_rows = (e->cfg_tie_rule && want_scan && e->cfg_tie_sets && shift && shift_mode == qm::kShiftDetect &&
-                      L->nblk == 1 && L->nw != qm::kShiftWaves3 && !(L->wide && L->direct)) ? nbricks_now : 0;
-        if (e->cfg_tie_rule && want_scan && !brick_rows && !e->user_rounds && e->cfg_groups == 0) {
+        p.brick_rows = (e->cfg_tie_rule && want_scan && e->cfg_tie_sets && shift && p.shift_mode == qm::kShiftDetect &&
+                        L->plain()) ? nbricks_now : 0;
+        if (e->cfg_tie_rule && want_scan && !p.brick_rows && !e->user_rounds && e->cfg_groups == 0) {
             // ... the other kernels: eight times as many, smaller sets, but never sets of fewer than four bricks:
             // the workgroup's fixed costs (C2: +8 % on the stacking launch at one brick per set)
-            const int fine = auto_groups(e, a.ntiles, std::max(1, nbricks_now / 4), lds_blocks_per_cu,
+            const int fine = auto_groups(e, p.ntiles, std::max(1, nbricks_now / 4), lds_blocks_per_cu,
                                          8 * (rounds > 0 ? rounds : e->cfg_rounds));
-            groups_lds = std::max(groups_lds, fine);
+            p.groups_lds = std::max(p.groups_lds, fine);
+        }
+        // which LDS kernel (the read-outs last_kernel / last_kernel_j; a direct-only launch keeps 0 and 0)
+        if (shift) {
+            p.family = kFamilyShift;
+            p.j = p.wide_tiles > 0 ? qm::kShiftWideSpl : 4;
+            // groups a wavefront sees before its running maximum is reset: bricks per workgroup x
+            // groups per (brick, wavefront)
+            // (brick maxima, tie_rule = 1: the wide tiles' loop raises them itself -- the running maximum lives as long
+            // as ever --, the other tiles fold and reset it after every brick)
+            const bool per_brick = p.brick_rows && p.wide_tiles == 0;
+            const int64_t life = (per_brick ? 1 : (int64_t)L->g.nbricks / std::max(1, p.groups_lds)) *
+                                 std::max(1, L->g.brick_nodes / 8 / L->nw);
+            p.lazy = e->cfg_shift_lazy >= 0 ? e->cfg_shift_lazy : (life >= qm::kShiftLazyGroups ? 1 : 0);
+            if (L->nblk > 1 && !L->direct) p.lazy = 0;  // (the register-staged form: eager only)
+        } else if (jp > 0) {
+            p.family = kFamilyPair;
+            p.j = 2 * jp;
+        } else {
+            // the exact-row-count kernels: fused detect and the marginalised map for up to 64 rows,
+            // volume-writing for 33-64 rows (up to 32 the paired kernel writes volumes), when the
+            // launch uses the table width's own samples per lane
+            const int S = e->g.n_rows;
+            const bool exact = e->cfg_exact && !e->cfg_generic && !accumulate && qm::exact_built(S, J) &&
+                               (marginal || !volume || S > qm::kPairMaxRows);
+            p.family = exact ? kFamilyExact : kFamilyChunked;
+            p.j = J;
         }
     }
-    if (use_direct) {
+    if (p.use_direct) {
         const int units = e->cfg_force_direct ? nbricks_now : n_wide_now;
-        groups_direct = e->cfg_groups > 0 ? std::min(e->cfg_groups, units)
-                                          : auto_groups(e, a.ntiles, units, 2048 / threads);
+        p.groups_direct = e->cfg_groups > 0 ? std::min(e->cfg_groups, units)
+                                            : auto_groups(e, p.ntiles, units, 2048 / threads);
+        // (force_direct: every brick, no list)
+        p.list = e->cfg_force_direct ? nullptr : p.layout->list.p;
+        p.n_list = units;
     }
-    const int sets = groups_lds + groups_direct;
-    // (from here on d_pmax and the last_* fields describe THIS launch: whatever a detect left for
-    // qm_engine_tie_partial is gone -- detect_core and the group's partial launches say so again)
-    e->last_sets_own = false;
-    if (want_scan) {
-        const size_t need = (size_t)sets * steps * n_chunk;
-        if (e->d_pmax.ensure(need) || e->d_psum.ensure(need) || e->d_pidx.ensure(need)) return 1;
-        if (brick_rows && e->d_bmax.ensure((size_t)brick_rows * steps * n_chunk)) return 1;
+    p.g = p.layout->g;
+    p.sets = p.groups_lds + p.groups_direct;
+    p.scan_n = p.steps * n_chunk;
+    *out = p;
+    return 0;
+}
+
+// The arguments of the plan's LDS launch (over every brick that fits: no list) or of its direct launch (the list)
+qm::StackArgs stack_args(const qm_engine *e, const StackLaunch &s, const StackPlan &p, bool direct) {
+    const auto *vol = std::get_if<StackLaunch::Volume>(&s.kind);
+    const auto *marg = std::get_if<StackLaunch::Marginal>(&s.kind);
+    qm::StackArgs a{};
+    a.g = p.g;
+    a.onsets = s.onsets;
+    a.lut = e->d_lut.p;
+    if (!p.shift) {                                     // (the shift-reuse tables travel in ShiftArgs)
+        a.rel = p.layout->rel.p;
+        a.brick_meta = p.layout->meta.p;
+        a.brick_total = p.layout->total.p;
     }
-    a.brick_max = brick_rows ? e->d_bmax.p : nullptr;
-    if (brick_rows && a.wide_tiles > 0) {
-        // (the wide tiles' loop raises its rows by atomic maxima, and only where a group comes near the running
-        // maximum: they start at -inf; the other tiles write theirs whole)
-        const size_t n = (size_t)brick_rows * steps * n_chunk;
-        hipLaunchKernelGGL(qm::fill_kernel, dim3((unsigned)std::min<size_t>((n + 1023) / 1024, 65535)), dim3(256), 0,
-                           e->stream, e->d_bmax.p, n, -std::numeric_limits<double>::infinity());
-        QM_HIP(hipGetLastError());
+    a.brick_list = direct ? p.list : nullptr;
+    a.n_list = direct ? p.n_list : 0;
+    a.T = s.T;
+    a.fsmp = s.fsmp;
+    a.n_samples = s.n_samples;
+    a.sample0 = s.sample0;
+    a.n_chunk = s.n_chunk;
+    // (the direct launch beside a shift-reuse one: its own whole tiles of 256 samples, clamped)
+    a.ntiles = direct && p.shift ? (s.n_chunk + qm::kShiftKT - 1) / qm::kShiftKT : p.ntiles;
+    a.ngroups = direct ? p.groups_direct : p.groups_lds;
+    a.tail_spl = direct ? 0 : p.tail_spl;
+    a.wide_tiles = direct ? 0 : p.wide_tiles;
+    if (p.steps > 1) {
+        a.n_steps = p.steps;
+        a.step_stride = s.step_stride;
     }
+    a.part_stride = p.scan_n;
+    a.cap_doubles = p.cap_doubles;
+    // coa = exp(stack/available) = 2^(stack * log2(e)/available)
+    a.z_scale = 1.4426950408889634074 / (double)s.available;
+    a.volume = vol ? vol->p : nullptr;
+    a.vol_stride = vol ? vol->stride : 0;
+    a.accumulate = vol ? vol->accumulate : 0;
     a.part_max = e->d_pmax.p;
     a.part_idx = e->d_pidx.p;
     a.part_sum = e->d_psum.p;
-    r.sets = sets;
-    e->last_sets = sets;
-    e->last_scan_n = steps * n_chunk;
-    e->last_g = a.g;
-    e->last_groups_lds = groups_lds;
-    e->last_brick_rows = brick_rows;
-    e->last_groups_direct = groups_direct;
-    e->last_list = !use_direct || e->cfg_force_direct ? nullptr : a.brick_list;
-    e->last_n_list = !use_direct ? 0 : e->cfg_force_direct ? nbricks_now : n_wide_now;
+    a.set0 = direct && p.use_lds ? p.groups_lds : 0;
+    a.brick_max = p.brick_rows && !direct ? e->d_bmax.p : nullptr;
+    a.want_scan = s.want_scan ? 1 : 0;
+    a.marginal = marg ? e->d_marg.p : nullptr;
+    a.m0 = marg ? marg->first : 0;
+    a.m1 = marg ? marg->end : 0;
+    a.n_nodes = e->n_nodes;
+    a.run_if = s.run_if;
+    return a;
+}
 
+// ---- the families' launch tables: the LDS launch of a plan -----------------------------------------
+// the round-2 kernels (they have the direct kernel's workgroup shape and publish area).  An exact-row-count kernel
+// the tables do not hold: the chunked kernel runs, and the plan says so.
+int launch_round2_lds(qm_engine *e, const qm::StackArgs &a, StackPlan *p) {
+    const int J = p->j, S = e->g.n_rows;
+    const bool VOLUME = a.volume != nullptr || a.marginal != nullptr;
+    const qm::LaunchShape shape = stack_shape(e, a, p->direct_threads,
+                                              std::max((size_t)e->cfg_lds_bytes, p->direct_publish));
+    bool exact = false;
+    if (p->family == kFamilyExact) {
+        const bool j4_wide = J == 4 && S > 40;     // the second variant of 41-64 rows
+        if (a.marginal != nullptr) {
+            if (S <= 32) QM_TABLE(qm::launch_exact_marginal_1_32(S, a, shape, &exact));
+            else if (!j4_wide) QM_TABLE(qm::launch_exact_marginal_33_64(S, a, shape, &exact));
+            else QM_TABLE(qm::launch_exact_marginal_j4_41_64(S, a, shape, &exact));
+        } else if (!VOLUME) {
+            if (S <= 32) QM_TABLE(qm::launch_exact_detect_1_32(S, a, shape, &exact));
+            else if (!j4_wide) QM_TABLE(qm::launch_exact_detect_33_64(S, a, shape, &exact));
+            else QM_TABLE(qm::launch_exact_detect_j4_41_64(S, a, shape, &exact));
+        } else {
+            if (!j4_wide) QM_TABLE(qm::launch_exact_volume_33_64(S, a, shape, &exact));
+            else QM_TABLE(qm::launch_exact_volume_j4_41_64(S, a, shape, &exact));
+        }
+    }
+    // Variants specialised on the number of 8-row offset chunks (whole-node offset prefetch;
+    // detect: software-pipelined node loop) for up to 64 table rows; otherwise, and for the
+    // reference's accumulate-into-volume semantics, the generic kernel.
+    if (!exact) {
+        p->family = kFamilyChunked;
+        int nch = (e->cfg_generic || a.accumulate) ? 0 : e->g.row_pad / 8;
+        if (nch > 8) nch = 0;
+        bool built = false;
+        if (VOLUME) QM_TABLE(qm::launch_chunked_volume(J, nch, a, shape, &built));
+        else QM_TABLE(qm::launch_chunked_detect(J, nch, a, shape, &built));
+        if (!built) return fail("no chunked stacking kernel for %d samples per lane", J);
+    }
+    return 0;
+}
+
+int launch_pair_lds(qm_engine *e, const qm::StackArgs &a) {
+    bool done = false;
+    const qm::LaunchShape shape = stack_shape(e, a, 1024, kPairLdsBytes);
+    if (a.volume) QM_TABLE(qm::launch_pair_volume(e->g.n_rows, a, shape, &done));
+    else QM_TABLE(qm::launch_pair_detect(e->g.n_rows, a, shape, &done));
+    if (!done) return fail("no paired kernel built for %d rows", e->g.n_rows);
+    return 0;
+}
+
+int launch_shift_lds(qm_engine *e, const qm::StackArgs &a, const StackPlan &p) {
+    const ShiftLayout &L = *p.shift;
+    const int mode = p.shift_mode;
+    qm::ShiftArgs s{};
+    s.a = a;
+    s.smeta = reinterpret_cast<const int4 *>(L.meta.p);
+    s.stotal = L.total.p;
+    s.sfit = L.fit.p;
+    s.stream = reinterpret_cast<const char *>(L.stream.p);
+    s.wmeta = reinterpret_cast<const int4 *>(L.wmeta.p);
+    s.wtotal = L.wtotal.p;
+    s.wstream = reinterpret_cast<const char *>(L.wstream.p);
+    s.rows2 = L.rows2;
+    s.nw = L.nw;
+    s.nblk = L.nblk;
+    s.sb = L.sb;
+    s.stage_slots = L.stage_slots;
+    s.stage_reach = L.stage_reach;
+    s.lazy = p.lazy;
+    const qm::LaunchShape shape = stack_shape(e, a, L.nw * qm::kWave, qm::shift_lds_bytes(L.nw));
+    const bool rows = L.nblk > 1, big = L.nw == qm::kShiftWaves8;
+    if (L.wide && L.direct) QM_TABLE(qm::launch_shift_wide_rows(s, shape));   // (also a single block)
+    else if (rows && L.quad && mode == qm::kShiftVolume) QM_TABLE(qm::launch_shift_rows4_volume(s, shape));
+    else if (rows && L.quad) QM_TABLE(qm::launch_shift_rows4(s, shape));
+    else if (rows && L.direct && mode == qm::kShiftVolume) QM_TABLE(qm::launch_shift_rows2_volume(s, shape));
+    else if (rows && L.direct) QM_TABLE(qm::launch_shift_rows2(s, shape));
+    else if (rows) QM_TABLE(qm::launch_shift_rows8(s, shape));
+    else if (mode == qm::kShiftMarginal && big) QM_TABLE(qm::launch_shift_marginal8(s, shape));
+    else if (mode == qm::kShiftMarginal) QM_TABLE(qm::launch_shift_marginal(s, shape));
+    else if (mode == qm::kShiftVolume && big) QM_TABLE(qm::launch_shift_volume8(s, shape));
+    else if (mode == qm::kShiftVolume) QM_TABLE(qm::launch_shift_volume(s, shape));
+    else if (L.nw == qm::kShiftWaves3) QM_TABLE(qm::launch_shift_detect3(s, shape));
+    else if (a.brick_max && big) QM_TABLE(qm::launch_shift_detect8_sets(s, shape));
+    else if (a.brick_max) QM_TABLE(qm::launch_shift_detect_sets(s, shape));
+    else if (big) QM_TABLE(qm::launch_shift_detect8(s, shape));
+    else QM_TABLE(qm::launch_shift_detect(s, shape));
+    return 0;
+}
+
+int launch_direct(qm_engine *e, const qm::StackArgs &a, const StackPlan &p) {
+    const qm::LaunchShape shape = stack_shape(e, a, p.direct_threads, p.direct_publish);
+    bool built = false;
+    // (the direct kernel's VOLUME covers the map too)
+    if (a.volume || a.marginal) QM_TABLE(qm::launch_direct_volume(p.direct_j, a, shape, &built));
+    else QM_TABLE(qm::launch_direct_detect(p.direct_j, a, shape, &built));
+    if (!built) return fail("no direct stacking kernel for %d samples per lane", p.direct_j);
+    return 0;
+}
+
+// The plan's launches, enqueued: scratch, the LDS launch over the bricks that fit the family's layout, the direct
+// launch over those on the layout's list (their partial sets behind the LDS launch's), the timing events around both
+int issue_stack(qm_engine *e, const StackLaunch &s, StackPlan *p) {
+    if (p->marg_tiles && e->d_marg.ensure((size_t)p->marg_tiles * e->n_nodes)) return 1;
+    const size_t rows_n = (size_t)p->brick_rows * p->scan_n;
+    if (s.want_scan) {
+        const size_t need = (size_t)p->sets * p->scan_n;
+        if (e->d_pmax.ensure(need) || e->d_psum.ensure(need) || e->d_pidx.ensure(need)) return 1;
+        if (p->brick_rows && e->d_bmax.ensure(rows_n)) return 1;
+    }
+    if (p->brick_rows && p->wide_tiles > 0) {
+        // (the wide tiles' loop raises its rows by atomic maxima, and only where a group comes near the running
+        // maximum: they start at -inf; the other tiles write theirs whole)
+        hipLaunchKernelGGL(qm::fill_kernel, dim3((unsigned)std::min<size_t>((rows_n + 1023) / 1024, 65535)), dim3(256),
+                           0, e->stream, e->d_bmax.p, rows_n, -std::numeric_limits<double>::infinity());
+        QM_HIP(hipGetLastError());
+    }
     // a conditional launch (the fallback of a screened step) is not part of the timing log: it
     // returns at once unless the step has to be redone
     const bool logged = s.run_if == nullptr;
-    hipEvent_t ev_begin = e->ev0, ev_end = e->ev1;
-    if (e->log_timing && logged) {
-        if (e->ev_used + 2 > e->ev_log.size()) {
-            for (int i = 0; i < 2; ++i) {
-                hipEvent_t ev;
-                QM_HIP(hipEventCreate(&ev));
-                e->ev_log.push_back(ev);
-            }
-        }
-        ev_begin = e->ev_log[e->ev_used];
-        ev_end = e->ev_log[e->ev_used + 1];
-        e->ev_used += 2;
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    if (logged) {
+        if (timing_events(e, &ev_begin, &ev_end)) return 1;
+        QM_HIP(hipEventRecord(ev_begin, e->stream));
     }
-    if (logged) QM_HIP(hipEventRecord(ev_begin, e->stream));
-    int rc = 0;
-#define QM_LAUNCH(JJ)                                                                        \
-    rc = (volume || marginal)                                                                 \
-             ? launch_stack_j<JJ, true>(e, a, groups_lds, groups_direct, use_lds, use_direct)  \
-                : launch_stack_j<JJ, false>(e, a, groups_lds, groups_direct, use_lds, use_direct)
-    if (shift)
-        rc = launch_shift_path(e, *L, a, groups_lds, groups_direct, use_lds, use_direct, shift_mode);
-    else if (jp == 2)
-        rc = volume ? launch_pair_path<2, true>(e, a, groups_lds, groups_direct, use_lds, use_direct)
-                    : launch_pair_path<2, false>(e, a, groups_lds, groups_direct, use_lds, use_direct);
-    else if (jp == 1)
-        rc = volume ? launch_pair_path<1, true>(e, a, groups_lds, groups_direct, use_lds, use_direct)
-                    : launch_pair_path<1, false>(e, a, groups_lds, groups_direct, use_lds, use_direct);
-    else switch (J) {
-        case 1: QM_LAUNCH(1); break;
-        case 2: QM_LAUNCH(2); break;
-        case 4: QM_LAUNCH(4); break;
-        default: return fail("samples_per_lane must be 1, 2 or 4 (got %d)", J);
+    if (p->use_lds) {
+        const qm::StackArgs a = stack_args(e, s, *p, false);
+        if (p->family == kFamilyShift ? launch_shift_lds(e, a, *p)
+            : p->family == kFamilyPair ? launch_pair_lds(e, a) : launch_round2_lds(e, a, p))
+            return 1;
     }
-#undef QM_LAUNCH
-    if (rc) return rc;
+    if (p->use_direct && launch_direct(e, stack_args(e, s, *p, true), *p)) return 1;
     if (logged) {
         QM_HIP(hipEventRecord(ev_end, e->stream));
         e->timed = !e->log_timing;
     }
+    return 0;
+}
+
+}  // namespace
+
+// the events around a launch: the engine's own pair, or -- the timing log -- the log's next two
+int timing_events(qm_engine *e, hipEvent_t *begin, hipEvent_t *end) {
+    *begin = e->ev0;
+    *end = e->ev1;
+    if (!e->log_timing) return 0;
+    while (e->ev_used + 2 > e->ev_log.size()) {
+        hipEvent_t ev;
+        QM_HIP(hipEventCreate(&ev));
+        e->ev_log.push_back(ev);
+    }
+    *begin = e->ev_log[e->ev_used];
+    *end = e->ev_log[e->ev_used + 1];
+    e->ev_used += 2;
+    return 0;
+}
+
+// Stack samples [sample0, sample0+n_chunk) of the scan: plan, issue, and e->last describes the launch.  Partials (if
+// want_scan) land in e->d_pmax/d_pidx/d_psum as [sets][n_steps * n_chunk]; a marginal launch leaves per-tile sums
+// over the samples [first, end) in e->d_marg as [e->last.marg_tiles][n_nodes] (the kernels differ in their tile
+// length).  n_steps > 1: that many timesteps in ONE launch (fused detect only); not every kernel can -- batched =
+// false then, and nothing was launched.
+StackResult run_stack(qm_engine *e, const StackLaunch &s) {
+    // (from here on d_pmax describes THIS launch: whatever a detect left for qm_engine_tie_partial is gone --
+    // detect_core and the group's partial launches say so again)
+    e->last.sets_own = false;
+    StackPlan p;
+    if (plan_stack(e, s, &p)) return 1;
+    StackResult r;
+    r.batched = p.batched;
+    if (!p.batched) return r;
+    if (issue_stack(e, s, &p)) return 1;
+    e->last = p;
+    r.sets = p.sets;
     return r;
 }
 
@@ -551,7 +512,7 @@ int combine(qm_engine *e, const SetView &in, CombineMode mode, int64_t node_offs
             const OutSeries &out, const int32_t *run_if) {
     // (tie_rule = 1 with a row of maxima per brick: the fold of the workgroups' own sets also leaves the largest z)
     double *o_z = nullptr;
-    if (e->cfg_tie_rule && e->last_brick_rows > 0 && in.max == e->d_pmax.p && run_if == nullptr) {
+    if (e->cfg_tie_rule && e->last.brick_rows > 0 && in.max == e->d_pmax.p && run_if == nullptr) {
         if (e->d_tie_zext.ensure(in.n)) return 1;
         o_z = e->d_tie_zext.p;
     }
@@ -569,7 +530,7 @@ StackResult stack_fold(qm_engine *e, const StackLaunch &s, CombineMode mode, int
     if (r.rc || !r.batched) return r;
     if (const auto *m = std::get_if<StackLaunch::Marginal>(&s.kind)) {
         hipLaunchKernelGGL(qm::marginal_reduce_kernel, dim3((unsigned)((e->n_nodes + 255) / 256)), dim3(256), 0,
-                           e->stream, e->d_marg.p, e->marg_tiles, e->n_nodes, m->map);
+                           e->stream, e->d_marg.p, e->last.marg_tiles, e->n_nodes, m->map);
         QM_HIP(hipGetLastError());
     }
     if (!s.want_scan) return r;
@@ -596,7 +557,7 @@ int detect_core(qm_engine *e, const double *d_on, int T, int fsmp, int ns, int a
     bool screened = false;
     // (the screened sweep leaves no float64 sets to refine near-ties from, and its conditional fallback cannot be
     // followed by a refinement nobody waits for: the two opt-ins exclude each other on the detect calls)
-    e->last_sets_own = false;                           // (the screened sweep writes d_pmax as well; a refused
+    e->last.sets_own = false;                           // (the screened sweep writes d_pmax as well; a refused
                                                         // call is no detect_partial either)
     if (e->cfg_screen && e->cfg_tie_rule)
         return fail("detect: the config keys screen = 1 and tie_rule = 1 cannot be combined (the screened detect "
@@ -611,7 +572,7 @@ int detect_core(qm_engine *e, const double *d_on, int T, int fsmp, int ns, int a
     // (d_pmax holds the float64 launch's sets for certain -- and they are those of a detect_partial, the only call
     // qm_engine_tie_partial follows: a final detect of other onsets at the same sample count is refused like any
     // other launch in between)
-    e->last_sets_own = !screened && mode == kCombinePartial;
+    e->last.sets_own = !screened && mode == kCombinePartial;
     return 0;
 }
 
@@ -629,7 +590,7 @@ int scan_fold(qm_engine *e, const double *vol, int64_t stride, int ns, int64_t n
     const int64_t per = (n_nodes + sets - 1) / sets;
     sets = (n_nodes + per - 1) / per;
     const size_t need = (size_t)sets * ns;
-    e->last_sets_own = false;                           // (a volume's sets overwrite a detect's: qm_engine_tie_partial)
+    e->last.sets_own = false;                           // (a volume's sets overwrite a detect's: qm_engine_tie_partial)
     if (e->d_pmax.ensure(need) || e->d_psum.ensure(need) || e->d_pidx.ensure(need)) return 1;
     hipLaunchKernelGGL(qm::scan_volume_kernel, dim3(xgroups, (unsigned)sets), dim3(waves * qm::kWave), 0, e->stream,
                        vol, stride, ns, n_nodes, per, e->d_pmax.p, e->d_pidx.p, e->d_psum.p);
@@ -639,13 +600,13 @@ int scan_fold(qm_engine *e, const double *vol, int64_t stride, int ns, int64_t n
                    nullptr);
 }
 
-// tie_rule = 1 (qm_ties.hpp): the index series o_idx of `launch`, whose partial sets lie in d_pmax (as the
-// last_* fields describe them), refined.  n_steps > 1: the launch held several timesteps.  zext / o_key:
+// tie_rule = 1 (qm_ties.hpp): the index series o_idx of `launch`, whose partial sets lie in d_pmax (as
+// e->last describes them), refined.  n_steps > 1: the launch held several timesteps.  zext / o_key:
 // a sharded detect's engine -- its sets against the grid's maxima, the outcome exported (tie_export_kernel)
 // instead of applied.
 int refine_ties(qm_engine *e, const StackLaunch &launch, int64_t *o_idx, const double *zext,
                 unsigned long long *o_key) {
-    const int n_steps = launch.n_steps, n_chunk = launch.n_chunk, sets = e->last_sets;
+    const int n_steps = launch.n_steps, n_chunk = launch.n_chunk, sets = e->last.sets;
     const int n = n_chunk * std::max(1, n_steps);
     if (n > INT32_MAX / (2 * qm::kTieMaxSets)) return fail("tie_rule: %d samples in one launch are too many", n);
     const int max_pairs = qm::kTieMaxSets * n;
@@ -660,12 +621,12 @@ int refine_ties(qm_engine *e, const StackLaunch &launch, int64_t *o_idx, const d
     // (brick maxima: the sample's largest z is already in the workgroups' few partial sets; the per-brick rows are
     // read once, for the candidates)
     // (... and the sample's largest z came out of the combine that preceded this call)
-    const int rows = e->last_brick_rows;
+    const int rows = e->last.brick_rows;
     if (rows > 0 && !zext) zext = e->d_tie_zext.p;
     hipLaunchKernelGGL(qm::tie_pairs_kernel, dim3((n + 63) / 64), dim3(64, qm::kTieSetLanes), 0, s,
                        rows > 0 ? (const double *)e->d_bmax.p : (const double *)e->d_pmax.p, rows > 0 ? rows : sets,
-                       (const double *)e->d_pmax.p + (int64_t)e->last_groups_lds * n,
-                       rows > 0 ? e->last_groups_direct : 0, n, (int64_t)n, e->d_tie_z.p, pairs,
+                       (const double *)e->d_pmax.p + (int64_t)e->last.groups_lds * n,
+                       rows > 0 ? e->last.groups_direct : 0, n, (int64_t)n, e->d_tie_z.p, pairs,
                        e->d_tie_count.p, max_pairs, e->d_tie_emax.p, e->d_tie_imin.p, e->d_tie_count.p + 1, zext);
     QM_HIP(hipGetLastError());
     // How many pairs there are is known on the device only, and nobody waits for it: the evaluation is
@@ -675,7 +636,7 @@ int refine_ties(qm_engine *e, const StackLaunch &launch, int64_t *o_idx, const d
     ++e->tie_refined_steps;
     e->tie_counts_pending = true;
     qm::TieArgs a{};
-    a.g = e->last_g;
+    a.g = e->last.g;
     a.onsets = launch.onsets;
     a.lut = e->d_lut.p;
     a.T = launch.T; a.fsmp = launch.fsmp; a.sample0 = launch.sample0; a.n_chunk = n;
@@ -683,13 +644,13 @@ int refine_ties(qm_engine *e, const StackLaunch &launch, int64_t *o_idx, const d
     a.step_stride = launch.step_stride;
     a.z_scale = 1.4426950408889634074 / (double)launch.available;
     a.recip = 1.0 / (double)launch.available;
-    a.groups_lds = e->last_groups_lds;
-    a.groups_direct = e->last_groups_direct;
+    a.groups_lds = e->last.groups_lds;
+    a.groups_direct = e->last.groups_direct;
     a.brick_rows = rows;
-    a.brick_list = e->last_list;
-    a.n_list = e->last_n_list;
+    a.brick_list = e->last.list;
+    a.n_list = e->last.n_list;
     // workgroups per pair: ~2048 nodes each
-    const int64_t per_set = (int64_t)e->n_nodes / std::max(1, e->last_groups_lds + e->last_groups_direct);
+    const int64_t per_set = (int64_t)e->n_nodes / std::max(1, e->last.groups_lds + e->last.groups_direct);
     a.chunks = rows > 0 ? 1 : (int)std::max<int64_t>(1, std::min<int64_t>(64, per_set / 2048));   // (rows: a brick)
     a.zbest = e->d_tie_z.p;
     a.pairs = pairs;
@@ -976,20 +937,21 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     else if (k == "screen_pairs") *v = e->last_plan_jp;
     else if (k == "screen_big") *v = e->last_plan_big;
     else if (k == "screen_brick_nodes") *v = e->screen.g.brick_nodes;
-    else if (k == "last_kernel") *v = e->last_kernel;
-    else if (k == "last_kernel_j") *v = e->last_j;
+    else if (k == "last_kernel") *v = e->last.family;
+    else if (k == "last_kernel_j") *v = e->last.j;
     else if (k == "shift") *v = e->cfg_shift;
     else if (k == "shift_ok") *v = e->sh.built && e->sh.ok ? 1 : 0;
-    else if (k == "shift_waves")                        // (of the layout the last shift-reuse launch ran on)
-        *v = e->shift_wide_last > 0 && e->shw.ok ? e->shw.nw : e->sh.ok ? e->sh.nw : e->cfg_shift_waves;
-    else if (k == "shift_lazy") *v = e->shift_lazy_last;
+    else if (k == "shift_waves")                        // (of the layout the last launch ran on, if shift-reuse and
+        // still this table's: a table change voids the layouts, invalidate_derived)
+        *v = e->last.shift && e->last.shift->ok ? e->last.shift->nw : e->sh.ok ? e->sh.nw : e->cfg_shift_waves;
+    else if (k == "shift_lazy") *v = e->last.lazy;
     else if (k == "shift_tail") *v = e->cfg_shift_tail;
-    else if (k == "shift_tail_spl") *v = e->shift_tail_last;
+    else if (k == "shift_tail_spl") *v = e->last.tail_spl;
     else if (k == "shift_wide") *v = e->cfg_shift_wide;
     else if (k == "shift_wide_ok") *v = e->shw.built && e->shw.ok ? 1 : 0;
     else if (k == "shift_wide_rows") *v = e->cfg_shift_wide_rows;
     else if (k == "shift_wide_row_blocks") *v = e->shw.ok ? e->shw.nblk : 0;
-    else if (k == "shift_wide_tiles") *v = e->shift_wide_last;
+    else if (k == "shift_wide_tiles") *v = e->last.wide_tiles;
     else if (k == "shift_wide_brick_nodes") *v = e->shw.ok ? e->shw.g.brick_nodes : 0;
     else if (k == "shift_wide_direct_bricks") *v = e->shw.ok ? e->shw.n_list : 0;
     else if (k == "shift_wide_operands_per_add_x1000")   // 8-byte LDS operands fetched per add of a wide tile (x 1000)
@@ -1000,7 +962,7 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     else if (k == "stream_pull") *v = e->cfg_stream_pull;
     else if (k == "preproc_skew") *v = e->cfg_preproc_skew;
     else if (k == "pick_lds_samples") *v = qm::kPicksLdsSamples;
-    else if (k == "tie_brick_rows") *v = e->last_brick_rows;
+    else if (k == "tie_brick_rows") *v = e->last.brick_rows;
 
     else if (k == "tie_refined_steps") *v = e->tie_refined_steps;
     else if (k == "tie_overflow_samples" || k == "tie_pairs") {
@@ -1166,7 +1128,7 @@ int qm_engine_tie_partial(qm_engine *e, const double *log_onsets, int onsets_on_
     int ns = 0;
     if (check_step(e, T, fsmp, lsmp, available, &ns)) return 1;
     if (!e->cfg_tie_rule) return fail("qm_engine_tie_partial: the engine was not configured with tie_rule = 1");
-    if (e->last_scan_n != ns || e->last_sets < 1 || !e->last_sets_own)
+    if (e->last.scan_n != ns || e->last.sets < 1 || !e->last.sets_own)
         return fail("qm_engine_tie_partial: no partial sets of a float64 detect of %d samples on this engine "
                     "(call qm_engine_detect_partial for the step first, with no other launch, volume scan or "
                     "table change in between; the screened sweep leaves none)", ns);

@@ -4,9 +4,9 @@
 //   qm_tables.hip    everything derived from ONE travel-time table: load, layout search, the kernels'
 //                    derived tables (round-2 offsets, paired, shift-reuse, screening), parked tables,
 //                    on-device serving
-//   qm_engine.hip    engine handle, tunables, the stacking launches, one core per launch kind and the step
-//                    entry points around them (detect / detect_batch / partial / finalize / migrate / marginal /
-//                    find_max_coa)
+//   qm_engine.hip    engine handle, tunables, the stacking launch (run_stack: plan_stack decides into a StackPlan,
+//                    issue_stack enqueues it, e->last keeps it), one core per launch kind and the step entry points
+//                    around them (detect / detect_batch / partial / finalize / migrate / marginal / find_max_coa)
 //   qm_screen.hip    the opt-in screened detect's launch sequence
 //   qm_stream.hip    the continuous detect pipeline (pinned ring, copies overlapped with compute), also over
 //                    several engines that hold the same table (replicas: launches round-robin)
@@ -158,6 +158,9 @@ struct ShiftLayout : BrickLayout {          // (list: the bricks that do not fit
     DevBuf<uint32_t> wstream;
     int64_t wquads = 0;                     // quads fetched by the wide tiles' windows (per 48 adds, not 32)
 
+    // this layout's kernel has tail tiles, a step axis and per-brick maxima: neither row blocks nor the 12-wave shape
+    // (`sh` is never wide, so the test means the same on it as where only `shw` can be at hand)
+    bool plain() const { return nblk == 1 && nw != qm::kShiftWaves3 && !(wide && direct); }
     void invalidate() { built = false; }
     void release() {
         PoolReleaseScope one_wait;
@@ -223,6 +226,34 @@ struct TableSlot {
 };
 
 struct qm_stream;                    // a continuous-detect pipeline on an engine (qm_stream.hip)
+
+// One stacking launch (StackLaunch below) as plan_stack decides it and issue_stack enqueues it (qm_engine.hip).
+// qm_engine::last is the plan of the last launch enqueued, assigned whole by run_stack: the only description of
+// that launch, for the refinement, the folds and the read-outs of qm_engine_get alike.
+enum StackFamily : int { kFamilyChunked = 0, kFamilyExact = 1, kFamilyPair = 2, kFamilyShift = 3 };   // "last_kernel"
+struct StackPlan {
+    StackFamily family = kFamilyChunked;    // the LDS launch's kernel and its samples per lane (a launch of the
+    int j = 0;                              // ... direct kernel alone: 0 and 0)
+    const BrickLayout *layout = nullptr;    // the layout whose bricks the launch runs on ...
+    const ShiftLayout *shift = nullptr;     // ... the same, where it is a shift-reuse launch
+    int shift_mode = 0, lazy = 0;           // shift-reuse: detect / volume / marginal, the detect loop's flavour,
+    int tail_spl = 0, wide_tiles = 0;       // ... samples per lane of the tail tile (0: none), wide tiles in front
+    int ntiles = 0, cap_doubles = 0;        // the LDS launch's time tiles, its LDS window capacity
+    int steps = 1;                          // timesteps in the launch
+    bool use_lds = false, use_direct = false;
+    int groups_lds = 0, groups_direct = 0;
+    int direct_j = 0, direct_threads = 0;   // the direct launch: samples per lane, workgroup, publish area
+    size_t direct_publish = 0;
+    int brick_rows = 0;                     // rows of maxima per brick in d_bmax (StackArgs::brick_max), 0: none
+    int marg_tiles = 0;                     // time tiles of a marginal-map launch (rows of d_marg)
+    bool batched = true;                    // false: the kernel cannot hold the launch's n_steps -- not launched
+    // which bricks the partial sets in d_pmax stand for (qm_ties.hpp): the grid, the direct launch's bricks,
+    qm::GridDesc g{};
+    const int32_t *list = nullptr;
+    int n_list = 0;
+    int sets = 0, scan_n = 0;               // ... their number, the samples each one spans
+    bool sets_own = false;                  // ... left by a float64 detect_partial (detect_core, the group's launches)
+};
 
 struct qm_engine : TableState {
     int device = 0;
@@ -294,23 +325,13 @@ struct qm_engine : TableState {
     DevBuf<int64_t> d_cand_idx;
     int64_t screened_steps = 0, fallback_steps = 0, last_candidates = 0;
     int last_plan_jp = 0, last_plan_big = 0;
-    int last_kernel = 0, last_j = 0;        // stacking kernel of the last launch: 0 chunked, 1 exact-row-count, 2 paired
     int32_t *h_flags = nullptr;             // pinned ring of per-step (flags, candidates) pairs
     int flags_pending = 0, flags_head = 0;  // not yet folded into the counters
-    int shift_lazy_last = 0;                // loop flavour the last shift-reuse launch took
-    int shift_tail_last = 0;                // samples per lane of the last launch's tail tile (0: none)
-    int shift_wide_last = 0;                // wide tiles of the last shift-reuse launch
     int last_batched = 1;                   // timesteps the last detect_batch put into one launch
-    // which bricks the partial sets of the last stacking launch stand for (qm_ties.hpp)
-    qm::GridDesc last_g{};
-    int last_groups_lds = 0, last_groups_direct = 0, last_n_list = 0;
-    int last_brick_rows = 0;                            // (a row of maxima per brick besides: StackArgs::brick_max)
-    DevBuf<double> d_bmax;
-    int last_sets = 0, last_scan_n = 0;                 // their number, the samples each one spans
-    bool last_sets_own = false;                         // ... left by a float64 detect (not by the screened sweep)
+    StackPlan last;                                     // the last stacking launch (run_stack)
+    DevBuf<double> d_bmax;                              // its row of maxima per brick (StackPlan::brick_rows)
     DevBuf<double> d_tie_zext;                          // the largest z per sample, left by the combine of the own sets
     DevBuf<double> d_tie_zgrid;                         // sharded detects: the GRID's largest z per sample
-    const int32_t *last_list = nullptr;
     DevBuf<double> d_tie_z;
     DevBuf<int32_t> d_tie_pairs, d_tie_imin, d_tie_count, d_tie_cands;
     DevBuf<unsigned long long> d_tie_emax, d_tie_keys;
@@ -334,7 +355,6 @@ struct qm_engine : TableState {
 
     // scratch
     DevBuf<double> d_onsets, d_pmax, d_psum, d_out_a, d_chunk, d_marg, d_marg_out;
-    int marg_tiles = 0;             // time tiles of the last marginal-map launch (rows of d_marg)
     DevBuf<int64_t> d_pidx;
     // locate fits: three map-sized work buffers, reduction partials, device-side scalars
     DevBuf<double> d_fit_a, d_fit_b, d_fit_c, d_fit_part, d_fit_val, d_fit_win;
@@ -445,6 +465,8 @@ int ensure_screen_tables(qm_engine *e, const ScreenPlan &plan);
 
 // ---- qm_engine.hip ------------------------------------------------------------------------------
 int auto_groups(const qm_engine *e, int ntiles, int units, int blocks_per_cu, int rounds = 0);
+// the two events around a timed launch (the timing log's next pair, or the engine's own)
+int timing_events(qm_engine *e, hipEvent_t *begin, hipEvent_t *end);
 StackResult run_stack(qm_engine *e, const StackLaunch &s);
 // the sets the last stacking launch or volume scan left: [n_sets][n] in d_pmax / d_pidx / d_psum
 SetView engine_sets(const qm_engine *e, int n_sets, int n);

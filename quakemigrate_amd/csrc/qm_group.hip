@@ -554,7 +554,7 @@ int qm_group_marginal(qm_group *g, const double *log_onsets, int32_t T, int32_t 
             if (check_step(e, T, fsmp, lsmp, available, &ns_k) ||
                 stack_fold(e, s, kCombinePartial, 0, packed_set(q.pack + k * 3 * (int64_t)ns, ns)).rc)
                 return failed(g);
-            e->last_sets_own = want_scan;
+            e->last.sets_own = want_scan;
         }
     }
     if (want_scan && exchange(g, T, fsmp, lsmp, available, ns)) return failed(g);
@@ -603,7 +603,7 @@ int qm_group_migrate(qm_group *g, const double *log_onsets, int32_t T, int32_t f
             if (check_step(e, T, fsmp, lsmp, available, &ns_k) ||
                 stack_fold(e, s, kCombinePartial, 0, packed_set(q.pack + k * 3 * (int64_t)ns, ns)).rc)
                 return failed(g);
-            e->last_sets_own = want_scan;
+            e->last.sets_own = want_scan;
         }
     }
     if (want_scan && exchange(g, T, fsmp, lsmp, available, ns)) return failed(g);

@@ -90,19 +90,8 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
     const size_t need = (size_t)sets * ns;
     if (e->d_pmax.ensure(need) || e->d_psum.ensure(need) || e->d_pidx.ensure(need)) return 1;
 
-    hipEvent_t ev_begin = e->ev0, ev_end = e->ev1;
-    if (e->log_timing) {
-        if (e->ev_used + 2 > e->ev_log.size()) {
-            for (int i = 0; i < 2; ++i) {
-                hipEvent_t ev;
-                QM_HIP(hipEventCreate(&ev));
-                e->ev_log.push_back(ev);
-            }
-        }
-        ev_begin = e->ev_log[e->ev_used];
-        ev_end = e->ev_log[e->ev_used + 1];
-        e->ev_used += 2;
-    }
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    if (timing_events(e, &ev_begin, &ev_end)) return 1;
     hipStream_t s = e->stream;
     QM_HIP(hipMemsetAsync(e->d_counts.p, 0, (size_t)ns * sizeof(int32_t), s));
     QM_HIP(hipMemsetAsync(e->d_flags.p, 0, 4 * sizeof(int32_t), s));

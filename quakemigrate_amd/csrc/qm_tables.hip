@@ -540,7 +540,7 @@ int qm_engine_load_lut(qm_engine *e, const int32_t *lut, int lut_on_device, int3
     // "resident" and stack through a foreign table.
     if (e->have_lut) e->cur_keyed = false;
     e->have_lut = false;
-    e->last_sets_own = false;                           // (the sets of a detect on the former table: qm_engine_tie_partial)
+    e->last.sets_own = false;                           // (the sets of a detect on the former table: qm_engine_tie_partial)
     const size_t lut_elems = (size_t)n_nodes * n_rows;
     if (e->d_lut.ensure(lut_elems) || e->d_scalar.ensure(4)) return 1;
     if (lut_on_device)
@@ -693,7 +693,7 @@ int qm_engine_table_select(qm_engine *e, uint64_t key, int32_t capacity, int32_t
         return 0;
     }
     DeviceGuard guard(e->device);
-    e->last_sets_own = false;                           // (another table from here on: qm_engine_tie_partial)
+    e->last.sets_own = false;                           // (another table from here on: qm_engine_tie_partial)
     TableState &cur = *e;
     const bool park = e->have_lut && e->cur_keyed && capacity > 0;
     // Is the requested table parked?  Then it trades places with the current one in ITS slot -- looked

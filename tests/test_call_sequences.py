@@ -5,7 +5,7 @@ One engine for the life of a process: call sequences against fresh engines.
 DESIGN.md section 0 and include/qmhip.h promise that the kernel a call runs and the bits it returns depend on the
 table, the configuration and the call -- not on what the engine did before.  MigrationScan, the drop-in symbols
 and the sharded detectors rely on it: they keep ONE engine whose scratch only grows, whose layouts are built at the
-first launch that takes them and parked with their table, and whose ``last_*`` fields later calls read.
+first launch that takes them and parked with their table, and whose record of the last launch later calls read.
 
 * ``test_walk``: a seeded plan (tests/sequence_plan.py; its coverage is checked on the CPU by
   tests/test_sequence_plan.py) drives one long-lived engine of each flavour through loads, selects, every kind of
@@ -246,12 +246,11 @@ def _run(lib, eng, req):
         out["series"] = series
     else:
         raise AssertionError(f"unknown kind {req.kind}")
-    # Read-outs of THIS launch.  shift_wide_tiles / shift_tail_spl describe the last shift-reuse launch and
-    # steps_per_launch the last detect_batch (include/qmhip.h): they are compared where this call was one.
-    keys = ["last_kernel", "last_kernel_j", "tie_brick_rows"]
+    # Read-outs of THIS launch (include/qmhip.h: they describe the last launch whatever its family -- after one that
+    # is not shift-reuse the three shift_* values are 0 on the long-lived engine as on the fresh one).
+    # steps_per_launch describes the last detect_batch: it is compared where this call was one.
+    keys = ["last_kernel", "last_kernel_j", "tie_brick_rows", "shift_wide_tiles", "shift_tail_spl", "shift_lazy"]
     read = {k: _get(lib, eng, k) for k in keys}
-    if read["last_kernel"] == 3:
-        read.update({k: _get(lib, eng, k) for k in ("shift_wide_tiles", "shift_tail_spl")})
     if req.kind == "detect_batch":
         read["steps_per_launch"] = _get(lib, eng, "steps_per_launch")
     # ... and of the layout it ran on: a table that comes back from parking, or is loaded over another, has the
@@ -595,7 +594,7 @@ INTERLEAVINGS = ["marginal_map", "migrate_device_scan_out", "migrate_host_chunks
 @pytest.mark.parametrize("name", INTERLEAVINGS)
 def test_tie_partial_after_an_intervening_call(lib, oracle, name, cfg):
     """qm_engine_tie_partial refines the sets its engine's LAST detect_partial left in the engine's scratch.  A call
-    in between overwrites them (every stacking launch, find_max_coa) or re-describes them (the ``last_*`` fields,
+    in between overwrites them (every stacking launch, find_max_coa) or re-describes them (the last launch's record,
     another table): the only acceptable outcomes are a QMHipError that asks for detect_partial first, or the
     correct index series -- never another one -- and after a refusal the engine works as before.  Both forms of
     the refinement: from the rows of maxima per brick (d_bmax), and from the workgroups' sets (``tie_sets = 0``:
