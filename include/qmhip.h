@@ -210,7 +210,12 @@ int qm_engine_synchronize(qm_engine *e);
  * shift_lazy, shift_tail_spl and shift_wide_tiles are 0 (shift_waves: the resident table's 256-sample layout's),
  * after a launch of the direct kernel alone (force_direct, every brick too wide) last_kernel and last_kernel_j are 0.
  * table_hits, table_misses, table_evictions, tables_parked, table_bytes, tables_parked_bytes, table_digests;
- * pick_lds_samples (the longest onset row qm_engine_pick_phases takes: row and selection keys live in LDS). */
+ * pick_lds_samples (the longest onset row qm_engine_pick_phases takes: row and selection keys live in LDS);
+ * the trigger stage's compile-time tunables (csrc/qm_trigger.hpp): trigger_max_radius (the largest smoothing radius
+ * qm_engine_trigger takes), trigger_smooth_tile, trigger_run_block, trigger_merge_stride; with the key
+ * trigger_timing (0 / 1 [0], measurement: HIP events around every stage of qm_engine_trigger) set, the last call's
+ * stage times in nanoseconds: trigger_ns_smooth, trigger_ns_stats, trigger_ns_runs (count and scan),
+ * trigger_ns_compact, trigger_ns_peaks, trigger_ns_merge (0: the stage did not run). */
 int qm_engine_config(qm_engine *e, const char *key, int64_t value);
 int qm_engine_get(qm_engine *e, const char *key, int64_t *value);
 
@@ -468,6 +473,50 @@ int qm_engine_pick_phases(qm_engine *e, const double *onsets, int onsets_on_devi
                           const int32_t *row_group, double sampling_rate, const double *halfwidth,
                           int threshold_mode, double mad_multiplier, const double *thresholds_in,
                           double *picks, int32_t *status);
+
+/* Trigger on the device -- the step between the detect sweep and the location: what Trigger._trigger_batch does to
+ * the coalescence series of a batch (quakemigrate/signal/trigger.py:318-638; the rules on arrays:
+ * tests/trigger_ref.py).  coa, coa_n: f64 [n], host arrays, uniformly sampled, already cut to the batch and its pads.
+ * All times are int64 nanoseconds from the first sample, t(i) = i period_ns.
+ *   a. smooth_weights != NULL: both series go through scipy.ndimage.gaussian_filter1d -- smooth_weights [2 r + 1]
+ *      with r = smooth_radius, symmetric, as the caller computed them; boundary "reflect" (d c b a | a b c d | d c b a,
+ *      also for n <= r); out = x[i] w[r], then for j = r .. 1: out += (x[i - j] + x[i + j]) w[r - j], no contraction:
+ *      SciPy's bits.
+ *   b. the trigger series is coa_n (trigger_on = 1) or coa (0), smoothed if a. ran.  threshold_method 0: the constant
+ *      threshold_value.  1 / 2: per chunk of chunk_samples samples counted from sample 0 (the last one shorter, one
+ *      chunk when n < chunk_samples) med = median(chunk) and 1: med + (1.4826 median(|chunk - med|)) threshold_value,
+ *      2: med threshold_value -- exact selection, NumPy's operation order, no contraction: NumPy's bits.
+ *   c. candidates: the maximal runs [f, l] of trig[i] >= threshold[i / chunk_samples]; p = the FIRST maximum of COA
+ *      (not of the trigger series) over the run; MinTime = t(p) - mei_ns if t(p) - t(f) < mw_ns else t(f) - (mei_ns -
+ *      mw_ns); MaxTime = t(p) + mei_ns if t(l) - t(p) < mw_ns else t(l) + (mei_ns - mw_ns).
+ *   d. candidates k and k + 1 are separate events iff MaxTime[k] < t(p[k + 1]) - mw_ns and MinTime[k + 1] > t(p[k]) +
+ *      mw_ns; per event the member with the FIRST largest trig[p] gives the peak, MinTime is the members' smallest,
+ *      MaxTime their largest.
+ * Out: *n_candidates, *n_events; events_i i64 [n_events][4]: peak index, MinTime, MaxTime, members; events_f f64
+ * [n_events][3]: TRIG_COA = trig[p], COA = coa[p], COA_NORM = coa_n[p] (smoothed if a. ran).  Optional (NULL: not
+ * wanted): thresholds f64 [chunks] (one value under method 0), smoothed f64 [2][n] (written only when a. ran),
+ * candidates i64 [n_candidates][5]: f, l, p, MinTime, MaxTime, with room for max_candidates rows.
+ * The time window, the region test and the EventID are the caller's (quakemigrate_amd/trigger.py).
+ * Refused, with every output untouched: a NULL argument (the optional ones excepted), n < 1 or above 2^30, a
+ * trigger_on other than 0 / 1, a threshold_method outside 0..2, chunk_samples < 1 under method 1 / 2, smooth_radius
+ * outside 0.."trigger_max_radius", period_ns < 1, mw_ns < 0, mei_ns < 2 mw_ns, a non-finite sample in either series
+ * (the message names their number; the reference would compute NaN thresholds and trigger nothing), more candidates
+ * than max_candidates where the table is wanted, more events than max_events (the message names the number needed).
+ * qm_engine_last_kernel_ms reports the launch sequence, its two read-backs of counts included. */
+typedef struct {
+    int32_t trigger_on;             /* 0: COA, 1: COA_N */
+    int32_t threshold_method;       /* 0: static, 1: MAD, 2: median ratio */
+    double threshold_value;         /* the constant (method 0) or the multiplier */
+    int64_t chunk_samples;          /* methods 1 and 2 */
+    int32_t smooth_radius;          /* r */
+    int32_t reserved;               /* 0 */
+    const double *smooth_weights;   /* [2 r + 1], NULL: no smoothing */
+    int64_t period_ns, mw_ns, mei_ns;
+} qm_trigger_params;
+int qm_engine_trigger(qm_engine *e, const double *coa, const double *coa_n, int64_t n, const qm_trigger_params *params,
+                      int64_t max_events, int64_t *n_candidates, int64_t *n_events, int64_t *events_i,
+                      double *events_f, double *thresholds, double *smoothed, int64_t *candidates,
+                      int64_t max_candidates);
 
 /* exp(x) rounded to nearest from a double-double evaluation (csrc/qm_ties.hpp): the function the
  * opt-in arg-max rule "tie_rule" = 1 compares near-tied nodes on (the reference exponentiates, then

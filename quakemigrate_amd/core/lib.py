@@ -119,6 +119,18 @@ qmlib.qm_engine_preprocess.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32,
                                        ctypes.c_int]
 qmlib.qm_engine_pick_phases.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32, _vp, _vp, ctypes.c_double, _vp,
                                         ctypes.c_int, ctypes.c_double, _vp, _vp, _vp]
+
+
+class TriggerParams(ctypes.Structure):
+    """``qm_trigger_params`` (include/qmhip.h)."""
+    _fields_ = [("trigger_on", c_int32), ("threshold_method", c_int32), ("threshold_value", ctypes.c_double),
+                ("chunk_samples", c_int64), ("smooth_radius", c_int32), ("reserved", c_int32),
+                ("smooth_weights", _vp), ("period_ns", c_int64), ("mw_ns", c_int64), ("mei_ns", c_int64)]
+
+
+qmlib.qm_engine_trigger.argtypes = [_vp, _vp, _vp, c_int64, ctypes.POINTER(TriggerParams), c_int64,
+                                    ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), _vp, _vp, _vp, _vp, _vp,
+                                    c_int64]
 qmlib.qm_engine_find_max_coa.argtypes = [_vp, _vp, ctypes.c_int, c_int32,
                                          c_int64, _vp, _vp, _vp, ctypes.c_int]
 qmlib.qm_exp2f_max_error.argtypes = [_vp, ctypes.c_float, ctypes.c_float,
@@ -719,6 +731,61 @@ class Engine:
             _host(halfwidth), int(threshold_mode), float(mad_multiplier), pt, _host(picks), _host(status)))
         return picks, status
 
+    TRIGGER_METHODS = {"static": 0, "mad": 1, "median_ratio": 2}
+
+    def trigger_series(self, coa, coa_n, period_ns, mw_ns, mei_ns, trigger_on=0, method="static", value=1.5,
+                       chunk_samples=1, weights=None, max_events=65536, want_candidates=False):
+        """
+        The trigger stage on the GPU, the step between detect and locate (``Trigger._trigger_batch``'s smoothing,
+        threshold, candidates and merge, trigger.py:318-638; include/qmhip.h: ``qm_engine_trigger``).  ``coa``,
+        ``coa_n`` (n,): float64 host arrays, contiguous, already cut to the batch and its pads; times in int64
+        nanoseconds from the first sample.  ``trigger_on`` 0: COA, 1: COA_N; ``method`` "static" (``value``: the
+        threshold), "mad" or "median_ratio" (``value``: the multiplier, per chunk of ``chunk_samples``); ``weights``
+        (2 r + 1,): the Gaussian kernel of the smoothing, None: none.  Returns a dict: ``n_candidates``, ``n_events``,
+        ``events_i`` (n_events, 4) int64 [peak index, MinTime, MaxTime, members], ``events_f`` (n_events, 3) [TRIG_COA,
+        COA, COA_NORM], ``thresholds`` (chunks,), ``smoothed`` (2, n) or None and -- ``want_candidates`` --
+        ``candidates`` (n_candidates, 5) int64 [f, l, p, MinTime, MaxTime].  More than ``max_events`` events: refused,
+        the message names the number.
+        """
+        for name, a in (("coa", coa), ("coa_n", coa_n)):
+            if not isinstance(a, np.ndarray):
+                raise TypeError(f"{name}: a NumPy array expected, got {type(a).__name__}")
+            if a.dtype != np.float64:
+                raise TypeError(f"{name}: expected float64, got {a.dtype}")
+            if a.ndim != 1 or not a.flags["C_CONTIGUOUS"]:
+                raise ValueError(f"{name} must be one-dimensional and C-contiguous")
+        if coa_n.shape != coa.shape:
+            raise ValueError(f"coa_n of shape {coa_n.shape} for coa of shape {coa.shape}")
+        if method not in self.TRIGGER_METHODS:
+            raise ValueError(f"method must be one of {sorted(self.TRIGGER_METHODS)}, got {method!r}")
+        n, code = int(coa.shape[0]), self.TRIGGER_METHODS[method]
+        par = TriggerParams(int(trigger_on), code, float(value), int(chunk_samples), 0, 0, _vp(None), int(period_ns),
+                            int(mw_ns), int(mei_ns))
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64)
+            if weights.ndim != 1 or weights.size % 2 != 1:
+                raise ValueError(f"weights of shape {weights.shape}: an odd number (2 r + 1) expected")
+            par.smooth_radius, par.smooth_weights = weights.size // 2, _host(weights)
+        # one threshold per chunk (a chunk longer than the series is the series); what the call refuses gets one slot
+        chunks = -(-n // min(int(chunk_samples), n)) if code != 0 and chunk_samples >= 1 and n >= 1 else 1
+        max_events = int(max_events)
+        events_i = np.zeros((max(max_events, 0), 4), dtype=np.int64)
+        events_f = np.zeros((max(max_events, 0), 3))
+        thresholds = np.zeros(max(chunks, 1))
+        smoothed = np.zeros((2, n)) if weights is not None else None
+        room = (n + 1) // 2 if want_candidates else 0
+        candidates = np.zeros((room, 5), dtype=np.int64) if want_candidates else None
+        nc, ne = c_int64(0), c_int64(0)
+        _check(qmlib.qm_engine_trigger(
+            self._h, _host(coa), _host(coa_n), n, ctypes.byref(par), max_events, ctypes.byref(nc), ctypes.byref(ne),
+            _host(events_i), _host(events_f), _host(thresholds), _host(smoothed) if smoothed is not None else _vp(None),
+            _host(candidates) if want_candidates else _vp(None), room))
+        out = {"n_candidates": int(nc.value), "n_events": int(ne.value), "events_i": events_i[:ne.value].copy(),
+               "events_f": events_f[:ne.value].copy(), "thresholds": thresholds, "smoothed": smoothed}
+        if want_candidates:
+            out["candidates"] = candidates[:nc.value].copy()
+        return out
+
     def find_max_coa(self, map4d, n_samples, n_nodes, out=None):
         if out is None:
             out = (np.zeros(n_samples), np.zeros(n_samples),
@@ -1074,6 +1141,9 @@ class EngineReplicas:
 
     def pick_phases(self, *args, **kwargs):
         return self.lead.pick_phases(*args, **kwargs)
+
+    def trigger_series(self, *args, **kwargs):
+        return self.lead.trigger_series(*args, **kwargs)
 
 
 def timeit(*args_, **kwargs_):

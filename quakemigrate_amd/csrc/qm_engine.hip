@@ -771,6 +771,8 @@ void qm_engine_destroy(qm_engine *e) {
     e->d_sig.release(); e->d_sta.release(); e->d_lta.release(); e->d_raw.release();
     e->d_pre_coef.release(); e->d_pre_out.release(); e->d_pre_meta.release();
     e->d_pick_val.release(); e->d_pick_meta.release();
+    e->d_trg_x.release(); e->d_trg_par.release(); e->d_trg_val.release(); e->d_trg_cnt.release();
+    e->d_trg_run.release(); e->d_trg_tot.release(); e->d_trg_cand.release();
     e->d_onset_meta.release(); e->d_scalar.release(); e->d_digest.release();
     e->d_onsets.release(); e->d_pmax.release(); e->d_psum.release(); e->d_out_a.release();
     e->d_chunk.release(); e->d_marg.release(); e->d_marg_out.release(); e->d_pidx.release();
@@ -784,6 +786,7 @@ void qm_engine_destroy(qm_engine *e) {
     e->d_tie_emax.release(); e->d_tie_cands.release(); e->d_tie_keys.release();
     if (e->h_flags) (void)hipHostFree(e->h_flags);
     for (hipEvent_t ev : e->ev_log) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->trg_ev) (void)hipEventDestroy(ev);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->own_stream) {
@@ -903,6 +906,8 @@ int qm_engine_config(qm_engine *e, const char *key, int64_t v) {
         e->cfg_stream_stamps = v ? 1 : 0;
     } else if (k == "preproc_skew") {
         e->cfg_preproc_skew = v ? 1 : 0;
+    } else if (k == "trigger_timing") {
+        e->cfg_trigger_timing = v ? 1 : 0;
     } else if (k == "log_timing") {
         e->log_timing = v != 0;
         e->ev_used = 0;
@@ -962,6 +967,17 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     else if (k == "stream_pull") *v = e->cfg_stream_pull;
     else if (k == "preproc_skew") *v = e->cfg_preproc_skew;
     else if (k == "pick_lds_samples") *v = qm::kPicksLdsSamples;
+    else if (k == "trigger_max_radius") *v = qm::kTrigMaxRadius;
+    else if (k == "trigger_timing") *v = e->cfg_trigger_timing;
+    else if (k == "trigger_ns_smooth") *v = e->trg_ns[qm::kTrigSmooth];
+    else if (k == "trigger_ns_stats") *v = e->trg_ns[qm::kTrigStats];
+    else if (k == "trigger_ns_runs") *v = e->trg_ns[qm::kTrigRuns];
+    else if (k == "trigger_ns_compact") *v = e->trg_ns[qm::kTrigCompact];
+    else if (k == "trigger_ns_peaks") *v = e->trg_ns[qm::kTrigPeaks];
+    else if (k == "trigger_ns_merge") *v = e->trg_ns[qm::kTrigMerge];
+    else if (k == "trigger_smooth_tile") *v = qm::kTrigSmoothTile;
+    else if (k == "trigger_run_block") *v = qm::kTrigRunBlock;
+    else if (k == "trigger_merge_stride") *v = qm::kTrigMergeThreads;
     else if (k == "tie_brick_rows") *v = e->last.brick_rows;
 
     else if (k == "tie_refined_steps") *v = e->tie_refined_steps;

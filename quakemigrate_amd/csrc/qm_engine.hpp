@@ -13,6 +13,7 @@
 //   qm_widen.hip     the rows next to the path: onset stage, locate fits, RBF peak
 //   qm_preproc.hip   the row before the onset stage: detrend, taper, zero-phase band-pass of the component traces
 //   qm_picks.hip     the row after the location: phase picks, a Gaussian fitted to every onset row of an event
+//   qm_trigger.hip   the row after the detect sweep: coalescence series in, triggered events out
 //   qm_compat.hip    the five reference-signature symbols (qmlib.h:28-44)
 //   qm_group.hip     engine groups: one process driving the boxes of a column partition on several devices
 // Everything declared here lives in the library only (hidden visibility).
@@ -42,6 +43,7 @@
 #include "qm_ties.hpp"
 #include "qm_preproc.hpp"
 #include "qm_picks.hpp"
+#include "qm_trigger.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -352,6 +354,14 @@ struct qm_engine : TableState {
     // phase-pick stage scratch: half-widths, thresholds and picks; windows, groups and status
     DevBuf<double> d_pick_val;
     DevBuf<int32_t> d_pick_meta;
+    // trigger stage scratch: the two series (raw, then smoothed), weights and thresholds, the run kernels' counts and
+    // totals; sized once the candidate count is known: run starts and ends, candidate and event tables, their values
+    DevBuf<double> d_trg_x, d_trg_par, d_trg_val;
+    DevBuf<int32_t> d_trg_cnt, d_trg_run;
+    DevBuf<int64_t> d_trg_tot, d_trg_cand;
+    int cfg_trigger_timing = 0;             // 1: HIP events around every stage of the trigger sequence (measurement)
+    std::vector<hipEvent_t> trg_ev;         // ... a pair per stage
+    int64_t trg_ns[qm::kTrigStages] = {};   // ... the last call's stage times ("trigger_ns_<stage>"), 0: did not run
 
     // scratch
     DevBuf<double> d_onsets, d_pmax, d_psum, d_out_a, d_chunk, d_marg, d_marg_out;
