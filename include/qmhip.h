@@ -440,6 +440,47 @@ int qm_engine_preprocess(qm_engine *e, const double *signals, int signals_on_dev
                          const double *taper_right, int32_t n_right, int zero_phase, double *filtered,
                          int out_on_device);
 
+/* Resampling on the device -- the step upstream of the pre-processing: what util.resample does to every raw trace of
+ * a timestep (quakemigrate/util.py:404-604): upsampling by linear interpolation with constant pads at the window's
+ * ends, decimation behind a detrend, a taper and a zero-phase low-pass, the trims to the window.  Raw traces go in,
+ * each at its own rate and length, packed into one buffer of int32 (raw_dtype 0, as miniSEED holds them; converted
+ * exactly) or float64 (raw_dtype 1) samples, host or device; out: f64 [n_traces][t_samples], host or device, what
+ * qm_engine_preprocess takes.  The caller plans the work (Python: quakemigrate_amd.preprocess.ResampleStage):
+ * records [n_traces][11] int64, per trace
+ *    0 raw_offset, 1 n_raw   its samples x[0..n_raw) in the raw buffer (elements), n_raw >= 1
+ *    2 up                    u >= 1
+ *    3 pad_left, 4 pad_right copies of x[0] in front of / of x[n_raw - 1] behind the upsampled series (0 with u == 1)
+ *    5 up_first, 6 n_up      the slice of the padded series that is kept (the reference's trim)
+ *    7 dec                   d >= 1
+ *    8 lowpass               d > 1: its low-pass, an index into sos_lp [n_lowpass][n_sections_lp][6] (SciPy's layout,
+ *                            a0 == 1)
+ *    9 taper                 d > 1: its taper, an index into taper_table [n_tapers][2] = (offset, m): the weights
+ *                            taper_weights[offset .. offset + m) of the first m samples, then [offset + m .. offset + 2 m)
+ *                            of the last m
+ *   10 out_first             first decimated sample of the output row
+ * Per trace, one workgroup:
+ *   1. upsample: the series of (n_raw - 1) u + 1 samples with sample j u = x[j] and sample j u + i, 0 < i < u,
+ *      = (double(i) / u) x[j + 1] + (double(u - i) / u) x[j] -- two quotients, two products, one sum, no contraction:
+ *      NumPy's bits for the reference's expression -- then the pads; K = samples [up_first, up_first + n_up) of it.
+ *   2. d > 1: detrend = 1: qm_engine_preprocess' step 1 over K (the same fixed-order sums); K[k] *= w[k],
+ *      K[n_up - m + k] *= w[m + k] for k < m with w the taper's weights; the cascade of the low-pass forward, then over
+ *      the reversed result, reversed back: scipy.signal.sosfilt's bits, as in qm_engine_preprocess; then D[k] = K[k d]
+ *      for k < ceil(n_up / d) (obspy's decimate without its own filter, data[::d]).  d == 1: D = K, nothing else runs.
+ *   3. out[i][0 .. t_samples) = D[out_first .. out_first + t_samples).
+ * K lives in LDS up to 20 480 samples, else in engine scratch: the same bits.  "preproc_skew" = 0 selects the plain
+ * filter form here too.
+ * Refused, with the output untouched: a NULL argument (sos_lp, taper_table, taper_weights may be NULL where their
+ * count is 0), a raw_dtype other than 0 / 1, n_traces < 1, t_samples < 1, n_raw < 1, raw samples outside
+ * [0, total_raw_samples), up < 1, dec < 1, a pad with up == 1 or below 0, a kept slice that leaves the padded series,
+ * out_first + t_samples > ceil(n_up / d), n_sections_lp outside 1..8, a section whose a0 is not 1, a taper that
+ * leaves taper_weights, and for d > 1 a lowpass or taper index out of range or 2 m > n_up.
+ * qm_engine_last_kernel_ms reports the launch. */
+int qm_engine_resample(qm_engine *e, const void *raw, int raw_dtype, int raw_on_device, int64_t total_raw_samples,
+                       int32_t n_traces, const int64_t *records, const double *sos_lp, int32_t n_lowpass,
+                       int32_t n_sections_lp, int detrend, const int32_t *taper_table, int32_t n_tapers,
+                       const double *taper_weights, int64_t n_taper_weights, int32_t t_samples, double *out,
+                       int out_on_device);
+
 /* Phase picks on the device -- the step after the location: what GaussianPicker.pick_phases does to every onset row
  * (one station x phase) of a located event (quakemigrate/signal/pickers/gaussian.py:319-560).  One launch, one
  * workgroup per row; onsets: f64 [n_rows][t_samples], the UN-LOGGED onset functions (qm_engine_onsets' raw_onsets
@@ -578,6 +619,23 @@ int qm_stream_set_onset_stage(qm_stream *s, int32_t n_traces, const int32_t *tra
                               const int32_t *nsta, const int32_t *nlta, int transform, int position,
                               int32_t taper_pad, double min_onset_value);
 int qm_stream_push_signals(qm_stream *s, const double *signals);
+/* Raw waveforms in: with a resampling stage on top of its onset stage the stream takes a timestep's packed raw
+ * traces (host, total_raw_samples int32 or float64 samples, laid out as the records say) through qm_stream_push_raw,
+ * and a slot's launch becomes pull or copy of the raw bytes -> qm_engine_resample's kernel over the slot's
+ * (step, trace)s -> the sequence of qm_stream_set_onset_stage: every timestep's bits are those of the staged calls.
+ * The arguments are qm_engine_resample's; every array is copied to the device here, and the ring's pinned slots are
+ * sized for the raw bytes (the signals' pinned buffers go at the first qm_stream_push_raw).  A stage that fails --
+ * over replicas: on any lane -- leaves the stream as it was.  qm_stream_set_resample_stage is called once, after qm_stream_set_onset_stage and before
+ * the first push; t_samples must be the stream's and n_traces the onset stage's.  Refused: a stage without an onset
+ * stage, a second one, one after a push, qm_stream_push_raw without the stage, qm_stream_push_signals or
+ * qm_stream_push mixed with qm_stream_push_raw on one stream, and what qm_engine_resample refuses.  Over replicas
+ * the stage and the pushes go lane by lane.  qm_stream_push_raw returns what qm_stream_push returns. */
+int qm_stream_set_resample_stage(qm_stream *s, int32_t n_traces, const int64_t *records, const double *sos_lp,
+                                 int32_t n_lowpass, int32_t n_sections_lp, int detrend,
+                                 const int32_t *taper_table, int32_t n_tapers, const double *taper_weights,
+                                 int64_t n_taper_weights, int32_t t_samples, int raw_dtype,
+                                 int64_t total_raw_samples);
+int qm_stream_push_raw(qm_stream *s, const void *raw);
 /* One pipeline over several engines that hold the SAME table (checked by digest): the continuous stream split by
  * time, not by grid.  Launch j (K timesteps) runs on engine j mod n_engines, each engine with
  * `depth` slots of its own; qm_stream_pop returns timesteps in push order.  Same qm_stream handle: push / flush /
@@ -591,8 +649,8 @@ int qm_stream_create_replicas(qm_engine *const *engines, int32_t n_engines, int3
                               int32_t depth, qm_stream **out);
 
 /* Duration (ms, HIP events on the engine stream) of the stacking kernel(s) of
- * the most recent detect / migrate call, or of the pick kernel of a more recent
- * qm_engine_pick_phases; negative if none.  Synchronises. */
+ * the most recent detect / migrate call, or of the kernel of a more recent
+ * qm_engine_pick_phases or qm_engine_resample; negative if none.  Synchronises. */
 int qm_engine_last_kernel_ms(qm_engine *e, double *ms);
 
 /* With config "log_timing" = 1 every stacking launch is bracketed by its own

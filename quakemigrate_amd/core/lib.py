@@ -117,6 +117,9 @@ qmlib.qm_engine_onsets.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32, c_i
 qmlib.qm_engine_preprocess.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32, c_i32Pt, c_dPt, c_int32, c_int32,
                                        ctypes.c_int, c_dPt, c_int32, c_dPt, c_int32, ctypes.c_int, _vp,
                                        ctypes.c_int]
+qmlib.qm_engine_resample.argtypes = [_vp, _vp, ctypes.c_int, ctypes.c_int, c_int64, c_int32, c_i64Pt, c_dPt, c_int32,
+                                     c_int32, ctypes.c_int, c_i32Pt, c_int32, c_dPt, c_int64, c_int32, _vp,
+                                     ctypes.c_int]
 qmlib.qm_engine_pick_phases.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32, _vp, _vp, ctypes.c_double, _vp,
                                         ctypes.c_int, ctypes.c_double, _vp, _vp, _vp]
 
@@ -149,6 +152,9 @@ qmlib.qm_stream_push_signals.argtypes = [_vp, _vp]
 qmlib.qm_stream_set_onset_stage.argtypes = [_vp, c_int32, c_i32Pt, c_i32Pt, c_dPt, c_int32, c_int32, ctypes.c_int,
                                             c_dPt, c_int32, c_dPt, c_int32, c_i32Pt, c_i32Pt, ctypes.c_int,
                                             ctypes.c_int, c_int32, ctypes.c_double]
+qmlib.qm_stream_push_raw.argtypes = [_vp, _vp]
+qmlib.qm_stream_set_resample_stage.argtypes = [_vp, c_int32, c_i64Pt, c_dPt, c_int32, c_int32, ctypes.c_int, c_i32Pt,
+                                               c_int32, c_dPt, c_int64, c_int32, ctypes.c_int, c_int64]
 qmlib.qm_stream_flush.argtypes = [_vp]
 qmlib.qm_stream_pop.argtypes = [_vp, c_int32, _vp, _vp, _vp]
 qmlib.qm_stream_pending.argtypes = [_vp, ctypes.POINTER(c_int32), ctypes.POINTER(c_int32)]
@@ -174,6 +180,60 @@ qmlib.qm_group_synchronize.argtypes = [_vp]
 qmlib.qm_group_n_parts.argtypes = [_vp, _i32p]
 qmlib.qm_group_part_info.argtypes = [_vp, c_int32, _i32p, _i32p, _i32p, ctypes.POINTER(c_int64),
                                      ctypes.POINTER(ctypes.c_double)]
+
+
+RAW_DTYPES = {np.dtype(np.int32): 0, np.dtype(np.float64): 1}       # qm_engine_resample's raw_dtype
+
+
+def resample_arrays(stage, t_samples=None):
+    """The checked, contiguous arrays of a resampling stage -- a :class:`quakemigrate_amd.preprocess.ResampleStage`
+    (then ``t_samples`` is needed) or the dict its ``arrays(t_samples)`` returns -- in the order the C ABI takes them:
+    ``(records, sos_lp, taper_table, taper_weights, detrend, t_samples, total_raw_samples)``."""
+    if hasattr(stage, "arrays"):
+        if t_samples is None:
+            raise ValueError("a ResampleStage needs the t_samples of the windows")
+        stage = stage.arrays(int(t_samples))
+    a = stage
+    records = np.ascontiguousarray(a["records"], dtype=np.int64)
+    sos = np.ascontiguousarray(a["sos_lp"], dtype=np.float64)
+    table = np.ascontiguousarray(a["taper_table"], dtype=np.int32).reshape(-1, 2)
+    weights = np.ascontiguousarray(a["taper_weights"], dtype=np.float64).reshape(-1)
+    if records.ndim != 2 or records.shape[1] != 11:
+        raise ValueError(f"records of shape {records.shape}: (n_traces, 11) expected")
+    if sos.ndim != 3 or sos.shape[2] != 6:
+        raise ValueError(f"sos_lp of shape {sos.shape}: (n_lowpass, n_sections, 6) expected")
+    if t_samples is not None and int(a["t_samples"]) != int(t_samples):
+        raise ValueError(f"the stage was planned for windows of {a['t_samples']} samples, not {t_samples}")
+    total = a.get("total_raw_samples")
+    if total is None:
+        total = int(np.max(records[:, 0] + records[:, 1])) if len(records) else 0
+    return records, sos, table, weights, int(a.get("detrend", 1)), int(a["t_samples"]), int(total)
+
+
+def pack_raw(raw, records, total, dtype=None):
+    """A timestep's raw traces as one packed host array: ``raw`` is a list of 1-D arrays, one per trace (each goes to
+    its record's raw offset), or the packed array itself.  int32 or float64 (``dtype``: the one asked for)."""
+    if isinstance(raw, (list, tuple)):
+        if len(raw) != len(records):
+            raise ValueError(f"{len(raw)} raw traces, the stage plans {len(records)}")
+        kind = np.dtype(dtype) if dtype is not None else np.result_type(*[np.asarray(x).dtype for x in raw])
+        packed = np.zeros(total, dtype=kind)
+        for i, (x, rec) in enumerate(zip(raw, records)):
+            x = np.asarray(x)
+            if x.ndim != 1 or len(x) != rec[1] or rec[0] < 0 or rec[0] + rec[1] > total:
+                raise ValueError(f"raw trace {i} of shape {x.shape}: the stage plans {int(rec[1])} samples for it")
+            if x.dtype != kind:
+                raise TypeError(f"raw trace {i}: expected {kind}, got {x.dtype}")
+            packed[rec[0]:rec[0] + rec[1]] = x
+        raw = packed
+    if isinstance(raw, np.ndarray):
+        if dtype is not None and raw.dtype != np.dtype(dtype):
+            raise TypeError(f"raw samples: expected {np.dtype(dtype)}, got {raw.dtype}")
+        if raw.dtype not in RAW_DTYPES:
+            raise TypeError(f"raw samples of type {raw.dtype}: int32 or float64")
+        if raw.ndim != 1 or not raw.flags["C_CONTIGUOUS"] or raw.size < total:
+            raise ValueError(f"packed raw samples of shape {raw.shape}: one contiguous axis of at least {total}")
+    return raw
 
 
 class QMHipError(RuntimeError):
@@ -697,6 +757,40 @@ class Engine:
             po, dev_o))
         return out
 
+    def resample(self, raw, stage, out=None, t_samples=None):
+        """
+        Resampling on the GPU, the step before :meth:`preprocess` (the reference's ``util.resample``, util.py:404-604;
+        include/qmhip.h: ``qm_engine_resample``): raw component traces in, each at its own rate and length, the
+        (n_traces, t_samples) float64 traces at the scan rate out.
+
+        ``raw``: a list of 1-D arrays, one per trace, or the packed 1-D array the records' offsets point into -- a
+        host array or a torch device tensor --, int32 or float64.  ``stage``: a
+        :class:`quakemigrate_amd.preprocess.ResampleStage` (then ``t_samples`` or ``out`` says how long the windows
+        are) or the dict its ``arrays(t_samples)`` returns.  Returns the traces (``out``, host or device, or a new
+        host array).
+        """
+        if t_samples is None and out is not None and hasattr(stage, "arrays"):
+            t_samples = int(out.shape[-1])
+        records, sos, table, weights, detrend, t_samples, total = resample_arrays(stage, t_samples)
+        n_traces = len(records)
+        if hasattr(raw, "data_ptr"):
+            names = {"torch.int32": 0, "torch.float64": 1}
+            if str(raw.dtype) not in names:
+                raise TypeError(f"raw samples of type {raw.dtype}: int32 or float64")
+            code = names[str(raw.dtype)]
+            pr, dev_r = self._ptr(raw, None, total)
+        else:
+            raw = pack_raw(raw, records, total)
+            code = RAW_DTYPES[raw.dtype]
+            pr, dev_r = _host(raw), 0
+        if out is None:
+            out = np.zeros((n_traces, t_samples))
+        po, dev_o = self._ptr(out, np.float64, n_traces * t_samples)
+        _check(qmlib.qm_engine_resample(
+            self._h, pr, code, dev_r, total, n_traces, records.reshape(-1), sos.reshape(-1), int(sos.shape[0]),
+            int(sos.shape[1]), detrend, table.reshape(-1), len(table), weights, len(weights), t_samples, po, dev_o))
+        return out
+
     def pick_phases(self, onsets, windows, row_group, sampling_rate, halfwidth, threshold_mode=0,
                     mad_multiplier=8.0, thresholds=None):
         """
@@ -1138,6 +1232,9 @@ class EngineReplicas:
 
     def preprocess(self, *args, **kwargs):
         return self.lead.preprocess(*args, **kwargs)
+
+    def resample(self, *args, **kwargs):
+        return self.lead.resample(*args, **kwargs)
 
     def pick_phases(self, *args, **kwargs):
         return self.lead.pick_phases(*args, **kwargs)

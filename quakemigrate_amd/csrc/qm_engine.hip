@@ -770,6 +770,7 @@ void qm_engine_destroy(qm_engine *e) {
     e->d_grids.release(); e->d_rows.release(); e->d_served.release();
     e->d_sig.release(); e->d_sta.release(); e->d_lta.release(); e->d_raw.release();
     e->d_pre_coef.release(); e->d_pre_out.release(); e->d_pre_meta.release();
+    e->d_rs_meta.release(); e->d_rs_coef.release(); e->d_rs_raw.release(); e->d_rs_scratch.release();
     e->d_pick_val.release(); e->d_pick_meta.release();
     e->d_trg_x.release(); e->d_trg_par.release(); e->d_trg_val.release(); e->d_trg_cnt.release();
     e->d_trg_run.release(); e->d_trg_tot.release(); e->d_trg_cand.release();

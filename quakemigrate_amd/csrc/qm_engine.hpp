@@ -12,6 +12,7 @@
 //                    several engines that hold the same table (replicas: launches round-robin)
 //   qm_widen.hip     the rows next to the path: onset stage, locate fits, RBF peak
 //   qm_preproc.hip   the row before the onset stage: detrend, taper, zero-phase band-pass of the component traces
+//   qm_resample.hip  the row before that: raw traces, each at its own rate and length, upsampled and decimated to the scan rate
 //   qm_picks.hip     the row after the location: phase picks, a Gaussian fitted to every onset row of an event
 //   qm_trigger.hip   the row after the detect sweep: coalescence series in, triggered events out
 //   qm_compat.hip    the five reference-signature symbols (qmlib.h:28-44)
@@ -42,6 +43,7 @@
 #include "qm_shift.hpp"
 #include "qm_ties.hpp"
 #include "qm_preproc.hpp"
+#include "qm_resample.hpp"
 #include "qm_picks.hpp"
 #include "qm_trigger.hpp"
 
@@ -351,6 +353,10 @@ struct qm_engine : TableState {
     // pre-processing stage scratch: coefficients and taper weights, the traces' filters, the filtered traces
     DevBuf<double> d_pre_coef, d_pre_out;
     DevBuf<int32_t> d_pre_meta;
+    // resampling stage scratch: records and taper table, low-pass coefficients and taper weights, the raw samples
+    // (bytes, in doubles), the kept series of traces above the LDS limit; host results go through d_pre_out
+    DevBuf<int64_t> d_rs_meta;
+    DevBuf<double> d_rs_coef, d_rs_raw, d_rs_scratch;
     // phase-pick stage scratch: half-widths, thresholds and picks; windows, groups and status
     DevBuf<double> d_pick_val;
     DevBuf<int32_t> d_pick_meta;
@@ -521,6 +527,15 @@ int check_preproc(const char *what, int32_t n_traces, int32_t t_samples, const i
                   const double *taper_right, int32_t n_right);
 // the pre-processing kernel over n_traces traces on the engine's stream: enqueue only
 int launch_preproc_stage(qm_engine *e, const qm::PreprocArgs &a, int64_t n_traces);
+
+// ---- qm_resample.hip ----------------------------------------------------------------------------
+// what qm_engine_resample and qm_stream_set_resample_stage refuse (host arrays); *max_kept: the longest kept series
+int check_resample(const char *what, int raw_dtype, int64_t total_raw_samples, int32_t n_traces, int32_t t_samples,
+                   const int64_t *records, const double *sos_lp, int32_t n_lowpass, int32_t n_sections_lp,
+                   const int32_t *taper_table, int32_t n_tapers, const double *taper_weights, int64_t n_taper_weights,
+                   int64_t *max_kept);
+// the resampling kernel over n_traces traces on the engine's stream: enqueue only
+int launch_resample_stage(qm_engine *e, const qm::ResampleArgs &a, int64_t n_traces, int64_t max_kept);
 
 // ---- qm_screen.hip ------------------------------------------------------------------------------
 constexpr int kFlagRing = 1024;

@@ -1,0 +1,143 @@
+// qm_resample.hip -- the resampling stage's host side: the checks of the records, staging, the launch (kernel and
+// its notes: qm_resample.hpp).  qm_engine_resample is the staged call; the pipeline (qm_stream.hip) launches the same
+// kernel over the (step, trace)s of a slot through launch_resample_stage.
+#define QM_TU_RESAMPLE 1
+#include "qm_engine.hpp"
+
+int check_resample(const char *what, int raw_dtype, int64_t total_raw_samples, int32_t n_traces, int32_t t_samples,
+                   const int64_t *records, const double *sos_lp, int32_t n_lowpass, int32_t n_sections_lp,
+                   const int32_t *taper_table, int32_t n_tapers, const double *taper_weights, int64_t n_taper_weights,
+                   int64_t *max_kept) {
+    using namespace qm;
+    if (!records) return fail("%s: NULL argument", what);
+    if (raw_dtype != kRawInt32 && raw_dtype != kRawFloat64)
+        return fail("%s: raw_dtype %d: 0 (int32) or 1 (float64)", what, raw_dtype);
+    if (n_traces < 1 || t_samples < 1 || total_raw_samples < 1) return fail("%s: empty input", what);
+    if (n_lowpass < 0 || n_tapers < 0 || n_taper_weights < 0 || (n_lowpass > 0 && !sos_lp) ||
+        (n_tapers > 0 && !taper_table) || (n_taper_weights > 0 && !taper_weights))
+        return fail("%s: %d low-passes, %d tapers, %lld taper weights without their arrays", what, n_lowpass, n_tapers,
+                    (long long)n_taper_weights);
+    if (n_sections_lp < 1 || n_sections_lp > kPreprocMaxSections)
+        return fail("%s: n_sections_lp must be in 1..%d (got %d)", what, kPreprocMaxSections, n_sections_lp);
+    for (int k = 0; k < n_lowpass * n_sections_lp; ++k)
+        if (sos_lp[6 * k + 3] != 1.0)
+            return fail("%s: low-pass %d, section %d: a0 = %.17g, sections must be normalised to a0 == 1", what,
+                        k / n_sections_lp, k % n_sections_lp, sos_lp[6 * k + 3]);
+    for (int t = 0; t < n_tapers; ++t) {
+        const int64_t off = taper_table[2 * t], m = taper_table[2 * t + 1];
+        if (off < 0 || m < 0 || off + 2 * m > n_taper_weights)
+            return fail("%s: taper %d: 2 x %lld weights from %lld on, %lld weights given", what, t, (long long)m,
+                        (long long)off, (long long)n_taper_weights);
+    }
+    int64_t kept = 0;
+    for (int i = 0; i < n_traces; ++i) {
+        const int64_t *r = records + (size_t)i * kResampleFields;
+        const int64_t n_raw = r[kRsNRaw], u = r[kRsUp], d = r[kRsDec], n_up = r[kRsNUp];
+        if (n_raw < 1) return fail("%s: trace %d: n_raw = %lld, at least one raw sample is needed", what, i, (long long)n_raw);
+        if (r[kRsRawOffset] < 0 || r[kRsRawOffset] + n_raw > total_raw_samples)
+            return fail("%s: trace %d: raw samples [%lld, %lld) leave the raw buffer of %lld", what, i,
+                        (long long)r[kRsRawOffset], (long long)(r[kRsRawOffset] + n_raw), (long long)total_raw_samples);
+        if (u < 1 || u > INT32_MAX || d < 1 || d > INT32_MAX)
+            return fail("%s: trace %d: up = %lld, dec = %lld: factors of at least 1", what, i, (long long)u, (long long)d);
+        if (r[kRsPadLeft] < 0 || r[kRsPadRight] < 0 || r[kRsPadLeft] > INT32_MAX || r[kRsPadRight] > INT32_MAX ||
+            (u == 1 && (r[kRsPadLeft] || r[kRsPadRight])))
+            return fail("%s: trace %d: pads of %lld + %lld samples with up = %lld (pads go with an upsampling, >= 0)",
+                        what, i, (long long)r[kRsPadLeft], (long long)r[kRsPadRight], (long long)u);
+        const int64_t padded = r[kRsPadLeft] + (n_raw - 1) * u + 1 + r[kRsPadRight];
+        if (n_raw > INT32_MAX || padded > INT32_MAX || n_up > INT32_MAX)     // (the kernel counts them in int)
+            return fail("%s: trace %d: too many samples", what, i);
+        if (r[kRsUpFirst] < 0 || n_up < 1 || r[kRsUpFirst] + n_up > padded)
+            return fail("%s: trace %d: the kept slice [%lld, %lld) leaves the padded series of %lld samples", what, i,
+                        (long long)r[kRsUpFirst], (long long)(r[kRsUpFirst] + n_up), (long long)padded);
+        if (r[kRsOutFirst] < 0 || r[kRsOutFirst] + t_samples > (n_up + d - 1) / d)
+            return fail("%s: trace %d: output samples [%lld, %lld) of %lld decimated ones (n_up = %lld, dec = %lld)",
+                        what, i, (long long)r[kRsOutFirst], (long long)(r[kRsOutFirst] + t_samples),
+                        (long long)((n_up + d - 1) / d), (long long)n_up, (long long)d);
+        if (d > 1) {
+            if (r[kRsLowpass] < 0 || r[kRsLowpass] >= n_lowpass)
+                return fail("%s: trace %d: low-pass %lld out of range (%d low-passes)", what, i, (long long)r[kRsLowpass],
+                            n_lowpass);
+            if (r[kRsTaper] < 0 || r[kRsTaper] >= n_tapers)
+                return fail("%s: trace %d: taper %lld out of range (%d tapers)", what, i, (long long)r[kRsTaper], n_tapers);
+            const int64_t m = taper_table[2 * r[kRsTaper] + 1];
+            if (2 * m > n_up)
+                return fail("%s: trace %d: its taper's ramps cover 2 x %lld samples, the kept series holds %lld", what, i,
+                            (long long)m, (long long)n_up);
+        }
+        kept = std::max(kept, n_up);
+    }
+    *max_kept = kept;
+    return 0;
+}
+
+int launch_resample_stage(qm_engine *e, const qm::ResampleArgs &a, int64_t n_traces, int64_t max_kept) {
+    // one workgroup per trace; LDS for the longest kept series that fits (longer ones live in their scratch rows)
+    const size_t lds = (size_t)std::min<int64_t>(max_kept, qm::kPreprocLdsSamples) * sizeof(double);
+    QM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&qm::resample_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(qm::resample_kernel, dim3((unsigned)n_traces), dim3(256), lds, e->stream, a);
+    QM_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+
+int qm_engine_resample(qm_engine *e, const void *raw, int raw_dtype, int raw_on_device, int64_t total_raw_samples,
+                       int32_t n_traces, const int64_t *records, const double *sos_lp, int32_t n_lowpass,
+                       int32_t n_sections_lp, int detrend, const int32_t *taper_table, int32_t n_tapers,
+                       const double *taper_weights, int64_t n_taper_weights, int32_t t_samples, double *out,
+                       int out_on_device) {
+    const char *what = "qm_engine_resample";
+    if (!e || !raw || !out) return fail("%s: NULL argument", what);
+    int64_t max_kept = 0;
+    if (check_resample(what, raw_dtype, total_raw_samples, n_traces, t_samples, records, sos_lp, n_lowpass,
+                       n_sections_lp, taper_table, n_tapers, taper_weights, n_taper_weights, &max_kept))
+        return 1;
+    DeviceGuard guard(e->device);
+    const size_t n_rec = (size_t)n_traces * qm::kResampleFields, n_meta = n_rec + 2 * (size_t)n_tapers;
+    const size_t n_coef = (size_t)n_lowpass * n_sections_lp * 6, n_w = n_coef + (size_t)n_taper_weights;
+    const size_t sig = (size_t)n_traces * t_samples;
+    const bool spill = max_kept > qm::kPreprocLdsSamples;
+    if (e->d_rs_meta.ensure(n_meta) || e->d_rs_coef.ensure(std::max<size_t>(n_w, 1))) return 1;
+    if (spill && e->d_rs_scratch.ensure((size_t)n_traces * max_kept)) return 1;
+    std::vector<int64_t> meta(records, records + n_rec);
+    meta.insert(meta.end(), taper_table, taper_table + 2 * (size_t)n_tapers);
+    std::vector<double> w(sos_lp, sos_lp + n_coef);
+    w.insert(w.end(), taper_weights, taper_weights + n_taper_weights);
+    QM_HIP(copy_in(e->d_rs_meta.p, meta.data(), n_meta * sizeof(int64_t), e->stream));
+    if (n_w) QM_HIP(copy_in(e->d_rs_coef.p, w.data(), n_w * sizeof(double), e->stream));
+    const void *d_raw = raw;
+    if (!raw_on_device) {
+        const size_t bytes = (size_t)total_raw_samples * (raw_dtype == qm::kRawInt32 ? 4 : 8);
+        if (e->d_rs_raw.ensure((bytes + 7) / 8)) return 1;
+        QM_HIP(copy_in(e->d_rs_raw.p, raw, bytes, e->stream));
+        d_raw = e->d_rs_raw.p;
+    }
+    double *d_out = out;
+    if (!out_on_device) {
+        if (e->d_pre_out.ensure(sig)) return 1;
+        d_out = e->d_pre_out.p;
+    }
+    qm::ResampleArgs a{};
+    a.raw = d_raw;
+    a.rec = e->d_rs_meta.p;
+    a.tapers = e->d_rs_meta.p + n_rec;
+    a.sos = e->d_rs_coef.p;
+    a.taper_w = e->d_rs_coef.p + n_coef;
+    a.out = d_out;
+    a.scratch = spill ? e->d_rs_scratch.p : nullptr;
+    a.scratch_stride = spill ? max_kept : 0;
+    a.T = t_samples; a.n_sections = n_sections_lp; a.raw_dtype = raw_dtype;
+    a.detrend = detrend ? 1 : 0; a.skew = e->cfg_preproc_skew;
+    QM_HIP(hipEventRecord(e->ev0, e->stream));
+    if (launch_resample_stage(e, a, n_traces, max_kept)) return 1;
+    QM_HIP(hipEventRecord(e->ev1, e->stream));
+    e->timed = true;
+    if (!out_on_device) {
+        QM_HIP(copy_back(out, d_out, sig * sizeof(double), e->stream));
+        QM_HIP(hipStreamSynchronize(e->stream));
+    }
+    return 0;
+}
+
+}  // extern "C"

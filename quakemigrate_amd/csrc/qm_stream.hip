@@ -19,6 +19,11 @@
 //   engine's stream : pull or copy as above, then the pre-processing kernel (detrend, taper, zero-phase band-pass;
 //                     qm_preproc.hpp) over the slot's (step, trace)s, the two onset kernels over its (step, trace)s and
 //                     (step, row)s -- their output IS the slot's device log-onsets -- and the fused detect as above
+//   -- or, with a resampling stage on top of that (qm_stream_set_resample_stage), the RAW traces cross the bus, each
+//   at its own rate and length, int32 as miniSEED holds them or float64:
+//   caller's thread : qm_stream_push_raw   CPU copy of a step's packed raw samples, pinned
+//   engine's stream : pull or copy as above, then the resampling kernel (qm_resample.hpp) over the slot's
+//                     (step, trace)s -- its output IS the slot's device signals -- and the sequence above
 //   caller's thread : qm_stream_pop    waits for the launch's event, CPU copy of a step's three series
 //
 // Round 4 drove a pipeline like this from Python (three D2H copies, three events and NumPy staging per
@@ -44,6 +49,9 @@ struct qm_stream {
         double *d_on = nullptr;         // device, the same
         double *h_sig = nullptr;        // onset stage: pinned [K][n_traces][T] component traces
         double *d_sig = nullptr;        // ... device, the same; filtered in place
+        double *h_raw = nullptr;        // resampling stage: pinned [K][raw_step] packed raw samples (h_sig is given up
+                                        // at the first raw step)
+        double *d_raw = nullptr;        // ... device, the same
         double *h_out = nullptr;        // pinned [3][K * ns]: max_coa, max_norm_coa, indices (int64 bits) --
                                         // written by the kernels themselves
         hipEvent_t copied = nullptr;    // the inputs are on the device
@@ -61,7 +69,7 @@ struct qm_stream {
     // Onset stage (qm_stream_set_onset_stage): the slot's log-onsets are made on the device from pushed signals.
     // Everything the kernels read is on the device from set-up on, replicated over the K steps of a launch:
     // (step, trace) is the kernels' trace, (step, row) their row.
-    enum Feed { kNothingYet = 0, kLogOnsets = 1, kSignals = 2 };
+    enum Feed { kNothingYet = 0, kLogOnsets = 1, kSignals = 2, kRaw = 3 };
     int feed = kNothingYet;             // what the pushes carry: one kind per stream
     bool staged = false;
     int n_traces = 0;
@@ -70,6 +78,15 @@ struct qm_stream {
     double *d_coef = nullptr;           // sos, taper_left, taper_right
     double *d_sta = nullptr, *d_lta = nullptr;  // [K][n_traces][T] scratch of the onset kernels
     int32_t *d_meta = nullptr;          // trace_filter [K][n_traces], trace_row the same, nsta [K][n_rows], nlta
+    // Resampling stage (qm_stream_set_resample_stage): the slot's signals are made on the device from pushed raw
+    // samples.  The records stand K times on the device, step k's raw offsets k raw steps further on.
+    bool resampled = false;
+    qm::ResampleArgs rs{};              // raw / out: per slot
+    int64_t rs_max_kept = 0;
+    size_t raw_bytes = 0, raw_step = 0; // a timestep's raw bytes as pushed; in doubles as the slot holds it (rounded up)
+    int64_t *d_rs_meta = nullptr;       // records [K][n_traces][kResampleFields], taper table
+    double *d_rs_coef = nullptr;        // low-pass sections, taper weights
+    double *d_rs_scratch = nullptr;     // [K][n_traces][rs_max_kept] where a kept series is above the LDS limit
     // A stream over replicas (qm_stream_create_replicas) holds no slots of its own: one ordinary stream per
     // engine (a LANE, registered on that engine like any other stream) and the launches in push order.  Launch j
     // goes to lane j mod n; the entry points dispatch to the replicas_* functions below.
@@ -118,6 +135,8 @@ void free_slot(qm_stream::Slot &sl) {
     if (sl.h_on) (void)hipHostFree(sl.h_on);
     if (sl.h_out) (void)hipHostFree(sl.h_out);
     if (sl.h_sig) (void)hipHostFree(sl.h_sig);
+    if (sl.h_raw) (void)hipHostFree(sl.h_raw);
+    if (sl.d_raw) pool_free(sl.d_raw);
     if (sl.d_on) pool_free(sl.d_on);
     if (sl.d_sig) pool_free(sl.d_sig);
     for (hipEvent_t ev : {sl.copied, sl.done})
@@ -155,8 +174,12 @@ void release_stream(qm_stream *s) {
         if (s->d_sta) pool_free(s->d_sta);
         if (s->d_lta) pool_free(s->d_lta);
         if (s->d_meta) pool_free(s->d_meta);
-        s->d_coef = s->d_sta = s->d_lta = nullptr;
+        if (s->d_rs_meta) pool_free(s->d_rs_meta);
+        if (s->d_rs_coef) pool_free(s->d_rs_coef);
+        if (s->d_rs_scratch) pool_free(s->d_rs_scratch);
+        s->d_coef = s->d_sta = s->d_lta = s->d_rs_coef = s->d_rs_scratch = nullptr;
         s->d_meta = nullptr;
+        s->d_rs_meta = nullptr;
     }
     if (s->copy_stream) park_stream(s->e->device, s->copy_stream);
     s->copy_stream = nullptr;
@@ -176,10 +199,11 @@ int launch_slot(qm_stream *s) {
                     (unsigned long long)(e->have_lut ? e->serial : 0), e->have_lut ? e->g.n_rows : 0,
                     (unsigned long long)s->table_serial, s->n_rows);
     const size_t kns = (size_t)s->K * s->ns;
-    const bool signals = s->feed == qm_stream::kSignals;
-    const size_t words = (size_t)n * (signals ? step_sig(s) : step_in(s));
-    const double *h_in = signals ? sl.h_sig : sl.h_on;
-    double *d_in = signals ? sl.d_sig : sl.d_on;
+    const bool raw = s->feed == qm_stream::kRaw;
+    const bool signals = raw || s->feed == qm_stream::kSignals;
+    const size_t words = (size_t)n * (raw ? s->raw_step : signals ? step_sig(s) : step_in(s));
+    const double *h_in = raw ? sl.h_raw : signals ? sl.h_sig : sl.h_on;
+    double *d_in = raw ? sl.d_raw : signals ? sl.d_sig : sl.d_on;
     const bool pull = e->cfg_stream_pull > 0 || (e->cfg_stream_pull < 0 && words * sizeof(double) <= kPullBytes);
     // ("stream_stamps" = 1, measurement: the GPU's clock before and behind every launch -- two one-thread kernels;
     // the digest goes to stderr when the stream is destroyed.  What found round 6's one-off stall: tools/diag_stream.py)
@@ -205,6 +229,14 @@ int launch_slot(qm_stream *s) {
         QM_HIP(hipStreamWaitEvent(e->stream, sl.copied, 0));
     }
     s->pulled = pull;
+    if (raw) {
+        // raw samples -> the n steps' traces at the scan rate, straight into the slot's d_sig
+        qm::ResampleArgs r = s->rs;
+        r.raw = sl.d_raw;
+        r.out = sl.d_sig;
+        r.skew = e->cfg_preproc_skew;
+        if (launch_resample_stage(e, r, (int64_t)n * s->n_traces, s->rs_max_kept)) return 1;
+    }
     if (signals) {
         // waveforms -> log-onsets, all on the engine's stream: the n steps' traces filtered in place, then the onset
         // kernels with (step, trace) as their trace and (step, row) as their row, straight into the slot's d_on
@@ -246,6 +278,23 @@ int launch_slot(qm_stream *s) {
 // Launches go round the lanes in push order, so a lane's next slot is in flight only when all n x depth launches
 // are un-popped -- and then the oldest launch is on that lane: "pop the oldest launch, push again" still frees it.
 
+// a resampling stage that did not come about, on this stream or on a later lane: its buffers go back and the stream
+// is what it was before, an onset stage with signals going in (the engine's device is current)
+void resample_stage_undo(qm_stream *s) {
+    PoolReleaseScope one_wait;
+    for (qm_stream::Slot &sl : s->slots) {
+        if (sl.h_raw) (void)hipHostFree(sl.h_raw);
+        if (sl.d_raw) pool_free(sl.d_raw);
+        sl.h_raw = sl.d_raw = nullptr;
+    }
+    if (s->d_rs_meta) pool_free(s->d_rs_meta);
+    if (s->d_rs_coef) pool_free(s->d_rs_coef);
+    if (s->d_rs_scratch) pool_free(s->d_rs_scratch);
+    s->d_rs_meta = nullptr;
+    s->d_rs_coef = s->d_rs_scratch = nullptr;
+    s->resampled = false;
+}
+
 int replicas_alive(const qm_stream *s, const char *what) {
     for (const qm_stream *lane : s->lanes)
         if (alive(lane, what)) return 1;
@@ -267,14 +316,16 @@ int replicas_flush(qm_stream *s) {
     return 0;
 }
 
-int replicas_push(qm_stream *s, const double *step, bool signals) {
-    if (replicas_alive(s, signals ? "qm_stream_push_signals" : "qm_stream_push")) return 1;
+int replicas_push(qm_stream *s, const void *step, int feed, const char *what) {
+    if (replicas_alive(s, what)) return 1;
     // (a full slot whose launch failed -- the table changed under the stream -- goes out first, as on one engine;
     // then this timestep goes to the next lane, not behind it on the same one)
     if (s->lanes[s->cur]->fill_n >= s->lanes[s->cur]->K && replicas_flush(s)) return 1;
     qm_stream *lane = s->lanes[s->cur];
     const int64_t before = lane->launched_steps;
-    const int rc = signals ? qm_stream_push_signals(lane, step) : qm_stream_push(lane, step);
+    const int rc = feed == qm_stream::kRaw ? qm_stream_push_raw(lane, step)
+                   : feed == qm_stream::kSignals ? qm_stream_push_signals(lane, static_cast<const double *>(step))
+                                                 : qm_stream_push(lane, static_cast<const double *>(step));
     if (lane->launched_steps != before) replicas_launched(s, lane->launched_steps - before);
     return rc;
 }
@@ -414,18 +465,26 @@ void qm_stream_destroy(qm_stream *s) {
     delete s;
 }
 
-// a timestep into the slot being filled: log-onsets, or (an onset stage) signals -- one kind per stream
-static int push_step(qm_stream *s, const double *step, int feed, const char *what) {
+// a timestep into the slot being filled: log-onsets, (an onset stage) signals or (a resampling stage as well) raw
+// samples -- one kind per stream
+static int push_step(qm_stream *s, const void *step, int feed, const char *what) {
     if (!step || !s) return fail("%s: NULL argument", what);
     const bool replicated = !s->lanes.empty();          // (the kind of input is the whole stream's, not a lane's)
     if (!replicated && alive(s, what)) return 1;
     if (feed == qm_stream::kSignals && !s->staged)
         return fail("qm_stream_push_signals: the stream has no onset stage (qm_stream_set_onset_stage)");
+    if (feed == qm_stream::kRaw && !s->resampled)
+        return fail("qm_stream_push_raw: the stream has no resampling stage (qm_stream_set_resample_stage)");
+    if (feed == qm_stream::kSignals && s->resampled)
+        return fail("qm_stream_push_signals: this stream takes raw traces (qm_stream_push_raw): one stream, one kind of "
+                    "input");
     if (s->feed != qm_stream::kNothingYet && s->feed != feed)
         return fail("%s: this stream takes %s: one stream, one kind of input", what,
-                    s->feed == qm_stream::kSignals ? "signals (qm_stream_push_signals)" : "log-onsets (qm_stream_push)");
+                    s->feed == qm_stream::kRaw       ? "raw traces (qm_stream_push_raw)"
+                    : s->feed == qm_stream::kSignals ? "signals (qm_stream_push_signals)"
+                                                     : "log-onsets (qm_stream_push)");
     if (replicated) {
-        const int rc = replicas_push(s, step, feed == qm_stream::kSignals);
+        const int rc = replicas_push(s, step, feed, what);
         if (rc == 0) s->feed = feed;
         return rc;
     }
@@ -442,7 +501,14 @@ static int push_step(qm_stream *s, const double *step, int feed, const char *wha
     }
     s->feed = feed;
     // (the slot's previous H2D has finished: its launch's results were popped)
-    if (feed == qm_stream::kSignals)
+    if (feed == qm_stream::kRaw && sl.h_sig)            // the first raw step: the ring's pinned slots hold raw bytes
+        for (qm_stream::Slot &other : s->slots) {       // from here on, the signals' pinned buffers are given up
+            (void)hipHostFree(other.h_sig);
+            other.h_sig = nullptr;
+        }
+    if (feed == qm_stream::kRaw)
+        host_copy(sl.h_raw + (size_t)s->fill_n * s->raw_step, step, s->raw_bytes);
+    else if (feed == qm_stream::kSignals)
         host_copy(sl.h_sig + (size_t)s->fill_n * step_sig(s), step, step_sig(s) * sizeof(double));
     else
         host_copy(sl.h_on + (size_t)s->fill_n * step_in(s), step, step_in(s) * sizeof(double));
@@ -456,6 +522,103 @@ int qm_stream_push(qm_stream *s, const double *log_onsets) {
 
 int qm_stream_push_signals(qm_stream *s, const double *signals) {
     return push_step(s, signals, qm_stream::kSignals, "qm_stream_push_signals");
+}
+
+int qm_stream_push_raw(qm_stream *s, const void *raw) {
+    return push_step(s, raw, qm_stream::kRaw, "qm_stream_push_raw");
+}
+
+int qm_stream_set_resample_stage(qm_stream *s, int32_t n_traces, const int64_t *records, const double *sos_lp,
+                                 int32_t n_lowpass, int32_t n_sections_lp, int detrend, const int32_t *taper_table,
+                                 int32_t n_tapers, const double *taper_weights, int64_t n_taper_weights,
+                                 int32_t t_samples, int raw_dtype, int64_t total_raw_samples) {
+    const char *what = "qm_stream_set_resample_stage";
+    if (!s || !records) return fail("%s: NULL argument", what);
+    if (!s->staged) return fail("%s: the stream has no onset stage (qm_stream_set_onset_stage comes first)", what);
+    if (s->resampled) return fail("%s: the stream has its resampling stage already (it is set once)", what);
+    if (s->feed != qm_stream::kNothingYet || s->fill_n > 0 || s->launched_steps > 0)
+        return fail("%s: the stage is set before the first push", what);
+    if (!s->lanes.empty()) {
+        for (qm_stream *lane : s->lanes)
+            if (qm_stream_set_resample_stage(lane, n_traces, records, sos_lp, n_lowpass, n_sections_lp, detrend,
+                                             taper_table, n_tapers, taper_weights, n_taper_weights, t_samples,
+                                             raw_dtype, total_raw_samples)) {
+                // all lanes or none: the lanes before this one give the stage back (the error text stays)
+                for (qm_stream *before : s->lanes) {
+                    if (before == lane) break;
+                    DeviceGuard guard(before->e->device);
+                    resample_stage_undo(before);
+                }
+                return 1;
+            }
+        s->resampled = true;
+        return 0;
+    }
+    if (alive(s, what)) return 1;
+    if (t_samples != s->T || n_traces != s->n_traces)
+        return fail("%s: %d traces of %d samples, the onset stage takes %d of %d", what, n_traces, t_samples,
+                    s->n_traces, s->T);
+    int64_t max_kept = 0;
+    if (check_resample(what, raw_dtype, total_raw_samples, n_traces, t_samples, records, sos_lp, n_lowpass,
+                       n_sections_lp, taper_table, n_tapers, taper_weights, n_taper_weights, &max_kept))
+        return 1;
+    const int K = s->K;
+    const size_t width = raw_dtype == qm::kRawInt32 ? 4 : 8;
+    const size_t raw_bytes = (size_t)total_raw_samples * width, raw_step = (raw_bytes + 7) / 8;
+    if ((double)K * (double)raw_step * 8.0 >= 0x1p40) return fail("%s: too many raw samples per launch", what);
+    qm_engine *e = s->e;
+    DeviceGuard guard(e->device);
+    // host images: the records K times, step k reading k raw steps further on
+    const size_t n_rec = (size_t)n_traces * qm::kResampleFields;
+    std::vector<int64_t> meta;
+    for (int k = 0; k < K; ++k) {
+        meta.insert(meta.end(), records, records + n_rec);
+        for (int i = 0; i < n_traces; ++i)
+            meta[((size_t)k * n_traces + i) * qm::kResampleFields + qm::kRsRawOffset] +=
+                (int64_t)k * (int64_t)(raw_step * 8 / width);
+    }
+    const size_t n_rec_all = meta.size();
+    meta.insert(meta.end(), taper_table, taper_table + 2 * (size_t)n_tapers);
+    const size_t n_coef = (size_t)n_lowpass * n_sections_lp * 6;
+    std::vector<double> coef(sos_lp, sos_lp + n_coef);
+    coef.insert(coef.end(), taper_weights, taper_weights + n_taper_weights);
+    coef.push_back(0.0);                                // (never empty)
+    const bool spill = max_kept > qm::kPreprocLdsSamples;
+    const size_t slot_bytes = (size_t)K * raw_step * sizeof(double);
+    hipError_t r = pool_alloc(reinterpret_cast<void **>(&s->d_rs_meta), meta.size() * sizeof(int64_t));
+    if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&s->d_rs_coef), coef.size() * sizeof(double));
+    if (r == hipSuccess && spill)
+        r = pool_alloc(reinterpret_cast<void **>(&s->d_rs_scratch), (size_t)K * n_traces * max_kept * sizeof(double));
+    for (qm_stream::Slot &sl : s->slots) {
+        if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&sl.h_raw), slot_bytes, hipHostMallocDefault);
+        if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&sl.d_raw), slot_bytes);
+        if (r == hipSuccess) std::memset(sl.h_raw, 0, slot_bytes);     // (the bytes a step's int32s leave over)
+    }
+    if (r != hipSuccess) {                              // the stream stays as it was: an onset stage, signals in
+        resample_stage_undo(s);
+        return fail("%s: %s (%d steps of %zu bytes per slot, %d slots)", what, hipGetErrorString(r), K, raw_bytes,
+                    s->depth);
+    }
+    if (copy_in(s->d_rs_meta, meta.data(), meta.size() * sizeof(int64_t), e->stream) != hipSuccess ||
+        copy_in(s->d_rs_coef, coef.data(), coef.size() * sizeof(double), e->stream) != hipSuccess) {
+        resample_stage_undo(s);
+        return fail("%s: the copy of the stage's arrays to the device failed", what);
+    }
+    // (the signals' pinned buffers are given up at the first qm_stream_push_raw: until then nothing is lost)
+    s->raw_bytes = raw_bytes;
+    s->raw_step = raw_step;
+    s->rs_max_kept = max_kept;
+    s->rs = qm::ResampleArgs{};
+    s->rs.rec = s->d_rs_meta;
+    s->rs.tapers = s->d_rs_meta + n_rec_all;
+    s->rs.sos = s->d_rs_coef;
+    s->rs.taper_w = s->d_rs_coef + n_coef;
+    s->rs.scratch = s->d_rs_scratch;
+    s->rs.scratch_stride = spill ? max_kept : 0;
+    s->rs.T = s->T; s->rs.n_sections = n_sections_lp; s->rs.raw_dtype = raw_dtype;
+    s->rs.detrend = detrend ? 1 : 0;
+    s->resampled = true;
+    return 0;
 }
 
 int qm_stream_set_onset_stage(qm_stream *s, int32_t n_traces, const int32_t *trace_row, const int32_t *trace_filter,

@@ -308,8 +308,10 @@ class MigrationScan:
         availability order, (n_traces, T) float64; the stage (``quakemigrate_amd.preprocess.OnsetStage``) names
         their filters, windows and row layout.  The device stage covers gap-free traces of the full timespan only
         (the reference's default, ``full_timespan=True, allow_gaps=False``): gappy traces (their second taper and
-        tiny-float padding, stalta.py:442-461), resampling and the ``env`` transforms stay on the host plugin
-        path -- ``device_stage`` returns ``None`` for a timestep it cannot describe and ``calculate_onsets`` is
+        tiny-float padding, stalta.py:442-461), the ``env`` transforms and -- in this loop -- resampling (the
+        device's resampling stage, ``StreamingDetector(resample_stage=...)``, takes a plan of the timestep's raw
+        traces; which ones a timestep has, and at what times, is the plugin's ``Stream`` bookkeeping) stay on the host
+        plugin path -- ``device_stage`` returns ``None`` for a timestep it cannot describe and ``calculate_onsets`` is
         called for it.  The new path is used on an ``Engine`` or ``EngineReplicas`` only; a group, and a plugin
         without ``device_stage``, run as before.  A changed stage (other windows, filters or layout) makes a new
         pipeline, as a changed table does.

@@ -49,10 +49,17 @@ class StreamingDetector:
         launch is then pre-processing (detrend, taper, zero-phase band-pass) -> onsets -> fused detect, every
         timestep's bits those of ``Engine.detect(Engine.onsets(Engine.preprocess(x)))``.  A stream takes one kind
         of window, never both.
+    resample_stage : ``None``, or -- on top of an onset stage -- the plan that makes those component traces on the
+        device from a timestep's RAW traces, each at its own rate and length (``push_raw``): a
+        :class:`quakemigrate_amd.preprocess.ResampleStage` or the dict its ``arrays(t_samples)`` returns;
+        ``raw_dtype``: what the raw samples are, int32 (as miniSEED holds them) or float64.  A slot's launch then
+        starts with the resampling kernel, every timestep's bits those of ``Engine.resample`` in front of the calls
+        above.
     """
 
     def __init__(self, engine, n_rows, t_samples, fsmp, lsmp, available, n_nodes_total=None,
-                 depth=2, device=None, steps_per_launch=1, onset_stage=None, sampling_rate=None):
+                 depth=2, device=None, steps_per_launch=1, onset_stage=None, sampling_rate=None,
+                 resample_stage=None, raw_dtype=np.int32):
         if engine.n_rows is None:
             raise _lib.QMHipError("no travel-time table resident: call load_lut first")
         if int(n_rows) != engine.n_rows:
@@ -79,8 +86,11 @@ class StreamingDetector:
 
         self._finalizer = weakref.finalize(self, _qm.qm_stream_destroy, h)
         self.n_traces = None
+        self.raw_dtype = self._raw_records = self.total_raw_samples = None
         if onset_stage is not None:
             self.set_onset_stage(onset_stage, sampling_rate)
+        if resample_stage is not None:
+            self.set_resample_stage(resample_stage, raw_dtype)
 
     def set_onset_stage(self, onset_stage, sampling_rate=None):
         """Once, before the first push (``qm_stream_set_onset_stage``)."""
@@ -106,6 +116,17 @@ class StreamingDetector:
             int(a.get("detrend", 1)), left, len(left), right, len(right), nsta, nlta, int(a["transform"]),
             int(a["position"]), int(a["taper_pad"]), float(a["min_onset_value"])))
         self.n_traces = len(trace_row)
+
+    def set_resample_stage(self, resample_stage, raw_dtype=np.int32):
+        """Once, after the onset stage and before the first push (``qm_stream_set_resample_stage``)."""
+        kind = np.dtype(raw_dtype)
+        if kind not in _lib.RAW_DTYPES:
+            raise TypeError(f"raw samples of type {kind}: int32 or float64")
+        records, sos, table, weights, detrend, t_samples, total = _lib.resample_arrays(resample_stage, self.t_samples)
+        _lib._check(_qm.qm_stream_set_resample_stage(
+            self._h, len(records), records.reshape(-1), sos.reshape(-1), int(sos.shape[0]), int(sos.shape[1]), detrend,
+            table.reshape(-1), len(table), weights, len(weights), t_samples, _lib.RAW_DTYPES[kind], total))
+        self.raw_dtype, self._raw_records, self.total_raw_samples = kind, records, total
 
     def close(self):
         self._finalizer()
@@ -135,6 +156,19 @@ class StreamingDetector:
         _lib._check(rc)
         return True
 
+    def push_raw(self, raw):
+        """One timestep's raw traces -- a list of 1-D arrays, one per trace, or the packed array, of the stage's
+        ``raw_dtype`` -- into a pipeline with a resampling stage; returns like :meth:`push`."""
+        if self._raw_records is None:                   # (the library's own refusal, before any list is packed)
+            raise _lib.QMHipError("qm_stream_push_raw: the stream has no resampling stage "
+                                  "(qm_stream_set_resample_stage)")
+        w = _lib.pack_raw(raw, self._raw_records, self.total_raw_samples, self.raw_dtype)
+        rc = _qm.qm_stream_push_raw(self._h, w.ctypes.data_as(ctypes.c_void_p))
+        if rc == 2:
+            return False
+        _lib._check(rc)
+        return True
+
     def flush(self):
         _lib._check(_qm.qm_stream_flush(self._h))
 
@@ -158,7 +192,8 @@ class StreamingDetector:
     def run(self, windows, on_result=None):
         """
         ``windows``: iterable of float64 arrays, one per timestep: (n_rows, t_samples), already logged --
-        or, on a stream with an onset stage, (n_traces, t_samples) resampled component traces.  Returns a list of ``(max_coa, max_norm_coa, max_coa_idx)`` NumPy triples (or
+        or, on a stream with an onset stage, (n_traces, t_samples) resampled component traces -- or, with a
+        resampling stage as well, the timestep's raw traces as :meth:`push_raw` takes them.  Returns a list of ``(max_coa, max_norm_coa, max_coa_idx)`` NumPy triples (or
         calls ``on_result(step, triple)`` and returns the number of steps).
         """
         results = []
@@ -176,6 +211,8 @@ class StreamingDetector:
                 step += 1
 
         push = self.push if self.n_traces is None else self.push_signals
+        if self._raw_records is not None:
+            push = self.push_raw
         for w in windows:
             while not push(w):
                 take(min(self.k, self.pending()[0]))     # the oldest launch's timesteps
