@@ -768,13 +768,12 @@ void qm_engine_destroy(qm_engine *e) {
     e->release_all();
     for (TableSlot &slot : e->slots) slot.state.release_all();
     e->d_grids.release(); e->d_rows.release(); e->d_served.release();
-    e->d_sig.release(); e->d_sta.release(); e->d_lta.release(); e->d_raw.release();
-    e->d_pre_coef.release(); e->d_pre_out.release(); e->d_pre_meta.release();
-    e->d_rs_meta.release(); e->d_rs_coef.release(); e->d_rs_raw.release(); e->d_rs_scratch.release();
+    e->rs_stage.release(); e->pre_stage.release(); e->on_stage.release();
+    e->d_sig.release(); e->d_raw.release(); e->d_pre_out.release(); e->d_rs_raw.release();
     e->d_pick_val.release(); e->d_pick_meta.release();
     e->d_trg_x.release(); e->d_trg_par.release(); e->d_trg_val.release(); e->d_trg_cnt.release();
     e->d_trg_run.release(); e->d_trg_tot.release(); e->d_trg_cand.release();
-    e->d_onset_meta.release(); e->d_scalar.release(); e->d_digest.release();
+    e->d_scalar.release(); e->d_digest.release();
     e->d_onsets.release(); e->d_pmax.release(); e->d_psum.release(); e->d_out_a.release();
     e->d_chunk.release(); e->d_marg.release(); e->d_marg_out.release(); e->d_pidx.release();
     e->d_fit_a.release(); e->d_fit_b.release(); e->d_fit_c.release(); e->d_fit_part.release();

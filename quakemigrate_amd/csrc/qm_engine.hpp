@@ -10,9 +10,13 @@
 //   qm_screen.hip    the opt-in screened detect's launch sequence
 //   qm_stream.hip    the continuous detect pipeline (pinned ring, copies overlapped with compute), also over
 //                    several engines that hold the same table (replicas: launches round-robin)
-//   qm_widen.hip     the rows next to the path: onset stage, locate fits, RBF peak
+//   qm_widen.hip     the rows next to the path: onset stage (OnsetStage), locate fits, RBF peak
 //   qm_preproc.hip   the row before the onset stage: detrend, taper, zero-phase band-pass of the component traces
-//   qm_resample.hip  the row before that: raw traces, each at its own rate and length, upsampled and decimated to the scan rate
+//                    (PreprocStage)
+//   qm_resample.hip  the row before that: raw traces, each at its own rate and length, upsampled and decimated to the
+//                    scan rate (ResampleStage)
+//                    -- each of the three: the stage's record below (checks, device arrays, launch), shared by the
+//                    engine's staged call, which lives beside it, and the pipeline
 //   qm_picks.hip     the row after the location: phase picks, a Gaussian fitted to every onset row of an event
 //   qm_trigger.hip   the row after the detect sweep: coalescence series in, triggered events out
 //   qm_compat.hip    the five reference-signature symbols (qmlib.h:28-44)
@@ -229,6 +233,56 @@ struct TableSlot {
     bool used = false;
 };
 
+// The stages in front of the fused detect -- resampling, pre-processing, onsets -- one record each.  A record is the
+// stage's small arrays on the device, `repeat` times over (a stream's launch holds that many timesteps: (step, trace)
+// is the kernels' trace, (step, row) their row), and the kernel's arguments as far as they do not change from launch
+// to launch.  An engine holds one of each for its staged calls (repeat = 1), a qm_stream its own (repeat = its steps
+// per launch): neither sees the other's.
+//   build    checks the caller's host arrays, makes their images, grows the buffers, copies in on e->stream (the
+//            images are consumed when it returns) and fills `args`.  It may be called again, after a failure as well.
+//   launch   n_steps timesteps of `in` to `out` on e->stream: enqueue only
+// Each is defined where its kernel is compiled: qm_preproc.hip, qm_widen.hip, qm_resample.hip.
+struct PreprocStage {
+    DevBuf<double> coef;                // sos, taper_left, taper_right
+    DevBuf<int32_t> meta;               // trace_filter [repeat][n_traces]
+    qm::PreprocArgs args{};
+    int n_traces = 0;                   // of one timestep
+    int build(qm_engine *e, const char *what, int repeat, int32_t n_traces, int32_t t_samples,
+              const int32_t *trace_filter, const double *sos, int32_t n_filters, int32_t n_sections, int detrend,
+              const double *taper_left, int32_t n_left, const double *taper_right, int32_t n_right, int zero_phase);
+    int launch(qm_engine *e, const double *in, double *out, int n_steps) const;
+    void release() { coef.release(); meta.release(); }
+};
+struct OnsetStage {
+    DevBuf<int32_t> meta;               // trace_row [repeat][n_traces] (step k's rows k * n_rows on), nsta, nlta [repeat][n_rows]
+    DevBuf<double> sta, lta;            // [repeat][n_traces][T] scratch of the two kernels
+    qm::OnsetArgs args{};
+    int n_traces = 0, n_rows = 0;       // of one timestep
+    int build(qm_engine *e, const char *what, int repeat, int32_t n_traces, int32_t t_samples, const int32_t *trace_row,
+              int32_t n_rows, const int32_t *nsta, const int32_t *nlta, int transform, int position, int32_t taper_pad,
+              double min_onset_value);
+    // raw_onsets: [n_steps][n_rows][T] or nullptr
+    int launch(qm_engine *e, const double *signals, double *raw_onsets, double *log_onsets, int n_steps) const;
+    void release() { meta.release(); sta.release(); lta.release(); }
+};
+struct ResampleStage {
+    DevBuf<int64_t> meta;               // records [repeat][n_traces][kResampleFields] (step k's raw offsets k raw steps on), taper table
+    DevBuf<double> coef, scratch;       // low-pass sections and taper weights; [repeat][n_traces][max_kept] where a
+    qm::ResampleArgs args{};            // ... kept series is above the LDS limit
+    int64_t max_kept = 0;               // the longest kept series
+    int n_traces = 0;                   // of one timestep
+    size_t raw_bytes = 0, raw_step = 0; // a timestep's raw samples in bytes; in doubles (step_doubles): what lies between two steps
+    static size_t step_doubles(int raw_dtype, int64_t total_raw_samples) {
+        return ((size_t)total_raw_samples * (raw_dtype == qm::kRawInt32 ? 4 : 8) + 7) / 8;
+    }
+    int build(qm_engine *e, const char *what, int repeat, int raw_dtype, int64_t total_raw_samples, int32_t n_traces,
+              int32_t t_samples, const int64_t *records, const double *sos_lp, int32_t n_lowpass, int32_t n_sections_lp,
+              int detrend, const int32_t *taper_table, int32_t n_tapers, const double *taper_weights,
+              int64_t n_taper_weights);
+    int launch(qm_engine *e, const void *raw, double *out, int n_steps) const;
+    void release() { meta.release(); coef.release(); scratch.release(); }
+};
+
 struct qm_stream;                    // a continuous-detect pipeline on an engine (qm_stream.hip)
 
 // One stacking launch (StackLaunch below) as plan_stack decides it and issue_stack enqueues it (qm_engine.hip).
@@ -347,16 +401,13 @@ struct qm_engine : TableState {
     DevBuf<int32_t> d_rows, d_served;
     int gx = 0, gy = 0, gz = 0, g_rows = 0;
 
-    // onset stage scratch
-    DevBuf<double> d_sig, d_sta, d_lta, d_raw;
-    DevBuf<int32_t> d_onset_meta;
-    // pre-processing stage scratch: coefficients and taper weights, the traces' filters, the filtered traces
-    DevBuf<double> d_pre_coef, d_pre_out;
-    DevBuf<int32_t> d_pre_meta;
-    // resampling stage scratch: records and taper table, low-pass coefficients and taper weights, the raw samples
-    // (bytes, in doubles), the kept series of traces above the LDS limit; host results go through d_pre_out
-    DevBuf<int64_t> d_rs_meta;
-    DevBuf<double> d_rs_coef, d_rs_raw, d_rs_scratch;
+    // the stages in front of the detect as the staged calls (qm_engine_resample / _preprocess / _onsets) last built
+    // them, and those calls' staging of host data: signals in, raw onsets, filtered or resampled traces out, raw
+    // samples in (bytes, in doubles); the log-onsets go through d_onsets
+    ResampleStage rs_stage;
+    PreprocStage pre_stage;
+    OnsetStage on_stage;
+    DevBuf<double> d_sig, d_raw, d_pre_out, d_rs_raw;
     // phase-pick stage scratch: half-widths, thresholds and picks; windows, groups and status
     DevBuf<double> d_pick_val;
     DevBuf<int32_t> d_pick_meta;
@@ -515,27 +566,6 @@ int fetch_out(qm_engine *e, int n, int out_on_device, const OutSeries &st, const
 // ---- qm_stream.hip ------------------------------------------------------------------------------
 // the engine is going away: its pipelines give their buffers back and refuse further calls
 void streams_orphan(qm_engine *e);
-
-// ---- qm_widen.hip -------------------------------------------------------------------------------
-// the two onset kernels on the engine's stream: enqueue only
-int launch_onset_stage(qm_engine *e, const qm::OnsetArgs &a);
-
-// ---- qm_preproc.hip -----------------------------------------------------------------------------
-// what qm_engine_preprocess and qm_stream_set_onset_stage refuse (host arrays)
-int check_preproc(const char *what, int32_t n_traces, int32_t t_samples, const int32_t *trace_filter,
-                  const double *sos, int32_t n_filters, int32_t n_sections, const double *taper_left, int32_t n_left,
-                  const double *taper_right, int32_t n_right);
-// the pre-processing kernel over n_traces traces on the engine's stream: enqueue only
-int launch_preproc_stage(qm_engine *e, const qm::PreprocArgs &a, int64_t n_traces);
-
-// ---- qm_resample.hip ----------------------------------------------------------------------------
-// what qm_engine_resample and qm_stream_set_resample_stage refuse (host arrays); *max_kept: the longest kept series
-int check_resample(const char *what, int raw_dtype, int64_t total_raw_samples, int32_t n_traces, int32_t t_samples,
-                   const int64_t *records, const double *sos_lp, int32_t n_lowpass, int32_t n_sections_lp,
-                   const int32_t *taper_table, int32_t n_tapers, const double *taper_weights, int64_t n_taper_weights,
-                   int64_t *max_kept);
-// the resampling kernel over n_traces traces on the engine's stream: enqueue only
-int launch_resample_stage(qm_engine *e, const qm::ResampleArgs &a, int64_t n_traces, int64_t max_kept);
 
 // ---- qm_screen.hip ------------------------------------------------------------------------------
 constexpr int kFlagRing = 1024;

@@ -1,8 +1,11 @@
-// qm_preproc.hip -- the pre-processing stage's host side: argument checks, staging, the launch (kernel and its
-// notes: qm_preproc.hpp).  qm_engine_preprocess is the staged call; the pipeline (qm_stream.hip) launches the same
-// kernel over the (step, trace)s of a slot through launch_preproc_stage.
+// qm_preproc.hip -- the pre-processing stage's host side (kernel and its notes: qm_preproc.hpp).  PreprocStage
+// (qm_engine.hpp) is the stage: build checks the caller's arrays and puts them on the device, launch runs the kernel over
+// the (step, trace)s of a launch.  qm_engine_preprocess is the staged call on the engine's record; the pipeline
+// (qm_stream.hip) holds a record of its own.
 #define QM_TU_PREPROC 1
 #include "qm_engine.hpp"
+
+namespace {
 
 int check_preproc(const char *what, int32_t n_traces, int32_t t_samples, const int32_t *trace_filter,
                   const double *sos, int32_t n_filters, int32_t n_sections, const double *taper_left, int32_t n_left,
@@ -26,15 +29,48 @@ int check_preproc(const char *what, int32_t n_traces, int32_t t_samples, const i
     return 0;
 }
 
-int launch_preproc_stage(qm_engine *e, const qm::PreprocArgs &a, int64_t n_traces) {
+}  // namespace
+
+int PreprocStage::build(qm_engine *e, const char *what, int repeat, int32_t n_traces_, int32_t t_samples,
+                        const int32_t *trace_filter, const double *sos, int32_t n_filters, int32_t n_sections,
+                        int detrend, const double *taper_left, int32_t n_left, const double *taper_right,
+                        int32_t n_right, int zero_phase) {
+    if (check_preproc(what, n_traces_, t_samples, trace_filter, sos, n_filters, n_sections, taper_left, n_left,
+                      taper_right, n_right))
+        return 1;
+    const size_t n_coef = (size_t)n_filters * n_sections * 6;
+    std::vector<double> w(sos, sos + n_coef);
+    w.insert(w.end(), taper_left, taper_left + n_left);
+    w.insert(w.end(), taper_right, taper_right + n_right);
+    std::vector<int32_t> filters;
+    for (int k = 0; k < repeat; ++k) filters.insert(filters.end(), trace_filter, trace_filter + n_traces_);
+    if (coef.ensure(w.size()) || meta.ensure(filters.size())) return 1;
+    QM_HIP(copy_in(coef.p, w.data(), w.size() * sizeof(double), e->stream));
+    QM_HIP(copy_in(meta.p, filters.data(), filters.size() * sizeof(int32_t), e->stream));
+    n_traces = n_traces_;
+    args = qm::PreprocArgs{};
+    args.trace_filter = meta.p;
+    args.sos = coef.p;
+    args.taper_left = coef.p + n_coef;
+    args.taper_right = coef.p + n_coef + n_left;
+    args.T = t_samples; args.n_sections = n_sections; args.n_left = n_left; args.n_right = n_right;
+    args.detrend = detrend ? 1 : 0; args.zero_phase = zero_phase ? 1 : 0;
+    return 0;
+}
+
+int PreprocStage::launch(qm_engine *e, const double *in, double *out, int n_steps) const {
+    qm::PreprocArgs a = args;
+    a.in = in;
+    a.out = out;
+    a.skew = e->cfg_preproc_skew;
     // one workgroup per trace; the trace lives in LDS if it fits (20 480 samples), else in its output row
     const size_t lds = (size_t)a.T * sizeof(double);
     const int in_lds = a.T <= qm::kPreprocLdsSamples ? 1 : 0;
     if (in_lds)
         QM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&qm::preproc_kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(qm::preproc_kernel, dim3((unsigned)n_traces), dim3(256), in_lds ? lds : 0, e->stream, a,
-                       in_lds);
+    hipLaunchKernelGGL(qm::preproc_kernel, dim3((unsigned)((int64_t)n_steps * n_traces)), dim3(256), in_lds ? lds : 0,
+                       e->stream, a, in_lds);
     QM_HIP(hipGetLastError());
     return 0;
 }
@@ -47,18 +83,11 @@ int qm_engine_preprocess(qm_engine *e, const double *signals, int signals_on_dev
                          const double *taper_right, int32_t n_right, int zero_phase, double *filtered,
                          int out_on_device) {
     if (!e || !signals || !filtered) return fail("qm_engine_preprocess: NULL argument");
-    if (check_preproc("qm_engine_preprocess", n_traces, t_samples, trace_filter, sos, n_filters, n_sections,
-                      taper_left, n_left, taper_right, n_right))
-        return 1;
     DeviceGuard guard(e->device);
+    if (e->pre_stage.build(e, "qm_engine_preprocess", 1, n_traces, t_samples, trace_filter, sos, n_filters, n_sections,
+                           detrend, taper_left, n_left, taper_right, n_right, zero_phase))
+        return 1;
     const size_t sig = (size_t)n_traces * t_samples;
-    const size_t n_coef = (size_t)n_filters * n_sections * 6, n_w = n_coef + n_left + n_right;
-    if (e->d_pre_coef.ensure(n_w) || e->d_pre_meta.ensure((size_t)n_traces)) return 1;
-    std::vector<double> w(sos, sos + n_coef);
-    w.insert(w.end(), taper_left, taper_left + n_left);
-    w.insert(w.end(), taper_right, taper_right + n_right);
-    QM_HIP(copy_in(e->d_pre_coef.p, w.data(), n_w * sizeof(double), e->stream));
-    QM_HIP(copy_in(e->d_pre_meta.p, trace_filter, (size_t)n_traces * sizeof(int32_t), e->stream));
     const double *d_sig = signals;
     if (!signals_on_device) {
         if (e->d_sig.ensure(sig)) return 1;
@@ -70,16 +99,7 @@ int qm_engine_preprocess(qm_engine *e, const double *signals, int signals_on_dev
         if (e->d_pre_out.ensure(sig)) return 1;
         d_out = e->d_pre_out.p;
     }
-    qm::PreprocArgs a{};
-    a.in = d_sig;
-    a.out = d_out;
-    a.trace_filter = e->d_pre_meta.p;
-    a.sos = e->d_pre_coef.p;
-    a.taper_left = e->d_pre_coef.p + n_coef;
-    a.taper_right = e->d_pre_coef.p + n_coef + n_left;
-    a.T = t_samples; a.n_sections = n_sections; a.n_left = n_left; a.n_right = n_right;
-    a.detrend = detrend ? 1 : 0; a.zero_phase = zero_phase ? 1 : 0; a.skew = e->cfg_preproc_skew;
-    if (launch_preproc_stage(e, a, n_traces)) return 1;
+    if (e->pre_stage.launch(e, d_sig, d_out, 1)) return 1;
     if (!out_on_device) {
         QM_HIP(copy_back(filtered, d_out, sig * sizeof(double), e->stream));
         QM_HIP(hipStreamSynchronize(e->stream));

@@ -1,9 +1,13 @@
-// qm_resample.hip -- the resampling stage's host side: the checks of the records, staging, the launch (kernel and
-// its notes: qm_resample.hpp).  qm_engine_resample is the staged call; the pipeline (qm_stream.hip) launches the same
-// kernel over the (step, trace)s of a slot through launch_resample_stage.
+// qm_resample.hip -- the resampling stage's host side (kernel and its notes: qm_resample.hpp).  ResampleStage
+// (qm_engine.hpp) is the stage: build checks the records and puts them on the device, launch runs the kernel over the
+// (step, trace)s of a launch.  qm_engine_resample is the staged call on the engine's record; the pipeline
+// (qm_stream.hip) holds a record of its own.
 #define QM_TU_RESAMPLE 1
 #include "qm_engine.hpp"
 
+namespace {
+
+// what build refuses; *max_kept: the longest kept series
 int check_resample(const char *what, int raw_dtype, int64_t total_raw_samples, int32_t n_traces, int32_t t_samples,
                    const int64_t *records, const double *sos_lp, int32_t n_lowpass, int32_t n_sections_lp,
                    const int32_t *taper_table, int32_t n_tapers, const double *taper_weights, int64_t n_taper_weights,
@@ -70,12 +74,63 @@ int check_resample(const char *what, int raw_dtype, int64_t total_raw_samples, i
     return 0;
 }
 
-int launch_resample_stage(qm_engine *e, const qm::ResampleArgs &a, int64_t n_traces, int64_t max_kept) {
+}  // namespace
+
+int ResampleStage::build(qm_engine *e, const char *what, int repeat, int raw_dtype, int64_t total_raw_samples,
+                         int32_t n_traces_, int32_t t_samples, const int64_t *records, const double *sos_lp,
+                         int32_t n_lowpass, int32_t n_sections_lp, int detrend, const int32_t *taper_table,
+                         int32_t n_tapers, const double *taper_weights, int64_t n_taper_weights) {
+    int64_t kept = 0;
+    if (check_resample(what, raw_dtype, total_raw_samples, n_traces_, t_samples, records, sos_lp, n_lowpass,
+                       n_sections_lp, taper_table, n_tapers, taper_weights, n_taper_weights, &kept))
+        return 1;
+    const size_t width = raw_dtype == qm::kRawInt32 ? 4 : 8;
+    const size_t bytes = (size_t)total_raw_samples * width, step = step_doubles(raw_dtype, total_raw_samples);
+    // the records `repeat` times, step k reading k raw steps further on
+    const size_t n_rec = (size_t)n_traces_ * qm::kResampleFields;
+    std::vector<int64_t> image;
+    for (int k = 0; k < repeat; ++k) {
+        image.insert(image.end(), records, records + n_rec);
+        for (int i = 0; i < n_traces_; ++i)
+            image[((size_t)k * n_traces_ + i) * qm::kResampleFields + qm::kRsRawOffset] +=
+                (int64_t)k * (int64_t)(step * 8 / width);
+    }
+    const size_t n_rec_all = image.size();
+    image.insert(image.end(), taper_table, taper_table + 2 * (size_t)n_tapers);
+    const size_t n_coef = (size_t)n_lowpass * n_sections_lp * 6;
+    std::vector<double> w(sos_lp, sos_lp + n_coef);
+    w.insert(w.end(), taper_weights, taper_weights + n_taper_weights);
+    const bool spill = kept > qm::kPreprocLdsSamples;
+    if (meta.ensure(image.size()) || coef.ensure(std::max<size_t>(w.size(), 1))) return 1;
+    if (spill && scratch.ensure((size_t)repeat * n_traces_ * kept)) return 1;
+    QM_HIP(copy_in(meta.p, image.data(), image.size() * sizeof(int64_t), e->stream));
+    if (!w.empty()) QM_HIP(copy_in(coef.p, w.data(), w.size() * sizeof(double), e->stream));
+    max_kept = kept;
+    n_traces = n_traces_;
+    raw_bytes = bytes;
+    raw_step = step;
+    args = qm::ResampleArgs{};
+    args.rec = meta.p;
+    args.tapers = meta.p + n_rec_all;
+    args.sos = coef.p;
+    args.taper_w = coef.p + n_coef;
+    args.scratch = spill ? scratch.p : nullptr;
+    args.scratch_stride = spill ? kept : 0;
+    args.T = t_samples; args.n_sections = n_sections_lp; args.raw_dtype = raw_dtype;
+    args.detrend = detrend ? 1 : 0;
+    return 0;
+}
+
+int ResampleStage::launch(qm_engine *e, const void *raw, double *out, int n_steps) const {
+    qm::ResampleArgs a = args;
+    a.raw = raw;
+    a.out = out;
+    a.skew = e->cfg_preproc_skew;
     // one workgroup per trace; LDS for the longest kept series that fits (longer ones live in their scratch rows)
     const size_t lds = (size_t)std::min<int64_t>(max_kept, qm::kPreprocLdsSamples) * sizeof(double);
     QM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&qm::resample_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(qm::resample_kernel, dim3((unsigned)n_traces), dim3(256), lds, e->stream, a);
+    hipLaunchKernelGGL(qm::resample_kernel, dim3((unsigned)((int64_t)n_steps * n_traces)), dim3(256), lds, e->stream, a);
     QM_HIP(hipGetLastError());
     return 0;
 }
@@ -87,30 +142,17 @@ int qm_engine_resample(qm_engine *e, const void *raw, int raw_dtype, int raw_on_
                        int32_t n_sections_lp, int detrend, const int32_t *taper_table, int32_t n_tapers,
                        const double *taper_weights, int64_t n_taper_weights, int32_t t_samples, double *out,
                        int out_on_device) {
-    const char *what = "qm_engine_resample";
-    if (!e || !raw || !out) return fail("%s: NULL argument", what);
-    int64_t max_kept = 0;
-    if (check_resample(what, raw_dtype, total_raw_samples, n_traces, t_samples, records, sos_lp, n_lowpass,
-                       n_sections_lp, taper_table, n_tapers, taper_weights, n_taper_weights, &max_kept))
-        return 1;
+    if (!e || !raw || !out) return fail("qm_engine_resample: NULL argument");
     DeviceGuard guard(e->device);
-    const size_t n_rec = (size_t)n_traces * qm::kResampleFields, n_meta = n_rec + 2 * (size_t)n_tapers;
-    const size_t n_coef = (size_t)n_lowpass * n_sections_lp * 6, n_w = n_coef + (size_t)n_taper_weights;
+    ResampleStage &rs = e->rs_stage;
+    if (rs.build(e, "qm_engine_resample", 1, raw_dtype, total_raw_samples, n_traces, t_samples, records, sos_lp,
+                 n_lowpass, n_sections_lp, detrend, taper_table, n_tapers, taper_weights, n_taper_weights))
+        return 1;
     const size_t sig = (size_t)n_traces * t_samples;
-    const bool spill = max_kept > qm::kPreprocLdsSamples;
-    if (e->d_rs_meta.ensure(n_meta) || e->d_rs_coef.ensure(std::max<size_t>(n_w, 1))) return 1;
-    if (spill && e->d_rs_scratch.ensure((size_t)n_traces * max_kept)) return 1;
-    std::vector<int64_t> meta(records, records + n_rec);
-    meta.insert(meta.end(), taper_table, taper_table + 2 * (size_t)n_tapers);
-    std::vector<double> w(sos_lp, sos_lp + n_coef);
-    w.insert(w.end(), taper_weights, taper_weights + n_taper_weights);
-    QM_HIP(copy_in(e->d_rs_meta.p, meta.data(), n_meta * sizeof(int64_t), e->stream));
-    if (n_w) QM_HIP(copy_in(e->d_rs_coef.p, w.data(), n_w * sizeof(double), e->stream));
     const void *d_raw = raw;
     if (!raw_on_device) {
-        const size_t bytes = (size_t)total_raw_samples * (raw_dtype == qm::kRawInt32 ? 4 : 8);
-        if (e->d_rs_raw.ensure((bytes + 7) / 8)) return 1;
-        QM_HIP(copy_in(e->d_rs_raw.p, raw, bytes, e->stream));
+        if (e->d_rs_raw.ensure(rs.raw_step)) return 1;
+        QM_HIP(copy_in(e->d_rs_raw.p, raw, rs.raw_bytes, e->stream));
         d_raw = e->d_rs_raw.p;
     }
     double *d_out = out;
@@ -118,19 +160,8 @@ int qm_engine_resample(qm_engine *e, const void *raw, int raw_dtype, int raw_on_
         if (e->d_pre_out.ensure(sig)) return 1;
         d_out = e->d_pre_out.p;
     }
-    qm::ResampleArgs a{};
-    a.raw = d_raw;
-    a.rec = e->d_rs_meta.p;
-    a.tapers = e->d_rs_meta.p + n_rec;
-    a.sos = e->d_rs_coef.p;
-    a.taper_w = e->d_rs_coef.p + n_coef;
-    a.out = d_out;
-    a.scratch = spill ? e->d_rs_scratch.p : nullptr;
-    a.scratch_stride = spill ? max_kept : 0;
-    a.T = t_samples; a.n_sections = n_sections_lp; a.raw_dtype = raw_dtype;
-    a.detrend = detrend ? 1 : 0; a.skew = e->cfg_preproc_skew;
     QM_HIP(hipEventRecord(e->ev0, e->stream));
-    if (launch_resample_stage(e, a, n_traces, max_kept)) return 1;
+    if (rs.launch(e, d_raw, d_out, 1)) return 1;
     QM_HIP(hipEventRecord(e->ev1, e->stream));
     e->timed = true;
     if (!out_on_device) {

@@ -33,6 +33,10 @@
 // host blocks only in qm_stream_pop, and only for the oldest launch: 8 timesteps per launch run at
 // x1.00 of the resident step on those grids.  The caller's pointers are never handed to the HIP
 // runtime.
+//
+// The stages in front of the detect are the records of qm_engine.hpp (ResampleStage, PreprocStage, OnsetStage): the
+// stream builds its own, steps_per_launch times over, where the stage is set, launches them slot by slot and
+// releases them with its slots.  Nothing here checks a stage's arrays or fills a kernel's arguments.
 #include "qm_engine.hpp"
 
 #include <deque>
@@ -44,14 +48,15 @@ struct qm_stream {
     int64_t n_nodes_total = 0;
     uint64_t table_serial = 0;          // the table the stream was made on (TableState::serial)
     hipStream_t copy_stream = nullptr;
+    // what the pushes carry, one kind per stream: log-onsets [n_rows][T]; with an onset stage the component traces
+    // [n_traces][T], from which the slot's log-onsets are made on the device; with a resampling stage as well the
+    // packed raw samples, from which the slot's traces are made
+    enum Feed { kNothingYet = 0, kLogOnsets = 1, kSignals = 2, kRaw = 3, kFeeds = 4 };
     struct Slot {
-        double *h_on = nullptr;         // pinned [K][n_rows][T]
-        double *d_on = nullptr;         // device, the same
-        double *h_sig = nullptr;        // onset stage: pinned [K][n_traces][T] component traces
-        double *d_sig = nullptr;        // ... device, the same; filtered in place
-        double *h_raw = nullptr;        // resampling stage: pinned [K][raw_step] packed raw samples (h_sig is given up
-                                        // at the first raw step)
-        double *d_raw = nullptr;        // ... device, the same
+        struct In {
+            double *h = nullptr;        // pinned [K][step_words[feed]] (the signals': given up at the first raw step)
+            double *d = nullptr;        // device, the same (the signals': filtered in place)
+        } in[kFeeds];                   // by Feed: log-onsets from create on, signals and raw samples from their stage on
         double *h_out = nullptr;        // pinned [3][K * ns]: max_coa, max_norm_coa, indices (int64 bits) --
                                         // written by the kernels themselves
         hipEvent_t copied = nullptr;    // the inputs are on the device
@@ -66,27 +71,15 @@ struct qm_stream {
     int64_t launched_steps = 0, popped_steps = 0, launches = 0;
     unsigned long long *h_stamp = nullptr;   // ("stream_stamps") pinned [2][4096]
     bool pulled = false;                // the last launch's inputs were pulled by a kernel (no copy command)
-    // Onset stage (qm_stream_set_onset_stage): the slot's log-onsets are made on the device from pushed signals.
-    // Everything the kernels read is on the device from set-up on, replicated over the K steps of a launch:
-    // (step, trace) is the kernels' trace, (step, row) their row.
-    enum Feed { kNothingYet = 0, kLogOnsets = 1, kSignals = 2, kRaw = 3 };
-    int feed = kNothingYet;             // what the pushes carry: one kind per stream
-    bool staged = false;
-    int n_traces = 0;
-    qm::PreprocArgs pre{};              // in / out: per slot
-    qm::OnsetArgs on{};                 // signals / logged, n_traces / n_rows: per slot and launch
-    double *d_coef = nullptr;           // sos, taper_left, taper_right
-    double *d_sta = nullptr, *d_lta = nullptr;  // [K][n_traces][T] scratch of the onset kernels
-    int32_t *d_meta = nullptr;          // trace_filter [K][n_traces], trace_row the same, nsta [K][n_rows], nlta
-    // Resampling stage (qm_stream_set_resample_stage): the slot's signals are made on the device from pushed raw
-    // samples.  The records stand K times on the device, step k's raw offsets k raw steps further on.
-    bool resampled = false;
-    qm::ResampleArgs rs{};              // raw / out: per slot
-    int64_t rs_max_kept = 0;
-    size_t raw_bytes = 0, raw_step = 0; // a timestep's raw bytes as pushed; in doubles as the slot holds it (rounded up)
-    int64_t *d_rs_meta = nullptr;       // records [K][n_traces][kResampleFields], taper table
-    double *d_rs_coef = nullptr;        // low-pass sections, taper weights
-    double *d_rs_scratch = nullptr;     // [K][n_traces][rs_max_kept] where a kept series is above the LDS limit
+    int feed = kNothingYet;
+    size_t step_words[kFeeds] = {};     // a timestep of each kind in doubles, as a slot holds it (raw bytes: rounded up)
+    size_t step_bytes[kFeeds] = {};     // ... in bytes, as it is pushed
+    // the stages (qm_engine.hpp), K times over: qm_stream_set_onset_stage builds `pre` and `on`,
+    // qm_stream_set_resample_stage `rs`
+    bool staged = false, resampled = false;
+    PreprocStage pre;
+    OnsetStage on;
+    ResampleStage rs;
     // A stream over replicas (qm_stream_create_replicas) holds no slots of its own: one ordinary stream per
     // engine (a LANE, registered on that engine like any other stream) and the launches in push order.  Launch j
     // goes to lane j mod n; the entry points dispatch to the replicas_* functions below.
@@ -122,23 +115,38 @@ __global__ __launch_bounds__(256) void pull_kernel(const pull2 *__restrict__ src
 // ("stream_stamps": the GPU's own clock before and behind every launch of a stream, digested at its destruction)
 __global__ void stamp_kernel(unsigned long long *slot) { *slot = wall_clock64(); }
 
-size_t step_in(const qm_stream *s) { return (size_t)s->n_rows * s->T; }
-size_t step_sig(const qm_stream *s) { return (size_t)s->n_traces * s->T; }
-
 int alive(const qm_stream *s, const char *what) {
     if (!s) return fail("%s: NULL argument", what);
     if (!s->e) return fail("%s: the stream's engine has been destroyed", what);
     return 0;
 }
 
+// every slot's buffers for one kind of input, K timesteps each (s->step_words[feed] is set)
+int alloc_inputs(qm_stream *s, int feed, const char *what) {
+    const size_t bytes = (size_t)s->K * s->step_words[feed] * sizeof(double);
+    hipError_t r = hipSuccess;
+    for (qm_stream::Slot &sl : s->slots) {
+        qm_stream::Slot::In &in = sl.in[feed];
+        if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&in.h), bytes, hipHostMallocDefault);
+        if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&in.d), bytes);
+        if (r == hipSuccess && feed == qm_stream::kRaw) std::memset(in.h, 0, bytes);    // (the bytes a step's int32s leave over)
+    }
+    if (r != hipSuccess)
+        return fail("%s: %s (%d steps of %zu bytes per slot, %d slots)", what, hipGetErrorString(r), s->K,
+                    s->step_bytes[feed], s->depth);
+    return 0;
+}
+
+void free_inputs(qm_stream::Slot &sl, int feed) {
+    qm_stream::Slot::In &in = sl.in[feed];
+    if (in.h) (void)hipHostFree(in.h);
+    if (in.d) pool_free(in.d);
+    in = {};
+}
+
 void free_slot(qm_stream::Slot &sl) {
-    if (sl.h_on) (void)hipHostFree(sl.h_on);
+    for (int feed = 0; feed < qm_stream::kFeeds; ++feed) free_inputs(sl, feed);
     if (sl.h_out) (void)hipHostFree(sl.h_out);
-    if (sl.h_sig) (void)hipHostFree(sl.h_sig);
-    if (sl.h_raw) (void)hipHostFree(sl.h_raw);
-    if (sl.d_raw) pool_free(sl.d_raw);
-    if (sl.d_on) pool_free(sl.d_on);
-    if (sl.d_sig) pool_free(sl.d_sig);
     for (hipEvent_t ev : {sl.copied, sl.done})
         if (ev) (void)hipEventDestroy(ev);
     sl = qm_stream::Slot{};
@@ -170,16 +178,7 @@ void release_stream(qm_stream *s) {
     {
         PoolReleaseScope one_wait;
         for (qm_stream::Slot &sl : s->slots) free_slot(sl);
-        if (s->d_coef) pool_free(s->d_coef);
-        if (s->d_sta) pool_free(s->d_sta);
-        if (s->d_lta) pool_free(s->d_lta);
-        if (s->d_meta) pool_free(s->d_meta);
-        if (s->d_rs_meta) pool_free(s->d_rs_meta);
-        if (s->d_rs_coef) pool_free(s->d_rs_coef);
-        if (s->d_rs_scratch) pool_free(s->d_rs_scratch);
-        s->d_coef = s->d_sta = s->d_lta = s->d_rs_coef = s->d_rs_scratch = nullptr;
-        s->d_meta = nullptr;
-        s->d_rs_meta = nullptr;
+        s->rs.release(); s->pre.release(); s->on.release();
     }
     if (s->copy_stream) park_stream(s->e->device, s->copy_stream);
     s->copy_stream = nullptr;
@@ -199,11 +198,9 @@ int launch_slot(qm_stream *s) {
                     (unsigned long long)(e->have_lut ? e->serial : 0), e->have_lut ? e->g.n_rows : 0,
                     (unsigned long long)s->table_serial, s->n_rows);
     const size_t kns = (size_t)s->K * s->ns;
-    const bool raw = s->feed == qm_stream::kRaw;
-    const bool signals = raw || s->feed == qm_stream::kSignals;
-    const size_t words = (size_t)n * (raw ? s->raw_step : signals ? step_sig(s) : step_in(s));
-    const double *h_in = raw ? sl.h_raw : signals ? sl.h_sig : sl.h_on;
-    double *d_in = raw ? sl.d_raw : signals ? sl.d_sig : sl.d_on;
+    const size_t words = (size_t)n * s->step_words[s->feed];
+    const double *h_in = sl.in[s->feed].h;
+    double *d_in = sl.in[s->feed].d;
     const bool pull = e->cfg_stream_pull > 0 || (e->cfg_stream_pull < 0 && words * sizeof(double) <= kPullBytes);
     // ("stream_stamps" = 1, measurement: the GPU's clock before and behind every launch -- two one-thread kernels;
     // the digest goes to stderr when the stream is destroyed.  What found round 6's one-off stall: tools/diag_stream.py)
@@ -229,35 +226,20 @@ int launch_slot(qm_stream *s) {
         QM_HIP(hipStreamWaitEvent(e->stream, sl.copied, 0));
     }
     s->pulled = pull;
-    if (raw) {
-        // raw samples -> the n steps' traces at the scan rate, straight into the slot's d_sig
-        qm::ResampleArgs r = s->rs;
-        r.raw = sl.d_raw;
-        r.out = sl.d_sig;
-        r.skew = e->cfg_preproc_skew;
-        if (launch_resample_stage(e, r, (int64_t)n * s->n_traces, s->rs_max_kept)) return 1;
-    }
-    if (signals) {
-        // waveforms -> log-onsets, all on the engine's stream: the n steps' traces filtered in place, then the onset
-        // kernels with (step, trace) as their trace and (step, row) as their row, straight into the slot's d_on
-        qm::PreprocArgs p = s->pre;
-        p.in = p.out = sl.d_sig;
-        p.skew = e->cfg_preproc_skew;
-        if (launch_preproc_stage(e, p, (int64_t)n * s->n_traces)) return 1;
-        qm::OnsetArgs o = s->on;
-        o.signals = sl.d_sig;
-        o.logged = sl.d_on;
-        o.n_traces = n * s->n_traces;
-        o.n_rows = n * s->n_rows;
-        if (launch_onset_stage(e, o)) return 1;
-    }
+    double *d_sig = sl.in[qm_stream::kSignals].d, *d_on = sl.in[qm_stream::kLogOnsets].d;
+    // raw samples -> the n steps' traces at the scan rate, straight into the slot's signals
+    if (s->feed == qm_stream::kRaw && s->rs.launch(e, d_in, d_sig, n)) return 1;
+    // waveforms -> log-onsets, all on the engine's stream: the n steps' traces filtered in place, then the onset
+    // kernels, straight into the slot's log-onsets
+    if (s->feed == qm_stream::kRaw || s->feed == qm_stream::kSignals)
+        if (s->pre.launch(e, d_sig, d_sig, n) || s->on.launch(e, d_sig, nullptr, d_on, n)) return 1;
     // The results are a few KB per timestep: the combine kernel writes them STRAIGHT into the slot's
     // pinned host buffer (pinned memory is device-accessible under one address; the event behind the
     // launch makes them visible to the host) -- no D2H copy command, no third stream.  (With a copy on a
     // download stream of its own, 8 timesteps per launch ran at x1.03-1.09 of the resident step on the
     // example-sized grids; now x1.00, profiles/r05_ab_runs.txt.)
     double *out = sl.h_out;
-    if (qm_engine_detect_batch(e, sl.d_on, 1, n, s->T, s->fsmp, s->lsmp, s->available, s->n_nodes_total,
+    if (qm_engine_detect_batch(e, d_on, 1, n, s->T, s->fsmp, s->lsmp, s->available, s->n_nodes_total,
                                out, out + kns, reinterpret_cast<int64_t *>(out + 2 * kns), 1))
         return 1;
     if (stamps)
@@ -274,25 +256,40 @@ int launch_slot(qm_stream *s) {
     return 0;
 }
 
+// A stage that did not come about, on this stream or on a later lane -- the onset stage (feed = kSignals) or the
+// resampling stage (kRaw): what it took goes back and the stream is what it was before (the engine's device is
+// current; the error text stays).  Returns 1.
+int stage_undo(qm_stream *s, int feed) {
+    PoolReleaseScope one_wait;
+    for (qm_stream::Slot &sl : s->slots) free_inputs(sl, feed);
+    if (feed == qm_stream::kRaw) {
+        s->rs.release();
+        s->resampled = false;
+    } else {
+        s->pre.release(); s->on.release();
+        s->staged = false;
+    }
+    return 1;
+}
+
 // ---- replicas: one pipeline over several engines that hold the same table -----------------------------------
 // Launches go round the lanes in push order, so a lane's next slot is in flight only when all n x depth launches
 // are un-popped -- and then the oldest launch is on that lane: "pop the oldest launch, push again" still frees it.
 
-// a resampling stage that did not come about, on this stream or on a later lane: its buffers go back and the stream
-// is what it was before, an onset stage with signals going in (the engine's device is current)
-void resample_stage_undo(qm_stream *s) {
-    PoolReleaseScope one_wait;
-    for (qm_stream::Slot &sl : s->slots) {
-        if (sl.h_raw) (void)hipHostFree(sl.h_raw);
-        if (sl.d_raw) pool_free(sl.d_raw);
-        sl.h_raw = sl.d_raw = nullptr;
-    }
-    if (s->d_rs_meta) pool_free(s->d_rs_meta);
-    if (s->d_rs_coef) pool_free(s->d_rs_coef);
-    if (s->d_rs_scratch) pool_free(s->d_rs_scratch);
-    s->d_rs_meta = nullptr;
-    s->d_rs_coef = s->d_rs_scratch = nullptr;
-    s->resampled = false;
+// a stage on every lane or on none: the lanes before the one that refused give it back
+template <typename Set>
+int replicas_stage(qm_stream *s, int feed, Set set) {
+    for (qm_stream *lane : s->lanes)
+        if (set(lane)) {
+            for (qm_stream *before : s->lanes) {
+                if (before == lane) break;
+                DeviceGuard guard(before->e->device);
+                stage_undo(before, feed);
+            }
+            return 1;
+        }
+    (feed == qm_stream::kRaw ? s->resampled : s->staged) = true;
+    return 0;
 }
 
 int replicas_alive(const qm_stream *s, const char *what) {
@@ -393,18 +390,18 @@ int qm_stream_create(qm_engine *e, int32_t t_samples, int32_t fsmp, int32_t lsmp
     };
     // (the copy stream is taken at the first launch that copies: slots that are pulled never need one)
     s->slots.resize((size_t)depth);
-    const size_t in_bytes = (size_t)s->K * step_in(s) * sizeof(double);
+    s->step_words[qm_stream::kLogOnsets] = (size_t)s->n_rows * s->T;
+    s->step_bytes[qm_stream::kLogOnsets] = s->step_words[qm_stream::kLogOnsets] * sizeof(double);
     const size_t out_bytes = 3 * (size_t)s->K * ns * sizeof(double);
     for (qm_stream::Slot &sl : s->slots) {
-        hipError_t r = hipHostMalloc(reinterpret_cast<void **>(&sl.h_on), in_bytes, hipHostMallocDefault);
-        if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&sl.h_out), out_bytes, hipHostMallocDefault);
-        if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&sl.d_on), in_bytes);
+        hipError_t r = hipHostMalloc(reinterpret_cast<void **>(&sl.h_out), out_bytes, hipHostMallocDefault);
         for (hipEvent_t *ev : {&sl.copied, &sl.done})
             if (r == hipSuccess) r = hipEventCreateWithFlags(ev, hipEventDisableTiming);
         if (r != hipSuccess)
-            return bail(fail("qm_stream_create: %s (%d steps of %zu bytes per slot, %d slots)",
-                             hipGetErrorString(r), s->K, step_in(s) * sizeof(double), depth));
+            return bail(fail("qm_stream_create: %s (%d steps of %zu bytes of results per slot, %d slots)",
+                             hipGetErrorString(r), s->K, out_bytes / s->K, depth));
     }
+    if (alloc_inputs(s, qm_stream::kLogOnsets, "qm_stream_create")) return bail(1);
     e->streams.push_back(s);
     *out = s;
     return 0;
@@ -501,17 +498,12 @@ static int push_step(qm_stream *s, const void *step, int feed, const char *what)
     }
     s->feed = feed;
     // (the slot's previous H2D has finished: its launch's results were popped)
-    if (feed == qm_stream::kRaw && sl.h_sig)            // the first raw step: the ring's pinned slots hold raw bytes
-        for (qm_stream::Slot &other : s->slots) {       // from here on, the signals' pinned buffers are given up
-            (void)hipHostFree(other.h_sig);
-            other.h_sig = nullptr;
+    if (feed == qm_stream::kRaw && sl.in[qm_stream::kSignals].h)    // the first raw step: the ring's pinned slots hold
+        for (qm_stream::Slot &other : s->slots) {       // raw bytes from here on, the signals' pinned buffers are given up
+            (void)hipHostFree(other.in[qm_stream::kSignals].h);
+            other.in[qm_stream::kSignals].h = nullptr;
         }
-    if (feed == qm_stream::kRaw)
-        host_copy(sl.h_raw + (size_t)s->fill_n * s->raw_step, step, s->raw_bytes);
-    else if (feed == qm_stream::kSignals)
-        host_copy(sl.h_sig + (size_t)s->fill_n * step_sig(s), step, step_sig(s) * sizeof(double));
-    else
-        host_copy(sl.h_on + (size_t)s->fill_n * step_in(s), step, step_in(s) * sizeof(double));
+    host_copy(sl.in[feed].h + (size_t)s->fill_n * s->step_words[feed], step, s->step_bytes[feed]);
     if (++s->fill_n < s->K) return 0;
     return launch_slot(s);
 }
@@ -533,90 +525,33 @@ int qm_stream_set_resample_stage(qm_stream *s, int32_t n_traces, const int64_t *
                                  int32_t n_tapers, const double *taper_weights, int64_t n_taper_weights,
                                  int32_t t_samples, int raw_dtype, int64_t total_raw_samples) {
     const char *what = "qm_stream_set_resample_stage";
-    if (!s || !records) return fail("%s: NULL argument", what);
+    if (!s) return fail("%s: NULL argument", what);
     if (!s->staged) return fail("%s: the stream has no onset stage (qm_stream_set_onset_stage comes first)", what);
     if (s->resampled) return fail("%s: the stream has its resampling stage already (it is set once)", what);
     if (s->feed != qm_stream::kNothingYet || s->fill_n > 0 || s->launched_steps > 0)
         return fail("%s: the stage is set before the first push", what);
-    if (!s->lanes.empty()) {
-        for (qm_stream *lane : s->lanes)
-            if (qm_stream_set_resample_stage(lane, n_traces, records, sos_lp, n_lowpass, n_sections_lp, detrend,
-                                             taper_table, n_tapers, taper_weights, n_taper_weights, t_samples,
-                                             raw_dtype, total_raw_samples)) {
-                // all lanes or none: the lanes before this one give the stage back (the error text stays)
-                for (qm_stream *before : s->lanes) {
-                    if (before == lane) break;
-                    DeviceGuard guard(before->e->device);
-                    resample_stage_undo(before);
-                }
-                return 1;
-            }
-        s->resampled = true;
-        return 0;
-    }
+    if (!s->lanes.empty())
+        return replicas_stage(s, qm_stream::kRaw, [&](qm_stream *lane) {
+            return qm_stream_set_resample_stage(lane, n_traces, records, sos_lp, n_lowpass, n_sections_lp, detrend,
+                                                taper_table, n_tapers, taper_weights, n_taper_weights, t_samples,
+                                                raw_dtype, total_raw_samples);
+        });
     if (alive(s, what)) return 1;
-    if (t_samples != s->T || n_traces != s->n_traces)
+    if (t_samples != s->T || n_traces != s->pre.n_traces)
         return fail("%s: %d traces of %d samples, the onset stage takes %d of %d", what, n_traces, t_samples,
-                    s->n_traces, s->T);
-    int64_t max_kept = 0;
-    if (check_resample(what, raw_dtype, total_raw_samples, n_traces, t_samples, records, sos_lp, n_lowpass,
-                       n_sections_lp, taper_table, n_tapers, taper_weights, n_taper_weights, &max_kept))
-        return 1;
-    const int K = s->K;
-    const size_t width = raw_dtype == qm::kRawInt32 ? 4 : 8;
-    const size_t raw_bytes = (size_t)total_raw_samples * width, raw_step = (raw_bytes + 7) / 8;
-    if ((double)K * (double)raw_step * 8.0 >= 0x1p40) return fail("%s: too many raw samples per launch", what);
+                    s->pre.n_traces, s->T);
+    if (total_raw_samples > 0 &&
+        (double)s->K * (double)ResampleStage::step_doubles(raw_dtype, total_raw_samples) * 8.0 >= 0x1p40)
+        return fail("%s: too many raw samples per launch", what);
     qm_engine *e = s->e;
     DeviceGuard guard(e->device);
-    // host images: the records K times, step k reading k raw steps further on
-    const size_t n_rec = (size_t)n_traces * qm::kResampleFields;
-    std::vector<int64_t> meta;
-    for (int k = 0; k < K; ++k) {
-        meta.insert(meta.end(), records, records + n_rec);
-        for (int i = 0; i < n_traces; ++i)
-            meta[((size_t)k * n_traces + i) * qm::kResampleFields + qm::kRsRawOffset] +=
-                (int64_t)k * (int64_t)(raw_step * 8 / width);
-    }
-    const size_t n_rec_all = meta.size();
-    meta.insert(meta.end(), taper_table, taper_table + 2 * (size_t)n_tapers);
-    const size_t n_coef = (size_t)n_lowpass * n_sections_lp * 6;
-    std::vector<double> coef(sos_lp, sos_lp + n_coef);
-    coef.insert(coef.end(), taper_weights, taper_weights + n_taper_weights);
-    coef.push_back(0.0);                                // (never empty)
-    const bool spill = max_kept > qm::kPreprocLdsSamples;
-    const size_t slot_bytes = (size_t)K * raw_step * sizeof(double);
-    hipError_t r = pool_alloc(reinterpret_cast<void **>(&s->d_rs_meta), meta.size() * sizeof(int64_t));
-    if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&s->d_rs_coef), coef.size() * sizeof(double));
-    if (r == hipSuccess && spill)
-        r = pool_alloc(reinterpret_cast<void **>(&s->d_rs_scratch), (size_t)K * n_traces * max_kept * sizeof(double));
-    for (qm_stream::Slot &sl : s->slots) {
-        if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&sl.h_raw), slot_bytes, hipHostMallocDefault);
-        if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&sl.d_raw), slot_bytes);
-        if (r == hipSuccess) std::memset(sl.h_raw, 0, slot_bytes);     // (the bytes a step's int32s leave over)
-    }
-    if (r != hipSuccess) {                              // the stream stays as it was: an onset stage, signals in
-        resample_stage_undo(s);
-        return fail("%s: %s (%d steps of %zu bytes per slot, %d slots)", what, hipGetErrorString(r), K, raw_bytes,
-                    s->depth);
-    }
-    if (copy_in(s->d_rs_meta, meta.data(), meta.size() * sizeof(int64_t), e->stream) != hipSuccess ||
-        copy_in(s->d_rs_coef, coef.data(), coef.size() * sizeof(double), e->stream) != hipSuccess) {
-        resample_stage_undo(s);
-        return fail("%s: the copy of the stage's arrays to the device failed", what);
-    }
+    if (s->rs.build(e, what, s->K, raw_dtype, total_raw_samples, n_traces, t_samples, records, sos_lp, n_lowpass,
+                    n_sections_lp, detrend, taper_table, n_tapers, taper_weights, n_taper_weights))
+        return stage_undo(s, qm_stream::kRaw);
     // (the signals' pinned buffers are given up at the first qm_stream_push_raw: until then nothing is lost)
-    s->raw_bytes = raw_bytes;
-    s->raw_step = raw_step;
-    s->rs_max_kept = max_kept;
-    s->rs = qm::ResampleArgs{};
-    s->rs.rec = s->d_rs_meta;
-    s->rs.tapers = s->d_rs_meta + n_rec_all;
-    s->rs.sos = s->d_rs_coef;
-    s->rs.taper_w = s->d_rs_coef + n_coef;
-    s->rs.scratch = s->d_rs_scratch;
-    s->rs.scratch_stride = spill ? max_kept : 0;
-    s->rs.T = s->T; s->rs.n_sections = n_sections_lp; s->rs.raw_dtype = raw_dtype;
-    s->rs.detrend = detrend ? 1 : 0;
+    s->step_words[qm_stream::kRaw] = s->rs.raw_step;
+    s->step_bytes[qm_stream::kRaw] = s->rs.raw_bytes;
+    if (alloc_inputs(s, qm_stream::kRaw, what)) return stage_undo(s, qm_stream::kRaw);
     s->resampled = true;
     return 0;
 }
@@ -627,80 +562,29 @@ int qm_stream_set_onset_stage(qm_stream *s, int32_t n_traces, const int32_t *tra
                               const int32_t *nsta, const int32_t *nlta, int transform, int position,
                               int32_t taper_pad, double min_onset_value) {
     const char *what = "qm_stream_set_onset_stage";
-    if (!s || !trace_row || !nsta || !nlta) return fail("%s: NULL argument", what);
+    if (!s) return fail("%s: NULL argument", what);
     if (s->staged) return fail("%s: the stream has its onset stage already (it is set once)", what);
     if (s->feed != qm_stream::kNothingYet || s->fill_n > 0 || s->launched_steps > 0)
         return fail("%s: the stage is set before the first push", what);
-    if (!s->lanes.empty()) {
-        for (qm_stream *lane : s->lanes)
-            if (qm_stream_set_onset_stage(lane, n_traces, trace_row, trace_filter, sos, n_filters, n_sections, detrend,
-                                          taper_left, n_left, taper_right, n_right, nsta, nlta, transform, position,
-                                          taper_pad, min_onset_value))
-                return 1;
-        s->staged = true;
-        return 0;
-    }
+    if (!s->lanes.empty())
+        return replicas_stage(s, qm_stream::kSignals, [&](qm_stream *lane) {
+            return qm_stream_set_onset_stage(lane, n_traces, trace_row, trace_filter, sos, n_filters, n_sections, detrend,
+                                             taper_left, n_left, taper_right, n_right, nsta, nlta, transform, position,
+                                             taper_pad, min_onset_value);
+        });
     if (alive(s, what)) return 1;
-    if (check_preproc(what, n_traces, s->T, trace_filter, sos, n_filters, n_sections, taper_left, n_left, taper_right,
-                      n_right))
-        return 1;
-    if (transform != 0 && transform != 1) return fail("transform must be 0 (energy) or 1 (abs)");
-    if (position < 0 || position > 2) return fail("position must be 0 (classic), 1 (centred) or 2 (recursive)");
-    const int n_rows = s->n_rows, K = s->K;
-    std::vector<int> per_row(n_rows, 0);
-    for (int i = 0; i < n_traces; ++i) {
-        if (trace_row[i] < 0 || trace_row[i] >= n_rows) return fail("%s: trace %d: row out of range", what, i);
-        ++per_row[trace_row[i]];
-    }
-    for (int r = 0; r < n_rows; ++r)
-        if (per_row[r] == 0) return fail("%s: onset row %d has no trace", what, r);
-    if ((int64_t)K * n_traces * s->T >= INT32_MAX || (int64_t)K * n_rows * s->T >= INT32_MAX)
+    if ((int64_t)s->K * n_traces * s->T >= INT32_MAX || (int64_t)s->K * s->n_rows * s->T >= INT32_MAX)
         return fail("%s: too many samples per launch", what);
     qm_engine *e = s->e;
     DeviceGuard guard(e->device);
-    // host images: everything K times, the rows of step k behind those of step k - 1
-    const size_t n_coef = (size_t)n_filters * n_sections * 6;
-    std::vector<double> coef(sos, sos + n_coef);
-    coef.insert(coef.end(), taper_left, taper_left + n_left);
-    coef.insert(coef.end(), taper_right, taper_right + n_right);
-    std::vector<int32_t> meta;
-    for (int k = 0; k < K; ++k) meta.insert(meta.end(), trace_filter, trace_filter + n_traces);
-    for (int k = 0; k < K; ++k)
-        for (int i = 0; i < n_traces; ++i) meta.push_back(k * n_rows + trace_row[i]);
-    for (int k = 0; k < K; ++k) meta.insert(meta.end(), nsta, nsta + n_rows);
-    for (int k = 0; k < K; ++k) meta.insert(meta.end(), nlta, nlta + n_rows);
-    s->n_traces = n_traces;
-    const size_t sig_bytes = (size_t)K * step_sig(s) * sizeof(double);
-    hipError_t r = pool_alloc(reinterpret_cast<void **>(&s->d_coef), coef.size() * sizeof(double));
-    if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&s->d_meta), meta.size() * sizeof(int32_t));
-    if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&s->d_sta), sig_bytes);
-    if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&s->d_lta), sig_bytes);
-    for (qm_stream::Slot &sl : s->slots) {
-        if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&sl.h_sig), sig_bytes, hipHostMallocDefault);
-        if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&sl.d_sig), sig_bytes);
-    }
-    if (r != hipSuccess)                                // (what was allocated goes back with the stream)
-        return fail("%s: %s (%d steps of %zu bytes per slot, %d slots)", what, hipGetErrorString(r), K,
-                    step_sig(s) * sizeof(double), s->depth);
-    QM_HIP(copy_in(s->d_coef, coef.data(), coef.size() * sizeof(double), e->stream));
-    QM_HIP(copy_in(s->d_meta, meta.data(), meta.size() * sizeof(int32_t), e->stream));
-    const size_t kt = (size_t)K * n_traces, kr = (size_t)K * n_rows;
-    s->pre = qm::PreprocArgs{};
-    s->pre.trace_filter = s->d_meta;
-    s->pre.sos = s->d_coef;
-    s->pre.taper_left = s->d_coef + n_coef;
-    s->pre.taper_right = s->d_coef + n_coef + n_left;
-    s->pre.T = s->T; s->pre.n_sections = n_sections; s->pre.n_left = n_left; s->pre.n_right = n_right;
-    s->pre.detrend = detrend ? 1 : 0; s->pre.zero_phase = 1;
-    s->on = qm::OnsetArgs{};
-    s->on.trace_row = s->d_meta + kt;
-    s->on.nsta = s->d_meta + 2 * kt;
-    s->on.nlta = s->d_meta + 2 * kt + kr;
-    s->on.sta = s->d_sta;
-    s->on.lta = s->d_lta;
-    s->on.T = s->T;
-    s->on.transform = transform; s->on.position = position; s->on.taper_pad = taper_pad;
-    s->on.min_onset_value = min_onset_value;
+    if (s->pre.build(e, what, s->K, n_traces, s->T, trace_filter, sos, n_filters, n_sections, detrend, taper_left, n_left,
+                     taper_right, n_right, /*zero_phase=*/1) ||
+        s->on.build(e, what, s->K, n_traces, s->T, trace_row, s->n_rows, nsta, nlta, transform, position, taper_pad,
+                    min_onset_value))
+        return stage_undo(s, qm_stream::kSignals);
+    s->step_words[qm_stream::kSignals] = (size_t)n_traces * s->T;
+    s->step_bytes[qm_stream::kSignals] = s->step_words[qm_stream::kSignals] * sizeof(double);
+    if (alloc_inputs(s, qm_stream::kSignals, what)) return stage_undo(s, qm_stream::kSignals);
     s->staged = true;
     return 0;
 }

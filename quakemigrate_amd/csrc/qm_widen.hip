@@ -1,5 +1,6 @@
 // qm_widen.hip -- the rows SURVEY.md section 8(f) marks "next", each side of the path: the onset
-// stage on the device (STALTAOnset._onset + lib.migrate's clip/log; stalta.py:491-583, onsetlib.c:35-148)
+// stage on the device (STALTAOnset._onset + lib.migrate's clip/log; stalta.py:491-583, onsetlib.c:35-148:
+// OnsetStage, the record the staged call and the pipeline share, and qm_engine_onsets)
 // and locate's post-reductions of the marginalised map (QuakeScan._calculate_location's array work,
 // scan.py:696-1077; the cubic RBF's fine-grid maximum, scan.py:777-812).
 #define QM_TU_WIDEN 1
@@ -43,7 +44,55 @@ int axis_taps(int n, double sgm, bool mirror, qm::Taps *t) {
 
 }  // namespace
 
-int launch_onset_stage(qm_engine *e, const qm::OnsetArgs &a) {
+// The onset stage (qm_engine.hpp): build checks the caller's arrays and puts them on the device, launch runs the two
+// kernels over the (step, trace)s and (step, row)s of a launch.  qm_engine_onsets is the staged call on the engine's
+// record; the pipeline (qm_stream.hip) holds a record of its own.
+int OnsetStage::build(qm_engine *e, const char *what, int repeat, int32_t n_traces_, int32_t t_samples,
+                      const int32_t *trace_row, int32_t n_rows_, const int32_t *nsta, const int32_t *nlta, int transform,
+                      int position, int32_t taper_pad, double min_onset_value) {
+    if (!trace_row || !nsta || !nlta) return fail("%s: NULL argument", what);
+    if (n_traces_ < 1 || n_rows_ < 1 || t_samples < 1) return fail("%s: empty input", what);
+    if (transform != 0 && transform != 1) return fail("%s: transform must be 0 (energy) or 1 (abs)", what);
+    if (position < 0 || position > 2)
+        return fail("%s: position must be 0 (classic), 1 (centred) or 2 (recursive)", what);
+    std::vector<int> per_row(n_rows_, 0);
+    for (int i = 0; i < n_traces_; ++i) {
+        if (trace_row[i] < 0 || trace_row[i] >= n_rows_) return fail("%s: trace %d: row out of range", what, i);
+        ++per_row[trace_row[i]];
+    }
+    for (int r = 0; r < n_rows_; ++r)
+        if (per_row[r] == 0) return fail("%s: onset row %d has no trace", what, r);
+    // everything `repeat` times, the rows of step k behind those of step k - 1
+    std::vector<int32_t> image;
+    for (int k = 0; k < repeat; ++k)
+        for (int i = 0; i < n_traces_; ++i) image.push_back(k * n_rows_ + trace_row[i]);
+    for (int k = 0; k < repeat; ++k) image.insert(image.end(), nsta, nsta + n_rows_);
+    for (int k = 0; k < repeat; ++k) image.insert(image.end(), nlta, nlta + n_rows_);
+    const size_t kt = (size_t)repeat * n_traces_, kr = (size_t)repeat * n_rows_;
+    if (meta.ensure(image.size()) || sta.ensure(kt * t_samples) || lta.ensure(kt * t_samples)) return 1;
+    QM_HIP(copy_in(meta.p, image.data(), image.size() * sizeof(int32_t), e->stream));
+    n_traces = n_traces_;
+    n_rows = n_rows_;
+    args = qm::OnsetArgs{};
+    args.trace_row = meta.p;
+    args.nsta = meta.p + kt;
+    args.nlta = meta.p + kt + kr;
+    args.sta = sta.p;
+    args.lta = lta.p;
+    args.T = t_samples;
+    args.transform = transform; args.position = position; args.taper_pad = taper_pad;
+    args.min_onset_value = min_onset_value;
+    return 0;
+}
+
+int OnsetStage::launch(qm_engine *e, const double *signals, double *raw_onsets, double *log_onsets,
+                       int n_steps) const {
+    qm::OnsetArgs a = args;
+    a.signals = signals;
+    a.raw = raw_onsets;
+    a.logged = log_onsets;
+    a.n_traces = n_steps * n_traces;
+    a.n_rows = n_steps * n_rows;
     // one workgroup per trace; the transformed trace lives in LDS if it fits (20 480 samples)
     const size_t lds = (size_t)a.T * sizeof(double);
     const int in_lds = lds <= 160 * 1024 ? 1 : 0;
@@ -65,20 +114,14 @@ int qm_engine_onsets(qm_engine *e, const double *signals, int signals_on_device,
                      const int32_t *nsta, const int32_t *nlta, int transform, int position,
                      int32_t taper_pad, double min_onset_value, double *raw_onsets,
                      double *log_onsets, int out_on_device) {
-    if (!e || !signals || !trace_row || !nsta || !nlta || !log_onsets)
-        return fail("qm_engine_onsets: NULL argument");
-    if (n_traces < 1 || n_rows < 1 || t_samples < 1) return fail("qm_engine_onsets: empty input");
-    if (transform != 0 && transform != 1) return fail("transform must be 0 (energy) or 1 (abs)");
-    if (position < 0 || position > 2)
-        return fail("position must be 0 (classic), 1 (centred) or 2 (recursive)");
-    std::vector<int> per_row(n_rows, 0);
-    for (int i = 0; i < n_traces; ++i) {
-        if (trace_row[i] < 0 || trace_row[i] >= n_rows) return fail("trace %d: row out of range", i);
-        ++per_row[trace_row[i]];
-    }
-    for (int r = 0; r < n_rows; ++r)
-        if (per_row[r] == 0) return fail("onset row %d has no trace", r);
+    if (!e || !signals || !log_onsets) return fail("qm_engine_onsets: NULL argument");
     DeviceGuard guard(e->device);
+    if (e->on_stage.build(e, "qm_engine_onsets", 1, n_traces, t_samples, trace_row, n_rows, nsta, nlta, transform,
+                          position, taper_pad, min_onset_value))
+        return 1;
+    // (the stage's image needs no wait: copy_in has consumed it when it returns.  The call has always drained the
+    // engine's stream before it enqueues its kernels, and keeps doing so)
+    QM_HIP(hipStreamSynchronize(e->stream));
     const size_t sig = (size_t)n_traces * t_samples, out = (size_t)n_rows * t_samples;
     const double *d_sig = signals;
     if (!signals_on_device) {
@@ -86,24 +129,6 @@ int qm_engine_onsets(qm_engine *e, const double *signals, int signals_on_device,
         QM_HIP(copy_in(e->d_sig.p, signals, sig * sizeof(double), e->stream));
         d_sig = e->d_sig.p;
     }
-    if (e->d_sta.ensure(sig) || e->d_lta.ensure(sig) ||
-        e->d_onset_meta.ensure((size_t)n_traces + 2 * n_rows))
-        return 1;
-    std::vector<int32_t> meta(trace_row, trace_row + n_traces);
-    meta.insert(meta.end(), nsta, nsta + n_rows);
-    meta.insert(meta.end(), nlta, nlta + n_rows);
-    QM_HIP(copy_in(e->d_onset_meta.p, meta.data(), meta.size() * sizeof(int32_t), e->stream));
-    QM_HIP(hipStreamSynchronize(e->stream));            // `meta` is a stack-lifetime buffer
-    qm::OnsetArgs a{};
-    a.signals = d_sig;
-    a.trace_row = e->d_onset_meta.p;
-    a.nsta = e->d_onset_meta.p + n_traces;
-    a.nlta = e->d_onset_meta.p + n_traces + n_rows;
-    a.sta = e->d_sta.p;
-    a.lta = e->d_lta.p;
-    a.n_traces = n_traces; a.n_rows = n_rows; a.T = t_samples;
-    a.transform = transform; a.position = position; a.taper_pad = taper_pad;
-    a.min_onset_value = min_onset_value;
     double *d_log = log_onsets, *d_raw = raw_onsets;
     if (!out_on_device) {
         if (e->d_onsets.ensure(out)) return 1;
@@ -113,9 +138,7 @@ int qm_engine_onsets(qm_engine *e, const double *signals, int signals_on_device,
             d_raw = e->d_raw.p;
         }
     }
-    a.raw = d_raw;
-    a.logged = d_log;
-    if (launch_onset_stage(e, a)) return 1;
+    if (e->on_stage.launch(e, d_sig, d_raw, d_log, 1)) return 1;
     if (!out_on_device) {
         QM_HIP(copy_back(log_onsets, d_log, out * sizeof(double), e->stream));
         if (raw_onsets)

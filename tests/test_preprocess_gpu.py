@@ -217,6 +217,58 @@ def test_pipeline_equals_the_staged_calls(lib, pipeline_case, K, replicas):
     assert np.ptp(want[0][0]) > 0                               # (not a flat series)
 
 
+def test_a_stream_and_its_engines_staged_calls_keep_their_own_stage(lib, pipeline_case):
+    """The stream's onset stage and the stage of the engine's own preprocess / onsets calls are two sets of device
+    arrays: staged calls with other arrays between the pushes change nothing in the stream, nor the stream in them."""
+    from quakemigrate_amd.stream import StreamingDetector
+
+    case, stage, signals, want = pipeline_case
+    T = case.onsets.shape[1]
+    sos = stable_sos(5, 2, 3)
+    left, right = np.linspace(0, 1, 15, endpoint=False), np.linspace(1, 0, 15, endpoint=False)
+    rows = np.array([0, 0, 1, 2, 2], dtype=np.int32)
+    nsta, nlta = np.array([4, 6, 5], dtype=np.int32), np.array([17, 23, 20], dtype=np.int32)
+    others = [pr.noisy_traces(31, 5, 301), pr.noisy_traces(33, 5, 64)]
+
+    def staged(e, x):
+        f = e.preprocess(x, TRACE_FILTER, sos, taper=(left, right))
+        raw, logged = e.onsets(f, rows, nsta, nlta, transform="abs", position="classic", taper_pad=3,
+                               min_onset_value=0.3)
+        return f, raw, logged
+
+    expect = []
+    for x in others:
+        fresh = lib.Engine(0)
+        try:
+            expect.append(staged(fresh, x))
+        finally:
+            fresh.close()
+    between = []
+    eng = lib.Engine(0)
+    try:
+        eng.load_lut(case.traveltimes)
+
+        def feed():
+            for k, x in enumerate(signals):
+                yield x
+                between.append((k % 2, staged(eng, others[k % 2])))     # (after step k's push, before the next)
+
+        det = StreamingDetector(eng, 6, T, case.fsmp, case.lsmp, case.available, depth=2, steps_per_launch=2,
+                                onset_stage=stage, sampling_rate=50)
+        got = det.run(feed())
+        det.close()
+    finally:
+        eng.close()
+    assert len(got) == N_STEPS and len(between) == N_STEPS
+    for step, (g, w) in enumerate(zip(got, want)):
+        for name, gs, ws in zip(("max_coa", "max_norm_coa", "max_coa_idx"), g, w):
+            assert np.array_equal(gs, ws), (step, name)
+    for step, (which, arrays) in enumerate(between):
+        for name, gs, ws in zip(("filtered", "raw", "logged"), arrays, expect[which]):
+            assert np.array_equal(gs, ws), (step, name)
+    assert np.ptp(expect[1][2]) > 0                             # (not a flat onset function)
+
+
 # -- 5. refusals --------------------------------------------------------------------------------------------------------
 def test_refusals_are_errors(lib, pipeline_case):
     from quakemigrate_amd.stream import StreamingDetector

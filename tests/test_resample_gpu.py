@@ -381,6 +381,59 @@ def test_push_raw_equals_resample_then_push_signals(lib, pipeline_case, K, repli
     assert np.ptp(want[0][0]) > 0                               # (not a flat series)
 
 
+@pytest.fixture(scope="module")
+def other_resamples(lib):
+    """The ragged float64 record sets of test_ragged_traces_device_resident_and_a_reused_engine, each with its result
+    on an engine of its own."""
+    out = []
+    for k, T in enumerate((64, 301, 33)):
+        _, raw, a = _ragged(T, 40 + k, np.float64)
+        fresh = lib.Engine(0)
+        try:
+            out.append((raw, a, fresh.resample(raw, a)))
+        finally:
+            fresh.close()
+    return out
+
+
+@pytest.mark.parametrize("replicas", [False, True], ids=["engine", "replicas"])
+def test_a_stream_and_its_engines_resample_calls_keep_their_own_stage(lib, pipeline_case, other_resamples, replicas):
+    """The stream's resampling stage (int32 raw traces) and the stage of the engine's own resample calls (other
+    records, float64) are two sets of device arrays: calls between the pushes change nothing in the stream, nor the
+    stream in them.  On replicas the calls run on the lead, which is lane 0's engine."""
+    from quakemigrate_amd.stream import StreamingDetector
+
+    case, onset, resample, raws, signals = pipeline_case
+    T = case.onsets.shape[1]
+    between = []
+    eng = lib.EngineReplicas([0, 0]) if replicas else lib.Engine(0)
+    try:
+        eng.load_lut(case.traveltimes)
+
+        def feed():
+            for k, step in enumerate(raws):
+                yield step
+                raw, a, _ = other_resamples[k % 3]              # (after step k's push, before the next)
+                between.append((k % 3, eng.resample(raw, a)))
+
+        kw = dict(depth=2, steps_per_launch=2, onset_stage=onset, sampling_rate=SCAN_RATE)
+        det = StreamingDetector(eng, 6, T, case.fsmp, case.lsmp, case.available, resample_stage=resample, **kw)
+        got = det.run(feed())
+        det.close()
+        det = StreamingDetector(eng, 6, T, case.fsmp, case.lsmp, case.available, **kw)
+        want = det.run(signals)
+        det.close()
+    finally:
+        eng.close()
+    assert len(got) == N_STEPS and len(want) == N_STEPS and len(between) == N_STEPS
+    for step, (g, w) in enumerate(zip(got, want)):
+        for name, gs, ws in zip(("max_coa", "max_norm_coa", "max_coa_idx"), g, w):
+            assert np.array_equal(gs, ws), (step, name)
+    for step, (which, out) in enumerate(between):
+        assert np.array_equal(out, other_resamples[which][2]), (step, which)
+    assert np.ptp(want[0][0]) > 0                               # (not a flat series)
+
+
 def test_pipeline_order_errors(lib, pipeline_case):
     from quakemigrate_amd.stream import StreamingDetector
 

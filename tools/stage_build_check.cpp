@@ -1,0 +1,168 @@
+// stage_build_check.cpp -- the three front-end stage records' build() on the CPU, under the sanitizers: their
+// refusals and the images they put on the "device" for repeat = 1 and 3.  A stand-alone host program: the runtime's
+// pool and copies are replaced below by malloc and memcpy, so no device is needed and every image lands in an
+// allocation of exactly the size build() asked for (an overrun is an AddressSanitizer report).  No kernel is launched.
+//
+//   cd quakemigrate_amd/csrc
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
+//         -Xarch_host -fno-sanitize-recover=undefined qm_preproc.hip qm_resample.hip qm_widen.hip \
+//         ../../tools/stage_build_check.cpp -o /tmp/stage_build_check && /tmp/stage_build_check
+//
+// Prints one line per stage and "stage_build_check: ok"; any mismatch or sanitizer report ends it with a non-zero status.
+#include "../quakemigrate_amd/csrc/qm_engine.hpp"
+
+static std::string g_error;
+int fail(const char *fmt, ...) {
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_error = buf;
+    return 1;
+}
+hipError_t pool_alloc(void **out, size_t bytes) {
+    *out = std::malloc(bytes);
+    return *out ? hipSuccess : hipErrorOutOfMemory;
+}
+void pool_free(void *p) { std::free(p); }
+hipError_t copy_in(void *dst, const void *src, size_t bytes, hipStream_t) {
+    std::memcpy(dst, src, bytes);
+    return hipSuccess;
+}
+hipError_t copy_back(void *dst, const void *src, size_t bytes, hipStream_t) {
+    std::memcpy(dst, src, bytes);
+    return hipSuccess;
+}
+PoolReleaseScope::PoolReleaseScope() {}
+PoolReleaseScope::~PoolReleaseScope() {}
+
+#define CHECK(cond)                                                                         \
+    do {                                                                                    \
+        if (!(cond)) {                                                                      \
+            std::fprintf(stderr, "stage_build_check: %s:%d: %s\n", __FILE__, __LINE__, #cond); \
+            std::exit(1);                                                                   \
+        }                                                                                   \
+    } while (0)
+#define REFUSED(call, text)                                        \
+    do {                                                           \
+        g_error.clear();                                           \
+        CHECK((call) != 0);                                        \
+        CHECK(g_error.find(text) != std::string::npos);            \
+    } while (0)
+
+int main() {
+    qm_engine *e = new qm_engine();
+    const int T = 100, n_traces = 5, n_rows = 3;
+
+    // -- pre-processing ------------------------------------------------------------------------------------------
+    const int32_t filter[n_traces] = {0, 1, 0, 1, 0};
+    std::vector<double> sos(2 * 2 * 6, 0.5), left(7, 0.25), right(4, 0.75);
+    for (int k = 0; k < 4; ++k) sos[6 * k + 3] = 1.0;
+    PreprocStage pre;
+    auto pre_build = [&](int repeat, const int32_t *f, const double *s, int n_sections, int n_left) {
+        return pre.build(e, "pre", repeat, n_traces, T, f, s, 2, n_sections, 1, left.data(), n_left, right.data(),
+                         (int)right.size(), 1);
+    };
+    REFUSED(pre_build(3, filter, sos.data(), 9, 7), "n_sections");
+    const int32_t bad_filter[n_traces] = {0, 1, 2, 1, 0};
+    REFUSED(pre_build(3, bad_filter, sos.data(), 2, 7), "out of range");
+    REFUSED(pre_build(3, filter, sos.data(), 2, T), "tapers cover");
+    std::vector<double> bad_sos = sos;
+    bad_sos[6 + 3] = 2.0;
+    REFUSED(pre_build(3, filter, bad_sos.data(), 2, 7), "a0");
+    REFUSED(pre_build(3, nullptr, sos.data(), 2, 7), "NULL");
+    for (int repeat : {3, 1, 3}) {                              // (grown, reused, reused)
+        CHECK(pre_build(repeat, filter, sos.data(), 2, 7) == 0);
+        for (int k = 0; k < repeat; ++k)
+            for (int i = 0; i < n_traces; ++i) CHECK(pre.args.trace_filter[k * n_traces + i] == filter[i]);
+        CHECK(std::equal(sos.begin(), sos.end(), pre.args.sos));
+        CHECK(std::equal(left.begin(), left.end(), pre.args.taper_left));
+        CHECK(std::equal(right.begin(), right.end(), pre.args.taper_right));
+        CHECK(pre.n_traces == n_traces && pre.args.T == T && pre.args.n_left == 7 && pre.args.n_right == 4);
+    }
+    std::printf("pre-processing: 5 refusals, images for repeat = 3, 1, 3\n");
+
+    // -- onsets --------------------------------------------------------------------------------------------------
+    const int32_t row[n_traces] = {0, 0, 1, 2, 2}, nsta[n_rows] = {4, 6, 5}, nlta[n_rows] = {17, 23, 20};
+    OnsetStage on;
+    auto on_build = [&](int repeat, const int32_t *r, int transform, int position) {
+        return on.build(e, "on", repeat, n_traces, T, r, n_rows, nsta, nlta, transform, position, 3, 0.3);
+    };
+    const int32_t orphan[n_traces] = {0, 0, 1, 1, 1}, outside[n_traces] = {0, 0, 1, 2, 3};
+    REFUSED(on_build(3, orphan, 0, 0), "row 2 has no trace");
+    REFUSED(on_build(3, outside, 0, 0), "trace 4: row out of range");
+    REFUSED(on_build(3, row, 2, 0), "transform");
+    REFUSED(on_build(3, row, 0, 3), "position");
+    REFUSED(on_build(3, nullptr, 0, 0), "NULL");
+    REFUSED(on.build(e, "on", 3, 0, T, row, n_rows, nsta, nlta, 0, 0, 3, 0.3), "empty input");
+    for (int repeat : {3, 1, 3}) {
+        CHECK(on_build(repeat, row, 1, 2) == 0);
+        for (int k = 0; k < repeat; ++k) {
+            for (int i = 0; i < n_traces; ++i) CHECK(on.args.trace_row[k * n_traces + i] == k * n_rows + row[i]);
+            for (int r = 0; r < n_rows; ++r)
+                CHECK(on.args.nsta[k * n_rows + r] == nsta[r] && on.args.nlta[k * n_rows + r] == nlta[r]);
+        }
+        CHECK(on.args.nsta == on.args.trace_row + repeat * n_traces && on.args.nlta == on.args.nsta + repeat * n_rows);
+        CHECK(on.sta.n >= (size_t)repeat * n_traces * T && on.lta.n >= (size_t)repeat * n_traces * T);
+        std::memset(on.args.sta, 0, (size_t)repeat * n_traces * T * sizeof(double));   // (all of it is the record's)
+        std::memset(on.args.lta, 0, (size_t)repeat * n_traces * T * sizeof(double));
+        CHECK(on.n_traces == n_traces && on.n_rows == n_rows && on.args.transform == 1 && on.args.position == 2);
+    }
+    std::printf("onsets: 6 refusals, images for repeat = 3, 1, 3\n");
+
+    // -- resampling: two traces, a pass-through slice and a decimation by 2; 251 raw samples (an odd count: an int32
+    //    step is rounded up to whole doubles)
+    using namespace qm;
+    const int n_rs = 2, total = 251;
+    int64_t rec[n_rs * kResampleFields] = {};
+    auto field = [&](int64_t *records, int i, int f) -> int64_t & { return records[i * kResampleFields + f]; };
+    for (int i = 0; i < n_rs; ++i) field(rec, i, kRsUp) = field(rec, i, kRsDec) = 1;
+    field(rec, 0, kRsRawOffset) = 0; field(rec, 0, kRsNRaw) = 50; field(rec, 0, kRsNUp) = 50;
+    field(rec, 1, kRsRawOffset) = 50; field(rec, 1, kRsNRaw) = 201; field(rec, 1, kRsNUp) = 201;
+    field(rec, 1, kRsDec) = 2;
+    const int32_t tapers[2] = {0, 10};
+    std::vector<double> lp(6, 0.5), weights(20, 0.5);
+    lp[3] = 1.0;
+    ResampleStage rs;
+    auto rs_build = [&](int repeat, int dtype, const int64_t *records, int t_samples) {
+        return rs.build(e, "rs", repeat, dtype, total, n_rs, t_samples, records, lp.data(), 1, 1, 1, tapers, 1,
+                        weights.data(), (int64_t)weights.size());
+    };
+    int64_t bad[n_rs * kResampleFields];
+    std::copy(std::begin(rec), std::end(rec), bad);
+    field(bad, 1, kRsDec) = 0;
+    REFUSED(rs_build(3, kRawInt32, bad, 50), "factors of at least 1");
+    std::copy(std::begin(rec), std::end(rec), bad);
+    field(bad, 1, kRsNRaw) = 202;
+    REFUSED(rs_build(3, kRawInt32, bad, 50), "leave the raw buffer");
+    REFUSED(rs_build(3, 2, rec, 50), "raw_dtype 2");
+    REFUSED(rs_build(3, kRawInt32, rec, 0), "empty input");
+    REFUSED(rs_build(3, kRawInt32, rec, 51), "decimated ones");
+    REFUSED(rs_build(3, kRawInt32, nullptr, 50), "NULL");
+    for (int dtype : {(int)kRawInt32, (int)kRawFloat64})
+        for (int repeat : {3, 1, 3}) {
+            CHECK(rs_build(repeat, dtype, rec, 50) == 0);
+            const int64_t step = dtype == kRawInt32 ? 252 : 251;        // raw elements between two steps
+            CHECK(rs.raw_bytes == (size_t)total * (dtype == kRawInt32 ? 4 : 8) && rs.raw_step == (rs.raw_bytes + 7) / 8);
+            for (int k = 0; k < repeat; ++k)
+                for (int i = 0; i < n_rs; ++i)
+                    for (int f = 0; f < kResampleFields; ++f)
+                        CHECK(rs.args.rec[(k * n_rs + i) * kResampleFields + f] ==
+                              field(rec, i, f) + (f == kRsRawOffset ? k * step : 0));
+            CHECK(rs.args.tapers == rs.args.rec + repeat * n_rs * kResampleFields);
+            CHECK(rs.args.tapers[0] == 0 && rs.args.tapers[1] == 10);
+            CHECK(std::equal(lp.begin(), lp.end(), rs.args.sos) && std::equal(weights.begin(), weights.end(), rs.args.taper_w));
+            CHECK(rs.max_kept == 201 && rs.args.scratch == nullptr && rs.args.scratch_stride == 0 && rs.n_traces == n_rs);
+        }
+    // no low-pass, no taper, no weights: the coefficient buffer is never empty
+    field(rec, 1, kRsDec) = 1;
+    CHECK(rs.build(e, "rs", 2, kRawFloat64, total, n_rs, 50, rec, nullptr, 0, 1, 0, nullptr, 0, nullptr, 0) == 0);
+    CHECK(rs.coef.n >= 1);
+    std::printf("resampling: 6 refusals, images for int32 and float64, repeat = 3, 1, 3\n");
+
+    pre.release(); on.release(); rs.release();
+    delete e;
+    std::printf("stage_build_check: ok\n");
+    return 0;
+}
