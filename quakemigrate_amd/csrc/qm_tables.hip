@@ -799,7 +799,9 @@ int qm_engine_serve(qm_engine *e, double sampling_rate, const int32_t *rows, int
     a.grids = e->d_grids.p;
     a.rows = e->d_rows.p;
     a.out = e->d_served.p;
-    // 256 nodes per workgroup while their rows fit 64 KB of LDS (up to 63 rows), else 64
+    // 256 nodes per workgroup while their rows fit 64 KB of LDS, else 64.  A node's row is padded to an odd
+    // pitch of S + 1 or S + 2 words, so 256 of them fit up to 62 rows (pitch 63); 63 and 64 rows (pitch 65)
+    // already take the 64-node kernel, which holds up to 254 rows (pitch 255)
     const int pitch = (n_rows + 1) | 1;
     const bool wide = (size_t)256 * pitch * sizeof(int32_t) <= 64 * 1024;
     const int npb = wide ? 256 : 64;
