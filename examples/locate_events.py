@@ -10,10 +10,12 @@ marginal_window``, trims the map to that window, marginalises it over time and f
 rules -- without the 4-D map: one fused detect launch over the event's window fixes the origin time, one
 marginal-map launch sums the window inside the stacking kernel.  With a ``picker`` the phase picks follow on the
 engine too (``quakemigrate_amd.picks.DevicePicker`` for the reference's ``GaussianPicker``: one launch over the
-event's onset rows).  Magnitudes and the event files remain the reference's (``on_event`` is where they would be
-called).  Everything here is synthetic and obspy-free.
+event's onset rows).  With ``--amplitudes`` the amplitude measurements of ``LocalMag`` follow as well
+(``quakemigrate_amd.amplitudes.DeviceAmplitude`` for the reference's ``Amplitude``, on synthetic Wood-Anderson traces).
+The magnitude algebra and the event files remain the reference's (``on_event`` is where they would be called).
+Everything here is synthetic and obspy-free.
 
-Run:  python examples/locate_events.py
+Run:  python examples/locate_events.py [--amplitudes]
 """
 
 import datetime as dt
@@ -29,12 +31,32 @@ if str(ROOT) not in sys.path:
 from quakemigrate_amd import picks, scan, synth  # noqa: E402
 
 
+WA_RATE = 100.0                                             # Hz, the synthetic Wood-Anderson traces
+WA_COMPONENTS = ("E", "N", "Z")
+
+
+def wa_trace(record, station, component, starttime, npts, arrivals):
+    """One synthetic Wood-Anderson displacement trace (metres): seeded noise with a decaying wavelet at each of the
+    ``arrivals`` (seconds after ``starttime``), the S wavelet three times the P one."""
+    rng = np.random.default_rng([record, station, WA_COMPONENTS.index(component)])
+    t = np.arange(npts) / WA_RATE
+    x = 2e-7 * rng.standard_normal(npts)
+    for k, at in enumerate(arrivals):
+        since = np.clip(t - at, 0.0, None)
+        x += (1 + 2 * k) * 4e-6 * since * np.exp(-3.0 * since) * np.sin(2 * np.pi * (6.0 - 2 * k) * since) * 8
+    return dict(id=f"XX.ST{station}..HH{component}", station=f"ST{station}", component=component,
+                starttime=starttime, sampling_rate=WA_RATE, data=x)
+
+
 def run(grid=(36, 32, 20), rows=12, rate=50, marginal_window=1.0, n_events=5, with_picker=True,
-        on_event=None):
+        on_event=None, amplitudes=None):
     """``n_events`` synthetic events, one per trigger, each somewhere inside a 12-s record; the trigger
     times are what a detect run would hand over: within a fraction of the marginal window of the truth.
     (The third record ends too early for its event's window: the archive raises, the event is dropped.)
-    ``with_picker=False`` stops after the location fits; ``on_event`` is handed to ``locate_compute``."""
+    ``with_picker=False`` stops after the location fits; ``on_event`` is handed to ``locate_compute``, as is
+    ``amplitudes`` (a ``quakemigrate_amd.amplitudes.DeviceAmplitude``: the amplitude table per event, measured on
+    synthetic Wood-Anderson traces -- three components per station, half a second longer than the window asked for on
+    either side)."""
     mw, spacing = marginal_window, 0.5
     n_win = int(4 * mw * rate) + 1
     cases = [synth.make_case("C3", step=10 + s, grid=grid, rows=rows, n_samples=600, n_events=1,
@@ -65,6 +87,18 @@ def run(grid=(36, 32, 20), rows=12, rate=50, marginal_window=1.0, n_events=5, wi
             d.onsets, d.starttime = cases[s].onsets[:, first:first + n], w_beg
             return d
 
+        def read_wa_waveforms(self, w_beg, w_end):
+            s = min(range(n_events), key=lambda k: abs((w_beg - record_start[k]).total_seconds()))
+            start = w_beg - dt.timedelta(seconds=0.5)
+            npts = int(round(((w_end - w_beg).total_seconds() + 1.0) * WA_RATE)) + 1
+            origin = (record_start[s] - start).total_seconds() + truth[s][1] / rate
+            xyz = np.asarray(truth[s][0], dtype=np.float64) * spacing
+            traces = []
+            for k in range(rows // 2):
+                tt = [np.sqrt(((c0.stations[row] - xyz) ** 2).sum()) / c0.velocities[row] for row in (k, k + rows // 2)]
+                traces += [wa_trace(s, k, comp, start, npts, [origin + v for v in tt]) for comp in WA_COMPONENTS]
+            return traces
+
     class OnsetData:
         sampling_rate = rate
         availability = dict.fromkeys(keys, 1)
@@ -89,6 +123,7 @@ def run(grid=(36, 32, 20), rows=12, rate=50, marginal_window=1.0, n_events=5, wi
     class Lut:
         node_spacing = np.array([spacing] * 3)
         fraction_tt = 0.1
+        max_traveltime = float(np.max(c0.traveltimes)) / rate
 
         def traveltime_to(self, phase, ijk, station):       # homogeneous velocities: no interpolation needed
             row = keys.index(f"{station}_{phase}")
@@ -103,13 +138,19 @@ def run(grid=(36, 32, 20), rows=12, rate=50, marginal_window=1.0, n_events=5, wi
 
     s = scan.MigrationScan(Lut(), Onset(), pre, post, stage="locate", scan_rate=rate)
     located = s.locate_compute(Archive(), triggers, mw, on_event=on_event,
-                               picker=picks.DevicePicker(s.onset) if with_picker else None)
+                               picker=picks.DevicePicker(s.onset) if with_picker else None, amplitudes=amplitudes)
     assert all(r["max_coa"].shape[0] <= n_win for r in located)
     return located, truth, record_start, rate
 
 
 if __name__ == "__main__":
-    located, truth, record_start, rate = run()
+    measure = None
+    if "--amplitudes" in sys.argv[1:]:                      # the step after the picks: the local-magnitude amplitudes
+        from quakemigrate_amd.amplitudes import DeviceAmplitude
+
+        measure = DeviceAmplitude({"signal_window": 1.0, "bandpass_filter": True, "bandpass_lowcut": 1.0,
+                                   "bandpass_highcut": 20.0})
+    located, truth, record_start, rate = run(amplitudes=measure)
     for r in located:
         k = int(r["uid"].split("_")[1])
         (node, t0), start = truth[k], record_start[k]
@@ -124,3 +165,7 @@ if __name__ == "__main__":
                     else f"no pick (status {p['status'][i]})")
             print(f"    {p['Station'][i]} {p['Phase'][i]}: modelled "
                   f"{(p['ModelledTime'][i] - start).total_seconds():.3f} s, {made}")
+        a = r.get("amplitudes")
+        for i in range(len(a["id"]) if a else 0):
+            print(f"    {a['id'][i]}: P {a['P_amp'][i]:.4g} mm at {a['P_freq'][i]:.3g} Hz, S {a['S_amp'][i]:.4g} mm at "
+                  f"{a['S_freq'][i]:.3g} Hz, noise {a['Noise_amp'][i]:.3g} mm, picked {a['is_picked'][i]}")

@@ -211,6 +211,7 @@ int qm_engine_synchronize(qm_engine *e);
  * after a launch of the direct kernel alone (force_direct, every brick too wide) last_kernel and last_kernel_j are 0.
  * table_hits, table_misses, table_evictions, tables_parked, table_bytes, tables_parked_bytes, table_digests;
  * pick_lds_samples (the longest onset row qm_engine_pick_phases takes: row and selection keys live in LDS);
+ * amp_lds_samples (the longest window qm_engine_measure_amplitudes keeps in LDS; longer ones work from scratch);
  * the trigger stage's compile-time tunables (csrc/qm_trigger.hpp): trigger_max_radius (the largest smoothing radius
  * qm_engine_trigger takes), trigger_smooth_tile, trigger_run_block, trigger_merge_stride; with the key
  * trigger_timing (0 / 1 [0], measurement: HIP events around every stage of qm_engine_trigger) set, the last call's
@@ -515,6 +516,82 @@ int qm_engine_pick_phases(qm_engine *e, const double *onsets, int onsets_on_devi
                           int threshold_mode, double mad_multiplier, const double *thresholds_in,
                           double *picks, int32_t *status);
 
+/* Local-magnitude amplitudes on the device -- the step after the picks: what Amplitude.get_amplitudes does to every
+ * component trace of a located event (quakemigrate/signal/local_mag/amplitude.py:174-371; the rules on arrays:
+ * tests/amplitudes_ref.py).  Wood-Anderson displacement traces go in (response removal stays with the caller), each at
+ * its own rate and length, packed into one buffer of float64 samples, host or device; every other array is a host
+ * array.  Two launches.
+ *   trace_records  [n_traces][4] int64: 0 offset, 1 n -- its samples x[0..n) in the buffer (elements), n >= 1;
+ *                  2 filter: an index into sos [n_filters][n_sections][6] (SciPy's layout, a0 == 1), -1: none;
+ *                  3 taper: an index into taper_table [n_tapers][2] = (offset, m) laid out as qm_engine_resample's,
+ *                  -1: none (read only where the trace has a filter).  Traces may share samples only where neither
+ *                  of them has a filter (stage A filters in place in the engine's working copy).
+ *   window_records [n_windows][4] int64: 0 trace, 1 lo, 2 hi -- samples [lo, hi) of that trace; 3 kind: 0 noise,
+ *                  1 signal.  Records are independent: the rows of several events may share a call.
+ * Stage A, per trace whose filter is >= 0, one workgroup (_filter_trace, amplitude.py:413-539):
+ *   1. the least-squares line over t = 0..n-1 subtracted in the centred form of qm_engine_preprocess' step 1, the
+ *      LINE ONLY (the reference calls detrend("linear") alone, :478, :529); the same fixed-order sums.
+ *   2. x[k] *= w[k], x[n - m + k] *= w[m + k] for k < m with w the taper's weights.
+ *   3. ONE forward pass of the cascade from a zero state (zerophase=False): scipy.signal.sosfilt's bits, as in
+ *      qm_engine_preprocess.  "preproc_skew" = 0 selects the plain filter form here too.
+ *   The trace lives in LDS up to 20 480 samples, else in the engine's working copy: the same bits.  Traces without a
+ *   filter are measured as given.  filtered_out (optional, f64 [total_samples], host): every trace as stage B saw it.
+ * Stage B, per window record, one wavefront, y = samples [lo, hi) of the record's trace:
+ *   1. hi == lo: status 1.  A non-finite sample: status 5.
+ *   2. kind 0 (noise, :954-962): max(y) == min(y): status 1 -- tested BEFORE the detrend; then the detrend and the
+ *      average.  kind 1 (signal, :763-817): the detrend first, then max(y) == min(y) on the detrended samples: status 1.
+ *   3. the detrend (detrend_windows = 1): y[i] = x[i] - (mean + slope (i - tbar)), tbar = (n - 1) / 2, slope =
+ *      sum (i - tbar)(x[i] - mean) / sum (i - tbar)^2 (0 where n == 1), three fixed-order sums, no second demean.
+ *      detrend_windows = 0: the window is measured as it is.
+ *   4. the average: average_method 0 RMS sqrt(mean(y^2)), 1 STD sqrt(mean(|y - mean(y)|^2)), fixed-order sums; and
+ *      max|y|.
+ *   5. kind 1: peaks as scipy.signal.find_peaks gives them (_local_maxima_1d): a sample, or a plateau of equal
+ *      samples, strictly above both neighbours counts once, at (left + right) / 2 rounded down; a window's first and
+ *      last sample are never peaks.  Troughs: the same on -y.
+ *   6. prominence_multiplier > 0: a peak stays if its prominence is >= prominence_multiplier * max|y|
+ *      (_peak_prominences without wlen: to each side walk from the peak until a sample HIGHER than it or the window's
+ *      end, take the minimum over each walk; the prominence is the peak minus the larger of the two minima); troughs
+ *      the same on -y.  With the multiplier 0 nothing is computed.
+ *   7. pairing (:862-901, in its order), P peaks and T troughs in sample order: P == 0 or T == 0: status 2.
+ *      P == T == 1: full = |y[p0] - y[t0]|; full == 0: status 4.  P == T: (a, b) = (peaks, troughs) and, where
+ *      p0 < t0, (c, d) = (peaks[1:], troughs[:-1]), else (peaks[:-1], troughs[1:]).  |P - T| != 1: status 3.
+ *      P > T: p0 < t0 or status 3; (a, b, c, d) = (peaks[:-1], troughs, peaks[1:], troughs).  P < T: p0 > t0 or status
+ *      3; (a, b, c, d) = (peaks, troughs[1:], peaks, troughs[:-1]).  fp1 = |y[a] - y[b]|, fp2 = |y[c] - y[d]|;
+ *      max fp1 >= max fp2: the FIRST argmax of fp1 gives the pair, else the first argmax of fp2.
+ * values [n_windows][4] f64: 0 full peak-to-trough |y[p] - y[t]| (input units; 0 without a measurement), 1 the average
+ * (input units), 2 max|y|, 3 reserved: 0.  Columns 1 and 2 are written for status 0, 2, 3, 4 (the caller applies the
+ * reference's `continue`), 0 for status 1 and 5.
+ * index [n_windows][4] i32: 0 status, 1 peak sample, 2 trough sample (both counted from the trace's first sample, -1
+ * without a measurement), 3 peaks kept (0 for kind 0).
+ * status: 0 measured; 1 empty or flat; 2 no peak or no trough; 3 "consecutive peaks/troughs", both of the reference's
+ * cases; 4 one peak and one trough of equal value (a DEVIATION: the reference's `if not full_amp` falls through to
+ * unbound names there and raises UnboundLocalError.  It cannot occur on finite samples: between such a peak and
+ * trough, say the peak first, the samples fall below their common value v and rise above it again, so the highest
+ * of them, M > v, is a peak; both of its prominence walks pass samples <= v, so its prominence is >= M - v, while the
+ * trough's left walk meets nothing above M and its prominence is <= M - v: the peak at M is kept whenever the trough
+ * is, and there are two peaks.  The status is a guard); 5 a non-finite sample in the window (a DEVIATION: the reference's
+ * result there is an accident of comparisons with NaN).
+ * A window keeps its samples and its extremum lists in LDS up to "amp_lds_samples" samples (qm_engine_get), above
+ * that in engine scratch: the same results.  All reductions and the ordered compaction of the extrema are fixed-order
+ * (lane-strided sums, ballots and prefix counts, no atomics): a call gives the same bits every time.
+ * Not here: the envelope average (noise_measure "ENV": scipy.signal.hilbert stays with the caller, as for the "env"
+ * onset transforms, see qm_engine_onsets), the units, frequencies, times and the filter gain (quakemigrate_amd/
+ * amplitudes.py).
+ * Refused, with the outputs untouched: a NULL argument (sos, taper_table, taper_weights may be NULL where their count
+ * is 0; filtered_out is optional), n_traces < 1, n_windows < 1, total_samples < 1, a trace with n < 1 or that leaves
+ * the buffer, a window whose trace is out of range, that leaves its trace or has lo > hi, a kind other than 0 / 1, an
+ * average_method or detrend_windows other than 0 / 1, a negative or non-finite prominence_multiplier, n_sections
+ * outside 1..8, a section whose a0 is not 1, a filter or taper index out of range (below -1 included), a taper that
+ * leaves taper_weights, a filtered trace whose taper has 2 m > n, a filtered trace that shares samples with another
+ * trace.  qm_engine_last_kernel_ms reports the two launches. */
+int qm_engine_measure_amplitudes(qm_engine *e, const double *traces, int traces_on_device, int64_t total_samples,
+                                 int32_t n_traces, const int64_t *trace_records, const double *sos, int32_t n_filters,
+                                 int32_t n_sections, const int32_t *taper_table, int32_t n_tapers,
+                                 const double *taper_weights, int64_t n_taper_weights, int32_t n_windows,
+                                 const int64_t *window_records, int detrend_windows, int average_method,
+                                 double prominence_multiplier, double *values /*[n_windows][4]*/,
+                                 int32_t *index /*[n_windows][4]*/, double *filtered_out);
+
 /* Trigger on the device -- the step between the detect sweep and the location: what Trigger._trigger_batch does to
  * the coalescence series of a batch (quakemigrate/signal/trigger.py:318-638; the rules on arrays:
  * tests/trigger_ref.py).  coa, coa_n: f64 [n], host arrays, uniformly sampled, already cut to the batch and its pads.
@@ -650,7 +727,8 @@ int qm_stream_create_replicas(qm_engine *const *engines, int32_t n_engines, int3
 
 /* Duration (ms, HIP events on the engine stream) of the stacking kernel(s) of
  * the most recent detect / migrate call, or of the kernel of a more recent
- * qm_engine_pick_phases or qm_engine_resample; negative if none.  Synchronises. */
+ * qm_engine_pick_phases or qm_engine_resample, or of the two launches of a more recent
+ * qm_engine_measure_amplitudes; negative if none.  Synchronises. */
 int qm_engine_last_kernel_ms(qm_engine *e, double *ms);
 
 /* With config "log_timing" = 1 every stacking launch is bracketed by its own

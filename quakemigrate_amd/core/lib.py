@@ -122,7 +122,9 @@ qmlib.qm_engine_resample.argtypes = [_vp, _vp, ctypes.c_int, ctypes.c_int, c_int
                                      ctypes.c_int]
 qmlib.qm_engine_pick_phases.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32, _vp, _vp, ctypes.c_double, _vp,
                                         ctypes.c_int, ctypes.c_double, _vp, _vp, _vp]
-
+qmlib.qm_engine_measure_amplitudes.argtypes = [_vp, _vp, ctypes.c_int, c_int64, c_int32, c_i64Pt, c_dPt, c_int32,
+                                               c_int32, c_i32Pt, c_int32, c_dPt, c_int64, c_int32, c_i64Pt,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, _vp, _vp]
 
 class TriggerParams(ctypes.Structure):
     """``qm_trigger_params`` (include/qmhip.h)."""
@@ -825,6 +827,61 @@ class Engine:
             _host(halfwidth), int(threshold_mode), float(mad_multiplier), pt, _host(picks), _host(status)))
         return picks, status
 
+    AVERAGE_METHODS = {"RMS": 0, "STD": 1}
+
+    def measure_amplitudes(self, traces, trace_records, window_records, sos=None, taper_table=None,
+                           taper_weights=None, detrend_windows=True, average_method="RMS", prominence_multiplier=0.0,
+                           want_filtered=False):
+        """
+        Local-magnitude amplitudes on the GPU, the step after the picks (``Amplitude.get_amplitudes``' filter, window
+        detrend, ``find_peaks``, peak/trough pairing and average per component trace, amplitude.py:174-371;
+        include/qmhip.h: ``qm_engine_measure_amplitudes``).  ``traces``: the packed 1-D float64 samples of every
+        trace, host array or device tensor like :meth:`pick_phases`, or a list of 1-D arrays that is packed here in
+        the records' order; ``trace_records`` (n_traces, 4) int64 ``[offset, n, filter (-1: none), taper (-1:
+        none)]`` -- a trace with a filter shares no sample with another trace --; ``window_records`` (n_windows, 4) int64 ``[trace, lo, hi, kind (0 noise, 1 signal)]``; ``sos``
+        (n_filters, n_sections, 6), SciPy's layout with ``a0 == 1``; ``taper_table`` (n_tapers, 2) int32 and
+        ``taper_weights`` as :meth:`resample` takes them.  Returns ``(values (n_windows, 4) float64, index
+        (n_windows, 4) int32)`` -- values: full peak-to-trough, average, max|y|, 0; index: status, peak sample, trough
+        sample, peaks kept -- and with ``want_filtered`` the packed traces as the windows were cut from them as a
+        third entry.
+        """
+        trace_records = np.ascontiguousarray(trace_records, dtype=np.int64)
+        window_records = np.ascontiguousarray(window_records, dtype=np.int64)
+        if trace_records.ndim != 2 or trace_records.shape[1] != 4:
+            raise ValueError(f"trace_records of shape {trace_records.shape}: (n_traces, 4) expected")
+        if window_records.ndim != 2 or window_records.shape[1] != 4:
+            raise ValueError(f"window_records of shape {window_records.shape}: (n_windows, 4) expected")
+        if average_method not in self.AVERAGE_METHODS:
+            raise ValueError(f"average_method must be 'RMS' or 'STD', got {average_method!r} (the envelope average "
+                             "stays on the host: quakemigrate_amd.amplitudes)")
+        if isinstance(traces, (list, tuple)):
+            total = int(max((r[0] + r[1] for r in trace_records), default=0))
+            packed = np.zeros(total)
+            for r, x in zip(trace_records, traces):
+                if len(x) != r[1]:
+                    raise ValueError(f"a trace of {len(x)} samples where its record says {r[1]}")
+                packed[r[0]:r[0] + r[1]] = x
+            traces = packed
+        total = int(traces.numel() if hasattr(traces, "numel") else traces.size)
+        pt, dev = self._ptr(traces, np.float64)
+        sos = np.zeros((0, 1, 6)) if sos is None else np.ascontiguousarray(sos, dtype=np.float64)
+        if sos.ndim != 3 or sos.shape[2] != 6:
+            raise ValueError(f"sos of shape {sos.shape}: (n_filters, n_sections, 6) expected")
+        table = np.ascontiguousarray(np.zeros((0, 2)) if taper_table is None else taper_table, dtype=np.int32)
+        weights = np.ascontiguousarray([] if taper_weights is None else taper_weights, dtype=np.float64).reshape(-1)
+        if table.ndim != 2 or table.shape[1] != 2:
+            raise ValueError(f"taper_table of shape {table.shape}: (n_tapers, 2) expected")
+        n_windows = len(window_records)
+        values, index = np.zeros((n_windows, 4)), np.zeros((n_windows, 4), dtype=np.int32)
+        filtered = np.zeros(total) if want_filtered else None
+        _check(qmlib.qm_engine_measure_amplitudes(
+            self._h, pt, dev, total, len(trace_records), trace_records.reshape(-1), sos.reshape(-1), int(sos.shape[0]),
+            int(sos.shape[1]), table.reshape(-1), len(table), weights, len(weights), n_windows,
+            window_records.reshape(-1), 1 if detrend_windows else 0, self.AVERAGE_METHODS[average_method],
+            float(prominence_multiplier), _host(values), _host(index),
+            _host(filtered) if want_filtered else _vp(None)))
+        return (values, index, filtered) if want_filtered else (values, index)
+
     TRIGGER_METHODS = {"static": 0, "mad": 1, "median_ratio": 2}
 
     def trigger_series(self, coa, coa_n, period_ns, mw_ns, mei_ns, trigger_on=0, method="static", value=1.5,
@@ -1238,6 +1295,9 @@ class EngineReplicas:
 
     def pick_phases(self, *args, **kwargs):
         return self.lead.pick_phases(*args, **kwargs)
+
+    def measure_amplitudes(self, *args, **kwargs):
+        return self.lead.measure_amplitudes(*args, **kwargs)
 
     def trigger_series(self, *args, **kwargs):
         return self.lead.trigger_series(*args, **kwargs)

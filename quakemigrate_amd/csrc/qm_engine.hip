@@ -771,6 +771,8 @@ void qm_engine_destroy(qm_engine *e) {
     e->rs_stage.release(); e->pre_stage.release(); e->on_stage.release();
     e->d_sig.release(); e->d_raw.release(); e->d_pre_out.release(); e->d_rs_raw.release();
     e->d_pick_val.release(); e->d_pick_meta.release();
+    e->d_amp_work.release(); e->d_amp_scratch.release(); e->d_amp_coef.release(); e->d_amp_val.release();
+    e->d_amp_meta.release(); e->d_amp_idx.release();
     e->d_trg_x.release(); e->d_trg_par.release(); e->d_trg_val.release(); e->d_trg_cnt.release();
     e->d_trg_run.release(); e->d_trg_tot.release(); e->d_trg_cand.release();
     e->d_scalar.release(); e->d_digest.release();
@@ -967,6 +969,7 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     else if (k == "stream_pull") *v = e->cfg_stream_pull;
     else if (k == "preproc_skew") *v = e->cfg_preproc_skew;
     else if (k == "pick_lds_samples") *v = qm::kPicksLdsSamples;
+    else if (k == "amp_lds_samples") *v = qm::kAmpLdsSamples;
     else if (k == "trigger_max_radius") *v = qm::kTrigMaxRadius;
     else if (k == "trigger_timing") *v = e->cfg_trigger_timing;
     else if (k == "trigger_ns_smooth") *v = e->trg_ns[qm::kTrigSmooth];

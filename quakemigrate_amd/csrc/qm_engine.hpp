@@ -19,6 +19,8 @@
 //                    engine's staged call, which lives beside it, and the pipeline
 //   qm_picks.hip     the row after the location: phase picks, a Gaussian fitted to every onset row of an event
 //   qm_trigger.hip   the row after the detect sweep: coalescence series in, triggered events out
+//   qm_amplitudes.hip  the row after the picks: local-magnitude amplitudes, filtered traces and time windows in,
+//                    peak-to-trough measurements out
 //   qm_compat.hip    the five reference-signature symbols (qmlib.h:28-44)
 //   qm_group.hip     engine groups: one process driving the boxes of a column partition on several devices
 // Everything declared here lives in the library only (hidden visibility).
@@ -50,6 +52,7 @@
 #include "qm_resample.hpp"
 #include "qm_picks.hpp"
 #include "qm_trigger.hpp"
+#include "qm_amplitudes.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -411,6 +414,11 @@ struct qm_engine : TableState {
     // phase-pick stage scratch: half-widths, thresholds and picks; windows, groups and status
     DevBuf<double> d_pick_val;
     DevBuf<int32_t> d_pick_meta;
+    // amplitude stage scratch: the working copy of the packed traces, windows above the LDS limit; trace records, taper
+    // table and window records; sections and taper weights; the two output tables
+    DevBuf<double> d_amp_work, d_amp_scratch, d_amp_coef, d_amp_val;
+    DevBuf<int64_t> d_amp_meta;
+    DevBuf<int32_t> d_amp_idx;
     // trigger stage scratch: the two series (raw, then smoothed), weights and thresholds, the run kernels' counts and
     // totals; sized once the candidate count is known: run starts and ends, candidate and event tables, their values
     DevBuf<double> d_trg_x, d_trg_par, d_trg_val;

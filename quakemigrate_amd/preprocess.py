@@ -64,6 +64,24 @@ def butter_lowpass_sos(freq, sampling_rate, corners=2):
     return np.ascontiguousarray(zpk2sos(z, p, k), dtype=np.float64)
 
 
+def butter_highpass_sos(freq, sampling_rate, corners):
+    """
+    Second-order sections (n_sections, 6) of the Butterworth high-pass the reference's amplitude measurement filters
+    with (amplitude.py:500-539), built as obspy's ``highpass`` builds them: ``scipy.signal.iirfilter(corners,
+    freq / nyquist, btype="highpass", ftype="butter", output="zpk")``, then ``zpk2sos``; ``corners`` corners give
+    ``ceil(corners / 2)`` sections.  Raises ``ImportError`` without SciPy and ``ValueError`` for a ``freq`` at or above
+    the Nyquist frequency.
+    """
+    from scipy.signal import iirfilter, zpk2sos
+
+    nyquist = 0.5 * float(sampling_rate)
+    if not 0.0 < float(freq) < nyquist:
+        raise ValueError(f"high-pass corner {freq} Hz: it must lie between 0 and the Nyquist frequency {nyquist} Hz "
+                         f"of {sampling_rate} Hz data")
+    z, p, k = iirfilter(int(corners), float(freq) / nyquist, btype="highpass", ftype="butter", output="zpk")
+    return np.ascontiguousarray(zpk2sos(z, p, k), dtype=np.float64)
+
+
 def cosine_taper_sides(npts, max_percentage=0.05):
     """
     The two ramps ``(left, right)`` of a cosine taper over ``int(max_percentage * npts)`` samples on each end:

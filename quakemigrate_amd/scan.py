@@ -454,7 +454,7 @@ class MigrationScan:
         drain()
 
     def locate_compute(self, archive, triggers, marginal_window, sgm=0.8, cov_thresh=0.90, on_event=None,
-                       picker=None):
+                       picker=None, amplitudes=None):
         """
         ``QuakeScan._locate_events``' loop around the path (reference scan.py:472-545), up to and including
         ``_calculate_location``: per triggered event read ``trigger_time -/+ (2 * marginal_window + pad)``
@@ -485,11 +485,25 @@ class MigrationScan:
         taper windows set to 1 (``onset.calculate_onsets(data, timespan=4 * marginal_window)``, gaussian.py:142-144),
         the hypocentre is the spline location, the traveltimes are ``lut.traveltime_to(phase, ijk, station)`` per
         row, and the result gets ``"picks"`` (the picker's table) before ``on_event`` sees it.
+
+        ``amplitudes`` (:class:`quakemigrate_amd.amplitudes.DeviceAmplitude`): the step after that, the amplitude
+        measurements of ``LocalMag.calc_magnitude`` (local_mag/amplitude.py:174-371), on the engine as well.  The
+        archive's ``read_wa_waveforms(otime - pre_pad, otime + post_pad)`` -- the pads of ``amplitudes.pad(
+        marginal_window, lut.max_traveltime, lut.fraction_tt)`` -- returns the Wood-Anderson displacement traces
+        (``id, station, component, starttime, sampling_rate, data``; response removal is the archive's); the
+        hypocentre is the location named by ``amplitudes.loc_method``, the traveltimes are the lookup table's, the
+        picks are ``result["picks"]`` where a picker ran and the modelled times otherwise, and the result gets
+        ``"amplitudes"`` (the reference's table as a dict of columns) before ``on_event`` sees it.
         """
         from quakemigrate_amd import locate
 
         if self.stage != "locate":
             raise ValueError("locate_compute is the locate stage's loop")
+        if amplitudes is not None and not hasattr(archive, "read_wa_waveforms"):
+            raise ValueError("locate_compute(amplitudes=...): the archive has no read_wa_waveforms(starttime, endtime) "
+                             "(the Wood-Anderson displacement traces of a window)")
+        if amplitudes is not None and amplitudes.loc_method not in ("spline", "gaussian", "covariance"):
+            raise ValueError(f"loc_method must be 'spline', 'gaussian' or 'covariance', got {amplitudes.loc_method!r}")
         mw = float(marginal_window)
         results = []
         triggers = list(triggers)
@@ -556,6 +570,8 @@ class MigrationScan:
             }
             if picker is not None:
                 result["picks"] = self._pick_phases(picker, eng, data, onset_data, result, mw)
+            if amplitudes is not None:
+                result["amplitudes"] = self._measure_amplitudes(amplitudes, eng, archive, onset_data, result, mw)
             results.append(result)
             if on_event is not None:
                 on_event(result)
@@ -574,6 +590,36 @@ class MigrationScan:
         return picker.pick(eng, raw_onsets, keys, getattr(raw_data, "starttime", data.starttime),
                            raw_data.sampling_rate, result["otime"], mw, traveltimes,
                            fraction_tt=getattr(self.lut, "fraction_tt", None))
+
+    def _hypocentre_ijk(self, fits, loc_method):
+        """The location estimate named by the reference's ``loc_method`` as fractional grid indices: the spline and
+        Gaussian fits are that already; the covariance fit's is its expectation, xyz from the grid's lower-left corner
+        (``LocationFits.expectation``), over the node spacing."""
+        if loc_method in ("spline", "gaussian"):
+            ijk = np.asarray(getattr(fits, loc_method), dtype=np.float64)
+        elif loc_method == "covariance":
+            ijk = np.asarray(fits.expectation, dtype=np.float64) / np.asarray(self.lut.node_spacing, dtype=np.float64)
+        else:
+            raise ValueError(f"loc_method must be 'spline', 'gaussian' or 'covariance', got {loc_method!r}")
+        if ijk.shape != (3,):
+            raise ValueError(f"the {loc_method} location has shape {ijk.shape}, (3,) expected")
+        return ijk
+
+    def _measure_amplitudes(self, amplitudes, eng, archive, onset_data, result, mw):
+        """The located event's amplitude table: one call over its Wood-Anderson traces
+        (``DeviceAmplitude.get_amplitudes``).  ``distance_fn``, where the measurer has one, is handed the hypocentre
+        as fractional grid indices (``ev_loc``): the transform to geographic coordinates is the caller's, with its
+        lookup table."""
+        fraction_tt = self.lut.fraction_tt
+        pre_pad, post_pad = amplitudes.pad(mw, self.lut.max_traveltime, fraction_tt)
+        tr_start, tr_end = _shift(result["otime"], -float(pre_pad)), _shift(result["otime"], float(post_pad))
+        wa_traces = archive.read_wa_waveforms(tr_start, tr_end)
+        stations = list(dict.fromkeys(key.rpartition("_")[0] for key in onset_data.availability))
+        ijk = self._hypocentre_ijk(result["fits"], amplitudes.loc_method)
+        p_tt, s_tt = ([float(np.ravel(self.lut.traveltime_to(phase, ijk, station))[0]) for station in stations]
+                      for phase in ("P", "S"))
+        return amplitudes.get_amplitudes(eng, wa_traces, stations, result.get("picks"), result["otime"], mw, p_tt,
+                                         s_tt, fraction_tt, ev_loc=ijk, tr_start=tr_start, tr_end=tr_end)
 
     def marginal_coalescence(self, data, first_sample, end_sample):
         """
