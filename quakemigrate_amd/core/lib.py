@@ -187,6 +187,35 @@ qmlib.qm_group_part_info.argtypes = [_vp, c_int32, _i32p, _i32p, _i32p, ctypes.P
 RAW_DTYPES = {np.dtype(np.int32): 0, np.dtype(np.float64): 1}       # qm_engine_resample's raw_dtype
 
 
+def _sections(sos, name="sos", count="n_filters"):
+    """``sos`` as the contiguous float64 (n, n_sections, 6) array the C ABI takes."""
+    sos = np.ascontiguousarray(sos, dtype=np.float64)
+    if sos.ndim != 3 or sos.shape[2] != 6:
+        raise ValueError(f"{name} of shape {sos.shape}: ({count}, n_sections, 6) expected")
+    return sos
+
+
+def _taper_arrays(table, weights):
+    """A taper table (n_tapers, 2) int32 and its weights, float64 and flat; ``None``: none."""
+    table = np.ascontiguousarray(np.zeros((0, 2)) if table is None else table, dtype=np.int32)
+    weights = np.ascontiguousarray([] if weights is None else weights, dtype=np.float64).reshape(-1)
+    if table.ndim != 2 or table.shape[1] != 2:
+        raise ValueError(f"taper_table of shape {table.shape}: (n_tapers, 2) expected")
+    return table, weights
+
+
+def _pack_by_records(traces, offsets, lengths, total, dtype, refuse):
+    """A list of traces as one packed array of ``total`` elements, trace i at ``offsets[i]``.  ``refuse(i, x, fits)``
+    raises the caller's error for a trace it does not take; ``fits``: x is the 1-D array of ``lengths[i]`` samples that
+    its record plans, inside the packed array."""
+    packed = np.zeros(total, dtype=dtype)
+    for i, (x, off, n) in enumerate(zip(traces, offsets, lengths)):
+        x = np.asarray(x)
+        refuse(i, x, x.ndim == 1 and len(x) == n and off >= 0 and off + n <= total)
+        packed[off:off + n] = x
+    return packed
+
+
 def resample_arrays(stage, t_samples=None):
     """The checked, contiguous arrays of a resampling stage -- a :class:`quakemigrate_amd.preprocess.ResampleStage`
     (then ``t_samples`` is needed) or the dict its ``arrays(t_samples)`` returns -- in the order the C ABI takes them:
@@ -197,13 +226,10 @@ def resample_arrays(stage, t_samples=None):
         stage = stage.arrays(int(t_samples))
     a = stage
     records = np.ascontiguousarray(a["records"], dtype=np.int64)
-    sos = np.ascontiguousarray(a["sos_lp"], dtype=np.float64)
-    table = np.ascontiguousarray(a["taper_table"], dtype=np.int32).reshape(-1, 2)
-    weights = np.ascontiguousarray(a["taper_weights"], dtype=np.float64).reshape(-1)
     if records.ndim != 2 or records.shape[1] != 11:
         raise ValueError(f"records of shape {records.shape}: (n_traces, 11) expected")
-    if sos.ndim != 3 or sos.shape[2] != 6:
-        raise ValueError(f"sos_lp of shape {sos.shape}: (n_lowpass, n_sections, 6) expected")
+    sos = _sections(a["sos_lp"], "sos_lp", "n_lowpass")
+    table, weights = _taper_arrays(np.reshape(a["taper_table"], (-1, 2)), a["taper_weights"])
     if t_samples is not None and int(a["t_samples"]) != int(t_samples):
         raise ValueError(f"the stage was planned for windows of {a['t_samples']} samples, not {t_samples}")
     total = a.get("total_raw_samples")
@@ -219,15 +245,15 @@ def pack_raw(raw, records, total, dtype=None):
         if len(raw) != len(records):
             raise ValueError(f"{len(raw)} raw traces, the stage plans {len(records)}")
         kind = np.dtype(dtype) if dtype is not None else np.result_type(*[np.asarray(x).dtype for x in raw])
-        packed = np.zeros(total, dtype=kind)
-        for i, (x, rec) in enumerate(zip(raw, records)):
-            x = np.asarray(x)
-            if x.ndim != 1 or len(x) != rec[1] or rec[0] < 0 or rec[0] + rec[1] > total:
-                raise ValueError(f"raw trace {i} of shape {x.shape}: the stage plans {int(rec[1])} samples for it")
+
+        def refuse(i, x, fits):
+            if not fits:
+                n = int(records[i][1])
+                raise ValueError(f"raw trace {i} of shape {x.shape}: the stage plans {n} samples for it")
             if x.dtype != kind:
                 raise TypeError(f"raw trace {i}: expected {kind}, got {x.dtype}")
-            packed[rec[0]:rec[0] + rec[1]] = x
-        raw = packed
+
+        raw = _pack_by_records(raw, [r[0] for r in records], [r[1] for r in records], total, kind, refuse)
     if isinstance(raw, np.ndarray):
         if dtype is not None and raw.dtype != np.dtype(dtype):
             raise TypeError(f"raw samples: expected {np.dtype(dtype)}, got {raw.dtype}")
@@ -743,11 +769,9 @@ class Engine:
         """
         n_traces, t_samples = (int(v) for v in signals.shape)
         trace_filter = np.ascontiguousarray(trace_filter, dtype=np.int32)
-        sos = np.ascontiguousarray(sos, dtype=np.float64)
         if trace_filter.shape != (n_traces,):
             raise ValueError(f"trace_filter of shape {trace_filter.shape} for {n_traces} traces")
-        if sos.ndim != 3 or sos.shape[2] != 6:
-            raise ValueError(f"sos of shape {sos.shape}: (n_filters, n_sections, 6) expected")
+        sos = _sections(sos)
         left, right = (np.ascontiguousarray([] if w is None else w, dtype=np.float64).reshape(-1) for w in taper)
         ps, dev_s = self._ptr(signals, np.float64)
         if out is None:
@@ -856,21 +880,16 @@ class Engine:
                              "stays on the host: quakemigrate_amd.amplitudes)")
         if isinstance(traces, (list, tuple)):
             total = int(max((r[0] + r[1] for r in trace_records), default=0))
-            packed = np.zeros(total)
-            for r, x in zip(trace_records, traces):
-                if len(x) != r[1]:
-                    raise ValueError(f"a trace of {len(x)} samples where its record says {r[1]}")
-                packed[r[0]:r[0] + r[1]] = x
-            traces = packed
+
+            def refuse(i, x, fits):
+                if not fits:
+                    raise ValueError(f"a trace of {len(x)} samples where its record says {trace_records[i][1]}")
+
+            traces = _pack_by_records(traces, trace_records[:, 0], trace_records[:, 1], total, np.float64, refuse)
         total = int(traces.numel() if hasattr(traces, "numel") else traces.size)
         pt, dev = self._ptr(traces, np.float64)
-        sos = np.zeros((0, 1, 6)) if sos is None else np.ascontiguousarray(sos, dtype=np.float64)
-        if sos.ndim != 3 or sos.shape[2] != 6:
-            raise ValueError(f"sos of shape {sos.shape}: (n_filters, n_sections, 6) expected")
-        table = np.ascontiguousarray(np.zeros((0, 2)) if taper_table is None else taper_table, dtype=np.int32)
-        weights = np.ascontiguousarray([] if taper_weights is None else taper_weights, dtype=np.float64).reshape(-1)
-        if table.ndim != 2 or table.shape[1] != 2:
-            raise ValueError(f"taper_table of shape {table.shape}: (n_tapers, 2) expected")
+        sos = _sections(np.zeros((0, 1, 6)) if sos is None else sos)
+        table, weights = _taper_arrays(taper_table, taper_weights)
         n_windows = len(window_records)
         values, index = np.zeros((n_windows, 4)), np.zeros((n_windows, 4), dtype=np.int32)
         filtered = np.zeros(total) if want_filtered else None

@@ -23,24 +23,15 @@ int qm_engine_measure_amplitudes(qm_engine *e, const double *traces, int traces_
         (n_tapers > 0 && !taper_table) || (n_taper_weights > 0 && !taper_weights))
         return fail("%s: %d filters, %d tapers, %lld taper weights without their arrays", what, n_filters, n_tapers,
                     (long long)n_taper_weights);
-    if (n_sections < 1 || n_sections > kPreprocMaxSections)
-        return fail("%s: n_sections must be in 1..%d (got %d)", what, kPreprocMaxSections, n_sections);
+    if (check_sections(what, "filter", "n_sections", sos, n_filters, n_sections) ||
+        check_taper_table(what, taper_table, n_tapers, n_taper_weights))
+        return 1;
     if (detrend_windows != 0 && detrend_windows != 1)
         return fail("%s: detrend_windows must be 0 or 1 (got %d)", what, detrend_windows);
     if (average_method != 0 && average_method != 1)
         return fail("%s: average_method must be 0 (RMS) or 1 (STD), got %d", what, average_method);
     if (!(prominence_multiplier >= 0.0) || !std::isfinite(prominence_multiplier))
         return fail("%s: prominence_multiplier must be finite and >= 0 (got %g)", what, prominence_multiplier);
-    for (int k = 0; k < n_filters * n_sections; ++k)
-        if (sos[6 * k + 3] != 1.0)
-            return fail("%s: filter %d, section %d: a0 = %.17g, sections must be normalised to a0 == 1", what,
-                        k / n_sections, k % n_sections, sos[6 * k + 3]);
-    for (int t = 0; t < n_tapers; ++t) {
-        const int64_t off = taper_table[2 * t], m = taper_table[2 * t + 1];
-        if (off < 0 || m < 0 || off + 2 * m > n_taper_weights)
-            return fail("%s: taper %d: 2 x %lld weights from %lld on, %lld weights given", what, t, (long long)m,
-                        (long long)off, (long long)n_taper_weights);
-    }
     bool any_filter = false;
     int64_t longest_filtered = 0;
     for (int i = 0; i < n_traces; ++i) {
@@ -144,16 +135,10 @@ int qm_engine_measure_amplitudes(qm_engine *e, const double *traces, int traces_
     QM_HIP(hipEventRecord(e->ev0, e->stream));
     if (any_filter) {
         const size_t lds = (size_t)std::min<int64_t>(longest_filtered, kPreprocLdsSamples) * sizeof(double);
-        QM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_filter_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(amp_filter_kernel, dim3((unsigned)n_traces), dim3(256), lds, e->stream, a);
-        QM_HIP(hipGetLastError());
+        if (launch_with_lds(e, amp_filter_kernel, (unsigned)n_traces, 256, lds, a)) return 1;
     }
-    const size_t lds = amp_lds_bytes(longest_lds);
-    QM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&amp_window_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(amp_window_kernel, dim3((unsigned)n_windows), dim3(kAmpWindowThreads), lds, e->stream, a);
-    QM_HIP(hipGetLastError());
+    if (launch_with_lds(e, amp_window_kernel, (unsigned)n_windows, kAmpWindowThreads, amp_lds_bytes(longest_lds), a))
+        return 1;
     QM_HIP(hipEventRecord(e->ev1, e->stream));
     e->timed = true;
     QM_HIP(copy_back(values, a.values, nw * kAmpColumns * sizeof(double), e->stream));

@@ -5,9 +5,8 @@
 // _peak_to_trough_amplitude (:858-901) and an RMS / STD average (:994-997).
 //
 // Two kernels, two launches per call.
-//   stage A  amp_filter_kernel, one workgroup of four wavefronts per trace that has a filter, in the mould of
-//            qm_preproc.hpp, whose fixed-order sums (wave_sum) and filter passes (sos_pass_skewed / sos_pass_plain) run
-//            here unchanged: the least-squares line subtracted (line only: the reference calls detrend("linear") alone,
+//   stage A  amp_filter_kernel, one workgroup of four wavefronts per trace that has a filter, on qm_condition.hpp's
+//            steps: the least-squares line subtracted (line only: the reference calls detrend("linear") alone,
 //            amplitude.py:478, :529), the taper's ramps, ONE forward pass from a zero state (zerophase=False) --
 //            scipy.signal.sosfilt's bits.  The trace lives in LDS up to kPreprocLdsSamples samples (all 160 KB, so the
 //            kernel holds no other LDS), else it is worked on in place in the engine's working copy: the same
@@ -62,31 +61,14 @@ inline size_t amp_scratch_doubles(int64_t n) { return (amp_lds_bytes(n) + 7) / 8
 __device__ __forceinline__ void amp_filter_trace(const AmpArgs &a, const int64_t *r, double *buf) {
 #pragma clang fp contract(off)
     const int n = (int)r[1];
-    // preproc_trace's detrend without its second step: the centred least-squares line, the same three sums
-    const double mean = wave_sum(n, [&](int i) { return buf[i]; }) / (double)n;
-    const double tbar = 0.5 * (double)(n - 1);
-    const double sxx = wave_sum(n, [&](int i) { const double c = (double)i - tbar; return c * c; });
-    const double sxy = wave_sum(n, [&](int i) { return ((double)i - tbar) * (buf[i] - mean); });
-    const double slope = sxx > 0.0 ? sxy / sxx : 0.0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += blockDim.x) buf[i] = buf[i] - (mean + slope * ((double)i - tbar));
-    __syncthreads();
-    if (r[3] >= 0) {                                    // (2 m <= n: no sample has two weights)
+    detrend_line(buf, n, false);                        // (the line only)
+    if (r[3] >= 0) {                                    // (2 m <= n)
         const int64_t *tp = a.tapers + 2 * r[3];
         const double *w = a.taper_w + tp[0];
         const int m = (int)tp[1];
-        for (int k = threadIdx.x; k < m; k += blockDim.x) {
-            buf[k] *= w[k];
-            buf[n - m + k] *= w[m + k];
-        }
-        __syncthreads();
+        taper_ends(buf, n, w, m, w + m, m);
     }
-    if (threadIdx.x < 64) {                             // wavefront 0
-        const double *c = a.sos + r[2] * a.n_sections * 6;
-        if (a.skew) sos_pass_skewed(buf, n, false, c, a.n_sections);
-        else if (threadIdx.x == 0) sos_pass_plain(buf, n, false, c, a.n_sections);
-    }
-    __syncthreads();
+    sos_passes(buf, n, a.sos + r[2] * a.n_sections * 6, a.n_sections, 1, a.skew);
 }
 
 // ---- stage B ----------------------------------------------------------------------------------------------------
@@ -180,16 +162,7 @@ __device__ __forceinline__ void amp_window(const AmpArgs &a, const int64_t *r, d
     bool flat = false;
     if (status == kAmpMeasured && kind == 0)            // noise: flat is tested BEFORE the detrend (amplitude.py:955)
         flat = wave_max(n, [&](int i) { return y[i]; }) == -wave_max(n, [&](int i) { return -y[i]; });
-    if (status == kAmpMeasured && !flat && a.detrend_windows) {
-        const double mean = wave_sum(n, [&](int i) { return y[i]; }) / (double)n;
-        const double tbar = 0.5 * (double)(n - 1);
-        const double sxx = wave_sum(n, [&](int i) { const double c = (double)i - tbar; return c * c; });
-        const double sxy = wave_sum(n, [&](int i) { return ((double)i - tbar) * (y[i] - mean); });
-        const double slope = sxx > 0.0 ? sxy / sxx : 0.0;
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += kAmpWindowThreads) y[i] = y[i] - (mean + slope * ((double)i - tbar));
-        __syncthreads();
-    }
+    if (status == kAmpMeasured && !flat && a.detrend_windows) detrend_line(y, n, false);
     if (status == kAmpMeasured && kind == 1)            // signal: ... AFTER it (:765-771)
         flat = wave_max(n, [&](int i) { return y[i]; }) == -wave_max(n, [&](int i) { return -y[i]; });
     if (flat) status = kAmpEmptyOrFlat;

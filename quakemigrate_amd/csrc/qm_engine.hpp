@@ -447,6 +447,42 @@ struct DeviceGuard {
     }
 };
 
+// What the trace stages (pre-processing, resampling, amplitudes) all refuse in their sections and taper tables.
+// sos: [n_filters][n_sections][6]; `noun` is what the stage calls a filter ("filter", "low-pass"), `name` its
+// section-count argument.
+inline int check_sections(const char *what, const char *noun, const char *name, const double *sos, int32_t n_filters,
+                          int32_t n_sections) {
+    if (n_sections < 1 || n_sections > qm::kPreprocMaxSections)
+        return fail("%s: %s must be in 1..%d (got %d)", what, name, qm::kPreprocMaxSections, n_sections);
+    for (int k = 0; k < n_filters * n_sections; ++k)
+        if (sos[6 * k + 3] != 1.0)
+            return fail("%s: %s %d, section %d: a0 = %.17g, sections must be normalised to a0 == 1", what, noun,
+                        k / n_sections, k % n_sections, sos[6 * k + 3]);
+    return 0;
+}
+// table: [n_tapers][2], offset into the weights and ramp length m: 2 m weights from there on
+inline int check_taper_table(const char *what, const int32_t *table, int32_t n_tapers, int64_t n_weights) {
+    for (int t = 0; t < n_tapers; ++t) {
+        const int64_t off = table[2 * t], m = table[2 * t + 1];
+        if (off < 0 || m < 0 || off + 2 * m > n_weights)
+            return fail("%s: taper %d: 2 x %lld weights from %lld on, %lld weights given", what, t, (long long)m,
+                        (long long)off, (long long)n_weights);
+    }
+    return 0;
+}
+
+// `kernel` over blocks x threads on e->stream with `lds` bytes of dynamic LDS, its limit raised to that (lds == 0:
+// the kernel's limit is left alone)
+template <typename... P, typename... A>
+int launch_with_lds(qm_engine *e, void (*kernel)(P...), unsigned blocks, unsigned threads, size_t lds, A... args) {
+    if (lds)
+        QM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)lds));
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds, e->stream, args...);
+    QM_HIP(hipGetLastError());
+    return 0;
+}
+
 // pairs of samples per lane: time tile = 128 * JP; 0 = this table is not screened
 // How the sweep is launched: JP pairs of samples per lane (time tile 128*JP) and either two
 // 8-wave workgroups per CU with 80 KB of LDS each, or ("big") one 16-wave workgroup with all

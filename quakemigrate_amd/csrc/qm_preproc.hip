@@ -13,8 +13,7 @@ int check_preproc(const char *what, int32_t n_traces, int32_t t_samples, const i
     if (!trace_filter || !sos) return fail("%s: NULL argument", what);
     if (n_traces < 1 || t_samples < 1) return fail("%s: empty input", what);
     if (n_filters < 1) return fail("%s: at least one filter is needed (got %d)", what, n_filters);
-    if (n_sections < 1 || n_sections > qm::kPreprocMaxSections)
-        return fail("%s: n_sections must be in 1..%d (got %d)", what, qm::kPreprocMaxSections, n_sections);
+    if (check_sections(what, "filter", "n_sections", sos, n_filters, n_sections)) return 1;
     if (n_left < 0 || n_right < 0 || (n_left > 0 && !taper_left) || (n_right > 0 && !taper_right))
         return fail("%s: taper of %d + %d samples without weights", what, n_left, n_right);
     if ((int64_t)n_left + n_right > t_samples)
@@ -22,10 +21,6 @@ int check_preproc(const char *what, int32_t n_traces, int32_t t_samples, const i
     for (int i = 0; i < n_traces; ++i)
         if (trace_filter[i] < 0 || trace_filter[i] >= n_filters)
             return fail("%s: trace %d: filter %d out of range (%d filters)", what, i, trace_filter[i], n_filters);
-    for (int k = 0; k < n_filters * n_sections; ++k)
-        if (sos[6 * k + 3] != 1.0)
-            return fail("%s: filter %d, section %d: a0 = %.17g, sections must be normalised to a0 == 1", what,
-                        k / n_sections, k % n_sections, sos[6 * k + 3]);
     return 0;
 }
 
@@ -64,15 +59,9 @@ int PreprocStage::launch(qm_engine *e, const double *in, double *out, int n_step
     a.out = out;
     a.skew = e->cfg_preproc_skew;
     // one workgroup per trace; the trace lives in LDS if it fits (20 480 samples), else in its output row
-    const size_t lds = (size_t)a.T * sizeof(double);
     const int in_lds = a.T <= qm::kPreprocLdsSamples ? 1 : 0;
-    if (in_lds)
-        QM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&qm::preproc_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(qm::preproc_kernel, dim3((unsigned)((int64_t)n_steps * n_traces)), dim3(256), in_lds ? lds : 0,
-                       e->stream, a, in_lds);
-    QM_HIP(hipGetLastError());
-    return 0;
+    const size_t lds = in_lds ? (size_t)a.T * sizeof(double) : 0;
+    return launch_with_lds(e, qm::preproc_kernel, (unsigned)((int64_t)n_steps * n_traces), 256, lds, a, in_lds);
 }
 
 extern "C" {

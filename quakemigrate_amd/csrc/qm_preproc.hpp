@@ -4,29 +4,14 @@
 //
 // One workgroup of four wavefronts per trace.  The trace is staged in LDS (up to kPreprocLdsSamples samples: all
 // 160 KB of a CU -- so the kernel holds NO other LDS; longer traces are worked on in place in the output row).
-//   sums       every wavefront computes each detrend sum for itself: lane l adds samples l, l + 64, ... in that
-//              order, a fixed butterfly adds the 64 partials.  The four wavefronts get the same bits, the result
-//              does not depend on the run, and nothing has to cross wavefronts (there is no LDS left for that).
-//   detrend,   elementwise, all 256 threads
-//   taper
-//   filter     the recurrence is the serial part.  A cascade of S second-order sections over T samples is
-//              T x S dependent steps on one lane; here section s runs on lane s of wavefront 0 at sample
-//              n - s (a software pipeline across lanes): lane s hands its output to lane s + 1 with a DPP
-//              row shift, lane 0 takes the next sample, lane S - 1 delivers.  Every (section, sample)
-//              operation is the one SciPy's _sosfilt does, in its order, without contraction -- the bits are
-//              SciPy's -- and the critical path is T + S steps.  Samples enter and leave in blocks of 64: one
-//              LDS read, one LDS write per block, v_readlane in between.
-//              "preproc_skew" = 0 keeps the plain form (lane 0 walks sample by sample, section by section):
-//              the in-device cross-check.
+// The conditioning steps themselves -- fixed-order sums, detrend, taper, the skewed filter passes -- are
+// qm_condition.hpp's; this file stages the trace and calls them.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "qm_condition.hpp"
 
 namespace qm {
 
 constexpr int kPreprocLdsSamples = 20480;       // 160 KB of float64: the onset stage's limit as well
-constexpr int kPreprocMaxSections = 8;
 
 struct PreprocArgs {
     const double *in;           // [n][T] resampled component traces
@@ -39,84 +24,6 @@ struct PreprocArgs {
     int detrend, zero_phase, skew;
 };
 
-// sum over i < n of f(i), the same bits in every lane of the wavefront and in every run
-template <typename F>
-__device__ __forceinline__ double wave_sum(int n, F f) {
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    double acc = 0.0;
-    for (int i = lane; i < n; i += 64) acc += f(i);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
-    return acc;
-}
-
-__device__ __forceinline__ double lane_below(double v) {       // lane l <- lane l - 1 within a row of 16
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x111, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x111, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double from_lane(double v, int lane) {      // `lane` is uniform
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane),
-                            __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-
-// One pass of the cascade over buf[0..T), logical sample i at buf[rev ? T - 1 - i : i], in place.
-// Called by the whole of wavefront 0.  c: this filter's [S][6].
-__device__ __forceinline__ void sos_pass_skewed(double *buf, int T, bool rev, const double *c, int S) {
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x;
-    double b0 = 0.0, b1 = 0.0, b2 = 0.0, a1 = 0.0, a2 = 0.0;
-    if (lane < S) {
-        b0 = c[6 * lane]; b1 = c[6 * lane + 1]; b2 = c[6 * lane + 2];
-        a1 = c[6 * lane + 4]; a2 = c[6 * lane + 5];
-    }
-    double z0 = 0.0, z1 = 0.0, xn = 0.0;
-    const int steps = T + S - 1;                        // step k: lane s works on sample k - s
-    for (int base = 0; base < steps; base += 64) {
-        const int i = base + lane;
-        const double xv = i < T ? buf[rev ? T - 1 - i : i] : 0.0;
-        double yv = 0.0;
-        const int jn = min(64, steps - base);
-        for (int j = 0; j < jn; ++j) {
-            const double handed = lane_below(xn);       // the section below, one step ago: its sample k - s
-            const double xc = lane == 0 ? from_lane(xv, j) : handed;
-            const double t = b0 * xc + z0;
-            const double n0 = b1 * xc - a1 * t + z1;
-            const double n1 = b2 * xc - a2 * t;
-            if (base + j >= lane) {                     // (before its first sample a section keeps its zero state)
-                xn = t;
-                z0 = n0;
-                z1 = n1;
-            }
-            const double y = from_lane(xn, S - 1);
-            if (lane == j) yv = y;
-        }
-        const int o = i - (S - 1);                      // lane j holds step base + j's delivery: sample k - (S - 1)
-        if (lane < jn && o >= 0 && o < T) buf[rev ? T - 1 - o : o] = yv;
-    }
-}
-
-// the same pass on lane 0 alone
-__device__ __forceinline__ void sos_pass_plain(double *buf, int T, bool rev, const double *c, int S) {
-#pragma clang fp contract(off)
-    double z[kPreprocMaxSections][2];
-    for (int s = 0; s < S; ++s) z[s][0] = z[s][1] = 0.0;
-    for (int i = 0; i < T; ++i) {
-        double *p = buf + (rev ? T - 1 - i : i);
-        double xc = *p;
-        for (int s = 0; s < S; ++s) {
-            const double *k = c + 6 * s;
-            const double xn = k[0] * xc + z[s][0];
-            z[s][0] = k[1] * xc - k[4] * xn + z[s][1];
-            z[s][1] = k[2] * xc - k[5] * xn;
-            xc = xn;
-        }
-        *p = xc;
-    }
-}
-
 template <bool IN_LDS>
 __device__ __forceinline__ void preproc_trace(const PreprocArgs &a, double *buf) {
 #pragma clang fp contract(off)
@@ -127,35 +34,10 @@ __device__ __forceinline__ void preproc_trace(const PreprocArgs &a, double *buf)
     if (IN_LDS || x != out)
         for (int i = threadIdx.x; i < n; i += blockDim.x) buf[i] = x[i];
     __syncthreads();
-    if (a.detrend) {
-        // the least-squares line in its centred form, then the mean of what is left (the reference calls
-        // detrend("linear") and detrend("constant"), stalta.py:447-448)
-        const double mean = wave_sum(n, [&](int i) { return buf[i]; }) / (double)n;
-        const double tbar = 0.5 * (double)(n - 1);
-        const double sxx = wave_sum(n, [&](int i) { const double d = (double)i - tbar; return d * d; });
-        const double sxy = wave_sum(n, [&](int i) { return ((double)i - tbar) * (buf[i] - mean); });
-        const double slope = sxx > 0.0 ? sxy / sxx : 0.0;
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += blockDim.x) buf[i] = buf[i] - (mean + slope * ((double)i - tbar));
-        __syncthreads();
-        const double rest = wave_sum(n, [&](int i) { return buf[i]; }) / (double)n;
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += blockDim.x) buf[i] = buf[i] - rest;
-        __syncthreads();
-    }
-    // (n_left + n_right <= T: no sample has two weights)
-    for (int k = threadIdx.x; k < a.n_left; k += blockDim.x) buf[k] *= a.taper_left[k];
-    for (int k = threadIdx.x; k < a.n_right; k += blockDim.x) buf[n - a.n_right + k] *= a.taper_right[k];
-    __syncthreads();
-    if (threadIdx.x < 64) {                             // wavefront 0
-        const double *c = a.sos + (int64_t)a.trace_filter[tr] * a.n_sections * 6;
-        for (int pass = 0; pass < (a.zero_phase ? 2 : 1); ++pass) {
-            if (pass) __threadfence_block();            // (the backward pass reads what other lanes delivered)
-            if (a.skew) sos_pass_skewed(buf, n, pass == 1, c, a.n_sections);
-            else if (threadIdx.x == 0) sos_pass_plain(buf, n, pass == 1, c, a.n_sections);
-        }
-    }
-    __syncthreads();
+    if (a.detrend) detrend_line(buf, n, true);
+    taper_ends(buf, n, a.taper_left, a.n_left, a.taper_right, a.n_right);
+    const double *c = a.sos + (int64_t)a.trace_filter[tr] * a.n_sections * 6;
+    sos_passes(buf, n, c, a.n_sections, a.zero_phase ? 2 : 1, a.skew);
     if (IN_LDS)
         for (int i = threadIdx.x; i < n; i += blockDim.x) out[i] = buf[i];
 }

@@ -21,18 +21,9 @@ int check_resample(const char *what, int raw_dtype, int64_t total_raw_samples, i
         (n_tapers > 0 && !taper_table) || (n_taper_weights > 0 && !taper_weights))
         return fail("%s: %d low-passes, %d tapers, %lld taper weights without their arrays", what, n_lowpass, n_tapers,
                     (long long)n_taper_weights);
-    if (n_sections_lp < 1 || n_sections_lp > kPreprocMaxSections)
-        return fail("%s: n_sections_lp must be in 1..%d (got %d)", what, kPreprocMaxSections, n_sections_lp);
-    for (int k = 0; k < n_lowpass * n_sections_lp; ++k)
-        if (sos_lp[6 * k + 3] != 1.0)
-            return fail("%s: low-pass %d, section %d: a0 = %.17g, sections must be normalised to a0 == 1", what,
-                        k / n_sections_lp, k % n_sections_lp, sos_lp[6 * k + 3]);
-    for (int t = 0; t < n_tapers; ++t) {
-        const int64_t off = taper_table[2 * t], m = taper_table[2 * t + 1];
-        if (off < 0 || m < 0 || off + 2 * m > n_taper_weights)
-            return fail("%s: taper %d: 2 x %lld weights from %lld on, %lld weights given", what, t, (long long)m,
-                        (long long)off, (long long)n_taper_weights);
-    }
+    if (check_sections(what, "low-pass", "n_sections_lp", sos_lp, n_lowpass, n_sections_lp) ||
+        check_taper_table(what, taper_table, n_tapers, n_taper_weights))
+        return 1;
     int64_t kept = 0;
     for (int i = 0; i < n_traces; ++i) {
         const int64_t *r = records + (size_t)i * kResampleFields;
@@ -128,11 +119,7 @@ int ResampleStage::launch(qm_engine *e, const void *raw, double *out, int n_step
     a.skew = e->cfg_preproc_skew;
     // one workgroup per trace; LDS for the longest kept series that fits (longer ones live in their scratch rows)
     const size_t lds = (size_t)std::min<int64_t>(max_kept, qm::kPreprocLdsSamples) * sizeof(double);
-    QM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&qm::resample_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(qm::resample_kernel, dim3((unsigned)((int64_t)n_steps * n_traces)), dim3(256), lds, e->stream, a);
-    QM_HIP(hipGetLastError());
-    return 0;
+    return launch_with_lds(e, qm::resample_kernel, (unsigned)((int64_t)n_steps * n_traces), 256, lds, a);
 }
 
 extern "C" {

@@ -3,8 +3,8 @@
 // linear-interpolation upsampling by an integer factor with constant padding at the window's ends, then decimation
 // behind a detrend, a cosine taper and a zero-phase Butterworth low-pass.
 //
-// One workgroup of four wavefronts per trace, in the mould of qm_preproc.hpp, whose fixed-order sums (wave_sum) and
-// filter passes (sos_pass_skewed / sos_pass_plain) run here unchanged: the low-pass is SciPy's sosfilt bit for bit.
+// One workgroup of four wavefronts per trace; detrend, taper and filter passes are qm_condition.hpp's, the ones the
+// pre-processing stage runs: the low-pass is SciPy's sosfilt bit for bit.
 // A trace's record (ResampleField) says which raw samples it reads and which of the steps it takes; the host plans
 // the records (quakemigrate_amd/preprocess.py: ResampleStage) and checks them (qm_resample.hip: check_resample), the
 // kernel trusts them.
@@ -79,39 +79,12 @@ __device__ __forceinline__ void resample_trace(const ResampleArgs &a, const int6
     }
     __syncthreads();
     if (d > 1) {
-        if (a.detrend) {
-            // preproc_trace's detrend: the centred least-squares line, then the mean of the rest, the same sums
-            const double mean = wave_sum(n, [&](int i) { return buf[i]; }) / (double)n;
-            const double tbar = 0.5 * (double)(n - 1);
-            const double sxx = wave_sum(n, [&](int i) { const double c = (double)i - tbar; return c * c; });
-            const double sxy = wave_sum(n, [&](int i) { return ((double)i - tbar) * (buf[i] - mean); });
-            const double slope = sxx > 0.0 ? sxy / sxx : 0.0;
-            __syncthreads();
-            for (int i = threadIdx.x; i < n; i += blockDim.x) buf[i] = buf[i] - (mean + slope * ((double)i - tbar));
-            __syncthreads();
-            const double rest = wave_sum(n, [&](int i) { return buf[i]; }) / (double)n;
-            __syncthreads();
-            for (int i = threadIdx.x; i < n; i += blockDim.x) buf[i] = buf[i] - rest;
-            __syncthreads();
-        }
-        // (2 m <= n_up: no sample has two weights)
-        const int64_t *tp = a.tapers + 2 * r[kRsTaper];
+        if (a.detrend) detrend_line(buf, n, true);
+        const int64_t *tp = a.tapers + 2 * r[kRsTaper];     // (2 m <= n_up)
         const double *w = a.taper_w + tp[0];
         const int m = (int)tp[1];
-        for (int k = threadIdx.x; k < m; k += blockDim.x) {
-            buf[k] *= w[k];
-            buf[n - m + k] *= w[m + k];
-        }
-        __syncthreads();
-        if (threadIdx.x < 64) {                         // wavefront 0
-            const double *c = a.sos + r[kRsLowpass] * a.n_sections * 6;
-            for (int pass = 0; pass < 2; ++pass) {
-                if (pass) __threadfence_block();        // (the backward pass reads what other lanes delivered)
-                if (a.skew) sos_pass_skewed(buf, n, pass == 1, c, a.n_sections);
-                else if (threadIdx.x == 0) sos_pass_plain(buf, n, pass == 1, c, a.n_sections);
-            }
-        }
-        __syncthreads();
+        taper_ends(buf, n, w, m, w + m, m);
+        sos_passes(buf, n, a.sos + r[kRsLowpass] * a.n_sections * 6, a.n_sections, 2, a.skew);
     }
     // every d-th sample from out_first on (obspy's decimate without its own filter: data[::d])
     double *out = a.out + (int64_t)blockIdx.x * a.T;

@@ -103,10 +103,8 @@ class StreamingDetector:
         f64 = lambda x: np.ascontiguousarray(x, dtype=np.float64)   # noqa: E731
         trace_row, trace_filter = i32(a["trace_row"]), i32(a["trace_filter"])
         nsta, nlta = i32(a["nsta"]), i32(a["nlta"])
-        sos = f64(a["sos"])
         left, right = f64(a["taper_left"]).reshape(-1), f64(a["taper_right"]).reshape(-1)
-        if sos.ndim != 3 or sos.shape[2] != 6:
-            raise ValueError(f"sos of shape {sos.shape}: (n_filters, n_sections, 6) expected")
+        sos = _lib._sections(a["sos"])
         if trace_filter.shape != trace_row.shape or trace_row.ndim != 1:
             raise ValueError("trace_row and trace_filter: one entry per trace each")
         if nsta.shape != (self.n_rows,) or nlta.shape != (self.n_rows,):

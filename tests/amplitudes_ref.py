@@ -19,14 +19,7 @@ MEASURED, EMPTY_OR_FLAT, NO_EXTREMUM, CONSECUTIVE, EQUAL_PAIR, NON_FINITE = rang
 # ---- stage A -----------------------------------------------------------------------------------------------------
 def line_detrend(x):
     """The least-squares line over i = 0..n-1 subtracted in its centred form; no second demean."""
-    x = np.asarray(x, dtype=np.float64)
-    n = len(x)
-    i = np.arange(n, dtype=np.float64)
-    tbar = 0.5 * (n - 1)
-    mean = x.mean()
-    sxx = np.sum((i - tbar) ** 2)
-    slope = np.sum((i - tbar) * (x - mean)) / sxx if sxx > 0 else 0.0
-    return x - (mean + slope * (i - tbar))
+    return pp.detrend(x, also_mean=False)
 
 
 def filter_trace(x, sos, weights=None):

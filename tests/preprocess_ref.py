@@ -10,8 +10,9 @@ the filter to ``scipy.signal.sosfilt`` bit for bit and the detrend to ``scipy.si
 import numpy as np
 
 
-def detrend(x):
-    """Least-squares line over t = 0..n-1 subtracted, then the mean of the rest.  x: (..., n)."""
+def detrend(x, also_mean=True):
+    """Least-squares line over t = 0..n-1 subtracted, then (``also_mean``) the mean of the rest.  x: (..., n).  The
+    tolerance-level restatement: NumPy's sums add in another order than the device."""
     x = np.asarray(x, dtype=np.float64)
     n = x.shape[-1]
     t = np.arange(n, dtype=np.float64)
@@ -20,7 +21,35 @@ def detrend(x):
     sxx = np.sum((t - tbar) ** 2)
     slope = np.sum((t - tbar) * (x - mean), axis=-1, keepdims=True) / sxx if sxx > 0 else 0.0
     y = x - (mean + slope * (t - tbar))
-    return y - y.mean(axis=-1, keepdims=True)
+    return y - y.mean(axis=-1, keepdims=True) if also_mean else y
+
+
+def wave_sum(values):
+    """The sum as a wavefront of the device adds it (csrc/qm_condition.hpp: wave_sum): lane l adds elements l, l + 64,
+    ... one after the other from 0.0, then a butterfly over the 64 partials; lane 0's value."""
+    values = np.asarray(values, dtype=np.float64)
+    padded = np.zeros(-(-max(len(values), 1) // 64) * 64)
+    padded[:len(values)] = values
+    acc = np.zeros(64)
+    for row in padded.reshape(-1, 64):                  # (row by row: np.sum is pairwise and gives other bits)
+        acc = acc + row
+    for m in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[np.arange(64) ^ m]
+    return float(acc[0])
+
+
+def detrend_device_order(x, also_mean):
+    """``detrend`` of one trace with the device's expressions in the device's order (csrc/qm_condition.hpp:
+    detrend_line): the bit-level restatement.  Elementwise NumPy rounds each product and sum separately."""
+    x = np.asarray(x, dtype=np.float64)
+    n = len(x)
+    centred = np.arange(n, dtype=np.float64) - 0.5 * float(n - 1)
+    mean = wave_sum(x) / float(n)
+    sxx = wave_sum(centred * centred)
+    sxy = wave_sum(centred * (x - mean))
+    slope = sxy / sxx if sxx > 0.0 else 0.0
+    y = x - (mean + slope * centred)
+    return y - wave_sum(y) / float(n) if also_mean else y
 
 
 def taper(x, left, right):
@@ -60,10 +89,14 @@ def sosfilt_zero_phase(sos, x):
     return sosfilt(sos, sosfilt(sos, x)[..., ::-1])[..., ::-1]
 
 
-def preprocess(signals, trace_filter, sos, left=(), right=(), detrend_on=True, zero_phase=True):
-    """The whole stage: signals (n_traces, T), sos (n_filters, n_sections, 6)."""
+def preprocess(signals, trace_filter, sos, left=(), right=(), detrend_on=True, zero_phase=True, device_order=False):
+    """The whole stage: signals (n_traces, T), sos (n_filters, n_sections, 6).  ``device_order``: the detrend's sums as
+    the device adds them -- then every step is bit-level."""
     x = np.asarray(signals, dtype=np.float64)
-    y = detrend(x) if detrend_on else x.copy()
+    if detrend_on and device_order:
+        y = np.stack([detrend_device_order(row, True) for row in x])
+    else:
+        y = detrend(x) if detrend_on else x.copy()
     y = taper(y, left, right)
     out = np.empty_like(y)
     trace_filter = np.asarray(trace_filter)

@@ -50,10 +50,13 @@ def kept_series(x, up, pad_left, pad_right, up_first, n_up):
     return padded[up_first:up_first + n_up]
 
 
-def lowpassed(kept, sos, left=(), right=(), detrend_on=True):
+def lowpassed(kept, sos, left=(), right=(), detrend_on=True, device_order=False):
     """The decimation's filter chain over one kept series (or several of one length): detrend, taper, zero-phase
-    cascade."""
-    y = pr.detrend(kept) if detrend_on else np.array(kept, dtype=np.float64)
+    cascade.  ``device_order`` (one series): the detrend's sums as the device adds them."""
+    if detrend_on and device_order:
+        y = pr.detrend_device_order(kept, True)
+    else:
+        y = pr.detrend(kept) if detrend_on else np.array(kept, dtype=np.float64)
     return pr.sosfilt_zero_phase(sos, pr.taper(y, left, right))
 
 

@@ -273,6 +273,66 @@ def test_windows_at_the_lds_limit(engine):
     assert np.all(err[:, 1] <= bound + 2 * n * U * want_v[:, 1])
 
 
+# -- the detrends, bit for bit: their sums restated in the device's order (preprocess_ref.detrend_device_order) -------
+TRACE_LDS_SAMPLES = 20480
+
+
+def test_filter_stage_is_the_device_order_restatement_bit_for_bit(lib):
+    """Traces of 1 (the line's slope is guarded: sxx == 0), 2, 65, 301 and 20 481 (filtered in place) samples, each with
+    a taper and without: line detrend in the device's order, then the bit-level taper and one forward pass."""
+    import resample_ref as rr
+
+    lengths = [1, 2, 65, 301, TRACE_LDS_SAMPLES + 1]
+    sos = rr.stable_sos(13, 2, 2)
+    rng = np.random.default_rng(13)
+    traces, trecs, table, weights = [], [], [], []
+    for k, n in enumerate(lengths):
+        m = n // 3
+        table.append([len(weights), m])
+        weights += list(np.sort(rng.uniform(0, 1, m))) + list(np.sort(rng.uniform(0, 1, m))[::-1])
+        for taper in (k, -1):
+            traces.append(pp.noisy_traces(100 * n + taper + 1, 1, n)[0])
+            trecs.append([0, n, len(traces) % 2, taper])
+    packed, offsets = ar.pack(traces)
+    trecs = np.array(trecs, dtype=np.int64)
+    trecs[:, 0] = offsets
+    weights = np.array(weights)
+    want = []
+    for x, (_, n, f, taper) in zip(traces, trecs):
+        y = pp.detrend_device_order(x, False)
+        if taper >= 0:
+            o, m = table[taper]
+            y = pp.taper(y, weights[o:o + m], weights[o + m:o + 2 * m])
+        want.append(pp.sosfilt(sos[f], y))
+    recs = [[k, 0, len(x), 0] for k, x in enumerate(traces)]
+    for skew in (1, 0):
+        eng = lib.Engine(0, preproc_skew=skew)
+        try:
+            _, _, filtered = eng.measure_amplitudes(packed, trecs, recs, sos=sos, taper_table=table,
+                                                    taper_weights=weights, want_filtered=True)
+        finally:
+            eng.close()
+        assert np.array_equal(bits(filtered), bits(np.concatenate(want))), skew
+
+
+def test_window_detrend_is_the_device_order_restatement_bit_for_bit(engine):
+    """Noise windows of 3, 64, 65 and ``amp_lds_samples`` + 1 (in scratch) samples through the window detrend: RMS and
+    max|y| are the same quantities of the restated detrended window, the RMS's sum in the device's order as well.  A
+    signal window of one sample goes through the guarded slope (sxx == 0) and comes out flat."""
+    limit = engine.get("amp_lds_samples")
+    lengths = [3, 64, 65, limit + 1]
+    x = pp.noisy_traces(43, 1, sum(lengths) + 1)[0]
+    bounds = np.concatenate([[0], np.cumsum(lengths)])
+    recs = [[0, int(lo), int(hi), 0] for lo, hi in zip(bounds[:-1], bounds[1:])] + [[0, len(x) - 1, len(x), 1]]
+    values, index = engine.measure_amplitudes(x, [[0, len(x), -1, -1]], recs, detrend_windows=True)
+    assert [int(s) for s in index[:, 0]] == [0, 0, 0, 0, ar.EMPTY_OR_FLAT]
+    assert np.all(values[4] == 0.0)
+    for k, (_, lo, hi, _) in enumerate(recs[:4]):
+        y = pp.detrend_device_order(x[lo:hi], False)
+        want = [0.0, np.sqrt(pp.wave_sum(y * y) / float(hi - lo)), np.max(np.abs(y)), 0.0]
+        assert np.array_equal(bits(values[k]), bits(want)), (hi - lo, values[k], want)
+
+
 # -- calls -----------------------------------------------------------------------------------------------------------
 def test_device_traces_repeats_and_engines(lib, engine, fam, filtered_family):
     torch = pytest.importorskip("torch")

@@ -117,6 +117,48 @@ def test_whole_stage_against_the_restatement(engine, T):
         assert ramp <= tol
 
 
+def _tapers(T, seed):
+    """No taper, ramps of T // 2 on both ends, ramps of unequal length."""
+    rng = np.random.default_rng(seed)
+    return [(np.sort(rng.uniform(0, 1, n_left)), np.sort(rng.uniform(0, 1, n_right))[::-1].copy())
+            for n_left, n_right in ((0, 0), (T // 2, T // 2), ((T + 1) // 2, T // 4))]
+
+
+@pytest.mark.parametrize("T", [1, 2, 63, 64, 65, 129, 301])
+def test_whole_stage_is_the_device_order_restatement_bit_for_bit(engine, T):
+    """The detrend's sums restated in the device's order (preprocess_ref.detrend_device_order), then the bit-level taper
+    and filter: the whole stage has the restatement's bits.  T = 1: the line's slope is guarded (sxx == 0)."""
+    sos = stable_sos(T, 2, 2)
+    x = pr.noisy_traces(300 + T, 5, T)
+    try:
+        for left, right in _tapers(T, T):
+            for zero_phase in (False, True):
+                want = pr.preprocess(x, TRACE_FILTER, sos, left, right, zero_phase=zero_phase, device_order=True)
+                for skew in (1, 0):
+                    engine.config("preproc_skew", skew)
+                    got = engine.preprocess(x, TRACE_FILTER, sos, taper=(left, right), zero_phase=zero_phase)
+                    assert np.array_equal(got, want), (len(left), len(right), zero_phase, skew,
+                                                       float(np.max(np.abs(got - want))))
+    finally:
+        engine.config("preproc_skew", 1)
+
+
+def test_whole_stage_of_a_trace_above_the_lds_limit_bit_for_bit(engine):
+    T = LDS_SAMPLES + 1                                         # worked on in place in its output row
+    sos = stable_sos(79, 2, 2)
+    x = pr.noisy_traces(79, 2, T)
+    tf = np.array([1, 0], dtype=np.int32)
+    left, right = _tapers(T, 79)[2]
+    want = pr.preprocess(x, tf, sos, left, right, device_order=True)
+    try:
+        for skew in (1, 0):
+            engine.config("preproc_skew", skew)
+            got = engine.preprocess(x, tf, sos, taper=(left, right))
+            assert np.array_equal(got, want), (skew, float(np.max(np.abs(got - want))))
+    finally:
+        engine.config("preproc_skew", 1)
+
+
 # -- 3. device-resident in and out, scratch reuse --------------------------------------------------------------------
 def test_device_resident_equals_host_and_a_reused_engine_equals_a_fresh_one(lib, engine):
     import torch

@@ -150,6 +150,28 @@ def test_kept_series_above_and_at_the_lds_limit(engine):
         engine.config("preproc_skew", 1)
 
 
+@pytest.mark.parametrize("n_up", [1, 2, 64, 65, 301, LDS_SAMPLES + 1])
+def test_decimation_with_detrend_is_the_device_order_restatement_bit_for_bit(engine, n_up):
+    """One decimating record with the detrend on: its sums restated in the device's order
+    (preprocess_ref.detrend_device_order), then the bit-level taper and low-pass.  n_up = 1: the line's slope is
+    guarded (sxx == 0); 20 481: the kept series lives in global scratch."""
+    sos = rr.stable_sos(n_up, 2, 2)
+    x = rr.raw_traces(500 + n_up, [n_up])[0]
+    m = n_up // 20
+    rng = np.random.default_rng(n_up)
+    weights = np.concatenate([np.sort(rng.uniform(0, 1, m)), np.sort(rng.uniform(0, 1, m))[::-1]])
+    d = 2
+    a = _arrays([rr.record(0, n_up, dec=d, lowpass=1)], -(-n_up // d), sos, [[0, m]], weights, detrend=1)
+    want = rr.lowpassed(x, sos[1], weights[:m], weights[m:], device_order=True)[None, ::d]
+    try:
+        for skew in (1, 0):
+            engine.config("preproc_skew", skew)
+            got = engine.resample(x, a)
+            assert np.array_equal(got, want), (skew, float(np.max(np.abs(got - want))))
+    finally:
+        engine.config("preproc_skew", 1)
+
+
 # -- 4. the whole stage --------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("T", [301, 1033])
 def test_whole_stage_against_the_restatement(engine, T):

@@ -1,5 +1,6 @@
 // stage_build_check.cpp -- the three front-end stage records' build() on the CPU, under the sanitizers: their
-// refusals and the images they put on the "device" for repeat = 1 and 3.  A stand-alone host program: the runtime's
+// refusals and the images they put on the "device" for repeat = 1 and 3; then the two checks the trace stages share
+// (check_sections, check_taper_table: qm_engine.hpp), every refusal with its whole message.  A stand-alone host program: the runtime's
 // pool and copies are replaced below by malloc and memcpy, so no device is needed and every image lands in an
 // allocation of exactly the size build() asked for (an overrun is an AddressSanitizer report).  No kernel is launched.
 //
@@ -160,6 +161,27 @@ int main() {
     CHECK(rs.build(e, "rs", 2, kRawFloat64, total, n_rs, 50, rec, nullptr, 0, 1, 0, nullptr, 0, nullptr, 0) == 0);
     CHECK(rs.coef.n >= 1);
     std::printf("resampling: 6 refusals, images for int32 and float64, repeat = 3, 1, 3\n");
+
+    // -- the checks the trace stages share (the amplitude entry point calls them as well): every refusal, whole message
+    auto refused_with = [&](int rc, const char *text) { return rc != 0 && g_error == text; };
+    CHECK(refused_with(check_sections("amp", "filter", "n_sections", sos.data(), 2, 0),
+                       "amp: n_sections must be in 1..8 (got 0)"));
+    CHECK(refused_with(check_sections("rs", "low-pass", "n_sections_lp", sos.data(), 2, 9),
+                       "rs: n_sections_lp must be in 1..8 (got 9)"));
+    CHECK(refused_with(check_sections("amp", "filter", "n_sections", bad_sos.data(), 2, 2),
+                       "amp: filter 0, section 1: a0 = 2, sections must be normalised to a0 == 1"));
+    CHECK(refused_with(check_sections("rs", "low-pass", "n_sections_lp", bad_sos.data(), 4, 1),
+                       "rs: low-pass 1, section 0: a0 = 2, sections must be normalised to a0 == 1"));
+    CHECK(check_sections("amp", "filter", "n_sections", nullptr, 0, 1) == 0);      // (no filter: nothing is read)
+    CHECK(check_sections("pre", "filter", "n_sections", sos.data(), 2, 2) == 0);
+    const int32_t table[6] = {0, 10, 20, 0, 4, 8};
+    CHECK(check_taper_table("amp", table, 3, 20) == 0);
+    CHECK(refused_with(check_taper_table("amp", table, 3, 19), "amp: taper 0: 2 x 10 weights from 0 on, 19 weights given"));
+    const int32_t negative[4] = {-1, 2, 0, -3};
+    CHECK(refused_with(check_taper_table("rs", negative, 2, 20), "rs: taper 0: 2 x 2 weights from -1 on, 20 weights given"));
+    CHECK(refused_with(check_taper_table("rs", negative + 2, 1, 20), "rs: taper 0: 2 x -3 weights from 0 on, 20 weights given"));
+    CHECK(check_taper_table("rs", nullptr, 0, 0) == 0);
+    std::printf("shared checks: 7 refusals, whole messages\n");
 
     pre.release(); on.release(); rs.release();
     delete e;
