@@ -112,7 +112,15 @@ int qm_engine_synchronize(qm_engine *e);
 /* Tunables (qm_engine_config) and read-outs (qm_engine_get).  Nothing has to be set: every default is
  * the automatic choice, every setting gives the same max_coa / max_coa_idx bits
  * and the same stored values unless the row says otherwise.  Layout keys take effect at the next
- * qm_engine_load_lut / qm_engine_serve.
+ * qm_engine_load_lut / qm_engine_serve.  A refused value changes nothing.
+ * Every key can be read with qm_engine_get.  It reads back AS SET, except:
+ *   brick_x, _y, _z, samples_per_lane   once a table is resident: that table's brick shape and samples per lane
+ *   waves, lds_bytes                    as set where the caller set them; else the resident table's layout's
+ *                                       (no table: the defaults, 8 and 80 KiB)
+ *   shift_waves                         the last launch's layout's, else the resident table's 256-sample layout's,
+ *                                       else as set
+ *   shift_lazy                          the last launch's flavour (0 before any)
+ *   screen_pairs, screen_big            the last screened step's plan (0 before any)
  *
  * key (config)          values [default]         meaning
  * --------------------  -----------------------  -------------------------------------------------------
@@ -195,6 +203,7 @@ int qm_engine_synchronize(qm_engine *e);
  *                                                the GPU's clock; busy time per launch and the gaps between launches
  *                                                go to stderr when the stream is destroyed
  * log_timing            0 / 1 [0]                HIP events around every stacking launch (qm_engine_kernel_log)
+ * trigger_timing        0 / 1 [0]                HIP events around every stage of qm_engine_trigger: trigger_ns_* below
  *
  * read-outs (qm_engine_get), besides the keys above: n_cu, n_nodes, n_rows, nx, ny, nz, n_bricks,
  * n_wide_bricks, mean_span; last_kernel (0 chunked, 1 exact-row-count, 2 paired, 3 shift-reuse),
@@ -214,7 +223,7 @@ int qm_engine_synchronize(qm_engine *e);
  * amp_lds_samples (the longest window qm_engine_measure_amplitudes keeps in LDS; longer ones work from scratch);
  * the trigger stage's compile-time tunables (csrc/qm_trigger.hpp): trigger_max_radius (the largest smoothing radius
  * qm_engine_trigger takes), trigger_smooth_tile, trigger_run_block, trigger_merge_stride; with the key
- * trigger_timing (0 / 1 [0], measurement: HIP events around every stage of qm_engine_trigger) set, the last call's
+ * trigger_timing set, the last call's
  * stage times in nanoseconds: trigger_ns_smooth, trigger_ns_stats, trigger_ns_runs (count and scan),
  * trigger_ns_compact, trigger_ns_peaks, trigger_ns_merge (0: the stage did not run). */
 int qm_engine_config(qm_engine *e, const char *key, int64_t value);

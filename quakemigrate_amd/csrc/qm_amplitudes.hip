@@ -130,7 +130,7 @@ int qm_engine_measure_amplitudes(qm_engine *e, const double *traces, int traces_
     a.scratch = e->d_amp_scratch.p;
     a.values = e->d_amp_val.p;
     a.index = e->d_amp_idx.p;
-    a.n_sections = n_sections; a.skew = e->cfg_preproc_skew;
+    a.n_sections = n_sections; a.skew = e->cfg.preproc_skew;
     a.detrend_windows = detrend_windows; a.method = average_method; a.multiplier = prominence_multiplier;
     QM_HIP(hipEventRecord(e->ev0, e->stream));
     if (any_filter) {

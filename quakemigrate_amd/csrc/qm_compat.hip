@@ -215,13 +215,11 @@ void migrate(double *onsets, int32_t *lookup_tables, double *map4d, int32_t fsmp
                                        n_stations);
             if (compat_failed(rc, "migrate/load")) return poison();
         } else {
-            e->cfg_bx = gx ? 0 : 1;
-            e->cfg_by = gx ? 0 : 1;
-            e->cfg_bz = gx ? 0 : 32;
-            if (compat_failed(qm_engine_load_lut(e, lookup_tables, 0, gx ? gx : 1, gx ? gy : 1,
-                                                 gx ? gz : (int32_t)n_nodes, n_stations, 0),
-                              "migrate/load"))
-                return poison();
+            int rc = qm_engine_config(e, "brick_x", gx ? 0 : 1) || qm_engine_config(e, "brick_y", gx ? 0 : 1) ||
+                     qm_engine_config(e, "brick_z", gx ? 0 : 32) ||
+                     qm_engine_load_lut(e, lookup_tables, 0, gx ? gx : 1, gx ? gy : 1, gx ? gz : (int32_t)n_nodes,
+                                        n_stations, 0);
+            if (compat_failed(rc, "migrate/load")) return poison();
         }
         g_compat_table.hash = h;
         g_compat_table.hash2 = h2;

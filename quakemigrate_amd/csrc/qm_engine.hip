@@ -28,8 +28,8 @@ bool pair_built(int S) { return S >= 1 && S <= qm::kPairMaxRows; }
 // without tail flavours (row blocks, the 12-wave shape) and remainders of more than 192 samples pull a
 // last whole tile back over its predecessor, which needs a scan of at least one tile.
 bool shift_wanted(const qm_engine *e, int n_chunk, bool plain, bool volume, int64_t vol_stride) {
-    if (!plain || e->cfg_shift == 0 || e->cfg_generic || e->cfg_force_direct ||
-        e->user_waves || e->user_lds || e->cfg_j > 0 || e->cfg_pair == 2)
+    if (!plain || e->cfg.shift == 0 || e->cfg.generic || e->cfg.force_direct ||
+        e->cfg.user_waves || e->cfg.user_lds || e->cfg.samples_per_lane > 0 || e->cfg.pair == 2)
         return false;
     // volume-writing launches: the row stride goes into a 32-bit byte count (as do, for the marginal
     // map, the offsets of a group's nodes: an x-plane of fewer than 2^29 nodes)
@@ -42,7 +42,7 @@ bool shift_wanted(const qm_engine *e, int n_chunk, bool plain, bool volume, int6
 // `rest` samples a scan leaves beyond the tiles in front
 int shift_tail_spl(const qm_engine *e, int rest) {
     const int rem = rest % qm::kShiftKT;
-    if (rem == 0 || rem > 192 || !e->cfg_shift_tail) return 0;
+    if (rem == 0 || rem > 192 || !e->cfg.shift_tail) return 0;
     return (rem + qm::kWave - 1) / qm::kWave;
 }
 
@@ -72,7 +72,7 @@ int auto_groups(const qm_engine *e, int ntiles, int units, int blocks_per_cu, in
     // than 4; flat beyond); the partial sets stay a few tens of MB.  Never more groups than
     // there are bricks.
     const int64_t slots = (int64_t)e->n_cu * blocks_per_cu;
-    int64_t want = ((int64_t)(rounds > 0 ? rounds : e->cfg_rounds) * slots) / ntiles;
+    int64_t want = ((int64_t)(rounds > 0 ? rounds : e->cfg.rounds) * slots) / ntiles;
     if (want < 1) want = std::max<int64_t>(1, slots / ntiles);
     want = std::max<int64_t>(1, std::min<int64_t>(want, units));
     // Group g runs on XCD g % 8 (the XCD-aware workgroup map of the stacking kernels), so a
@@ -118,14 +118,14 @@ int plan_stack(qm_engine *e, const StackLaunch &s, StackPlan *out) {
     const ShiftLayout *L = &e->sh;
     const int64_t wide_work = (int64_t)((e->g.nx + 7) / 8) * ((e->g.ny + 7) / 8) * ((e->g.nz + 15) / 16) *
                               ((n_chunk + qm::kShiftWideKT - 1) / qm::kShiftWideKT);
-    if (shift && p.shift_mode == qm::kShiftDetect && e->cfg_shift_wide != 0 && n_chunk >= qm::kShiftWideKT &&
+    if (shift && p.shift_mode == qm::kShiftDetect && e->cfg.shift_wide != 0 && n_chunk >= qm::kShiftWideKT &&
         // (tie_rule = 1 WITHOUT a row of maxima per brick -- tie_sets = 0, round 5's form -- re-stacks one set of bricks per
         // sample: the wide layout's few long workgroups would publish sets of tens of thousands of nodes)
-        (e->cfg_shift_wide == 1 || (wide_work >= 8 * (int64_t)e->n_cu && n_chunk >= 4 * qm::kShiftWideKT &&
-                                    (!e->cfg_tie_rule || e->cfg_tie_sets) &&
+        (e->cfg.shift_wide == 1 || (wide_work >= 8 * (int64_t)e->n_cu && n_chunk >= 4 * qm::kShiftWideKT &&
+                                    (!e->cfg.tie_rule || e->cfg.tie_sets) &&
                                     std::min(e->g.nx, std::min(e->g.ny, e->g.nz)) >= 8)) &&   // (thin boxes of a
                                     // rank's column partition: their 8 x 8 x 16 bricks would be mostly empty)
-        e->cfg_shift_waves == 0) {
+        e->cfg.shift_waves == 0) {
         if (ensure_shift_tables(e, e->shw)) return 1;
         if (e->shw.ok) L = &e->shw;
     }
@@ -179,17 +179,17 @@ int plan_stack(qm_engine *e, const StackLaunch &s, StackPlan *out) {
     }
     if (marginal) p.marg_tiles = p.ntiles;
     const int n_wide_now = p.layout->n_list, nbricks_now = p.layout->g.nbricks;
-    p.use_direct = e->cfg_force_direct || n_wide_now > 0;
-    p.use_lds = !e->cfg_force_direct && n_wide_now < nbricks_now;
+    p.use_direct = e->cfg.force_direct || n_wide_now > 0;
+    p.use_lds = !e->cfg.force_direct && n_wide_now < nbricks_now;
     // the direct launch: the LDS kernel's tile length (64 * J = 128 * JP; the shift-reuse launch's bricks on whole
     // 256-sample tiles of their own, clamped), the wavefronts' publish area
     p.direct_j = shift ? 4 : jp > 0 ? 2 * jp : J;
-    p.direct_threads = shift ? 512 : jp > 0 ? 1024 : e->cfg_waves * qm::kWave;
+    p.direct_threads = shift ? 512 : jp > 0 ? 1024 : run_waves(e) * qm::kWave;
     p.direct_publish = (size_t)3 * (p.direct_threads / qm::kWave) * qm::kWave * p.direct_j * sizeof(double);
     const int threads = p.direct_threads;
     const int lds_blocks_per_cu =
         shift ? (L->nw == qm::kShiftWaves ? 2 : 1) : jp > 0 ? 1
-               : std::max(1, std::min(160 * 1024 / std::max(1, e->cfg_lds_bytes), 2048 / threads));
+               : std::max(1, std::min(160 * 1024 / std::max(1, run_lds_bytes(e)), 2048 / threads));
     if (p.use_lds) {
         // (several timesteps per launch: the group count is the single step's -- the groups are the
         // order in which a sample's coalescence is summed over the nodes, and a step's result must
@@ -197,16 +197,16 @@ int plan_stack(qm_engine *e, const StackLaunch &s, StackPlan *out) {
         // (bricks of <= 64 nodes -- coarse grids with wide tables, 4 nodes per wavefront and brick: a
         // workgroup's fixed costs weigh more than the grid's tail, three rounds instead of twelve:
         // E2 0.418 -> 0.394 ms, profiles/r04_rounds_sweep.txt)
-        int rounds = (!shift && jp == 0 && !e->user_rounds && e->g.brick_nodes <= 64) ? 3 : 0;
+        int rounds = (!shift && jp == 0 && !e->cfg.user_rounds && e->g.brick_nodes <= 64) ? 3 : 0;
         // (the wide layout's 8-wave workgroups, one per CU: FEW, long workgroups -- C3 41.7 / 42.1 / 42.3 / 42.6 ms
         // at 1 / 4 / 8 / 12 rounds, where the 4-wave shape runs 50.1 / 46.5 / 45.7 at 4 / 8 / 12,
         // profiles/r06_ab_runs.txt: the fewest rounds that leave no slot idle, 0.2 % charged per round)
         // (the 8-wave shape of 33-64 rows likewise: a C4 slab, 47 tiles, 170.2 ms at 12 rounds = 64 groups, 168.6 at
         // 16 groups = 2.94 rounds, 181.5 at 40 groups = 7.3 rounds: what the count must avoid is a last round that is
         // mostly empty)
-        if (shift && (wide || (L->nw == qm::kShiftWaves8 && L->nblk == 1)) && !e->user_rounds) {
+        if (shift && (wide || (L->nw == qm::kShiftWaves8 && L->nblk == 1)) && !e->cfg.user_rounds) {
             double best = 1e300;
-            for (int r = 1; r <= e->cfg_rounds; ++r) {
+            for (int r = 1; r <= e->cfg.rounds; ++r) {
                 const int g = auto_groups(e, p.ntiles, nbricks_now, lds_blocks_per_cu, r);
                 const double busy = (double)p.ntiles * g / ((double)r * e->n_cu * lds_blocks_per_cu);
                 const double cost = (1.0 - std::min(1.0, busy)) + 0.002 * r;
@@ -215,18 +215,18 @@ int plan_stack(qm_engine *e, const StackLaunch &s, StackPlan *out) {
         }
         // (tie_rule = 1 stacks one SET of bricks again per sample, qm_ties.hpp: eight times as many,
         // smaller sets -- the refinement's cost falls with the set size, the stacking launch loses ~1 %)
-        p.groups_lds = e->cfg_groups > 0 ? std::min(e->cfg_groups, nbricks_now)
+        p.groups_lds = e->cfg.groups > 0 ? std::min(e->cfg.groups, nbricks_now)
                                          : auto_groups(e, p.ntiles, nbricks_now, lds_blocks_per_cu, rounds);
         // Round 6: the shift-reuse fused detect leaves the largest z PER BRICK and sample beside its workgroups'
         // partial sets (StackArgs::brick_max): the refinement stacks one brick per sample, the launch keeps its
         // group count -- and its bits
-        p.brick_rows = (e->cfg_tie_rule && want_scan && e->cfg_tie_sets && shift && p.shift_mode == qm::kShiftDetect &&
+        p.brick_rows = (e->cfg.tie_rule && want_scan && e->cfg.tie_sets && shift && p.shift_mode == qm::kShiftDetect &&
                         L->plain()) ? nbricks_now : 0;
-        if (e->cfg_tie_rule && want_scan && !p.brick_rows && !e->user_rounds && e->cfg_groups == 0) {
+        if (e->cfg.tie_rule && want_scan && !p.brick_rows && !e->cfg.user_rounds && e->cfg.groups == 0) {
             // ... the other kernels: eight times as many, smaller sets, but never sets of fewer than four bricks:
             // the workgroup's fixed costs (C2: +8 % on the stacking launch at one brick per set)
             const int fine = auto_groups(e, p.ntiles, std::max(1, nbricks_now / 4), lds_blocks_per_cu,
-                                         8 * (rounds > 0 ? rounds : e->cfg_rounds));
+                                         8 * (rounds > 0 ? rounds : e->cfg.rounds));
             p.groups_lds = std::max(p.groups_lds, fine);
         }
         // which LDS kernel (the read-outs last_kernel / last_kernel_j; a direct-only launch keeps 0 and 0)
@@ -240,7 +240,7 @@ int plan_stack(qm_engine *e, const StackLaunch &s, StackPlan *out) {
             const bool per_brick = p.brick_rows && p.wide_tiles == 0;
             const int64_t life = (per_brick ? 1 : (int64_t)L->g.nbricks / std::max(1, p.groups_lds)) *
                                  std::max(1, L->g.brick_nodes / 8 / L->nw);
-            p.lazy = e->cfg_shift_lazy >= 0 ? e->cfg_shift_lazy : (life >= qm::kShiftLazyGroups ? 1 : 0);
+            p.lazy = e->cfg.shift_lazy >= 0 ? e->cfg.shift_lazy : (life >= qm::kShiftLazyGroups ? 1 : 0);
             if (L->nblk > 1 && !L->direct) p.lazy = 0;  // (the register-staged form: eager only)
         } else if (jp > 0) {
             p.family = kFamilyPair;
@@ -250,18 +250,18 @@ int plan_stack(qm_engine *e, const StackLaunch &s, StackPlan *out) {
             // volume-writing for 33-64 rows (up to 32 the paired kernel writes volumes), when the
             // launch uses the table width's own samples per lane
             const int S = e->g.n_rows;
-            const bool exact = e->cfg_exact && !e->cfg_generic && !accumulate && qm::exact_built(S, J) &&
+            const bool exact = e->cfg.exact && !e->cfg.generic && !accumulate && qm::exact_built(S, J) &&
                                (marginal || !volume || S > qm::kPairMaxRows);
             p.family = exact ? kFamilyExact : kFamilyChunked;
             p.j = J;
         }
     }
     if (p.use_direct) {
-        const int units = e->cfg_force_direct ? nbricks_now : n_wide_now;
-        p.groups_direct = e->cfg_groups > 0 ? std::min(e->cfg_groups, units)
+        const int units = e->cfg.force_direct ? nbricks_now : n_wide_now;
+        p.groups_direct = e->cfg.groups > 0 ? std::min(e->cfg.groups, units)
                                             : auto_groups(e, p.ntiles, units, 2048 / threads);
         // (force_direct: every brick, no list)
-        p.list = e->cfg_force_direct ? nullptr : p.layout->list.p;
+        p.list = e->cfg.force_direct ? nullptr : p.layout->list.p;
         p.n_list = units;
     }
     p.g = p.layout->g;
@@ -328,7 +328,7 @@ int launch_round2_lds(qm_engine *e, const qm::StackArgs &a, StackPlan *p) {
     const int J = p->j, S = e->g.n_rows;
     const bool VOLUME = a.volume != nullptr || a.marginal != nullptr;
     const qm::LaunchShape shape = stack_shape(e, a, p->direct_threads,
-                                              std::max((size_t)e->cfg_lds_bytes, p->direct_publish));
+                                              std::max((size_t)run_lds_bytes(e), p->direct_publish));
     bool exact = false;
     if (p->family == kFamilyExact) {
         const bool j4_wide = J == 4 && S > 40;     // the second variant of 41-64 rows
@@ -350,7 +350,7 @@ int launch_round2_lds(qm_engine *e, const qm::StackArgs &a, StackPlan *p) {
     // reference's accumulate-into-volume semantics, the generic kernel.
     if (!exact) {
         p->family = kFamilyChunked;
-        int nch = (e->cfg_generic || a.accumulate) ? 0 : e->g.row_pad / 8;
+        int nch = (e->cfg.generic || a.accumulate) ? 0 : e->g.row_pad / 8;
         if (nch > 8) nch = 0;
         bool built = false;
         if (VOLUME) QM_TABLE(qm::launch_chunked_volume(J, nch, a, shape, &built));
@@ -452,7 +452,7 @@ int issue_stack(qm_engine *e, const StackLaunch &s, StackPlan *p) {
     if (p->use_direct && launch_direct(e, stack_args(e, s, *p, true), *p)) return 1;
     if (logged) {
         QM_HIP(hipEventRecord(ev_end, e->stream));
-        e->timed = !e->log_timing;
+        e->timed = !e->cfg.log_timing;
     }
     return 0;
 }
@@ -463,7 +463,7 @@ int issue_stack(qm_engine *e, const StackLaunch &s, StackPlan *p) {
 int timing_events(qm_engine *e, hipEvent_t *begin, hipEvent_t *end) {
     *begin = e->ev0;
     *end = e->ev1;
-    if (!e->log_timing) return 0;
+    if (!e->cfg.log_timing) return 0;
     while (e->ev_used + 2 > e->ev_log.size()) {
         hipEvent_t ev;
         QM_HIP(hipEventCreate(&ev));
@@ -512,7 +512,7 @@ int combine(qm_engine *e, const SetView &in, CombineMode mode, int64_t node_offs
             const OutSeries &out, const int32_t *run_if) {
     // (tie_rule = 1 with a row of maxima per brick: the fold of the workgroups' own sets also leaves the largest z)
     double *o_z = nullptr;
-    if (e->cfg_tie_rule && e->last.brick_rows > 0 && in.max == e->d_pmax.p && run_if == nullptr) {
+    if (e->cfg.tie_rule && e->last.brick_rows > 0 && in.max == e->d_pmax.p && run_if == nullptr) {
         if (e->d_tie_zext.ensure(in.n)) return 1;
         o_z = e->d_tie_zext.p;
     }
@@ -541,7 +541,7 @@ StackResult stack_fold(qm_engine *e, const StackLaunch &s, CombineMode mode, int
     // (the reference's rule on near-ties: final series of this engine's own nodes only -- the partial
     // sets of a sharded detect leave the engine before anyone knows the global maximum -- and not on the
     // screened step's fallback)
-    if (mode == kCombineFinal && e->cfg_tie_rule && s.run_if == nullptr && refine_ties(e, s, o.idx, nullptr, nullptr))
+    if (mode == kCombineFinal && e->cfg.tie_rule && s.run_if == nullptr && refine_ties(e, s, o.idx, nullptr, nullptr))
         return 1;
     return r;
 }
@@ -559,7 +559,7 @@ int detect_core(qm_engine *e, const double *d_on, int T, int fsmp, int ns, int a
     // followed by a refinement nobody waits for: the two opt-ins exclude each other on the detect calls)
     e->last.sets_own = false;                           // (the screened sweep writes d_pmax as well; a refused
                                                         // call is no detect_partial either)
-    if (e->cfg_screen && e->cfg_tie_rule)
+    if (e->cfg.screen && e->cfg.tie_rule)
         return fail("detect: the config keys screen = 1 and tie_rule = 1 cannot be combined (the screened detect "
                     "has no near-tie refinement): set one of them to 0");
     if (run_screen(e, d_on, T, fsmp, ns, available, &sets, &screened)) return 1;
@@ -578,13 +578,13 @@ int detect_core(qm_engine *e, const double *d_on, int T, int fsmp, int ns, int a
 
 int scan_fold(qm_engine *e, const double *vol, int64_t stride, int ns, int64_t n_nodes, int64_t node0,
               CombineMode mode, const OutSeries &out) {
-    // a workgroup = up to 16 adjacent tiles (one wavefront each); ~cfg_scan_waves wavefronts
+    // a workgroup = up to 16 adjacent tiles (one wavefront each); ~cfg.scan_waves wavefronts
     // per CU in total; at least 256 nodes per chunk
     const int tiles = (ns + qm::kWave - 1) / qm::kWave;
     const int groups = (tiles + qm::kScanWaves - 1) / qm::kScanWaves;
     const int waves = (tiles + groups - 1) / groups;          // per workgroup, balanced
     const int xgroups = (tiles + waves - 1) / waves;
-    int64_t sets = std::max<int64_t>(1, ((int64_t)e->cfg_scan_waves * e->n_cu + tiles - 1) / tiles);
+    int64_t sets = std::max<int64_t>(1, ((int64_t)e->cfg.scan_waves * e->n_cu + tiles - 1) / tiles);
     sets = std::min<int64_t>(sets, std::max<int64_t>(1, n_nodes / 256));
     sets = std::min<int64_t>(sets, 65535);
     const int64_t per = (n_nodes + sets - 1) / sets;
@@ -819,122 +819,27 @@ int qm_engine_synchronize(qm_engine *e) {
 
 int qm_engine_config(qm_engine *e, const char *key, int64_t v) {
     if (!e || !key) return fail("qm_engine_config: NULL argument");
-    const std::string k(key);
-    if (k == "brick_x" || k == "brick_y" || k == "brick_z") {
-        if (v < 0 || v > 64) return fail("%s must be in 0..64 (0 = automatic)", key);
-        (k == "brick_x" ? e->cfg_bx : k == "brick_y" ? e->cfg_by : e->cfg_bz) = (int)v;
-        if (e->cfg_bx > 0) {                           // an explicit shape needs all three
-            if (e->cfg_by < 1) e->cfg_by = 1;
-            if (e->cfg_bz < 1) e->cfg_bz = 1;
-        }
-    } else if (k == "samples_per_lane") {
-        if (v != 0 && v != 1 && v != 2 && v != 4)
-            return fail("samples_per_lane must be 0 (automatic), 1, 2 or 4");
-        e->cfg_j = (int)v;
-    } else if (k == "waves") {
-        if (v < 1 || v > 16) return fail("waves must be 1..16");
-        e->cfg_waves = (int)v;
-        e->user_waves = true;
-    } else if (k == "groups") {
-        if (v < 0) return fail("groups must be >= 0");
-        e->cfg_groups = (int)v;
-    } else if (k == "rounds") {
-        if (v < 1 || v > 1024) return fail("rounds must be in 1..1024");
-        e->cfg_rounds = (int)v;
-        e->user_rounds = true;
-    } else if (k == "lds_bytes") {
-        if (v < 1024 || v > 160 * 1024) return fail("lds_bytes must be in 1 KiB..160 KiB");
-        e->cfg_lds_bytes = (int)(v / 16 * 16);
-        e->user_lds = true;
-    } else if (k == "force_direct") {
-        e->cfg_force_direct = v ? 1 : 0;
-    } else if (k == "generic") {
-        e->cfg_generic = v ? 1 : 0;
-    } else if (k == "exact") {
-        e->cfg_exact = v ? 1 : 0;
-    } else if (k == "scan_waves") {
-        if (v < 1 || v > 4096) return fail("scan_waves must be in 1..4096");
-        e->cfg_scan_waves = (int)v;
-
-    } else if (k == "pair") {
-        if (v < 0 || v > 2) return fail("pair must be 0 (off), 1 (automatic) or 2 (any scan length)");
-        e->cfg_pair = (int)v;
-    } else if (k == "shift") {
-        if (v < -1 || v > 1) return fail("shift must be -1 (automatic), 0 (off) or 1");
-        e->cfg_shift = (int)v;
-    } else if (k == "shift_waves") {
-        if (v != 0 && v != qm::kShiftWaves && v != qm::kShiftWaves8 && v != qm::kShiftWaves3)
-            return fail("shift_waves must be 0 (automatic), 4, 8 or 12");
-        e->cfg_shift_waves = (int)v;
-        e->sh.invalidate();
-    } else if (k == "shift_rows_direct") {
-        if (v < 0 || v > 2) return fail("shift_rows_direct must be 0, 1 or 2");
-        e->cfg_shift_rows_direct = (int)v;
-        e->sh.invalidate();
-    } else if (k == "shift_tail") {
-        e->cfg_shift_tail = v ? 1 : 0;
-    } else if (k == "shift_wide") {
-        if (v < -1 || v > 1) return fail("shift_wide must be -1 (automatic), 0 (off) or 1");
-        e->cfg_shift_wide = (int)v;
-    } else if (k == "shift_wide_rows") {
-        if (v < 0 || v > 2) return fail("shift_wide_rows must be 0 (never), 1 (where all rows do not fit) or 2 (always)");
-        e->cfg_shift_wide_rows = (int)v;
-        e->shw.invalidate();
-    } else if (k == "tie_rule") {
-        if (v != 0 && v != 1) return fail("tie_rule must be 0 (largest sum) or 1 (the reference's exp rule)");
-        e->cfg_tie_rule = (int)v;
-    } else if (k == "tie_sets") {
-        e->cfg_tie_sets = v ? 1 : 0;
-    } else if (k == "shift_lazy") {
-        if (v < -1 || v > 1) return fail("shift_lazy must be -1 (automatic), 0 or 1");
-        e->cfg_shift_lazy = (int)v;
-    } else if (k == "screen") {
-        e->cfg_screen = v ? 1 : 0;
-    } else if (k == "screen_pairs") {
-        if (v != 0 && v != 1 && v != 2 && v != 4) return fail("screen_pairs must be 0, 1, 2 or 4");
-        e->cfg_screen_pairs = (int)v;
-        e->screen.invalidate();
-    } else if (k == "screen_brick16") {
-        e->cfg_screen_brick16 = v ? 1 : 0;
-        e->screen.invalidate();
-    } else if (k == "screen_big") {
-        if (v < -1 || v > 1) return fail("screen_big must be -1 (automatic), 0 or 1");
-        e->cfg_screen_big = (int)v;
-        e->screen.invalidate();
-    } else if (k == "stream_pull") {
-        if (v < -1 || v > 1) return fail("stream_pull must be -1 (slots of <= 1 MB), 0 (never) or 1 (always)");
-        e->cfg_stream_pull = (int)v;
-    } else if (k == "stream_stamps") {
-        e->cfg_stream_stamps = v ? 1 : 0;
-    } else if (k == "preproc_skew") {
-        e->cfg_preproc_skew = v ? 1 : 0;
-    } else if (k == "trigger_timing") {
-        e->cfg_trigger_timing = v ? 1 : 0;
-    } else if (k == "log_timing") {
-        e->log_timing = v != 0;
-        e->ev_used = 0;
-    } else if (k == "chunk_bytes") {
-        if (v < (1 << 20)) return fail("chunk_bytes must be >= 1 MiB");
-        e->cfg_chunk_bytes = v;
-    } else {
-        return fail("unknown config key '%s'", key);
-    }
+    unsigned effects = 0;
+    if (config_set(e->cfg, key, v, &effects)) return 1;
+    if (effects & kVoidShift) e->sh.invalidate();
+    if (effects & kVoidShiftWide) e->shw.invalidate();
+    if (effects & kVoidScreen) e->screen.invalidate();
+    if (effects & kResetTimingLog) e->ev_used = 0;
     return 0;
 }
 
+// In this order: the keys whose read-out is live (the resident table's brick shape, samples per lane and workgroup
+// shape; the last launch's or plan's shift_waves, shift_lazy, screen_pairs, screen_big), the read-outs that are no
+// tunables, the tunables as set (config_get).
 int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     if (!e || !key || !v) return fail("qm_engine_get: NULL argument");
     const std::string k(key);
-    if (k == "brick_x") *v = e->have_lut ? e->g.bx : e->cfg_bx;
-    else if (k == "brick_y") *v = e->have_lut ? e->g.by : e->cfg_by;
-    else if (k == "brick_z") *v = e->have_lut ? e->g.bz : e->cfg_bz;
-    else if (k == "samples_per_lane") *v = e->have_lut ? eff_j(e) : e->cfg_j;
-    else if (k == "waves") *v = e->cfg_waves;
-    else if (k == "groups") *v = e->cfg_groups;
-    else if (k == "lds_bytes") *v = e->cfg_lds_bytes;
-    else if (k == "force_direct") *v = e->cfg_force_direct;
-    else if (k == "chunk_bytes") *v = e->cfg_chunk_bytes;
-    else if (k == "screen") *v = e->cfg_screen;
+    if (e->have_lut && k == "brick_x") *v = e->g.bx;
+    else if (e->have_lut && k == "brick_y") *v = e->g.by;
+    else if (e->have_lut && k == "brick_z") *v = e->g.bz;
+    else if (e->have_lut && k == "samples_per_lane") *v = eff_j(e);
+    else if (k == "waves") *v = run_waves(e);
+    else if (k == "lds_bytes") *v = run_lds_bytes(e);
     else if (k == "screened_steps" || k == "fallback_steps" || k == "last_candidates") {
         DeviceGuard guard(e->device);
         if (drain_flags(e)) return 1;
@@ -946,17 +851,13 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     else if (k == "screen_brick_nodes") *v = e->screen.g.brick_nodes;
     else if (k == "last_kernel") *v = e->last.family;
     else if (k == "last_kernel_j") *v = e->last.j;
-    else if (k == "shift") *v = e->cfg_shift;
     else if (k == "shift_ok") *v = e->sh.built && e->sh.ok ? 1 : 0;
     else if (k == "shift_waves")                        // (of the layout the last launch ran on, if shift-reuse and
         // still this table's: a table change voids the layouts, invalidate_derived)
-        *v = e->last.shift && e->last.shift->ok ? e->last.shift->nw : e->sh.ok ? e->sh.nw : e->cfg_shift_waves;
+        *v = e->last.shift && e->last.shift->ok ? e->last.shift->nw : e->sh.ok ? e->sh.nw : e->cfg.shift_waves;
     else if (k == "shift_lazy") *v = e->last.lazy;
-    else if (k == "shift_tail") *v = e->cfg_shift_tail;
     else if (k == "shift_tail_spl") *v = e->last.tail_spl;
-    else if (k == "shift_wide") *v = e->cfg_shift_wide;
     else if (k == "shift_wide_ok") *v = e->shw.built && e->shw.ok ? 1 : 0;
-    else if (k == "shift_wide_rows") *v = e->cfg_shift_wide_rows;
     else if (k == "shift_wide_row_blocks") *v = e->shw.ok ? e->shw.nblk : 0;
     else if (k == "shift_wide_tiles") *v = e->last.wide_tiles;
     else if (k == "shift_wide_brick_nodes") *v = e->shw.ok ? e->shw.g.brick_nodes : 0;
@@ -964,14 +865,9 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     else if (k == "shift_wide_operands_per_add_x1000")   // 8-byte LDS operands fetched per add of a wide tile (x 1000)
         *v = e->shw.ok && e->shw.group_rows > 0 ? (e->shw.wquads * 4 * 1000) / (e->shw.group_rows * 48) : 0;
     else if (k == "steps_per_launch") *v = e->last_batched;
-    else if (k == "tie_rule") *v = e->cfg_tie_rule;
-    else if (k == "tie_sets") *v = e->cfg_tie_sets;
-    else if (k == "stream_pull") *v = e->cfg_stream_pull;
-    else if (k == "preproc_skew") *v = e->cfg_preproc_skew;
     else if (k == "pick_lds_samples") *v = qm::kPicksLdsSamples;
     else if (k == "amp_lds_samples") *v = qm::kAmpLdsSamples;
     else if (k == "trigger_max_radius") *v = qm::kTrigMaxRadius;
-    else if (k == "trigger_timing") *v = e->cfg_trigger_timing;
     else if (k == "trigger_ns_smooth") *v = e->trg_ns[qm::kTrigSmooth];
     else if (k == "trigger_ns_stats") *v = e->trg_ns[qm::kTrigStats];
     else if (k == "trigger_ns_runs") *v = e->trg_ns[qm::kTrigRuns];
@@ -1035,7 +931,7 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     else if (k == "nx") *v = e->g.nx;
     else if (k == "ny") *v = e->g.ny;
     else if (k == "nz") *v = e->g.nz;
-    else return fail("unknown key '%s'", key);
+    else if (!config_get(e->cfg, key, v)) return fail("unknown key '%s'", key);
     return 0;
 }
 
@@ -1116,7 +1012,7 @@ int qm_engine_detect_batch(qm_engine *e, const double *log_onsets, int onsets_on
     OutSeries st;
     if (stage_out(e, n_all, out_on_device, user, &st)) return 1;
     bool batched = false;
-    if (n_steps > 1 && !e->cfg_screen) {
+    if (n_steps > 1 && !e->cfg.screen) {
         // partial sets [sets][n_steps * ns] -> the steps' series back to back (tie_rule = 1 keeps the step
         // axis: the refinement reads the launch's sets with sample t = step * ns + ...)
         StackLaunch s(d_on, T, fsmp, ns, available);
@@ -1146,7 +1042,7 @@ int qm_engine_tie_partial(qm_engine *e, const double *log_onsets, int onsets_on_
     DeviceGuard guard(e->device);
     int ns = 0;
     if (check_step(e, T, fsmp, lsmp, available, &ns)) return 1;
-    if (!e->cfg_tie_rule) return fail("qm_engine_tie_partial: the engine was not configured with tie_rule = 1");
+    if (!e->cfg.tie_rule) return fail("qm_engine_tie_partial: the engine was not configured with tie_rule = 1");
     if (e->last.scan_n != ns || e->last.sets < 1 || !e->last.sets_own)
         return fail("qm_engine_tie_partial: no partial sets of a float64 detect of %d samples on this engine "
                     "(call qm_engine_detect_partial for the step first, with no other launch, volume scan or "
@@ -1199,7 +1095,7 @@ int qm_engine_migrate(qm_engine *e, const double *log_onsets, int onsets_on_devi
     } else {
         // host volume: stream it through a device chunk buffer, time-chunk by time-chunk
         const int KT = qm::kWave * eff_j(e);
-        int64_t chunk = e->cfg_chunk_bytes / (8 * e->n_nodes);
+        int64_t chunk = e->cfg.chunk_bytes / (8 * e->n_nodes);
         chunk = std::max<int64_t>(KT, chunk / KT * KT);
         chunk = std::min<int64_t>(chunk, ns);
         if (e->d_chunk.ensure((size_t)e->n_nodes * chunk)) return 1;
@@ -1274,7 +1170,7 @@ int qm_engine_find_max_coa(qm_engine *e, const double *map4d, int map_on_device,
     if (map_on_device) {
         if (scan_fold(e, map4d, n_samples, n_samples, n_nodes, 0, kCombineValues, st)) return 1;
     } else {
-        int64_t chunk = std::max<int64_t>(1, e->cfg_chunk_bytes / (8 * n_nodes));
+        int64_t chunk = std::max<int64_t>(1, e->cfg.chunk_bytes / (8 * n_nodes));
         chunk = std::min<int64_t>(chunk, n_samples);
         if (e->d_chunk.ensure((size_t)n_nodes * chunk)) return 1;
         for (int k0 = 0; k0 < n_samples; k0 += (int)chunk) {

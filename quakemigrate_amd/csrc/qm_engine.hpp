@@ -1,6 +1,8 @@
 // qm_engine.hpp -- internal header of the engine's host side (not installed; the C ABI is
 // include/qmhip.h).  The host runtime is split by what it deals with:
 //   qm_runtime.hip   error text, pooled streams, the pinned bounce buffers, the device-memory pool
+//   qm_config.hip    the tunables: one record, one table with a row per key, config_set / config_get (qm_config.hpp;
+//                    plain host C++)
 //   qm_tables.hip    everything derived from ONE travel-time table: load, layout search, the kernels'
 //                    derived tables (round-2 offsets, paired, shift-reuse, screening), parked tables,
 //                    on-device serving
@@ -42,6 +44,7 @@
 #include <variant>
 #include <vector>
 
+#include "qm_config.hpp"
 #include "qm_kernels.hpp"
 #include "qm_launch.hpp"
 #include "qm_screen.hpp"
@@ -324,8 +327,7 @@ struct qm_engine : TableState {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
-    // optional per-call timing log (bench): pairs of events around every stacking launch
-    bool log_timing = false;
+    // optional per-call timing log (cfg.log_timing; bench): pairs of events around every stacking launch
     std::vector<hipEvent_t> ev_log;     // 2 events per recorded call
     size_t ev_used = 0;
 
@@ -337,47 +339,7 @@ struct qm_engine : TableState {
     int64_t table_digests = 0;          // digest kernels run (qm_engine_table_digest: once per table)
     DevBuf<unsigned long long> d_digest;    // ... their sum
 
-    // tunables
-    int cfg_bx = 0, cfg_by = 0, cfg_bz = 0;      // 0 = choose the brick shape per table
-    int cfg_j = 0;                  // samples per lane (time tile = 64*J); 0 = by table width
-    int cfg_waves = 8;
-    bool user_waves = false, user_lds = false;   // set explicitly: no automatic layout
-    int cfg_groups = 0;
-    int cfg_rounds = 12;            // automatic group count: grid = this many rounds over the slots
-    bool user_rounds = false;       // ... set explicitly
-    int cfg_lds_bytes = 80 * 1024;
-    int cfg_force_direct = 0;
-    int cfg_generic = 0;            // 1 = always the generic (any row count) LDS kernel
-    int cfg_scan_waves = 32;        // find_max_coa of a volume: wavefronts per CU over the whole grid
-    int cfg_exact = 1;              // 1 = the exact-row-count kernel where one is built (see
-                                    //     qm_launch.hpp), 0 = the chunked kernels only
-    int64_t cfg_chunk_bytes = (int64_t)4 << 30;
-    int cfg_pair = 1;               // 1 = the 16-byte-operand kernel (qm_pair.hpp) where it applies
-    int cfg_screen = 0;             // 1 (opt-in): detect = float32 screening sweep + exact float64
-                                    // refinement (qm_screen.hpp); 0: every node-sample in float64
-    int cfg_screen_pairs = 0;       // pairs of samples per lane in the sweep (0 = automatic)
-    int cfg_screen_brick16 = 0;     // also try 16x8x8 bricks for the sweep
-    int cfg_screen_big = -1;        // 1: one 16-wave workgroup per CU with 160 KB of LDS; -1 = automatic
-    int cfg_shift = -1;                     // -1: where the table qualifies, 0: never, 1: as -1 (explicit)
-    int cfg_shift_waves = 0;                // workgroup shape: 4 (two per CU), 12 (one per CU), 0 = automatic
-    int cfg_shift_lazy = -1;                // detect loop flavour: -1 automatic, 0 eager, 1 lazy arg-max
-    int cfg_shift_tail = 1;                 // 1: a scan's remainder of <= 192 samples runs as one tail tile of
-                                            // 64 / 128 / 192 samples; 0: whole tiles only (round 3)
-    int cfg_shift_rows_direct = 1;
-    int cfg_shift_wide = -1;                // fused detect on WIDE tiles (384 samples, six per lane; round 6): -1 where
-                                            // they fit and the scan holds at least one, 0 never, 1 as -1 (explicit)
-    int cfg_shift_wide_rows = 1;            // ... on ROW BLOCKS where the windows of all rows do not fit (0: never,
-                                            // 2: row blocks whatever fits -- tests)
-    int cfg_stream_pull = -1;               // qm_stream: a slot's pinned inputs pulled by a kernel on the engine's stream
-                                            // instead of a copy command on another (-1: slots of <= 1 MB, 0, 1)
-    int cfg_stream_stamps = 0;              // qm_stream, measurement: GPU-clock stamps around every launch (stderr digest)
-    int cfg_preproc_skew = 1;               // pre-processing filter: 1 section s on lane s, one sample behind lane s - 1
-                                            // (qm_preproc.hpp); 0: every section on one lane (the cross-check)
-    int cfg_tie_rule = 0;                   // 0: largest float64 sum, lowest index among equal ones (default);
-                                            // 1: the reference's rule on near-ties (qm_ties.hpp)
-    int cfg_tie_sets = 1;                   // ... refined from a partial set PER BRICK where the stacking kernel has
-                                            // that flavour (the shift-reuse fused detect); 0: round 5's sets of
-                                            // four bricks everywhere (measurements)
+    EngineConfig cfg;                   // the tunables (qm_config.hpp): written by config_set only
 
     // per-step scratch of the screened detect (qm_screen.hpp) and its statistics
     DevBuf<int32_t> d_scalar, d_counts, d_cells, d_work, d_flags;
@@ -424,8 +386,7 @@ struct qm_engine : TableState {
     DevBuf<double> d_trg_x, d_trg_par, d_trg_val;
     DevBuf<int32_t> d_trg_cnt, d_trg_run;
     DevBuf<int64_t> d_trg_tot, d_trg_cand;
-    int cfg_trigger_timing = 0;             // 1: HIP events around every stage of the trigger sequence (measurement)
-    std::vector<hipEvent_t> trg_ev;         // ... a pair per stage
+    std::vector<hipEvent_t> trg_ev;         // cfg.trigger_timing: a pair of HIP events per stage of the trigger sequence
     int64_t trg_ns[qm::kTrigStages] = {};   // ... the last call's stage times ("trigger_ns_<stage>"), 0: did not run
 
     // scratch
@@ -492,7 +453,7 @@ struct ScreenPlan {
     bool big = false;
     int kt() const { return 128 * jp; }
     int lds_bytes(const qm_engine *e) const {
-        return big ? 160 * 1024 : (e->user_lds ? e->cfg_lds_bytes : 80 * 1024);
+        return big ? 160 * 1024 : (e->cfg.user_lds ? e->cfg.lds_bytes : 80 * 1024);
     }
     int window_bytes(const qm_engine *e) const {       // minus the cell-maximum row
         return (lds_bytes(e) - kt() * 4) / 16 * 16;
@@ -561,9 +522,15 @@ struct StackResult {
 };
 
 // ---- qm_tables.hip ------------------------------------------------------------------------------
-int lds_cap_doubles(const qm_engine *e);
+// the workgroup shape of the round-2 launches: the user's value if they set one, else the resident table's layout
+// search's choice, else the default (8 waves, 80 KiB)
+int run_waves(const qm_engine *e);
+int run_lds_bytes(const qm_engine *e);
+inline int lds_cap_doubles(int lds_bytes) { return lds_bytes / 8; }
+inline int lds_cap_doubles(const qm_engine *e) { return lds_cap_doubles(run_lds_bytes(e)); }
 int ensure_rel(qm_engine *e);
-int eff_j(const qm_engine *e);
+int eff_j(const qm_engine *e, int lds_bytes);          // ... under a trial LDS budget (the layout search)
+inline int eff_j(const qm_engine *e) { return eff_j(e, run_lds_bytes(e)); }
 int run_j(const qm_engine *e, int n_chunk);
 int plan_wide(qm_engine *e, int J);
 int pair_jp(const qm_engine *e, int n_chunk, bool volume);

@@ -173,7 +173,7 @@ int failed(qm_group *g) {
 int check_group(qm_group *g, const char *what) {
     if (!g) return fail("%s: group is NULL", what);
     if (!g->have_lut) return fail("%s: no travel-time table resident: call qm_group_load_lut first", what);
-    if (g->lead->cfg_screen || g->parts[0].eng[0]->cfg_screen)
+    if (g->lead->cfg.screen || g->parts[0].eng[0]->cfg.screen)
         return fail("%s: the screened detect (screen = 1) has no partial form: groups run float64 only", what);
     return 0;
 }
@@ -222,7 +222,7 @@ int exchange(qm_group *g, int T, int fsmp, int lsmp, int available, int ns) {
     if (qm_engine_finalize_packed(g->lead, g->d_gather.p, sets, ns, g->nx * g->ny * g->nz, o, o + ns,
                                   reinterpret_cast<int64_t *>(o + 2 * (size_t)ns), 1))
         return 1;
-    if (!g->lead->cfg_tie_rule) return 0;
+    if (!g->lead->cfg.tie_rule) return 0;
     {
         DeviceGuard lead(g->lead_dev);
         QM_HIP(hipEventRecord(g->ev_gathered, g->lead->stream));

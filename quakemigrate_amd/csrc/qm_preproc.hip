@@ -57,7 +57,7 @@ int PreprocStage::launch(qm_engine *e, const double *in, double *out, int n_step
     qm::PreprocArgs a = args;
     a.in = in;
     a.out = out;
-    a.skew = e->cfg_preproc_skew;
+    a.skew = e->cfg.preproc_skew;
     // one workgroup per trace; the trace lives in LDS if it fits (20 480 samples), else in its output row
     const int in_lds = a.T <= qm::kPreprocLdsSamples ? 1 : 0;
     const size_t lds = in_lds ? (size_t)a.T * sizeof(double) : 0;

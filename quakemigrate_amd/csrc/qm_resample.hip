@@ -116,7 +116,7 @@ int ResampleStage::launch(qm_engine *e, const void *raw, double *out, int n_step
     qm::ResampleArgs a = args;
     a.raw = raw;
     a.out = out;
-    a.skew = e->cfg_preproc_skew;
+    a.skew = e->cfg.preproc_skew;
     // one workgroup per trace; LDS for the longest kept series that fits (longer ones live in their scratch rows)
     const size_t lds = (size_t)std::min<int64_t>(max_kept, qm::kPreprocLdsSamples) * sizeof(double);
     return launch_with_lds(e, qm::resample_kernel, (unsigned)((int64_t)n_steps * n_traces), 256, lds, a);

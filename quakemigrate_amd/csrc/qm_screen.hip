@@ -70,11 +70,11 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
     const int S = g.n_rows;
     const int n_fit = g.nbricks - L.n_list;
     if (n_fit < 2) return 0;                            // a single cell: nothing to screen
-    const int groups = n_fit > 0 ? (e->cfg_groups > 0 ? std::min(e->cfg_groups, g.nbricks)
+    const int groups = n_fit > 0 ? (e->cfg.groups > 0 ? std::min(e->cfg.groups, g.nbricks)
                                                        : auto_groups(e, ntiles, g.nbricks, plan.big ? 1 : 2))
                                  : 0;
     const int groups_direct =
-        L.n_list > 0 ? (e->cfg_groups > 0 ? std::min(e->cfg_groups, L.n_list)
+        L.n_list > 0 ? (e->cfg.groups > 0 ? std::min(e->cfg.groups, L.n_list)
                                           : auto_groups(e, (ns + 63) / 64, L.n_list, 4))
                      : 0;
     const int sets = groups_direct + 1;
@@ -190,7 +190,7 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
                        e->d_pidx.p + (size_t)groups_direct * ns,
                        e->d_psum.p + (size_t)groups_direct * ns);
     QM_HIP(hipGetLastError());
-    e->timed = !e->log_timing;
+    e->timed = !e->cfg.log_timing;
     // the outcome travels to the host asynchronously (statistics only: the decision to redo the
     // step in float64 is taken on the device, see detect_core)
     if (e->flags_pending == kFlagRing && drain_flags(e)) return 1;

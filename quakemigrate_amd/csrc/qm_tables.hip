@@ -8,7 +8,10 @@
 #define QM_TU_TABLES 1
 #include "qm_engine.hpp"
 
-int lds_cap_doubles(const qm_engine *e) { return e->cfg_lds_bytes / 8; }
+int run_waves(const qm_engine *e) { return e->cfg.user_waves ? e->cfg.waves : e->tab_waves ? e->tab_waves : 8; }
+int run_lds_bytes(const qm_engine *e) {
+    return e->cfg.user_lds ? e->cfg.lds_bytes : e->tab_lds_bytes ? e->tab_lds_bytes : 80 * 1024;
+}
 
 // `g` cut into bricks of (at most) bx x by x bz nodes: bricks per axis, their number, nodes per brick.  The brick is
 // clamped to the grid -- `even`: to the grid's extents rounded up to even numbers, as the brick's own dimensions
@@ -44,13 +47,14 @@ int ensure_rel(qm_engine *e) {
 // whose S row windows leave >= 20 % of the LDS budget for the delay spans (J = 4 up to 64 rows:
 // beyond 40 its pipelined kernels spill a few offset chunks per node, and only the exact-row-count
 // kernels are built for that).
-int eff_j(const qm_engine *e) {
+int eff_j(const qm_engine *e, int lds_bytes) {
     const int S = e->n_rows_hint > 0 ? e->n_rows_hint : 1;
-    if (e->cfg_j > 0) return (e->cfg_j == 4 && S > qm::kJ4MaxRows) ? 2 : e->cfg_j;   // see below
+    const int set_j = e->cfg.samples_per_lane;
+    if (set_j > 0) return (set_j == 4 && S > qm::kJ4MaxRows) ? 2 : set_j;   // see below
     if (e->auto_j > 0) return e->auto_j;
     for (int j : {4, 2, 1}) {
         if (j == 4 && S > qm::kJ4MaxRows) continue;
-        if ((int64_t)S * qm::kWave * j * 8 * 5 <= (int64_t)e->cfg_lds_bytes * 4) return j;
+        if ((int64_t)S * qm::kWave * j * 8 * 5 <= (int64_t)lds_bytes * 4) return j;
     }
     return 1;
 }
@@ -61,7 +65,7 @@ int eff_j(const qm_engine *e) {
 // sample) -- e.g. the Icequake example's 625-sample timestep runs 5 tiles of 128, not 3 of 256.
 int run_j(const qm_engine *e, int n_chunk) {
     const int jmax = eff_j(e);
-    if (e->cfg_j > 0) return jmax;
+    if (e->cfg.samples_per_lane > 0) return jmax;
     int best = jmax;
     double best_cost = 1e300;
     for (int j : {4, 2, 1}) {
@@ -104,11 +108,11 @@ using qm::pair_jp_of;
 // 6.4 ms); the fused detect gains nothing from it (the LDS array moves the same bytes and is
 // ~80 % busy either way, profiles/r02_pmc_*) and keeps the two-workgroups-per-CU b64 kernel.
 int pair_jp(const qm_engine *e, int n_chunk, bool volume) {
-    if (!e->cfg_pair || e->cfg_generic || e->cfg_force_direct || e->user_waves || e->user_lds ||
-        e->cfg_j > 0)
+    if (!e->cfg.pair || e->cfg.generic || e->cfg.force_direct || e->cfg.user_waves || e->cfg.user_lds ||
+        e->cfg.samples_per_lane > 0)
         return 0;
     const int jp = pair_jp_of(e->g.n_rows);
-    if (e->cfg_pair == 2) return jp;                   // forced (tests): detect too, any scan length
+    if (e->cfg.pair == 2) return jp;                   // forced (tests): detect too, any scan length
     if (!volume) return 0;
     // short scans run on shorter tiles (run_j): leave those to the chunked kernels
     return (jp > 0 && run_j(e, n_chunk) == eff_j(e) && qm::kWave * eff_j(e) >= 128 * jp) ? jp : 0;
@@ -125,7 +129,7 @@ using BrickRelKernel = void (*)(qm::GridDesc, const int32_t *, const int4 *, con
 template <typename WantRel>
 static int search_bricks(qm_engine *e, BrickLayout &L, const int (*shapes)[3], int first, int n_shapes,
                          BrickFits fits, int KT, int budget, BrickRelKernel rel_kernel, WantRel want_rel) {
-    const bool fixed = e->cfg_bx > 0;
+    const bool fixed = e->cfg.brick_x > 0;
     if (fixed) first = 0, n_shapes = 1;
     qm::GridDesc g = e->g;
     std::vector<int32_t> total, wide;
@@ -179,7 +183,7 @@ int ensure_pair_tables(qm_engine *e, int jp) {
     // (with an explicit brick shape: whatever fits is paired, the rest goes to the direct kernel)
     // -- the offsets are built only for a table that is paired
     auto paired = [&](const qm::GridDesc &g, int n_list) {
-        P.ok = e->cfg_bx > 0 ? n_list < g.nbricks : (int64_t)n_list * 200 <= g.nbricks;
+        P.ok = e->cfg.brick_x > 0 ? n_list < g.nbricks : (int64_t)n_list * 200 <= g.nbricks;
         return P.ok;
     };
     if (search_bricks(e, P, kShapes, 0, (int)(sizeof(kShapes) / sizeof(kShapes[0])), qm::pair_fits, KT,
@@ -205,14 +209,14 @@ int ensure_shift_tables(qm_engine *e, ShiftLayout &L) {
     if (L.built) return 0;
     L.ok = false;
     const bool wide = &L == &e->shw;
-    int rc = wide && e->cfg_shift_wide_rows == 2 ? 0 : build_shift_tables(e, L, wide, false);
+    int rc = wide && e->cfg.shift_wide_rows == 2 ? 0 : build_shift_tables(e, L, wide, false);
     // (the wide layout: all rows of a brick in LDS where that fits -- up to ~36 rows of C3's geometry; beyond 64
     // rows, where the 256-sample tiles run on row blocks too, row blocks of <= 20 rows on 4x4x4 bricks: a C3 grid
     // x 128 rows x 1536 samples 44.0 ms against 48.6.  In between -- BASELINE configs[3]: 60 rows -- the row-block
     // form LOSES to the 8-wave kernel that holds all rows' 256-sample windows (a C4 slab 177.3 against 168.2 ms,
     // C3 x 60 rows 22.3 against 21.2, profiles/r06_ab_runs.txt): only on request there, shift_wide_rows = 2)
-    if (wide && rc == 0 && !L.ok && e->cfg_shift_wide_rows != 0 &&
-        (e->g.n_rows > qm::kShiftMaxRows || e->cfg_shift_wide_rows == 2))
+    if (wide && rc == 0 && !L.ok && e->cfg.shift_wide_rows != 0 &&
+        (e->g.n_rows > qm::kShiftMaxRows || e->cfg.shift_wide_rows == 2))
         rc = build_shift_tables(e, L, true, true);
     if (rc != 0 || !L.ok) {
         L.ok = false;
@@ -234,7 +238,7 @@ static int build_shift_tables(qm_engine *e, ShiftLayout &L, bool wide, bool wide
     // in registers while the rows are staged in nblk blocks of sb <= 64 rows.
     const bool blocks = wide ? wide_blocks : S > qm::kShiftMaxRows;
     if (wide && !blocks && S > qm::kShiftMaxRows) return 0;        // (all rows of a brick in LDS at once)
-    if (wide && blocks && (S < 2 || e->cfg_bx > 0)) return 0;
+    if (wide && blocks && (S < 2 || e->cfg.brick_x > 0)) return 0;
     // two forms (qm_shift.hpp): blocks of <= 34 rows staged by LDS-direct loads into the idle half of
     // a double-buffered LDS (default), or blocks of <= 64 staged through registers between two barriers
     // (that one only from 97 rows on: at 65-96 two blocks of <= 48 rows stage as often as they
@@ -243,19 +247,19 @@ static int build_shift_tables(qm_engine *e, ShiftLayout &L, bool wide, bool wide
     // nodes, single-buffered -- stack_shift_rows4_kernel)
     // (wide tiles: the double-buffered 8-wave form only, blocks of <= 20 rows -- 20 x (384 + span) samples in
     // each 80 KB half)
-    const int form = wide ? 1 : e->cfg_shift_rows_direct;   // 0 registers, 1 double-buffered 8 waves, 2 two x 4 waves
+    const int form = wide ? 1 : e->cfg.shift_rows_direct;   // 0 registers, 1 double-buffered 8 waves, 2 two x 4 waves
     const bool direct = form != 0;
     const bool quad = form == 2;
-    if (blocks && !direct && S <= 96 && e->cfg_shift != 1) return 0;
+    if (blocks && !direct && S <= 96 && e->cfg.shift != 1) return 0;
     const int block_rows = wide ? 20 : direct ? 34 : qm::kShiftMaxRows;
     const int nblk = blocks ? (S + block_rows - 1) / block_rows : 1;
     const int sb = blocks ? ((S + nblk - 1) / nblk + 1) / 2 * 2 : S;
-    if (S > 1024 || (blocks && !wide && e->cfg_shift_waves != 0 &&
-                     e->cfg_shift_waves != (quad ? qm::kShiftWaves : qm::kShiftWaves8)))
+    if (S > 1024 || (blocks && !wide && e->cfg.shift_waves != 0 &&
+                     e->cfg.shift_waves != (quad ? qm::kShiftWaves : qm::kShiftWaves8)))
         return 0;
     // a grid one node thick has half-empty 2x2x2 groups everywhere (e.g. the flat 1 x 1 x N view
     // of the reference-signature migrate): leave it to the other kernels unless asked explicitly
-    if (e->cfg_shift < 0 && (e->g.nx < 2 || e->g.ny < 2 || e->g.nz < 2)) return 0;
+    if (e->cfg.shift < 0 && (e->g.nx < 2 || e->g.ny < 2 || e->g.nz < 2)) return 0;
     // Workgroup shape (qm_shift.hpp): two 4-wave workgroups per CU up to ~32 rows; beyond, ONE 8-wave
     // workgroup with all 160 KB (smaller bricks, 33-64 rows); 12 waves only on request.  Bricks are
     // shaped so that their 2x2x2 groups deal evenly over the wavefronts.
@@ -269,8 +273,8 @@ static int build_shift_tables(qm_engine *e, ShiftLayout &L, bool wide, bool wide
     if (wide) {
         candidates[0] = qm::kShiftWaves8;
         n_candidates = 1;
-    } else if (e->cfg_shift_waves != 0) {
-        candidates[0] = e->cfg_shift_waves;
+    } else if (e->cfg.shift_waves != 0) {
+        candidates[0] = e->cfg.shift_waves;
         n_candidates = 1;
     } else if (blocks && quad) {
         candidates[0] = qm::kShiftWaves;
@@ -279,7 +283,7 @@ static int build_shift_tables(qm_engine *e, ShiftLayout &L, bool wide, bool wide
         candidates[0] = qm::kShiftWaves8;
         n_candidates = 1;
     }
-    const bool fixed = e->cfg_bx > 0 && !blocks;
+    const bool fixed = e->cfg.brick_x > 0 && !blocks;
     int n_shapes = fixed || blocks ? 1 : 5;
     // Round 6: a grid whose extent along one axis ends a node or two into a brick (the Icequake-sized C1: 57 nodes
     // in z = seven bricks of eight and one layer) pays a whole brick's staging and barriers for that layer.  Where a
@@ -322,7 +326,7 @@ static int build_shift_tables(qm_engine *e, ShiftLayout &L, bool wide, bool wide
                               : nw == qm::kShiftWaves3 ? kShapes12 : nw == qm::kShiftWaves8 ? kShapes8 : shapes4;
     const int n_try = kShapes == shapes4 ? n_shapes : std::min(n_shapes, 5);
     for (int s = 0; s < n_try; ++s) {
-        g = fixed ? rebrick(e->g, e->cfg_bx, e->cfg_by, e->cfg_bz, true)
+        g = fixed ? rebrick(e->g, e->cfg.brick_x, e->cfg.brick_y, e->cfg.brick_z, true)
                   : rebrick(e->g, kShapes[s][0], kShapes[s][1], kShapes[s][2], true);
         const size_t br = (size_t)g.nbricks * S;
         const size_t nvb = (size_t)g.nbricks * nblk;               // (brick, row block) pairs
@@ -439,7 +443,7 @@ bool screen_plan_feasible(const qm_engine *e, int S, const ScreenPlan &p) {
 // the brick-shape decision at load time)
 ScreenPlan screen_plan(const qm_engine *e, int S, int n_samples) {
     ScreenPlan best;
-    if (!e->cfg_screen || e->cfg_force_direct || (e->user_waves && e->cfg_waves != 8)) return best;
+    if (!e->cfg.screen || e->cfg.force_direct || (e->cfg.user_waves && e->cfg.waves != 8)) return best;
     double best_cost = 1e300;
     // relative cost per sample, measured on C3 / C4-sized tables (tools/ab.py): with the integer
     // sweep two pairs per lane in two 8-wave workgroups per CU run as fast as four pairs in one
@@ -450,8 +454,8 @@ ScreenPlan screen_plan(const qm_engine *e, int S, int n_samples) {
         ScreenPlan p;
         p.jp = o.jp;
         p.big = o.big;
-        if (e->cfg_screen_pairs && o.jp != e->cfg_screen_pairs) continue;
-        if (e->cfg_screen_big >= 0 && (int)o.big != e->cfg_screen_big) continue;
+        if (e->cfg.screen_pairs && o.jp != e->cfg.screen_pairs) continue;
+        if (e->cfg.screen_big >= 0 && (int)o.big != e->cfg.screen_big) continue;
         if (!screen_plan_feasible(e, S, p)) continue;
         double cost = o.cost;
         if (n_samples > 0) cost *= (double)((n_samples + p.kt() - 1) / p.kt()) * p.kt();
@@ -474,7 +478,7 @@ int ensure_screen_tables(qm_engine *e, const ScreenPlan &plan) {
     if (L.kt == KT && L.wb == wb) return 0;
     static const int kShapes[][3] = {{16, 8, 8}, {8, 8, 8}, {4, 8, 8}, {4, 4, 8}, {4, 4, 4},
                                      {2, 4, 4},  {2, 2, 4}, {2, 2, 2}, {1, 1, 2}, {1, 1, 1}};
-    if (search_bricks(e, L, kShapes, e->cfg_screen_brick16 ? 0 : 1, (int)(sizeof(kShapes) / sizeof(kShapes[0])),
+    if (search_bricks(e, L, kShapes, e->cfg.screen_brick16 ? 0 : 1, (int)(sizeof(kShapes) / sizeof(kShapes[0])),
                       qm::screen_fits, KT, wb, qm::screen_rel_kernel,
                       [](const qm::GridDesc &, int) { return true; }))   // (the offsets: always)
         return 1;
@@ -554,7 +558,7 @@ int qm_engine_load_lut(qm_engine *e, const int32_t *lut, int lut_on_device, int3
     // ones have smaller delay spans.  Bricks that still do not fit go to the direct kernel.
     static const int kShapes[][3] = {{8, 8, 8}, {4, 8, 8}, {4, 4, 8}, {4, 4, 4},
                                      {2, 4, 4}, {2, 2, 4}, {2, 2, 2}, {1, 1, 2}, {1, 1, 1}};
-    const int n_shapes = e->cfg_bx > 0 ? 1 : (int)(sizeof(kShapes) / sizeof(kShapes[0]));
+    const int n_shapes = e->cfg.brick_x > 0 ? 1 : (int)(sizeof(kShapes) / sizeof(kShapes[0]));
     e->n_rows_hint = n_rows;
     e->auto_j = 0;
     qm::GridDesc g{};
@@ -572,7 +576,7 @@ int qm_engine_load_lut(qm_engine *e, const int32_t *lut, int lut_on_device, int3
     int on_device = -1;
     auto measure = [&](int s) -> int {
         qm::GridDesc &gs = shapes[s];
-        gs = e->cfg_bx > 0 ? rebrick(table, e->cfg_bx, e->cfg_by, e->cfg_bz)
+        gs = e->cfg.brick_x > 0 ? rebrick(table, e->cfg.brick_x, e->cfg.brick_y, e->cfg.brick_z)
                            : rebrick(table, kShapes[s][0], kShapes[s][1], kShapes[s][2]);
         const size_t nbricks = gs.nbricks;
         const size_t br = nbricks * n_rows;
@@ -591,7 +595,12 @@ int qm_engine_load_lut(qm_engine *e, const int32_t *lut, int lut_on_device, int3
         on_device = s;
         return 0;
     };
-    // largest candidate shape whose windows fit for tile length 64 * J under the current budget
+    // The workgroup shape the table is laid out for: the user's where they set it, else the default until one of
+    // the two branches below decides otherwise.  The trial values stay here; the choice goes to tab_waves /
+    // tab_lds_bytes.
+    int waves = e->cfg.user_waves ? e->cfg.waves : 8;
+    int lds = e->cfg.user_lds ? e->cfg.lds_bytes : 80 * 1024;
+    // largest candidate shape whose windows fit for tile length 64 * J under the budget `lds`
     // (result: g and R.h_total; `chosen` = its index)
     int chosen = 0;
     auto search = [&](int J) -> int {
@@ -601,13 +610,13 @@ int qm_engine_load_lut(qm_engine *e, const int32_t *lut, int lut_on_device, int3
             chosen = s;
             int64_t wide = 0;
             for (int32_t t : totals[s])
-                if (!qm::brick_fits(t, n_rows, KT, lds_cap_doubles(e))) ++wide;
+                if (!qm::brick_fits(t, n_rows, KT, lds_cap_doubles(lds))) ++wide;
             if (wide * 200 <= (int64_t)totals[s].size()) break;   // <= 0.5 % of the bricks on the slow path
         }
         g = shapes[chosen];
         return 0;
     };
-    if (e->cfg_j == 0 && e->cfg_bx == 0 && !e->user_waves && !e->user_lds) {
+    if (e->cfg.samples_per_lane == 0 && e->cfg.brick_x == 0 && !e->cfg.user_waves && !e->cfg.user_lds) {
         // Automatic layout.  All S windows of a brick sit in LDS together, so workgroup shape
         // (two 8-wave workgroups with 80 KB each, or one 16-wave workgroup with all 160 KB --
         // measured 4 % slower at equal bricks: barriers), samples per lane and brick size trade
@@ -620,37 +629,37 @@ int qm_engine_load_lut(qm_engine *e, const int32_t *lut, int lut_on_device, int3
         double best_cost = 1e300;
         int best_j = 0, best_waves = 8, best_lds = 80 * 1024;
         for (int single = 0; single < 2; ++single) {
-            e->cfg_waves = single ? 16 : 8;
-            e->cfg_lds_bytes = single ? 160 * 1024 : 80 * 1024;
-            const int j_budget = eff_j(e);
+            waves = single ? 16 : 8;
+            lds = single ? 160 * 1024 : 80 * 1024;
+            const int j_budget = eff_j(e, lds);
             for (int j : {4, 2, 1}) {
                 if (j > j_budget || (j == 1 && j_budget > 1 && n_rows <= 64)) continue;
-                if (j == 4 && n_rows > 40 && !e->cfg_exact) continue;   // exact kernels only
+                if (j == 4 && n_rows > 40 && !e->cfg.exact) continue;   // exact kernels only
                 if (search(j)) return 1;
                 // (four samples per lane beyond 40 rows keep a ring of four offset chunks in
                 // registers instead of the whole node's: 7 % ahead of two samples per lane at
                 // equal bricks on the C3 grid x 60 rows)
                 double cost = (j == 4 ? (n_rows > 40 ? 1.04 : 1.0) : j == 2 ? 1.12 : 1.4) *
                               (1.0 + 30.0 / g.brick_nodes) * (single ? 1.04 : 1.0);
-                if (e->cfg_exact && qm::exact_built(n_rows, j)) cost *= 0.97;
+                if (e->cfg.exact && qm::exact_built(n_rows, j)) cost *= 0.97;
                 if (cost < best_cost) {
                     best_cost = cost;
                     best_j = j;
-                    best_waves = e->cfg_waves;
-                    best_lds = e->cfg_lds_bytes;
+                    best_waves = waves;
+                    best_lds = lds;
                 }
             }
         }
-        e->cfg_waves = best_waves;
-        e->cfg_lds_bytes = best_lds;
+        waves = best_waves;
+        lds = best_lds;
         e->auto_j = best_j;
-    } else if (!e->user_waves && !e->user_lds) {
+    } else if (!e->cfg.user_waves && !e->cfg.user_lds) {
         // brick shape or samples per lane given: the workgroup shape by the row count alone
         const bool big = n_rows > 40;
-        e->cfg_waves = big ? 16 : 8;
-        e->cfg_lds_bytes = big ? 160 * 1024 : 80 * 1024;
+        waves = big ? 16 : 8;
+        lds = big ? 160 * 1024 : 80 * 1024;
     }
-    if (search(eff_j(e))) return 1;
+    if (search(eff_j(e, lds))) return 1;
     if (on_device != chosen && measure(chosen)) return 1;   // the chosen shape's records on the device
     g = shapes[chosen];
     R.h_total = totals[chosen];
@@ -662,8 +671,8 @@ int qm_engine_load_lut(qm_engine *e, const int32_t *lut, int lut_on_device, int3
     R.g = g;
     e->n_nodes = n_nodes;
     e->node_offset = node_offset;
-    e->tab_waves = e->cfg_waves;                        // (what the layout search left in the tunables)
-    e->tab_lds_bytes = e->cfg_lds_bytes;
+    e->tab_waves = waves;
+    e->tab_lds_bytes = lds;
     e->invalidate_derived();
     e->have_lut = true;
     static std::atomic<uint64_t> next_serial{1};
@@ -712,8 +721,6 @@ int qm_engine_table_select(qm_engine *e, uint64_t key, int32_t capacity, int32_t
         }
         e->cur_key = key;
         e->cur_keyed = true;
-        if (!e->user_waves && e->tab_waves) e->cfg_waves = e->tab_waves;
-        if (!e->user_lds && e->tab_lds_bytes) e->cfg_lds_bytes = e->tab_lds_bytes;
         *resident = 1;
         ++e->table_hits;
         return 0;

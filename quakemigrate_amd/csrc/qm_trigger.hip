@@ -6,7 +6,7 @@
 
 // "trigger_timing": an event before (side 0) and after (side 1) a stage of the sequence
 static int trig_mark(qm_engine *e, int stage, int side, bool (&ran)[qm::kTrigStages]) {
-    if (!e->cfg_trigger_timing) return 0;
+    if (!e->cfg.trigger_timing) return 0;
     while (e->trg_ev.size() < 2 * (size_t)qm::kTrigStages) {
         hipEvent_t ev;
         QM_HIP(hipEventCreate(&ev));

@@ -887,3 +887,73 @@ def test_exp_correctly_rounded_is_correctly_rounded(built):
     got = np.array([f(float(x)) for x in xs])
     assert np.array_equal(got, want), np.flatnonzero(got != want)[:5]
     assert np.isnan(f(float("nan"))) and f(800.0) == np.inf and f(-800.0) == 0.0
+
+
+def _header_tunables():
+    """The keys the tunables comment of include/qmhip.h gives a row: the first column of the table between its heading
+    and the read-outs paragraph ("brick_x, _y, _z": the later names take the first one's stem)."""
+    text = (ROOT / "include" / "qmhip.h").read_text()
+    table = text[text.index(" * key (config) "):text.index(" * read-outs (qm_engine_get)")]
+    keys = []
+    for line in table.splitlines()[2:]:
+        first = line[3:25]
+        if not line.startswith(" * ") or line.startswith(" * --") or not first.strip() or first[0] == " ":
+            continue
+        for name in (n.strip() for n in first.split(",")):
+            if not name:
+                continue
+            keys.append(keys[-1][:keys[-1].rindex("_")] + name if name.startswith("_") else name)
+    return keys
+
+
+def test_tunables_table_matches_the_case_list_and_the_header(tmp_path):
+    """tools/config_check.cpp over csrc/qm_config.hip alone, built as host C++ under AddressSanitizer and UBSan:
+    every row of kTunables through the probes of tests/tunables_cases.py -- return code, whole refusal text, effects
+    and read-back -- the defaults of a fresh record, the brick fill-in; the table's keys are the list's, and the
+    header's tunables table names exactly them."""
+    import shutil
+    import subprocess
+
+    import tunables_cases as tc
+
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = tmp_path / "config_check"
+    subprocess.check_call([cxx, "-x", "c++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", str(ROOT / "tools" / "config_check.cpp"),
+                           str(ROOT / "quakemigrate_amd" / "csrc" / "qm_config.hip"), "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    lines = out.stdout.splitlines()
+    assert lines[-1] == "config_check: ok"
+
+    defaults = dict(line.split()[1:] for line in lines if line.startswith("default "))
+    assert {k: int(v) for k, v in defaults.items()} == tc.DEFAULTS
+    assert list(defaults) == list(tc.CASES), "the table's keys (and their order) are the case list's"
+
+    want = []
+    for key, probes in tc.CASES.items():
+        for value, outcome in probes:
+            if isinstance(outcome, str):
+                want.append(f"probe {key} {value} rc=1 effects=- get=- msg={outcome}")
+            else:
+                want.append(f"probe {key} {value} rc=0 effects={tc.EFFECTS.get(key, '-')} get={outcome} msg=")
+    assert [line for line in lines if line.startswith("probe ")] == want
+    assert "unknown unknown config key 'no_such_key'" in lines
+
+    # the brick fill-in: after every set the program prints all three dimensions
+    steps = [line.split()[1:] for line in lines if line.startswith("step ")]
+    state, at = {}, -1
+    for what, key, value in tc.BRICK_FILL_STEPS:
+        if what == "set":
+            at = next(i for i in range(at + 1, len(steps)) if steps[i][0] == "set")
+            assert steps[at] == ["set", key, str(value), "rc=0"]
+            state = {k: int(v) for _, k, v in steps[at + 1:at + 4]}
+        else:
+            assert state[key] == value, (key, value, state)
+    assert sum(s[0] == "set" for s in steps) == sum(s[0] == "set" for s in tc.BRICK_FILL_STEPS)
+
+    header = _header_tunables()
+    assert sorted(header) == sorted(tc.CASES), sorted(set(header) ^ set(tc.CASES))
+
