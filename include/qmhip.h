@@ -219,6 +219,10 @@ int qm_engine_synchronize(qm_engine *e);
  * shift_lazy, shift_tail_spl and shift_wide_tiles are 0 (shift_waves: the resident table's 256-sample layout's),
  * after a launch of the direct kernel alone (force_direct, every brick too wide) last_kernel and last_kernel_j are 0.
  * table_hits, table_misses, table_evictions, tables_parked, table_bytes, tables_parked_bytes, table_digests;
+ * pool_live_bytes (the bytes the process's device-memory pool has handed out on this engine's device and not yet got
+ * back -- parked or freed; blocks whose release waits for the end of a teardown still count.  Per device and per
+ * process, every engine, stream and group on that device included: equal before and after a stretch of work means the
+ * stretch gave back all it took; not comparable across the engines of a multi-device group);
  * pick_lds_samples (the longest onset row qm_engine_pick_phases takes: row and selection keys live in LDS);
  * amp_lds_samples (the longest window qm_engine_measure_amplitudes keeps in LDS; longer ones work from scratch);
  * the trigger stage's compile-time tunables (csrc/qm_trigger.hpp): trigger_max_radius (the largest smoothing radius

@@ -465,9 +465,9 @@ int timing_events(qm_engine *e, hipEvent_t *begin, hipEvent_t *end) {
     *end = e->ev1;
     if (!e->cfg.log_timing) return 0;
     while (e->ev_used + 2 > e->ev_log.size()) {
-        hipEvent_t ev;
-        QM_HIP(hipEventCreate(&ev));
-        e->ev_log.push_back(ev);
+        Event ev;
+        QM_HIP(ev.create());
+        e->ev_log.push_back(std::move(ev));
     }
     *begin = e->ev_log[e->ev_used];
     *end = e->ev_log[e->ev_used + 1];
@@ -746,16 +746,17 @@ int qm_engine_create(int device_id, qm_engine **out) {
     if (device_id < 0 || device_id >= n)
         return fail("device %d not available (%d HIP devices visible)", device_id, n);
     DeviceGuard guard(device_id);
-    qm_engine *e = new qm_engine();
+    // (destroyed as any engine is if a step below fails: what it holds by then goes back)
+    std::unique_ptr<qm_engine, decltype(&qm_engine_destroy)> e(new qm_engine(), qm_engine_destroy);
     e->device = device_id;
     hipDeviceProp_t prop;
     QM_HIP(hipGetDeviceProperties(&prop, device_id));
     e->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     QM_HIP(acquire_stream(device_id, &e->own_stream));
     e->stream = e->own_stream;
-    QM_HIP(hipEventCreate(&e->ev0));
-    QM_HIP(hipEventCreate(&e->ev1));
-    *out = e;
+    QM_HIP(e->ev0.create());
+    QM_HIP(e->ev1.create());
+    *out = e.release();
     return 0;
 }
 
@@ -763,38 +764,12 @@ void qm_engine_destroy(qm_engine *e) {
     if (!e) return;
     DeviceGuard guard(e->device);
     (void)hipStreamSynchronize(e->stream);
-    streams_orphan(e);
-    PoolReleaseScope one_wait;                          // every buffer of the engine behind ONE device-wide wait
-    e->release_all();
-    for (TableSlot &slot : e->slots) slot.state.release_all();
-    e->d_grids.release(); e->d_rows.release(); e->d_served.release();
-    e->rs_stage.release(); e->pre_stage.release(); e->on_stage.release();
-    e->d_sig.release(); e->d_raw.release(); e->d_pre_out.release(); e->d_rs_raw.release();
-    e->d_pick_val.release(); e->d_pick_meta.release();
-    e->d_amp_work.release(); e->d_amp_scratch.release(); e->d_amp_coef.release(); e->d_amp_val.release();
-    e->d_amp_meta.release(); e->d_amp_idx.release();
-    e->d_trg_x.release(); e->d_trg_par.release(); e->d_trg_val.release(); e->d_trg_cnt.release();
-    e->d_trg_run.release(); e->d_trg_tot.release(); e->d_trg_cand.release();
-    e->d_scalar.release(); e->d_digest.release();
-    e->d_onsets.release(); e->d_pmax.release(); e->d_psum.release(); e->d_out_a.release();
-    e->d_chunk.release(); e->d_marg.release(); e->d_marg_out.release(); e->d_pidx.release();
-    e->d_fit_a.release(); e->d_fit_b.release(); e->d_fit_c.release(); e->d_fit_part.release();
-    e->d_fit_val.release(); e->d_fit_win.release(); e->d_fit_pidx.release();
-    e->d_counts.release(); e->d_cells.release(); e->d_work.release(); e->d_flags.release();
-    e->d_onq.release(); e->d_sparams.release();
-    e->d_cell.release(); e->d_gmax.release(); e->d_pm.release(); e->d_rowmax.release(); e->d_ssum.release();
-    e->d_cand_z.release(); e->d_cand_idx.release();
-    e->d_bmax.release(); e->d_tie_zext.release(); e->d_tie_zgrid.release(); e->d_tie_z.release(); e->d_tie_pairs.release(); e->d_tie_imin.release(); e->d_tie_count.release();
-    e->d_tie_emax.release(); e->d_tie_cands.release(); e->d_tie_keys.release();
-    if (e->h_flags) (void)hipHostFree(e->h_flags);
-    for (hipEvent_t ev : e->ev_log) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->trg_ev) (void)hipEventDestroy(ev);
-    if (e->ev0) (void)hipEventDestroy(e->ev0);
-    if (e->ev1) (void)hipEventDestroy(e->ev1);
+    streams_orphan(e);                                  // (before the engine's own buffers go)
     if (e->own_stream) {
         (void)hipStreamSynchronize(e->own_stream);
         park_stream(e->device, e->own_stream);
     }
+    PoolReleaseScope one_wait;                          // every buffer of the engine behind ONE device-wide wait
     delete e;
 }
 
@@ -904,6 +879,7 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
         *v = 0;
         for (const TableSlot &sl : e->slots) *v += sl.used ? (int64_t)sl.state.device_bytes() : 0;
     }
+    else if (k == "pool_live_bytes") *v = (int64_t)pool_live_bytes(e->device);
     else if (k == "shift_row_blocks") *v = e->sh.ok ? e->sh.nblk : 0;
     else if (k == "shift_brick_nodes") *v = e->sh.ok ? e->sh.g.brick_nodes : 0;
     else if (k == "shift_wide_bricks") *v = e->sh.ok ? e->sh.n_list : 0;

@@ -25,6 +25,9 @@
 //                    peak-to-trough measurements out
 //   qm_compat.hip    the five reference-signature symbols (qmlib.h:28-44)
 //   qm_group.hip     engine groups: one process driving the boxes of a column partition on several devices
+// Who frees what: nobody by name.  Device buffers, pinned host buffers and events are the owning handles below
+// (DevBuf, PinnedBuf, Event); the structs here hold them as members and have no release lists.  What a teardown
+// still does itself -- one wait, the right device, the order -- stands with the handles.
 // Everything declared here lives in the library only (hidden visibility).
 #pragma once
 #include "../../include/qmhip.h"
@@ -38,6 +41,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -89,6 +93,7 @@ void host_copy(void *dst, const void *src, size_t n);
 hipError_t pool_alloc(void **out, size_t bytes);
 void pool_free(void *p);
 void pool_release_all_idle();
+size_t pool_live_bytes(int device);     // handed out on `device` and not yet parked or freed (whole process)
 // buffers released inside a scope are parked behind ONE device-wide wait when the outermost ends
 struct PoolReleaseScope {
     PoolReleaseScope();
@@ -96,25 +101,82 @@ struct PoolReleaseScope {
     PoolReleaseScope(const PoolReleaseScope &) = delete;
     PoolReleaseScope &operator=(const PoolReleaseScope &) = delete;
 };
+// pinned host memory and HIP events as the handles below take and return them: hipHostMalloc / hipHostFree,
+// hipEventCreateWithFlags / hipEventDestroy
+hipError_t pinned_alloc(void **out, size_t bytes, unsigned flags);
+void pinned_free(void *p);
+hipError_t event_create(hipEvent_t *out, unsigned flags);
+void event_destroy(hipEvent_t ev);
 
-template <typename T>
-struct DevBuf {
+// ---- owning handles ---------------------------------------------------------------------------------------------
+// Device buffers (DevBuf), pinned host buffers (PinnedBuf) and events (Event) belong to the handle that holds them:
+// move-only, a move leaves the source empty, the destructor gives back what is held.  A struct made of them (a layout,
+// a TableState, a stage record, a stream's slot, the engine) needs no list of what to free: dropping it -- delete,
+// `x = X{}` -- frees all of it, once.  What a teardown still sees to itself:
+//   one wait    pool_free outside a PoolReleaseScope waits for the whole device, once per block.  Whoever drops an
+//               owner opens a scope AROUND the delete or the assignment (member destructors run after a destructor's
+//               body: a scope inside the owner's own destructor ends too early).  Engine destroy, a table's eviction or
+//               un-keyed replacement, a stream's release, a stage's undo, a group's parts and its lead: one wait each.
+//   the device  the scope's end and pool_free wait for the CURRENT device: every owner is torn down under a DeviceGuard
+//               of its device (a group: each part under its own, the lead's buffers under the lead's).
+//   the order   an engine's streams are orphaned -- they release what they hold and forget the engine -- before the
+//               engine's own buffers go; an orphaned qm_stream destroyed later holds nothing and frees nothing.
+// release() is for giving something up EARLY, on purpose, while its owner lives on.
+struct PoolMem {
+    static hipError_t get(void **out, size_t bytes, unsigned) { return pool_alloc(out, bytes); }
+    static void put(void *p) { pool_free(p); }
+};
+struct PinnedMem {                                      // (flags: hipHostMallocDefault, hipHostMallocPortable)
+    static hipError_t get(void **out, size_t bytes, unsigned flags) { return pinned_alloc(out, bytes, flags); }
+    static void put(void *p) { pinned_free(p); }
+};
+template <typename T, typename Mem>
+struct OwnedBuf {
     T *p = nullptr;
     size_t n = 0;
-    int ensure(size_t count) {
-        if (count <= n) return 0;
-        if (p) pool_free(p);
-        p = nullptr;
-        n = 0;
-        QM_HIP(pool_alloc(reinterpret_cast<void **>(&p), count * sizeof(T)));
-        n = count;
+    OwnedBuf() = default;
+    OwnedBuf(OwnedBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }      // (declared moves: no copies)
+    OwnedBuf &operator=(OwnedBuf &&o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p; n = o.n;
+            o.p = nullptr; o.n = 0;
+        }
+        return *this;
+    }
+    ~OwnedBuf() { release(); }
+    hipError_t alloc(size_t count, unsigned flags = 0) {    // room for `count` elements: grows, never shrinks
+        if (count <= n) return hipSuccess;
+        release();
+        const hipError_t r = Mem::get(reinterpret_cast<void **>(&p), count * sizeof(T), flags);
+        if (r == hipSuccess) n = count;
+        return r;
+    }
+    int ensure(size_t count, unsigned flags = 0) {          // ... in the error convention
+        QM_HIP(alloc(count, flags));
         return 0;
     }
     void release() {
-        if (p) pool_free(p);
+        if (p) Mem::put(p);
         p = nullptr;
         n = 0;
     }
+};
+template <typename T> using DevBuf = OwnedBuf<T, PoolMem>;
+template <typename T> using PinnedBuf = OwnedBuf<T, PinnedMem>;
+
+// a HIP event; converts to hipEvent_t where one is recorded, waited for or timed
+struct Event {
+    struct Destroy { void operator()(hipEvent_t ev) const { event_destroy(ev); } };
+    std::unique_ptr<ihipEvent_t, Destroy> ev;
+    hipError_t create(unsigned flags = hipEventDefault) {   // (hipEventDisableTiming: an event that only orders)
+        hipEvent_t made = nullptr;
+        const hipError_t r = event_create(&made, flags);
+        ev.reset(made);
+        return r;
+    }
+    void release() { ev.reset(); }
+    operator hipEvent_t() const { return ev.get(); }
 };
 
 // The bricks of one kernel family over a table: brick grid, per-(brick, row) window records (`raw`: before the
@@ -128,10 +190,6 @@ struct BrickLayout {
     DevBuf<int32_t> raw, meta, total, list;
     DevBuf<uint16_t> rel;
     int n_list = 0;
-    void release() {
-        PoolReleaseScope one_wait;
-        raw.release(); meta.release(); total.release(); list.release(); rel.release();
-    }
     size_t device_bytes() const { return (raw.n + meta.n + total.n + list.n) * 4 + rel.n * 2; }
 };
 struct Round2Layout : BrickLayout {     // the round-2 kernels' (chunked, exact-row-count), on the table's own grid
@@ -176,9 +234,11 @@ struct ShiftLayout : BrickLayout {          // (list: the bricks that do not fit
     // (`sh` is never wide, so the test means the same on it as where only `shw` can be at hand)
     bool plain() const { return nblk == 1 && nw != qm::kShiftWaves3 && !(wide && direct); }
     void invalidate() { built = false; }
+    // early, on purpose (ensure_shift_tables: the table does not qualify, its step runs on the other kernels): the
+    // buffers go back now, grid and read-outs stay
     void release() {
         PoolReleaseScope one_wait;
-        BrickLayout::release();
+        raw.release(); meta.release(); total.release(); list.release(); rel.release();
         fit.release(); stream.release(); wmeta.release(); wtotal.release(); wstream.release();
     }
     size_t device_bytes() const {
@@ -221,11 +281,6 @@ struct TableState : Round2Layout {
         r2().invalidate(); screen.invalidate(); pair.invalidate(); sh.invalidate(); shw.invalidate();
         sh.ok = shw.ok = false;
     }
-    void release_all() {
-        PoolReleaseScope one_wait;
-        d_lut.release();
-        r2().release(); pair.release(); screen.release(); sh.release(); shw.release();
-    }
     size_t device_bytes() const {
         return d_lut.n * 4 + r2().device_bytes() + pair.device_bytes() + screen.device_bytes() +
                sh.device_bytes() + shw.device_bytes();
@@ -257,7 +312,6 @@ struct PreprocStage {
               const int32_t *trace_filter, const double *sos, int32_t n_filters, int32_t n_sections, int detrend,
               const double *taper_left, int32_t n_left, const double *taper_right, int32_t n_right, int zero_phase);
     int launch(qm_engine *e, const double *in, double *out, int n_steps) const;
-    void release() { coef.release(); meta.release(); }
 };
 struct OnsetStage {
     DevBuf<int32_t> meta;               // trace_row [repeat][n_traces] (step k's rows k * n_rows on), nsta, nlta [repeat][n_rows]
@@ -269,7 +323,6 @@ struct OnsetStage {
               double min_onset_value);
     // raw_onsets: [n_steps][n_rows][T] or nullptr
     int launch(qm_engine *e, const double *signals, double *raw_onsets, double *log_onsets, int n_steps) const;
-    void release() { meta.release(); sta.release(); lta.release(); }
 };
 struct ResampleStage {
     DevBuf<int64_t> meta;               // records [repeat][n_traces][kResampleFields] (step k's raw offsets k raw steps on), taper table
@@ -286,7 +339,6 @@ struct ResampleStage {
               int detrend, const int32_t *taper_table, int32_t n_tapers, const double *taper_weights,
               int64_t n_taper_weights);
     int launch(qm_engine *e, const void *raw, double *out, int n_steps) const;
-    void release() { meta.release(); coef.release(); scratch.release(); }
 };
 
 struct qm_stream;                    // a continuous-detect pipeline on an engine (qm_stream.hip)
@@ -325,10 +377,10 @@ struct qm_engine : TableState {
     int n_cu = 256;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Event ev0, ev1;
     bool timed = false;
     // optional per-call timing log (cfg.log_timing; bench): pairs of events around every stacking launch
-    std::vector<hipEvent_t> ev_log;     // 2 events per recorded call
+    std::vector<Event> ev_log;          // 2 events per recorded call
     size_t ev_used = 0;
 
     // parked tables (qm_engine_table_select) and the key of the one being worked on
@@ -348,7 +400,7 @@ struct qm_engine : TableState {
     DevBuf<int64_t> d_cand_idx;
     int64_t screened_steps = 0, fallback_steps = 0, last_candidates = 0;
     int last_plan_jp = 0, last_plan_big = 0;
-    int32_t *h_flags = nullptr;             // pinned ring of per-step (flags, candidates) pairs
+    PinnedBuf<int32_t> h_flags;             // pinned ring of per-step (flags, candidates) pairs
     int flags_pending = 0, flags_head = 0;  // not yet folded into the counters
     int last_batched = 1;                   // timesteps the last detect_batch put into one launch
     StackPlan last;                                     // the last stacking launch (run_stack)
@@ -386,7 +438,7 @@ struct qm_engine : TableState {
     DevBuf<double> d_trg_x, d_trg_par, d_trg_val;
     DevBuf<int32_t> d_trg_cnt, d_trg_run;
     DevBuf<int64_t> d_trg_tot, d_trg_cand;
-    std::vector<hipEvent_t> trg_ev;         // cfg.trigger_timing: a pair of HIP events per stage of the trigger sequence
+    std::vector<Event> trg_ev;              // cfg.trigger_timing: a pair of HIP events per stage of the trigger sequence
     int64_t trg_ns[qm::kTrigStages] = {};   // ... the last call's stage times ("trigger_ns_<stage>"), 0: did not run
 
     // scratch

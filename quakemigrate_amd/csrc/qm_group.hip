@@ -66,7 +66,7 @@ struct GroupPart {
     int n_boxes = 0;
     int32_t box[kMaxBoxes][kBoxInts] = {};
     int64_t node0 = 0, node1 = 0;            // flat node range of the boxes
-    hipEvent_t ev_done = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
+    Event ev_done, ev_t0, ev_t1;
     bool timed = false;
     DevBuf<double> d_on, d_pack, d_gcopy, d_tie, d_map, d_vol, d_fpack;
     double *pack = nullptr, *tie = nullptr, *fpack = nullptr;   // where this part's partials go on its device
@@ -82,26 +82,15 @@ struct qm_group {
     std::vector<std::pair<uint64_t, std::array<int64_t, 4>>> shapes;   // key -> (nx, ny, nz, rows) of keyed tables
     uint64_t miss_key = 0;                   // a table_select miss: the next load is known under this key
     bool miss = false;
-    hipEvent_t ev_gathered = nullptr;
+    Event ev_gathered;
     DevBuf<double> d_gather, d_tgather, d_fgather, d_out;
     int ready_ns = -1;                       // sample count the exchange buffers are laid out for
-    double *h_on = nullptr, *h_out = nullptr;
-    size_t h_on_n = 0, h_out_n = 0;
+    PinnedBuf<double> h_on, h_out;
 };
 
 #pragma GCC visibility pop
 
 namespace {
-
-int pinned(double **p, size_t *have, size_t need) {
-    if (need <= *have) return 0;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    *have = 0;
-    QM_HIP(hipHostMalloc(reinterpret_cast<void **>(p), need * sizeof(double), hipHostMallocPortable));
-    *have = need;
-    return 0;
-}
 
 // n_sets packed sets of `rows` rows: neutral partials (maximum -inf, no index, sum 0) or, rows == 2, neutral
 // tie outcomes (key 0, no index)
@@ -181,13 +170,13 @@ int check_group(qm_group *g, const char *what) {
 // The log-onsets staged once into pinned memory, one H2D per part on its stream
 int stage_onsets_all(qm_group *g, const double *log_onsets, int T) {
     const size_t n = (size_t)g->n_rows * T;
-    if (pinned(&g->h_on, &g->h_on_n, n)) return 1;
-    host_copy(g->h_on, log_onsets, n * sizeof(double));
+    if (g->h_on.ensure(n, hipHostMallocPortable)) return 1;
+    host_copy(g->h_on.p, log_onsets, n * sizeof(double));
     for (GroupPart &q : g->parts) {
         if (!q.n_boxes) continue;
         DeviceGuard guard(q.device);
         if (q.d_on.ensure(n)) return 1;
-        QM_HIP(hipMemcpyAsync(q.d_on.p, g->h_on, n * sizeof(double), hipMemcpyHostToDevice, q.stream));
+        QM_HIP(hipMemcpyAsync(q.d_on.p, g->h_on.p, n * sizeof(double), hipMemcpyHostToDevice, q.stream));
         QM_HIP(hipEventRecord(q.ev_t0, q.stream));
     }
     return 0;
@@ -258,13 +247,13 @@ int exchange(qm_group *g, int T, int fsmp, int lsmp, int available, int ns) {
 int fetch_series(qm_group *g, int ns, double *max_coa, double *max_norm, int64_t *idx) {
     DeviceGuard lead(g->lead_dev);
     const size_t n = 3 * (size_t)ns;
-    if (pinned(&g->h_out, &g->h_out_n, n)) return 1;
-    QM_HIP(hipMemcpyAsync(g->h_out, g->d_out.p, n * sizeof(double), hipMemcpyDeviceToHost, g->lead->stream));
+    if (g->h_out.ensure(n, hipHostMallocPortable)) return 1;
+    QM_HIP(hipMemcpyAsync(g->h_out.p, g->d_out.p, n * sizeof(double), hipMemcpyDeviceToHost, g->lead->stream));
     QM_HIP(hipStreamSynchronize(g->lead->stream));
     if (max_coa) {
-        host_copy(max_coa, g->h_out, ns * sizeof(double));
-        host_copy(max_norm, g->h_out + ns, ns * sizeof(double));
-        host_copy(idx, g->h_out + 2 * (size_t)ns, ns * sizeof(double));
+        host_copy(max_coa, g->h_out.p, ns * sizeof(double));
+        host_copy(max_norm, g->h_out.p + ns, ns * sizeof(double));
+        host_copy(idx, g->h_out.p + 2 * (size_t)ns, ns * sizeof(double));
     }
     return 0;
 }
@@ -314,36 +303,28 @@ int qm_group_create(const int32_t *device_ids, int32_t n, qm_group **out) {
     for (int i = 0; i < n; ++i)
         if (device_ids[i] >= count)
             return fail("qm_group_create: device %d not available (%d HIP devices visible)", device_ids[i], count);
-    qm_group *g = new qm_group();
+    // (destroyed as any group is if a step below fails)
+    std::unique_ptr<qm_group, decltype(&qm_group_destroy)> g(new qm_group(), qm_group_destroy);
     g->lead_dev = device_ids[0];
     g->parts.resize(n);
-    auto undo = [&]() {
-        qm_group_destroy(g);
-        return 1;
-    };
-    if (qm_engine_create(g->lead_dev, &g->lead)) return undo();
+    for (int i = 0; i < n; ++i) g->parts[i].device = device_ids[i];
+    if (qm_engine_create(g->lead_dev, &g->lead)) return 1;
     {
         DeviceGuard lead(g->lead_dev);
-        if (hipEventCreateWithFlags(&g->ev_gathered, hipEventDisableTiming) != hipSuccess) {
-            fail("qm_group_create: hipEventCreate failed");
-            return undo();
-        }
+        if (g->ev_gathered.create(hipEventDisableTiming) != hipSuccess)
+            return fail("qm_group_create: hipEventCreate failed");
     }
     for (int i = 0; i < n; ++i) {
         GroupPart &q = g->parts[i];
-        q.device = device_ids[i];
         q.on_lead = q.device == g->lead_dev;
         DeviceGuard guard(q.device);
-        if (acquire_stream(q.device, &q.stream) != hipSuccess || hipEventCreate(&q.ev_t0) != hipSuccess ||
-            hipEventCreate(&q.ev_t1) != hipSuccess ||
-            hipEventCreateWithFlags(&q.ev_done, hipEventDisableTiming) != hipSuccess) {
-            fail("qm_group_create: stream / events on device %d", q.device);
-            return undo();
-        }
+        if (acquire_stream(q.device, &q.stream) != hipSuccess || q.ev_t0.create() != hipSuccess ||
+            q.ev_t1.create() != hipSuccess || q.ev_done.create(hipEventDisableTiming) != hipSuccess)
+            return fail("qm_group_create: stream / events on device %d", q.device);
         for (int k = 0; k < kMaxBoxes; ++k)
-            if (qm_engine_create(q.device, &q.eng[k]) || qm_engine_set_stream(q.eng[k], q.stream, 0)) return undo();
+            if (qm_engine_create(q.device, &q.eng[k]) || qm_engine_set_stream(q.eng[k], q.stream, 0)) return 1;
     }
-    *out = g;
+    *out = g.release();
     return 0;
 }
 
@@ -352,28 +333,19 @@ void qm_group_destroy(qm_group *g) {
     for (GroupPart &q : g->parts) {
         DeviceGuard guard(q.device);
         if (q.stream) (void)hipStreamSynchronize(q.stream);
-        for (qm_engine *&e : q.eng) {
-            qm_engine_destroy(e);
-            e = nullptr;
-        }
-        PoolReleaseScope one_wait;
-        q.d_on.release(); q.d_pack.release(); q.d_gcopy.release(); q.d_tie.release(); q.d_map.release();
-        q.d_vol.release(); q.d_fpack.release();
-        for (hipEvent_t ev : {q.ev_done, q.ev_t0, q.ev_t1})
-            if (ev) (void)hipEventDestroy(ev);
+        for (qm_engine *e : q.eng) qm_engine_destroy(e);
         if (q.stream) park_stream(q.device, q.stream);
-    }
-    {
-        DeviceGuard lead(g->lead_dev);
-        if (g->lead) (void)hipStreamSynchronize(g->lead->stream);
         PoolReleaseScope one_wait;
-        g->d_gather.release(); g->d_tgather.release(); g->d_fgather.release(); g->d_out.release();
-        if (g->ev_gathered) (void)hipEventDestroy(g->ev_gathered);
+        q = GroupPart{};                                // (the part's buffers and events, on its device)
     }
-    qm_engine_destroy(g->lead);
-    if (g->h_on) (void)hipHostFree(g->h_on);
-    if (g->h_out) (void)hipHostFree(g->h_out);
-    delete g;
+    qm_engine *lead = g->lead;
+    {
+        DeviceGuard guard(g->lead_dev);
+        if (lead) (void)hipStreamSynchronize(lead->stream);
+        PoolReleaseScope one_wait;
+        delete g;                                       // (the parts are empty by now: the lead's buffers, on its device)
+    }
+    qm_engine_destroy(lead);
 }
 
 int qm_group_config(qm_group *g, const char *key, int64_t value) {

@@ -47,6 +47,12 @@ void park_stream(int device, hipStream_t s) {
     g_idle_streams.emplace_back(device, s);
 }
 
+// what PinnedBuf and Event (qm_engine.hpp) hold: the runtime's own calls, behind names a host-only build can replace
+hipError_t pinned_alloc(void **out, size_t bytes, unsigned flags) { return hipHostMalloc(out, bytes, flags); }
+void pinned_free(void *p) { (void)hipHostFree(p); }
+hipError_t event_create(hipEvent_t *out, unsigned flags) { return hipEventCreateWithFlags(out, flags); }
+void event_destroy(hipEvent_t ev) { (void)hipEventDestroy(ev); }
+
 // Results travel back to the host through a pinned bounce buffer and a CPU copy; inputs the same way
 // in the other direction (the caller's buffer is copied into pinned memory by the CPU before the call
 // returns, so it may be a temporary).  Both directions return when the data is in place.  One buffer
@@ -281,6 +287,16 @@ struct PoolBlock {
 };
 static std::mutex g_pool_mutex;
 static std::vector<PoolBlock> g_pool_idle, g_pool_live;
+static std::vector<size_t> g_pool_live_bytes;           // by device: the sum over g_pool_live ("pool_live_bytes")
+static void pool_went_out_locked(const PoolBlock &b) {
+    g_pool_live.push_back(b);
+    if (g_pool_live_bytes.size() <= (size_t)b.device) g_pool_live_bytes.resize((size_t)b.device + 1, 0);
+    g_pool_live_bytes[(size_t)b.device] += b.bytes;
+}
+size_t pool_live_bytes(int device) {
+    std::lock_guard<std::mutex> lock(g_pool_mutex);
+    return device >= 0 && (size_t)device < g_pool_live_bytes.size() ? g_pool_live_bytes[(size_t)device] : 0;
+}
 
 static size_t pool_keep_bytes() {
     static const size_t keep = [] {
@@ -338,7 +354,7 @@ hipError_t pool_alloc(void **out, size_t bytes) {
         if (best != g_pool_idle.size()) {
             *out = g_pool_idle[best].p;
             got = g_pool_idle[best].bytes;
-            g_pool_live.push_back(g_pool_idle[best]);
+            pool_went_out_locked(g_pool_idle[best]);
             g_pool_idle.erase(g_pool_idle.begin() + (long)best);
         }
     }
@@ -355,7 +371,7 @@ hipError_t pool_alloc(void **out, size_t bytes) {
         }
         got = want;
         std::lock_guard<std::mutex> lock(g_pool_mutex);
-        g_pool_live.push_back(PoolBlock{device, want, *out});
+        pool_went_out_locked(PoolBlock{device, want, *out});
     }
     if (pool_poison()) {
         r = hipMemset(*out, 0xFF, got);                 // (the null stream: ordered before everything after)
@@ -377,6 +393,7 @@ static void pool_park(void *p) {                               // (the device is
         if (g_pool_live[i].p != p) continue;
         const int device = g_pool_live[i].device;
         g_pool_idle.push_back(g_pool_live[i]);
+        g_pool_live_bytes[(size_t)device] -= g_pool_live[i].bytes;
         g_pool_live.erase(g_pool_live.begin() + (long)i);
         pool_trim_locked(device, pool_keep_bytes());
         return;

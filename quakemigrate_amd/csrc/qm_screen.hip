@@ -9,7 +9,7 @@ int drain_flags(qm_engine *e) {
     if (e->flags_pending == 0) return 0;
     QM_HIP(hipStreamSynchronize(e->stream));
     for (; e->flags_pending > 0; --e->flags_pending) {
-        const int32_t *f = e->h_flags + 2 * e->flags_head;
+        const int32_t *f = e->h_flags.p + 2 * e->flags_head;
         if (f[0] != 0) ++e->fallback_steps;
         else ++e->screened_steps;
         e->last_candidates = f[1];
@@ -61,9 +61,7 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
     e->last_plan_big = plan.big ? 1 : 0;
     const ScreenLayout &L = e->screen;                  // the sweep's bricks, those that do not fit: direct kernel
     const qm::GridDesc &g = L.g;
-    if (!e->h_flags)
-        QM_HIP(hipHostMalloc(reinterpret_cast<void **>(&e->h_flags),
-                             2 * kFlagRing * sizeof(int32_t), hipHostMallocDefault));
+    if (e->h_flags.ensure(2 * kFlagRing, hipHostMallocDefault)) return 1;
     const int KT = 128 * JP;
     const int ntiles = (ns + KT - 1) / KT;
     const int64_t ns_pad = (int64_t)ntiles * KT;
@@ -194,7 +192,7 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
     // the outcome travels to the host asynchronously (statistics only: the decision to redo the
     // step in float64 is taken on the device, see detect_core)
     if (e->flags_pending == kFlagRing && drain_flags(e)) return 1;
-    QM_HIP(hipMemcpyAsync(e->h_flags + 2 * ((e->flags_head + e->flags_pending) % kFlagRing),
+    QM_HIP(hipMemcpyAsync(e->h_flags.p + 2 * ((e->flags_head + e->flags_pending) % kFlagRing),
                           e->d_flags.p, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     ++e->flags_pending;
     *n_sets = sets;

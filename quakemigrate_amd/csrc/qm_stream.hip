@@ -54,13 +54,13 @@ struct qm_stream {
     enum Feed { kNothingYet = 0, kLogOnsets = 1, kSignals = 2, kRaw = 3, kFeeds = 4 };
     struct Slot {
         struct In {
-            double *h = nullptr;        // pinned [K][step_words[feed]] (the signals': given up at the first raw step)
-            double *d = nullptr;        // device, the same (the signals': filtered in place)
+            PinnedBuf<double> h;        // pinned [K][step_words[feed]] (the signals': given up at the first raw step)
+            DevBuf<double> d;           // device, the same (the signals': filtered in place)
         } in[kFeeds];                   // by Feed: log-onsets from create on, signals and raw samples from their stage on
-        double *h_out = nullptr;        // pinned [3][K * ns]: max_coa, max_norm_coa, indices (int64 bits) --
+        PinnedBuf<double> h_out;        // pinned [3][K * ns]: max_coa, max_norm_coa, indices (int64 bits) --
                                         // written by the kernels themselves
-        hipEvent_t copied = nullptr;    // the inputs are on the device
-        hipEvent_t done = nullptr;      // the launch has finished: the results are in h_out
+        Event copied;                   // the inputs are on the device
+        Event done;                     // the launch has finished: the results are in h_out
         int n = 0;                      // steps launched from this slot
         int taken = 0;                  // ... of which popped
         bool in_flight = false;
@@ -69,7 +69,7 @@ struct qm_stream {
     std::deque<int> order;              // slots in flight, oldest first
     int fill_slot = 0, fill_n = 0;      // slot being filled, steps pushed into it so far
     int64_t launched_steps = 0, popped_steps = 0, launches = 0;
-    unsigned long long *h_stamp = nullptr;   // ("stream_stamps") pinned [2][4096]
+    PinnedBuf<unsigned long long> h_stamp;   // ("stream_stamps") pinned [2][4096]
     bool pulled = false;                // the last launch's inputs were pulled by a kernel (no copy command)
     int feed = kNothingYet;
     size_t step_words[kFeeds] = {};     // a timestep of each kind in doubles, as a slot holds it (raw bytes: rounded up)
@@ -123,13 +123,14 @@ int alive(const qm_stream *s, const char *what) {
 
 // every slot's buffers for one kind of input, K timesteps each (s->step_words[feed] is set)
 int alloc_inputs(qm_stream *s, int feed, const char *what) {
-    const size_t bytes = (size_t)s->K * s->step_words[feed] * sizeof(double);
+    const size_t words = (size_t)s->K * s->step_words[feed];
     hipError_t r = hipSuccess;
     for (qm_stream::Slot &sl : s->slots) {
         qm_stream::Slot::In &in = sl.in[feed];
-        if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&in.h), bytes, hipHostMallocDefault);
-        if (r == hipSuccess) r = pool_alloc(reinterpret_cast<void **>(&in.d), bytes);
-        if (r == hipSuccess && feed == qm_stream::kRaw) std::memset(in.h, 0, bytes);    // (the bytes a step's int32s leave over)
+        if (r == hipSuccess) r = in.h.alloc(words, hipHostMallocDefault);
+        if (r == hipSuccess) r = in.d.alloc(words);
+        if (r == hipSuccess && feed == qm_stream::kRaw)         // (the bytes a step's int32s leave over)
+            std::memset(in.h.p, 0, words * sizeof(double));
     }
     if (r != hipSuccess)
         return fail("%s: %s (%d steps of %zu bytes per slot, %d slots)", what, hipGetErrorString(r), s->K,
@@ -137,31 +138,17 @@ int alloc_inputs(qm_stream *s, int feed, const char *what) {
     return 0;
 }
 
-void free_inputs(qm_stream::Slot &sl, int feed) {
-    qm_stream::Slot::In &in = sl.in[feed];
-    if (in.h) (void)hipHostFree(in.h);
-    if (in.d) pool_free(in.d);
-    in = {};
-}
-
-void free_slot(qm_stream::Slot &sl) {
-    for (int feed = 0; feed < qm_stream::kFeeds; ++feed) free_inputs(sl, feed);
-    if (sl.h_out) (void)hipHostFree(sl.h_out);
-    for (hipEvent_t ev : {sl.copied, sl.done})
-        if (ev) (void)hipEventDestroy(ev);
-    sl = qm_stream::Slot{};
-}
-
 // everything the stream holds on its engine's device goes back (the engine's device is current)
 void release_stream(qm_stream *s) {
     (void)hipStreamSynchronize(s->e->stream);
-    if (s->h_stamp) {
+    if (s->h_stamp.p) {
         // launch i: [begin_i, end_i]; gap_i = begin_i - end_(i-1)   (wall_clock64: 100 MHz)
         const int n = (int)std::min<int64_t>(s->launches, 4096);
+        const unsigned long long *stamp = s->h_stamp.p;
         std::vector<double> busy, gap;
         for (int i = 8; i < n; ++i) {
-            busy.push_back((double)(s->h_stamp[4096 + i] - s->h_stamp[i]) * 0.01);
-            gap.push_back((double)(s->h_stamp[i] - s->h_stamp[4096 + i - 1]) * 0.01);
+            busy.push_back((double)(stamp[4096 + i] - stamp[i]) * 0.01);
+            gap.push_back((double)(stamp[i] - stamp[4096 + i - 1]) * 0.01);
         }
         for (int i = 0; i < (int)gap.size(); ++i)
             if (gap[i] > 200.0) std::fprintf(stderr, "qm_stream stamps: gap of %.1f us before launch %d\n", gap[i], i + 8);
@@ -171,14 +158,15 @@ void release_stream(qm_stream *s) {
             std::fprintf(stderr, "qm_stream stamps: %d launches; launch busy us median %.1f p90 %.1f; gap between launches "
                          "us median %.1f p90 %.1f max %.1f\n", n, busy[busy.size() / 2], busy[busy.size() * 9 / 10],
                          gap[gap.size() / 2], gap[gap.size() * 9 / 10], gap.back());
-        (void)hipHostFree(s->h_stamp);
-        s->h_stamp = nullptr;
+        s->h_stamp.release();
     }
     if (s->copy_stream) (void)hipStreamSynchronize(s->copy_stream);
     {
         PoolReleaseScope one_wait;
-        for (qm_stream::Slot &sl : s->slots) free_slot(sl);
-        s->rs.release(); s->pre.release(); s->on.release();
+        for (qm_stream::Slot &sl : s->slots) sl = qm_stream::Slot{};
+        s->rs = ResampleStage{};
+        s->pre = PreprocStage{};
+        s->on = OnsetStage{};
     }
     if (s->copy_stream) park_stream(s->e->device, s->copy_stream);
     s->copy_stream = nullptr;
@@ -199,19 +187,18 @@ int launch_slot(qm_stream *s) {
                     (unsigned long long)s->table_serial, s->n_rows);
     const size_t kns = (size_t)s->K * s->ns;
     const size_t words = (size_t)n * s->step_words[s->feed];
-    const double *h_in = sl.in[s->feed].h;
-    double *d_in = sl.in[s->feed].d;
+    const double *h_in = sl.in[s->feed].h.p;
+    double *d_in = sl.in[s->feed].d.p;
     const bool pull = e->cfg.stream_pull > 0 || (e->cfg.stream_pull < 0 && words * sizeof(double) <= kPullBytes);
     // ("stream_stamps" = 1, measurement: the GPU's clock before and behind every launch -- two one-thread kernels;
     // the digest goes to stderr when the stream is destroyed.  What found round 6's one-off stall: tools/diag_stream.py)
     constexpr int kStamps = 4096;
     const bool stamps = e->cfg.stream_stamps != 0 && s->launches < kStamps;   // (the first 4096 launches of a stream)
-    if (stamps && !s->h_stamp) {
-        QM_HIP(hipHostMalloc(reinterpret_cast<void **>(&s->h_stamp), 2 * kStamps * sizeof(unsigned long long),
-                             hipHostMallocDefault));
-        std::memset(s->h_stamp, 0, 2 * kStamps * sizeof(unsigned long long));
+    if (stamps && !s->h_stamp.p) {
+        if (s->h_stamp.ensure(2 * kStamps, hipHostMallocDefault)) return 1;
+        std::memset(s->h_stamp.p, 0, 2 * kStamps * sizeof(unsigned long long));
     }
-    if (stamps) hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, e->stream, s->h_stamp + (s->launches % kStamps));
+    if (stamps) hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, e->stream, s->h_stamp.p + (s->launches % kStamps));
     if (pull) {
         const unsigned blocks = (unsigned)std::min<size_t>(4 * (size_t)e->n_cu, (words / 2 + 255) / 256 + 1);
         hipLaunchKernelGGL(pull_kernel, dim3(blocks), dim3(256), 0, e->stream,
@@ -226,7 +213,7 @@ int launch_slot(qm_stream *s) {
         QM_HIP(hipStreamWaitEvent(e->stream, sl.copied, 0));
     }
     s->pulled = pull;
-    double *d_sig = sl.in[qm_stream::kSignals].d, *d_on = sl.in[qm_stream::kLogOnsets].d;
+    double *d_sig = sl.in[qm_stream::kSignals].d.p, *d_on = sl.in[qm_stream::kLogOnsets].d.p;
     // raw samples -> the n steps' traces at the scan rate, straight into the slot's signals
     if (s->feed == qm_stream::kRaw && s->rs.launch(e, d_in, d_sig, n)) return 1;
     // waveforms -> log-onsets, all on the engine's stream: the n steps' traces filtered in place, then the onset
@@ -238,12 +225,12 @@ int launch_slot(qm_stream *s) {
     // launch makes them visible to the host) -- no D2H copy command, no third stream.  (With a copy on a
     // download stream of its own, 8 timesteps per launch ran at x1.03-1.09 of the resident step on the
     // example-sized grids; now x1.00, profiles/r05_ab_runs.txt.)
-    double *out = sl.h_out;
+    double *out = sl.h_out.p;
     if (qm_engine_detect_batch(e, d_on, 1, n, s->T, s->fsmp, s->lsmp, s->available, s->n_nodes_total,
                                out, out + kns, reinterpret_cast<int64_t *>(out + 2 * kns), 1))
         return 1;
     if (stamps)
-        hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, e->stream, s->h_stamp + kStamps + (s->launches % kStamps));
+        hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, e->stream, s->h_stamp.p + kStamps + (s->launches % kStamps));
     QM_HIP(hipEventRecord(sl.done, e->stream));
     sl.n = n;
     sl.taken = 0;
@@ -261,12 +248,13 @@ int launch_slot(qm_stream *s) {
 // current; the error text stays).  Returns 1.
 int stage_undo(qm_stream *s, int feed) {
     PoolReleaseScope one_wait;
-    for (qm_stream::Slot &sl : s->slots) free_inputs(sl, feed);
+    for (qm_stream::Slot &sl : s->slots) sl.in[feed] = {};
     if (feed == qm_stream::kRaw) {
-        s->rs.release();
+        s->rs = ResampleStage{};
         s->resampled = false;
     } else {
-        s->pre.release(); s->on.release();
+        s->pre = PreprocStage{};
+        s->on = OnsetStage{};
         s->staged = false;
     }
     return 1;
@@ -377,33 +365,30 @@ int qm_stream_create(qm_engine *e, int32_t t_samples, int32_t fsmp, int32_t lsmp
     if (check_step(e, t_samples, fsmp, lsmp, available, &ns)) return 1;
     if ((int64_t)steps_per_launch * ns >= INT32_MAX) return fail("qm_stream_create: too many samples per launch");
     DeviceGuard guard(e->device);
-    qm_stream *s = new qm_stream();
+    // (destroyed as any stream is if a step below fails; not yet on the engine's list, which destroy does not mind)
+    std::unique_ptr<qm_stream, decltype(&qm_stream_destroy)> s(new qm_stream(), qm_stream_destroy);
     s->e = e;
     s->n_rows = e->g.n_rows;
     s->table_serial = e->serial;
     s->T = t_samples; s->fsmp = fsmp; s->lsmp = lsmp; s->available = available; s->ns = ns;
     s->K = steps_per_launch; s->depth = depth;
     s->n_nodes_total = n_nodes_total > 0 ? n_nodes_total : e->n_nodes;
-    auto bail = [&](int rc) {
-        qm_stream_destroy(s);
-        return rc;
-    };
     // (the copy stream is taken at the first launch that copies: slots that are pulled never need one)
     s->slots.resize((size_t)depth);
     s->step_words[qm_stream::kLogOnsets] = (size_t)s->n_rows * s->T;
     s->step_bytes[qm_stream::kLogOnsets] = s->step_words[qm_stream::kLogOnsets] * sizeof(double);
     const size_t out_bytes = 3 * (size_t)s->K * ns * sizeof(double);
     for (qm_stream::Slot &sl : s->slots) {
-        hipError_t r = hipHostMalloc(reinterpret_cast<void **>(&sl.h_out), out_bytes, hipHostMallocDefault);
-        for (hipEvent_t *ev : {&sl.copied, &sl.done})
-            if (r == hipSuccess) r = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+        hipError_t r = sl.h_out.alloc(out_bytes / sizeof(double), hipHostMallocDefault);
+        for (Event *ev : {&sl.copied, &sl.done})
+            if (r == hipSuccess) r = ev->create(hipEventDisableTiming);
         if (r != hipSuccess)
-            return bail(fail("qm_stream_create: %s (%d steps of %zu bytes of results per slot, %d slots)",
-                             hipGetErrorString(r), s->K, out_bytes / s->K, depth));
+            return fail("qm_stream_create: %s (%d steps of %zu bytes of results per slot, %d slots)",
+                        hipGetErrorString(r), s->K, out_bytes / s->K, depth);
     }
-    if (alloc_inputs(s, qm_stream::kLogOnsets, "qm_stream_create")) return bail(1);
-    e->streams.push_back(s);
-    *out = s;
+    if (alloc_inputs(s.get(), qm_stream::kLogOnsets, "qm_stream_create")) return 1;
+    e->streams.push_back(s.get());
+    *out = s.release();
     return 0;
 }
 
@@ -436,17 +421,15 @@ int qm_stream_create_replicas(qm_engine *const *engines, int32_t n_engines, int3
         if (qm_engine_table_digest(engines[r], &d)) return 1;
         if (d != d0) return fail("qm_stream_create_replicas: replica %d holds another table than replica 0", r);
     }
-    qm_stream *s = new qm_stream();
+    std::unique_ptr<qm_stream, decltype(&qm_stream_destroy)> s(new qm_stream(), qm_stream_destroy);
     for (int r = 0; r < n_engines; ++r) {
         qm_stream *lane = nullptr;
         if (qm_stream_create(engines[r], t_samples, fsmp, lsmp, available, n_nodes_total, steps_per_launch, depth,
-                             &lane)) {
-            qm_stream_destroy(s);
+                             &lane))
             return 1;
-        }
         s->lanes.push_back(lane);
     }
-    *out = s;
+    *out = s.release();
     return 0;
 }
 
@@ -498,12 +481,10 @@ static int push_step(qm_stream *s, const void *step, int feed, const char *what)
     }
     s->feed = feed;
     // (the slot's previous H2D has finished: its launch's results were popped)
-    if (feed == qm_stream::kRaw && sl.in[qm_stream::kSignals].h)    // the first raw step: the ring's pinned slots hold
-        for (qm_stream::Slot &other : s->slots) {       // raw bytes from here on, the signals' pinned buffers are given up
-            (void)hipHostFree(other.in[qm_stream::kSignals].h);
-            other.in[qm_stream::kSignals].h = nullptr;
-        }
-    host_copy(sl.in[feed].h + (size_t)s->fill_n * s->step_words[feed], step, s->step_bytes[feed]);
+    if (feed == qm_stream::kRaw && sl.in[qm_stream::kSignals].h.p)  // the first raw step: the ring's pinned slots hold
+        for (qm_stream::Slot &other : s->slots)         // raw bytes from here on, the signals' pinned buffers are given up
+            other.in[qm_stream::kSignals].h.release();
+    host_copy(sl.in[feed].h.p + (size_t)s->fill_n * s->step_words[feed], step, s->step_bytes[feed]);
     if (++s->fill_n < s->K) return 0;
     return launch_slot(s);
 }
@@ -612,7 +593,7 @@ int qm_stream_pop(qm_stream *s, int32_t n_steps, double *max_coa, double *max_no
         qm_stream::Slot &sl = s->slots[s->order.front()];
         QM_HIP(hipEventSynchronize(sl.done));
         const int take = std::min(n_steps - k, sl.n - sl.taken);
-        const double *src = sl.h_out + (size_t)sl.taken * ns;
+        const double *src = sl.h_out.p + (size_t)sl.taken * ns;
         std::memcpy(max_coa + (size_t)k * ns, src, (size_t)take * ns * sizeof(double));
         std::memcpy(max_norm_coa + (size_t)k * ns, src + kns, (size_t)take * ns * sizeof(double));
         std::memcpy(max_coa_idx + (size_t)k * ns, src + 2 * kns, (size_t)take * ns * sizeof(int64_t));

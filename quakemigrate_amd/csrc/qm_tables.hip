@@ -702,6 +702,7 @@ int qm_engine_table_select(qm_engine *e, uint64_t key, int32_t capacity, int32_t
         return 0;
     }
     DeviceGuard guard(e->device);
+    PoolReleaseScope one_wait;                          // (a table dropped below: its buffers behind one wait)
     e->last.sets_own = false;                           // (another table from here on: qm_engine_tie_partial)
     TableState &cur = *e;
     const bool park = e->have_lut && e->cur_keyed && capacity > 0;
@@ -715,7 +716,6 @@ int qm_engine_table_select(qm_engine *e, uint64_t key, int32_t capacity, int32_t
             sl.key = e->cur_key;
             sl.stamp = ++e->table_clock;
         } else {                                        // (an un-keyed table, or nothing may be parked)
-            sl.state.release_all();
             sl.state = TableState{};
             sl.used = false;
         }
@@ -740,7 +740,6 @@ int qm_engine_table_select(qm_engine *e, uint64_t key, int32_t capacity, int32_t
             for (TableSlot &sl : e->slots)
                 if (sl.stamp < slot->stamp) slot = &sl;
             // (its device memory goes back to the pool: one wait for work that may still read it)
-            slot->state.release_all();
             slot->state = TableState{};
             ++e->table_evictions;
         }

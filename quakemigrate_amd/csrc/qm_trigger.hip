@@ -8,9 +8,9 @@
 static int trig_mark(qm_engine *e, int stage, int side, bool (&ran)[qm::kTrigStages]) {
     if (!e->cfg.trigger_timing) return 0;
     while (e->trg_ev.size() < 2 * (size_t)qm::kTrigStages) {
-        hipEvent_t ev;
-        QM_HIP(hipEventCreate(&ev));
-        e->trg_ev.push_back(ev);
+        Event ev;
+        QM_HIP(ev.create());
+        e->trg_ev.push_back(std::move(ev));
     }
     QM_HIP(hipEventRecord(e->trg_ev[2 * stage + side], e->stream));
     if (side) ran[stage] = true;

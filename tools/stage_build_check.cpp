@@ -3,6 +3,7 @@
 // (check_sections, check_taper_table: qm_engine.hpp), every refusal with its whole message.  A stand-alone host program: the runtime's
 // pool and copies are replaced below by malloc and memcpy, so no device is needed and every image lands in an
 // allocation of exactly the size build() asked for (an overrun is an AddressSanitizer report).  No kernel is launched.
+// The records own their device arrays: once they and the engine are gone, no block of the pool is out.
 //
 //   cd quakemigrate_amd/csrc
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
@@ -22,11 +23,21 @@ int fail(const char *fmt, ...) {
     g_error = buf;
     return 1;
 }
+static long g_blocks_out = 0;
 hipError_t pool_alloc(void **out, size_t bytes) {
     *out = std::malloc(bytes);
+    if (*out) ++g_blocks_out;
     return *out ? hipSuccess : hipErrorOutOfMemory;
 }
-void pool_free(void *p) { std::free(p); }
+void pool_free(void *p) {
+    --g_blocks_out;
+    std::free(p);
+}
+// (the engine's pinned ring and events are never made here: nothing to give back)
+hipError_t pinned_alloc(void **, size_t, unsigned) { return hipErrorNotSupported; }
+void pinned_free(void *) {}
+hipError_t event_create(hipEvent_t *, unsigned) { return hipErrorNotSupported; }
+void event_destroy(hipEvent_t) {}
 hipError_t copy_in(void *dst, const void *src, size_t bytes, hipStream_t) {
     std::memcpy(dst, src, bytes);
     return hipSuccess;
@@ -52,8 +63,9 @@ PoolReleaseScope::~PoolReleaseScope() {}
         CHECK(g_error.find(text) != std::string::npos);            \
     } while (0)
 
-int main() {
-    qm_engine *e = new qm_engine();
+static void stages() {
+    std::unique_ptr<qm_engine> engine(new qm_engine());
+    qm_engine *e = engine.get();
     const int T = 100, n_traces = 5, n_rows = 3;
 
     // -- pre-processing ------------------------------------------------------------------------------------------
@@ -183,8 +195,12 @@ int main() {
     CHECK(check_taper_table("rs", nullptr, 0, 0) == 0);
     std::printf("shared checks: 7 refusals, whole messages\n");
 
-    pre.release(); on.release(); rs.release();
-    delete e;
+    CHECK(g_blocks_out > 0);
+}
+
+int main() {
+    stages();
+    CHECK(g_blocks_out == 0);                           // (the records and the engine went out of scope)
     std::printf("stage_build_check: ok\n");
     return 0;
 }
