@@ -63,8 +63,8 @@ def run(out_dir, n_steps=12, grid=(36, 32, 20), rows=12, rate=50, n_samples=600)
         def index2coord(self, idx, unravel=True):
             return np.stack(np.unravel_index(idx, grid), axis=-1) * 0.5
 
-    sink = scanmseed.CoalescenceSink(out_dir, rate)
     s = scan.MigrationScan(Lut(), Onset(), pre, post, stage="detect")
+    sink = scanmseed.CoalescenceSink(out_dir, rate, engine=s.engine)         # (the day files are packed on the GPU)
     availability = s.continuous_compute(Archive(), t0, n_steps, timestep, rate, sink)
     return sink, availability, cases
 

@@ -83,8 +83,8 @@ def run(out_dir, n_steps=12, grid=(36, 32, 20), rows=12, rate=50, n_samples=600,
             return np.stack(np.unravel_index(idx, grid), axis=-1) * spacing
 
     # detect: the coalescence series of the run, one .scanmseed per day
-    sink = scanmseed.CoalescenceSink(out_dir, rate)
     detect = scan.MigrationScan(Lut(), Onset(), pre, post, stage="detect")
+    sink = scanmseed.CoalescenceSink(out_dir, rate, engine=detect.engine)    # (the day files are packed on the GPU)
     detect.continuous_compute(Archive(), t0, n_steps, timestep, rate, sink)
 
     # trigger: the day files in, events out

@@ -229,7 +229,11 @@ int qm_engine_synchronize(qm_engine *e);
  * qm_engine_trigger takes), trigger_smooth_tile, trigger_run_block, trigger_merge_stride; with the key
  * trigger_timing set, the last call's
  * stage times in nanoseconds: trigger_ns_smooth, trigger_ns_stats, trigger_ns_runs (count and scan),
- * trigger_ns_compact, trigger_ns_peaks, trigger_ns_merge (0: the stage did not run). */
+ * trigger_ns_compact, trigger_ns_peaks, trigger_ns_merge (0: the stage did not run);
+ * the .scanmseed codec's compile-time constants (csrc/qm_scanmseed.hpp): scanmseed_tile (positions per workgroup of
+ * the chain kernels), scanmseed_compose_chunk, and the last codec call's stage times in nanoseconds:
+ * scanmseed_ns_quantise, scanmseed_ns_scan, scanmseed_ns_compose, scanmseed_ns_pack, scanmseed_ns_frame (encode),
+ * scanmseed_ns_decode (0: the stage did not run). */
 int qm_engine_config(qm_engine *e, const char *key, int64_t value);
 int qm_engine_get(qm_engine *e, const char *key, int64_t *value);
 
@@ -648,6 +652,60 @@ int qm_engine_trigger(qm_engine *e, const double *coa, const double *coa_n, int6
                       int64_t max_events, int64_t *n_candidates, int64_t *n_events, int64_t *events_i,
                       double *events_f, double *thresholds, double *smoothed, int64_t *candidates,
                       int64_t max_candidates);
+/* ... the same call on series that are on the engine's GPU already (coa, coa_n: device f64 [n], read on the engine's
+ * stream; what qm_engine_scanmseed_decode leaves with out_on_device = 1): no host copy of the series is made.  Every
+ * other argument, every output and every refusal as above. */
+int qm_engine_trigger_resident(qm_engine *e, const double *coa, const double *coa_n, int64_t n,
+                               const qm_trigger_params *params, int64_t max_events, int64_t *n_candidates,
+                               int64_t *n_events, int64_t *events_i, double *events_f, double *thresholds,
+                               double *smoothed, int64_t *candidates, int64_t max_candidates);
+
+/* The day file's codec on the device -- the step between the detect sweep and the trigger: the STEIM2 payloads of the
+ * .scanmseed records that quakemigrate_amd/scanmseed.py writes and reads (what obspy / libmseed write for the
+ * reference: miniSEED 2, 4096-byte records, encoding 11; the rules on arrays: tests/scanmseed_ref.py; kernels:
+ * csrc/qm_scanmseed.hpp).  A record is 64 header bytes and 63 frames of 16 big-endian words; word 0 of a frame holds
+ * fifteen 2-bit codes, words 1 and 2 of frame 0 the record's first and last sample: 943 data words per record.
+ *
+ * qm_engine_scanmseed_encode.  series: [5][n], the channels COA, COA_N, X, Y, Z in this order, host or device
+ * (series_on_device), series_dtype 0: int32, already quantised (factors, clips: not read, may be NULL); 1: float64,
+ * quantised on the device as scanmseed.quantise does: min(x, clips[c]) (clips[c] = +infinity: no clip) times
+ * factors[c], rounded half to even, int32.
+ *   Differences are global and 64-bit: d[0] = 0, d[p] = x[p] - x[p - 1], across record boundaries too.  Words are
+ *   packed greedily: the first of 7x4, 6x5, 5x6, 4x8, 3x10, 2x15, 1x30 bits whose count is at most the differences
+ *   left in the TRACE and whose differences all fit.  A trace's words are cut into records every 943.
+ * Out: n_records i64 [5], the channels' record counts; records u8 [sum][4096], channel after channel: the 64 header
+ * bytes ZERO (BTIME, sequence number, blockette 1000 and the rest of the header are the caller's: scanmseed.py's
+ * write_trace), the payload complete, unused words and frames of a trace's last record zero; rec_first, rec_count
+ * i32 [sum]: every record's first sample index in its channel and its sample count.  All three have room for
+ * max_records records (never more than 5 ceil(n / 943) are needed); the count is known on the host before the device
+ * output is sized, as the trigger's candidate count is.  The same input gives the same bytes on every run.
+ * Deviations from the Python, all refusals: a float64 sample that is NaN, or whose scaled value is outside int32, is
+ * refused by channel and index -- NumPy's cast to int32 is platform-defined there, so there are no bytes to match; a
+ * difference outside 30 bits is refused by channel and index (the Python raises OverflowError).
+ * Refused, with every output untouched: a NULL argument (factors / clips under series_dtype 0 excepted), a
+ * series_dtype other than 0 / 1, n < 1 or above 2^28, a non-finite factor, a NaN clip, the three above, more records
+ * than max_records (the message names the number needed).  qm_engine_last_kernel_ms reports the launch sequence, its
+ * read-back of counts included.
+ *
+ * qm_engine_scanmseed_decode.  records: host u8 [n_records][4096], whole records with the payload at byte 64 (header
+ * parsing -- station, BTIME, sample count, blockette 1000, the 4096 / big-endian / encoding-11 checks -- is the
+ * caller's: scanmseed.py); rec_samples i32 [n_records]: the header's sample counts; rec_offset i64 [n_records]: where
+ * in `out` each record's samples go (the caller orders and concatenates: any channel layout); rec_factor f64
+ * [n_records], needed with out_f64 only.  Out: out i32 [n_total]; out_f64 (NULL: not wanted) f64 [n_total], sample /
+ * rec_factor: one IEEE division, NumPy's bits; both host, or both on the engine's GPU with out_on_device = 1 (then
+ * valid on the engine's stream; the call has waited for it when it returns).
+ * Refused: a NULL argument (the optional ones excepted), n_records < 1, n_total < 1, a record with fewer than 1
+ * sample or whose samples leave `out`, and -- naming the record, the smallest such index -- the Python's three
+ * ValueErrors in its order: an invalid code / dnib pair before the record's last difference, fewer differences than
+ * samples (a sample count above 6601 included), a last sample that is not the reverse integration constant.  None
+ * of these faults: every launch stays in bounds.  Host outputs are untouched by a refused call; device outputs may
+ * hold the records decoded so far. */
+int qm_engine_scanmseed_encode(qm_engine *e, const void *series, int series_dtype, int series_on_device, int64_t n,
+                               const double *factors /*[5]*/, const double *clips /*[5]*/, int64_t max_records,
+                               int64_t *n_records /*[5]*/, uint8_t *records, int32_t *rec_first, int32_t *rec_count);
+int qm_engine_scanmseed_decode(qm_engine *e, const uint8_t *records, int64_t n_records, const int32_t *rec_samples,
+                               const int64_t *rec_offset, const double *rec_factor, int64_t n_total, int32_t *out,
+                               double *out_f64, int out_on_device);
 
 /* exp(x) rounded to nearest from a double-double evaluation (csrc/qm_ties.hpp): the function the
  * opt-in arg-max rule "tie_rule" = 1 compares near-tied nodes on (the reference exponentiates, then

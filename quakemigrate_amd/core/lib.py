@@ -136,6 +136,10 @@ class TriggerParams(ctypes.Structure):
 qmlib.qm_engine_trigger.argtypes = [_vp, _vp, _vp, c_int64, ctypes.POINTER(TriggerParams), c_int64,
                                     ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), _vp, _vp, _vp, _vp, _vp,
                                     c_int64]
+qmlib.qm_engine_trigger_resident.argtypes = qmlib.qm_engine_trigger.argtypes
+qmlib.qm_engine_scanmseed_encode.argtypes = [_vp, _vp, ctypes.c_int, ctypes.c_int, c_int64, _vp, _vp, c_int64, _vp, _vp,
+                                             _vp, _vp]
+qmlib.qm_engine_scanmseed_decode.argtypes = [_vp, _vp, c_int64, _vp, _vp, _vp, c_int64, _vp, _vp, ctypes.c_int]
 qmlib.qm_engine_find_max_coa.argtypes = [_vp, _vp, ctypes.c_int, c_int32,
                                          c_int64, _vp, _vp, _vp, ctypes.c_int]
 qmlib.qm_exp2f_max_error.argtypes = [_vp, ctypes.c_float, ctypes.c_float,
@@ -908,7 +912,8 @@ class Engine:
         """
         The trigger stage on the GPU, the step between detect and locate (``Trigger._trigger_batch``'s smoothing,
         threshold, candidates and merge, trigger.py:318-638; include/qmhip.h: ``qm_engine_trigger``).  ``coa``,
-        ``coa_n`` (n,): float64 host arrays, contiguous, already cut to the batch and its pads; times in int64
+        ``coa_n`` (n,): float64 host arrays, contiguous, already cut to the batch and its pads -- or both tensors on this
+        engine's GPU (``scanmseed_decode(..., device=True)``'s: ``qm_engine_trigger_resident``, no host copy); times in int64
         nanoseconds from the first sample.  ``trigger_on`` 0: COA, 1: COA_N; ``method`` "static" (``value``: the
         threshold), "mad" or "median_ratio" (``value``: the multiplier, per chunk of ``chunk_samples``); ``weights``
         (2 r + 1,): the Gaussian kernel of the smoothing, None: none.  Returns a dict: ``n_candidates``, ``n_events``,
@@ -917,7 +922,14 @@ class Engine:
         ``candidates`` (n_candidates, 5) int64 [f, l, p, MinTime, MaxTime].  More than ``max_events`` events: refused,
         the message names the number.
         """
+        resident = all(hasattr(a, "data_ptr") and a.is_cuda for a in (coa, coa_n))
         for name, a in (("coa", coa), ("coa_n", coa_n)):
+            if resident:
+                # (device tensors, e.g. scanmseed_decode's with device=True: qm_engine_trigger_resident, no host copy)
+                if a.dim() != 1:
+                    raise ValueError(f"{name} must be one-dimensional and contiguous")
+                self._ptr(a, np.float64)
+                continue
             if not isinstance(a, np.ndarray):
                 raise TypeError(f"{name}: a NumPy array expected, got {type(a).__name__}")
             if a.dtype != np.float64:
@@ -946,8 +958,10 @@ class Engine:
         room = (n + 1) // 2 if want_candidates else 0
         candidates = np.zeros((room, 5), dtype=np.int64) if want_candidates else None
         nc, ne = c_int64(0), c_int64(0)
-        _check(qmlib.qm_engine_trigger(
-            self._h, _host(coa), _host(coa_n), n, ctypes.byref(par), max_events, ctypes.byref(nc), ctypes.byref(ne),
+        call = qmlib.qm_engine_trigger_resident if resident else qmlib.qm_engine_trigger
+        p_coa, p_coa_n = (_vp(coa.data_ptr()), _vp(coa_n.data_ptr())) if resident else (_host(coa), _host(coa_n))
+        _check(call(
+            self._h, p_coa, p_coa_n, n, ctypes.byref(par), max_events, ctypes.byref(nc), ctypes.byref(ne),
             _host(events_i), _host(events_f), _host(thresholds), _host(smoothed) if smoothed is not None else _vp(None),
             _host(candidates) if want_candidates else _vp(None), room))
         out = {"n_candidates": int(nc.value), "n_events": int(ne.value), "events_i": events_i[:ne.value].copy(),
@@ -955,6 +969,104 @@ class Engine:
         if want_candidates:
             out["candidates"] = candidates[:nc.value].copy()
         return out
+
+    SCANMSEED_RECLEN = 4096
+    SCANMSEED_RECORD_WORDS = 943            # data words of a record: a record holds at least that many samples
+
+    def scanmseed_encode(self, series, factors=None, clips=None):
+        """
+        The STEIM2 records of a ``.scanmseed`` file's five channels on the GPU (include/qmhip.h:
+        ``qm_engine_scanmseed_encode``).  ``series`` (5, n): COA, COA_N, X, Y, Z -- a NumPy array or a tensor on this
+        engine's GPU; int32: already quantised; float64: quantised on the device as ``scanmseed.quantise`` does, with
+        ``factors`` (5,) and ``clips`` (5,), ``inf`` or ``None`` where a channel has no clip.  Returns a dict:
+        ``n_records`` (5,) int64; ``records`` (sum, 4096) uint8, channel after channel, the 64 header bytes zero;
+        ``rec_first``, ``rec_count`` (sum,) int32: every record's first sample index and sample count.
+        """
+        on_device = hasattr(series, "data_ptr")
+        if not on_device and not isinstance(series, np.ndarray):
+            raise TypeError(f"series: a NumPy array or a device tensor expected, got {type(series).__name__}")
+        shape = tuple(series.shape)
+        if len(shape) != 2 or shape[0] != 5:
+            raise ValueError(f"series of shape {shape}: (5, n) expected")
+        kind = str(series.dtype).replace("torch.", "")
+        if kind not in ("int32", "float64"):
+            raise TypeError(f"series: expected int32 or float64, got {series.dtype}")
+        is_float = kind == "float64"
+        n = int(shape[1])
+        if n < 1:
+            raise ValueError("series holds no samples")
+        ps, dev = self._ptr(series, np.float64 if is_float else np.int32)
+        if on_device and not dev:
+            raise ValueError("series: a tensor on this engine's GPU expected (pass host data as a NumPy array)")
+        if on_device:
+            import torch
+
+            torch.cuda.synchronize(series.device)   # (what filled the tensor ran on a stream that is not the engine's)
+        pf = pc = _vp(None)
+        if is_float:
+            if factors is None:
+                raise ValueError("float64 series need factors")
+            factors = np.ascontiguousarray(factors, dtype=np.float64)
+            clips = np.ascontiguousarray([np.inf if c is None else c for c in (clips if clips is not None else [None] * 5)],
+                                         dtype=np.float64)
+            if factors.shape != (5,) or clips.shape != (5,):
+                raise ValueError(f"factors of shape {factors.shape}, clips of shape {clips.shape}: (5,) expected")
+            pf, pc = _host(factors), _host(clips)
+        room = 5 * -(-n // self.SCANMSEED_RECORD_WORDS)
+        records = np.empty((room, self.SCANMSEED_RECLEN), dtype=np.uint8)
+        rec_first, rec_count = np.empty(room, dtype=np.int32), np.empty(room, dtype=np.int32)
+        n_records = np.zeros(5, dtype=np.int64)
+        _check(qmlib.qm_engine_scanmseed_encode(self._h, ps, 1 if is_float else 0, dev, n, pf, pc, room,
+                                                _host(n_records), _host(records), _host(rec_first), _host(rec_count)))
+        total = int(n_records.sum())
+        return {"n_records": n_records, "records": records[:total], "rec_first": rec_first[:total],
+                "rec_count": rec_count[:total]}
+
+    def scanmseed_decode(self, records, rec_samples, rec_offset, n_total, rec_factor=None, device=False):
+        """
+        The samples of STEIM2 records on the GPU (include/qmhip.h: ``qm_engine_scanmseed_decode``).  ``records``
+        (n_records, 4096) uint8: whole records, payload at byte 64; ``rec_samples`` (n_records,): their headers' sample
+        counts; ``rec_offset`` (n_records,): where each record's samples go in the output of ``n_total`` samples;
+        ``rec_factor`` (n_records,): if given, the descaled float64 ``sample / factor`` is returned as well.  Returns
+        ``(int32, float64 or None)``: NumPy arrays, or -- ``device=True`` -- tensors on this engine's GPU.
+        """
+        if not isinstance(records, np.ndarray):
+            raise TypeError(f"records: a NumPy array expected, got {type(records).__name__}")
+        if records.dtype != np.uint8:
+            raise TypeError(f"records: expected uint8, got {records.dtype}")
+        if records.ndim != 2 or records.shape[1] != self.SCANMSEED_RECLEN or not records.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"records of shape {records.shape}: (n_records, {self.SCANMSEED_RECLEN}), C-contiguous, "
+                             f"expected")
+        nrec = int(records.shape[0])
+        rec_samples = np.ascontiguousarray(rec_samples, dtype=np.int32)
+        rec_offset = np.ascontiguousarray(rec_offset, dtype=np.int64)
+        if rec_samples.shape != (nrec,) or rec_offset.shape != (nrec,):
+            raise ValueError(f"rec_samples of shape {rec_samples.shape}, rec_offset of shape {rec_offset.shape}: "
+                             f"({nrec},) expected")
+        want_f = rec_factor is not None
+        if want_f:
+            rec_factor = np.ascontiguousarray(rec_factor, dtype=np.float64)
+            if rec_factor.shape != (nrec,):
+                raise ValueError(f"rec_factor of shape {rec_factor.shape}: ({nrec},) expected")
+        n_total = int(n_total)
+        if n_total < 1:
+            raise ValueError(f"n_total must be positive, got {n_total}")
+        if device:
+            import torch
+
+            where = torch.device("cuda", self.device)
+            out = torch.empty(n_total, dtype=torch.int32, device=where)
+            out_f = torch.empty(n_total, dtype=torch.float64, device=where) if want_f else None
+            torch.cuda.synchronize(where)           # (the allocator's stream is not the engine's)
+            po, pof = _vp(out.data_ptr()), _vp(out_f.data_ptr()) if want_f else _vp(None)
+        else:
+            out = np.empty(n_total, dtype=np.int32)
+            out_f = np.empty(n_total, dtype=np.float64) if want_f else None
+            po, pof = _host(out), _host(out_f) if want_f else _vp(None)
+        _check(qmlib.qm_engine_scanmseed_decode(self._h, _host(records), nrec, _host(rec_samples), _host(rec_offset),
+                                                _host(rec_factor) if want_f else _vp(None), n_total, po, pof,
+                                                1 if device else 0))
+        return out, out_f
 
     def find_max_coa(self, map4d, n_samples, n_nodes, out=None):
         if out is None:
@@ -1320,6 +1432,12 @@ class EngineReplicas:
 
     def trigger_series(self, *args, **kwargs):
         return self.lead.trigger_series(*args, **kwargs)
+
+    def scanmseed_encode(self, *args, **kwargs):
+        return self.lead.scanmseed_encode(*args, **kwargs)
+
+    def scanmseed_decode(self, *args, **kwargs):
+        return self.lead.scanmseed_decode(*args, **kwargs)
 
 
 def timeit(*args_, **kwargs_):

@@ -852,6 +852,14 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     else if (k == "trigger_smooth_tile") *v = qm::kTrigSmoothTile;
     else if (k == "trigger_run_block") *v = qm::kTrigRunBlock;
     else if (k == "trigger_merge_stride") *v = qm::kTrigMergeThreads;
+    else if (k == "scanmseed_tile") *v = qm::kSmsTile;
+    else if (k == "scanmseed_compose_chunk") *v = qm::kSmsComposeChunk;
+    else if (k == "scanmseed_ns_quantise") *v = e->sms_ns[qm::kSmsQuantise];
+    else if (k == "scanmseed_ns_scan") *v = e->sms_ns[qm::kSmsScan];
+    else if (k == "scanmseed_ns_compose") *v = e->sms_ns[qm::kSmsCompose];
+    else if (k == "scanmseed_ns_pack") *v = e->sms_ns[qm::kSmsPack];
+    else if (k == "scanmseed_ns_frame") *v = e->sms_ns[qm::kSmsFrame];
+    else if (k == "scanmseed_ns_decode") *v = e->sms_ns[qm::kSmsDecode];
     else if (k == "tie_brick_rows") *v = e->last.brick_rows;
 
     else if (k == "tie_refined_steps") *v = e->tie_refined_steps;

@@ -21,6 +21,8 @@
 //                    engine's staged call, which lives beside it, and the pipeline
 //   qm_picks.hip     the row after the location: phase picks, a Gaussian fitted to every onset row of an event
 //   qm_trigger.hip   the row after the detect sweep: coalescence series in, triggered events out
+//   qm_scanmseed.hip the file between the detect sweep and the trigger: the day's five series to and from the STEIM2
+//                    records of a .scanmseed file (encode, decode)
 //   qm_amplitudes.hip  the row after the picks: local-magnitude amplitudes, filtered traces and time windows in,
 //                    peak-to-trough measurements out
 //   qm_compat.hip    the five reference-signature symbols (qmlib.h:28-44)
@@ -60,6 +62,7 @@
 #include "qm_picks.hpp"
 #include "qm_trigger.hpp"
 #include "qm_amplitudes.hpp"
+#include "qm_scanmseed.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -440,6 +443,18 @@ struct qm_engine : TableState {
     DevBuf<int64_t> d_trg_tot, d_trg_cand;
     std::vector<Event> trg_ev;              // cfg.trigger_timing: a pair of HIP events per stage of the trigger sequence
     int64_t trg_ns[qm::kTrigStages] = {};   // ... the last call's stage times ("trigger_ns_<stage>"), 0: did not run
+
+    // .scanmseed codec scratch: the int32 series (quantised, copied in or decoded), float64 series in or descaled out,
+    // count(p) and the words' codes, the tiles' maps, entries and first words, totals and error slots, the records,
+    // their first samples and counts (decode: their sample counts), decode's offsets and factors
+    DevBuf<int32_t> d_sms_x, d_sms_tile, d_sms_rec;
+    DevBuf<double> d_sms_f, d_sms_fac;
+    DevBuf<uint8_t> d_sms_bytes;
+    DevBuf<uint32_t> d_sms_map, d_sms_out;
+    DevBuf<unsigned long long> d_sms_tot;
+    DevBuf<int64_t> d_sms_off;
+    std::vector<Event> sms_ev;              // a pair of HIP events per stage of the codec's sequences
+    int64_t sms_ns[qm::kSmsStages] = {};    // ... the last call's stage times ("scanmseed_ns_<stage>"), 0: did not run
 
     // scratch
     DevBuf<double> d_onsets, d_pmax, d_psum, d_out_a, d_chunk, d_marg, d_marg_out;

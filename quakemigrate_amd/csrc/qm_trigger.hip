@@ -24,13 +24,11 @@ static int trig_mark(qm_engine *e, int stage, int side, bool (&ran)[qm::kTrigSta
         if (trig_mark(e, stage, 1, ran)) return 1;             \
     } while (0)
 
-extern "C" {
-
-int qm_engine_trigger(qm_engine *e, const double *coa, const double *coa_n, int64_t n, const qm_trigger_params *p,
-                      int64_t max_events, int64_t *n_candidates, int64_t *n_events, int64_t *events_i,
-                      double *events_f, double *thresholds, double *smoothed, int64_t *candidates,
-                      int64_t max_candidates) {
-    const char *what = "qm_engine_trigger";
+// the two public calls: `resident` -- the series are on the engine's GPU already (device to device on the stream)
+static int trigger_run(qm_engine *e, const char *what, bool resident, const double *coa, const double *coa_n, int64_t n,
+                       const qm_trigger_params *p, int64_t max_events, int64_t *n_candidates, int64_t *n_events,
+                       int64_t *events_i, double *events_f, double *thresholds, double *smoothed, int64_t *candidates,
+                       int64_t max_candidates) {
     if (!e || !coa || !coa_n || !p || !n_candidates || !n_events || !events_i || !events_f)
         return fail("%s: NULL argument", what);
     if (n < 1) return fail("%s: empty input (%lld samples)", what, (long long)n);
@@ -68,8 +66,13 @@ int qm_engine_trigger(qm_engine *e, const double *coa, const double *coa_n, int6
         e->d_trg_cnt.ensure(5 * (size_t)nblocks) || e->d_trg_tot.ensure(4))
         return 1;
     double *d_raw = e->d_trg_x.p, *d_w = e->d_trg_par.p, *d_thr = e->d_trg_par.p + r + 1;
-    QM_HIP(copy_in(d_raw, coa, N * sizeof(double), e->stream));
-    QM_HIP(copy_in(d_raw + N, coa_n, N * sizeof(double), e->stream));
+    if (resident) {
+        QM_HIP(hipMemcpyAsync(d_raw, coa, N * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+        QM_HIP(hipMemcpyAsync(d_raw + N, coa_n, N * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    } else {
+        QM_HIP(copy_in(d_raw, coa, N * sizeof(double), e->stream));
+        QM_HIP(copy_in(d_raw + N, coa_n, N * sizeof(double), e->stream));
+    }
     if (smooth) QM_HIP(copy_in(d_w, p->smooth_weights, ((size_t)r + 1) * sizeof(double), e->stream));
     if (!dynamic) QM_HIP(copy_in(d_thr, &p->threshold_value, sizeof(double), e->stream));
 
@@ -164,6 +167,24 @@ int qm_engine_trigger(qm_engine *e, const double *coa, const double *coa_n, int6
     *n_candidates = nc;
     *n_events = ne;
     return 0;
+}
+
+extern "C" {
+
+int qm_engine_trigger(qm_engine *e, const double *coa, const double *coa_n, int64_t n, const qm_trigger_params *p,
+                      int64_t max_events, int64_t *n_candidates, int64_t *n_events, int64_t *events_i,
+                      double *events_f, double *thresholds, double *smoothed, int64_t *candidates,
+                      int64_t max_candidates) {
+    return trigger_run(e, "qm_engine_trigger", false, coa, coa_n, n, p, max_events, n_candidates, n_events, events_i,
+                       events_f, thresholds, smoothed, candidates, max_candidates);
+}
+
+int qm_engine_trigger_resident(qm_engine *e, const double *coa, const double *coa_n, int64_t n,
+                               const qm_trigger_params *p, int64_t max_events, int64_t *n_candidates,
+                               int64_t *n_events, int64_t *events_i, double *events_f, double *thresholds,
+                               double *smoothed, int64_t *candidates, int64_t max_candidates) {
+    return trigger_run(e, "qm_engine_trigger_resident", true, coa, coa_n, n, p, max_events, n_candidates, n_events,
+                       events_i, events_f, thresholds, smoothed, candidates, max_candidates);
 }
 
 }  // extern "C"

@@ -119,7 +119,11 @@ def steim2_encode(samples: np.ndarray, prev: int, max_frames: int = N_FRAMES):
     Pack as many of ``samples`` as fit into ``max_frames`` frames.  ``prev`` is the sample before
     the first one (difference 0 of the record).  Returns ``(payload bytes, n_packed)``.
     """
-    x = [int(v) for v in samples]
+    # only what the frames can consume -- 15 words of at most 7 differences each, less the two constants -- plus the
+    # look-ahead of a word is turned into Python ints (6601 + 7 samples for a record): the writer is linear in the
+    # trace.  `left` below still counts to the true end of `samples`
+    total = len(samples)
+    x = [int(v) for v in samples[:(max_frames * 15 - 2) * 7 + 7]]
     diffs = [x[0] - int(prev)] + [x[i] - x[i - 1] for i in range(1, len(x))]
     frames = [[0] * 16 for _ in range(max_frames)]
     pos = 0                                            # next difference to pack
@@ -128,9 +132,9 @@ def steim2_encode(samples: np.ndarray, prev: int, max_frames: int = N_FRAMES):
         for k in range(1, 16):
             if fi == 0 and k < 3:
                 continue
-            if pos >= len(diffs):
+            if pos >= total:
                 break
-            left = len(diffs) - pos
+            left = total - pos
             for count, bits, code, dnib in _LAYOUTS:
                 if count <= left and all(_fits(d, bits) for d in diffs[pos:pos + count]):
                     break
@@ -144,7 +148,7 @@ def steim2_encode(samples: np.ndarray, prev: int, max_frames: int = N_FRAMES):
             frame[k] = word
             frame[0] |= code << (30 - 2 * k)
             pos += count
-        if pos >= len(diffs):
+        if pos >= total:
             break
     frames[0][1] = x[0] & 0xFFFFFFFF
     frames[0][2] = x[pos - 1] & 0xFFFFFFFF
@@ -186,66 +190,178 @@ def _rate_fields(rate: float):
     raise ValueError("only integer sampling rates (samples per second) are supported")
 
 
+def record_header(station, network, starttime, sampling_rate, seq, pos, n) -> bytes:
+    """The 64 header bytes of the record that starts at sample ``pos`` of its trace and holds ``n`` samples: fixed
+    header with BTIME from ``timedelta(seconds=pos / rate)``, sequence number ``seq``, blockette 1000."""
+    factor, mult = _rate_fields(sampling_rate)
+    start = starttime + _dt.timedelta(seconds=pos / sampling_rate)
+    header = (f"{seq:06d}".encode() + b"D " + station.ljust(5).encode() + b"  "
+              + b"   " + network.ljust(2).encode() + _btime(start)
+              + struct.pack(">HhhBBBBiHH", n, factor, mult, 0, 0, 0, 1, 0, DATA_OFFSET, 48)
+              + struct.pack(">HHBBBB", 1000, 0, 11, 1, 12, 0))
+    return header.ljust(DATA_OFFSET, b"\x00")
+
+
 def write_trace(trace: Trace) -> bytes:
     """All records of one trace (what obspy writes for one ``Trace`` with STEIM2, reclen 4096)."""
     out = []
     data = np.asarray(trace.data, dtype=np.int32)
     pos, seq = 0, 1
-    factor, mult = _rate_fields(trace.sampling_rate)
+    _rate_fields(trace.sampling_rate)
     while pos < len(data):
         prev = int(data[pos - 1]) if pos else int(data[0])     # first record: difference 0 = 0
         payload, n = steim2_encode(data[pos:], prev)
-        start = trace.starttime + _dt.timedelta(seconds=pos / trace.sampling_rate)
-        header = (f"{seq:06d}".encode() + b"D " + trace.station.ljust(5).encode() + b"  "
-                  + b"   " + trace.network.ljust(2).encode() + _btime(start)
-                  + struct.pack(">HhhBBBBiHH", n, factor, mult, 0, 0, 0, 1, 0, DATA_OFFSET, 48)
-                  + struct.pack(">HHBBBB", 1000, 0, 11, 1, 12, 0))
-        out.append(header.ljust(DATA_OFFSET, b"\x00") + payload)
+        out.append(record_header(trace.station, trace.network, trace.starttime, trace.sampling_rate, seq, pos, n)
+                   + payload)
         pos += n
         seq += 1
     return b"".join(out)
 
 
-def write_scanmseed(path, starttime, sampling_rate, series, network="NW"):
-    """``series``: dict channel -> int32 array (see :func:`quantise`), written in CHANNELS order."""
-    blob = b"".join(write_trace(Trace(ch, network, starttime, sampling_rate, series[ch]))
-                    for ch in CHANNELS)
+def fill_headers(records, n_records, rec_first, rec_count, starttime, sampling_rate, network="NW"):
+    """
+    The headers of records whose payloads are packed already: ``records`` (sum, 4096) uint8 with the channels'
+    ``n_records`` records one after the other, ``rec_first`` / ``rec_count`` every record's first sample index and
+    sample count (what ``Engine.scanmseed_encode`` and ``tests/scanmseed_ref.py`` return).  In place; returns the bytes.
+    """
+    _rate_fields(sampling_rate)
+    r = 0
+    for ch, count in zip(CHANNELS, n_records):
+        for seq in range(1, int(count) + 1):
+            head = record_header(ch, network, starttime, sampling_rate, seq, int(rec_first[r]), int(rec_count[r]))
+            records[r, :DATA_OFFSET] = np.frombuffer(head, dtype=np.uint8)
+            r += 1
+    return records.tobytes()
+
+
+def encode_scanmseed(starttime, sampling_rate, series, network="NW", engine=None):
+    """The bytes of a ``.scanmseed`` file.  ``engine``: an ``Engine`` -- the payloads are packed on the GPU
+    (``Engine.scanmseed_encode``), the headers filled here; None: the Python encoder."""
+    if engine is None:
+        return b"".join(write_trace(Trace(ch, network, starttime, sampling_rate, series[ch])) for ch in CHANNELS)
+    rows = [np.asarray(series[ch], dtype=np.int32) for ch in CHANNELS]
+    if any(r.ndim != 1 or len(r) != len(rows[0]) for r in rows):
+        raise ValueError("the five channels must be one-dimensional and of one length")
+    _rate_fields(sampling_rate)
+    if len(rows[0]) == 0:
+        return b""
+    out = engine.scanmseed_encode(np.ascontiguousarray(np.stack(rows)))
+    return fill_headers(out["records"], out["n_records"], out["rec_first"], out["rec_count"], starttime,
+                        sampling_rate, network)
+
+
+def write_scanmseed(path, starttime, sampling_rate, series, network="NW", engine=None):
+    """``series``: dict channel -> int32 array (see :func:`quantise`), written in CHANNELS order.  ``engine``: see
+    :func:`encode_scanmseed`; the file's bytes are the same either way."""
+    blob = encode_scanmseed(starttime, sampling_rate, series, network, engine)
     with open(path, "wb") as f:
         f.write(blob)
     return len(blob)
+
+
+def parse_header(rec: bytes):
+    """``(station, network, starttime, sampling_rate, n_samples, data offset)`` of one record; refuses all but
+    big-endian 4096-byte STEIM2 records."""
+    station = rec[8:13].decode().strip()
+    network = rec[18:20].decode().strip()
+    start = _from_btime(rec[20:30])
+    n, factor, mult, _, _, _, nblk, _, dstart, bstart = struct.unpack(">HhhBBBBiHH", rec[30:48])
+    encoding = None
+    b = bstart
+    for _ in range(nblk):
+        btype, nxt = struct.unpack(">HH", rec[b:b + 4])
+        if btype == 1000:
+            encoding, order, reclen_exp = rec[b + 4], rec[b + 5], rec[b + 6]
+            if order != 1 or (1 << reclen_exp) != RECLEN:
+                raise ValueError("only big-endian 4096-byte records are supported")
+        b = nxt
+    if encoding != 11:
+        raise ValueError(f"encoding {encoding}: only STEIM2 (11) is supported")
+    rate = float(factor) * (mult if mult > 0 else -1.0 / mult) if factor > 0 else -1.0 / factor
+    return station, network, start, rate, n, dstart
 
 
 def read_records(blob: bytes):
     """Yield ``(station, network, starttime, sampling_rate, int32 data)`` per record."""
     for off in range(0, len(blob), RECLEN):
         rec = blob[off:off + RECLEN]
-        station = rec[8:13].decode().strip()
-        network = rec[18:20].decode().strip()
-        start = _from_btime(rec[20:30])
-        n, factor, mult, _, _, _, nblk, _, dstart, bstart = struct.unpack(">HhhBBBBiHH", rec[30:48])
-        encoding = None
-        b = bstart
-        for _ in range(nblk):
-            btype, nxt = struct.unpack(">HH", rec[b:b + 4])
-            if btype == 1000:
-                encoding, order, reclen_exp = rec[b + 4], rec[b + 5], rec[b + 6]
-                if order != 1 or (1 << reclen_exp) != RECLEN:
-                    raise ValueError("only big-endian 4096-byte records are supported")
-            b = nxt
-        if encoding != 11:
-            raise ValueError(f"encoding {encoding}: only STEIM2 (11) is supported")
-        rate = float(factor) * (mult if mult > 0 else -1.0 / mult) if factor > 0 else -1.0 / factor
+        station, network, start, rate, n, dstart = parse_header(rec)
         yield station, network, start, rate, steim2_decode(rec[dstart:], n)
 
 
-def read_scanmseed(path, ucf=1.0):
+def _read_with_engine(blob, ucf, engine, device):
+    """read_scanmseed's work with the payloads decoded on the GPU: headers parsed here, one decode call for the
+    channels that come back to the host and -- ``device`` -- one for COA and COA_N that leaves them on the GPU."""
+    if len(blob) % RECLEN:
+        raise ValueError(f"{len(blob)} bytes: not a whole number of {RECLEN}-byte records")
+    records = np.frombuffer(blob, dtype=np.uint8).reshape(-1, RECLEN)
+    pieces, start, rate = {}, {}, None
+    for r in range(len(records)):
+        station, _, t0, sr, n, dstart = parse_header(blob[r * RECLEN:(r + 1) * RECLEN])
+        if dstart != DATA_OFFSET:
+            raise ValueError(f"record {r}: data at byte {dstart}, the engine reads payloads at byte {DATA_OFFSET}")
+        pieces.setdefault(station, []).append((t0, r, n))
+        rate = sr
+        start[station] = min(start.get(station, t0), t0)
+    lengths = {}
+    for station, recs in pieces.items():
+        recs.sort(key=lambda x: x[0])
+        t = recs[0][0]
+        for t0, _, n in recs:
+            if abs((t0 - t).total_seconds()) > 0.5 / rate:
+                raise ValueError(f"gap in {station} at {t0}")
+            t = t0 + _dt.timedelta(seconds=n / rate)
+        lengths[station] = sum(n for _, _, n in recs)
+    f = scale_factors(ucf)
+
+    def decode(channels, on_device):
+        index, samples, offset, factor, at, base = [], [], [], [], 0, {}
+        for ch in channels:
+            base[ch] = at
+            for _, r, n in pieces[ch]:
+                index.append(r)
+                samples.append(n)
+                offset.append(at)
+                factor.append(f[ch])
+                at += n
+        try:
+            ints, vals = engine.scanmseed_decode(np.ascontiguousarray(records[index]), samples, offset, at,
+                                                 rec_factor=factor, device=on_device)
+        except RuntimeError as err:                 # (the message names the record by its index in this call)
+            import re
+
+            m = re.search(r"record (\d+)", str(err))
+            which = f": record {index[int(m.group(1))]} of the file" if m and int(m.group(1)) < len(index) else ""
+            raise ValueError(f"{err}{which}") from err
+        return ({ch: ints[base[ch]:base[ch] + lengths[ch]] for ch in channels},
+                {ch: vals[base[ch]:base[ch] + lengths[ch]] for ch in channels})
+
+    if device:
+        ints, cols = decode(CHANNELS[:2], True)
+        host_ints, host_cols = decode(CHANNELS[2:], False)
+        ints.update(host_ints)
+        cols.update(host_cols)
+    else:
+        ints, cols = decode(CHANNELS, False)
+    cols["int"] = ints
+    return start[CHANNELS[0]], rate, cols
+
+
+def read_scanmseed(path, ucf=1.0, engine=None, device=False):
     """
     Read one ``.scanmseed`` file: returns ``(starttime, sampling_rate, columns)`` with
     ``columns`` = dict of float64 arrays COA, COA_N, X, Y, Z, descaled as
     ``read_scanmseed`` does (scanmseed.py:300-305), plus the raw int32 series under ``"int"``.
+    ``engine``: an ``Engine`` -- the payloads are decoded on the GPU (``Engine.scanmseed_decode``), the values are the
+    same; with ``device=True`` COA and COA_N, descaled and int32, stay there as tensors (what
+    ``Engine.trigger_series`` takes without a host round trip), X, Y, Z come back as arrays.
     """
     with open(path, "rb") as f:
         blob = f.read()
+    if engine is not None:
+        return _read_with_engine(blob, ucf, engine, device)
+    if device:
+        raise ValueError("device=True needs an engine")
     pieces = {}
     start, rate = {}, None
     for station, _, t0, sr, data in read_records(blob):
@@ -282,8 +398,10 @@ class CoalescenceSink:
     ``<year>_<julday>.scanmseed`` per day, scanmseed.py:182-220).  Times are ``datetime`` (UTC).
     """
 
-    def __init__(self, directory, sampling_rate, continuous_write=False):
+    def __init__(self, directory, sampling_rate, continuous_write=False, engine=None):
         import pathlib
+
+        self.engine = engine                # an Engine: the day files' payloads are packed on the GPU (same bytes)
 
         self.directory = pathlib.Path(directory)
         self.sampling_rate = float(sampling_rate)
@@ -340,7 +458,7 @@ class CoalescenceSink:
         self.directory.mkdir(parents=True, exist_ok=True)
         t = self.starttime
         path = self.directory / f"{t.year}_{t.timetuple().tm_yday:03d}.scanmseed"
-        write_scanmseed(path, t, self.sampling_rate, self.series)
+        write_scanmseed(path, t, self.sampling_rate, self.series, engine=self.engine)
         if path not in self.files:
             self.files.append(path)
         self.written = True

@@ -143,8 +143,11 @@ class DeviceTrigger:
         # midnight belongs to the next day (trigger.py:343-347); the window read keeps the original batchend + pad
         if batchend.time() == _dt.time(0, 0):
             batchend = batchend - _dt.timedelta(microseconds=period_us)
-        coa = np.ascontiguousarray(columns["COA"][i_lo:i_hi + 1], dtype=np.float64)
-        coa_n = np.ascontiguousarray(columns["COA_N"][i_lo:i_hi + 1], dtype=np.float64)
+        if hasattr(columns["COA"], "data_ptr"):          # device-resident series (read_scanmseed, device=True)
+            coa, coa_n = columns["COA"][i_lo:i_hi + 1], columns["COA_N"][i_lo:i_hi + 1]
+        else:
+            coa = np.ascontiguousarray(columns["COA"][i_lo:i_hi + 1], dtype=np.float64)
+            coa_n = np.ascontiguousarray(columns["COA_N"][i_lo:i_hi + 1], dtype=np.float64)
         method, value, chunk, weights = self._engine_arguments(sampling_rate)
         out = engine.trigger_series(coa, coa_n, period_us * 1000, self._mw_us * 1000, self._mei_us * 1000,
                                     trigger_on=1 if self.normalise_coalescence else 0, method=method, value=value,
@@ -175,9 +178,11 @@ class DeviceTrigger:
         ``directory``: one batch per day between ``starttime`` and ``endtime``, the events of all of them in one
         list.  A batch's window -- the batch and its pads -- is clipped to its own day's file: the pads do not reach
         into the neighbouring days' files (what the reference effectively does for a run of a single day).  A day
-        without a file is logged and skipped.  ``engine``: the ``Engine`` to run on (default: the process's own,
-        ``core.lib.default_engine()``).
+        without a file is logged and skipped.  ``engine``: the ``Engine`` to run on; the day files are then decoded on
+        it as well and COA / COA_N go from the file to the trigger kernels without a host round trip (default: the
+        process's own engine, ``core.lib.default_engine()``, and the Python reader).
         """
+        resident = hasattr(engine, "scanmseed_decode")       # (an engine of the caller's that has the device codec)
         if engine is None:
             from quakemigrate_amd.core import lib
 
@@ -192,7 +197,9 @@ class DeviceTrigger:
             batchend = next_day if next_day <= endtime else endtime
             path = directory / f"{batchstart.year}_{batchstart.timetuple().tm_yday:03d}.scanmseed"
             if path.is_file():
-                t0, rate, columns = scanmseed.read_scanmseed(path, ucf)
+                # an engine of the caller's: the file is decoded on it and COA / COA_N stay there for the trigger
+                t0, rate, columns = (scanmseed.read_scanmseed(path, ucf, engine=engine, device=True) if resident
+                                     else scanmseed.read_scanmseed(path, ucf))
                 events += self.trigger_series(engine, t0, rate, columns, batchstart, batchend, region)
             else:
                 logging.info(f"\n\t    No .scanmseed file found for day {path.stem}!")
