@@ -12,7 +12,7 @@
 //            kernel holds no other LDS), else it is worked on in place in the engine's working copy: the same
 //            arithmetic in the same order.
 //   stage B  amp_window_kernel, ONE WAVEFRONT per window record: nothing crosses wavefronts, every reduction is a
-//            lane-strided sum closed by a fixed butterfly (wave_sum and its kin below) and the ordered compaction of
+//            lane-strided sum closed by a fixed butterfly (wave_sum and its kin, qm_block.hpp) and the ordered compaction of
 //            the extrema is a ballot and a prefix count per tile of 64 samples -- no atomics, the same bits in every
 //            run.  LDS holds the window (f64) and the two extremum lists (int32, at most n / 2 + 1 entries each):
 //            12 n + 8 bytes, n <= kAmpLdsSamples; a longer window has the same three arrays in its slice of scratch.
@@ -72,38 +72,6 @@ __device__ __forceinline__ void amp_filter_trace(const AmpArgs &a, const int64_t
 }
 
 // ---- stage B ----------------------------------------------------------------------------------------------------
-// max over i < n of f(i), the same in every lane
-template <typename F>
-__device__ __forceinline__ double wave_max(int n, F f) {
-    const int lane = threadIdx.x & 63;
-    double acc = -__builtin_inf();
-    for (int i = lane; i < n; i += 64) {
-        const double v = f(i);
-        acc = v > acc ? v : acc;
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const double o = __shfl_xor(acc, m, 64);
-        acc = o > acc ? o : acc;
-    }
-    return acc;
-}
-
-// smallest i < n with p(i), n where there is none
-template <typename P>
-__device__ __forceinline__ int wave_first(int n, P p) {
-    const int lane = threadIdx.x & 63;
-    int acc = n;
-    for (int i = lane; i < n; i += 64)
-        if (p(i) && i < acc) acc = i;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const int o = __shfl_xor(acc, m, 64);
-        acc = o < acc ? o : acc;
-    }
-    return acc;
-}
-
 // The local maxima of sign * y in SciPy's order into list[0..count), those below the prominence `need` left out
 // (need <= 0: nothing is computed); returns count.
 __device__ __forceinline__ int amp_extrema(const double *y, int n, double sign, double need, int32_t *list) {

@@ -3,9 +3,10 @@
 // computes it (sos_passes).  qm_preproc.hpp, qm_resample.hpp and qm_amplitudes.hpp call them on a trace that the whole
 // workgroup sees -- in LDS or in global memory: the address space is the call site's -- and keep what is theirs:
 // staging, records, upsampling, the window measurement.
-//   sums       every wavefront computes each sum for itself: lane l adds samples l, l + 64, ... in that order, a fixed
-//              butterfly adds the 64 partials.  All wavefronts get the same bits, the result does not depend on the
-//              run, and nothing has to cross wavefronts (the trace kernels have no LDS left for that).
+//   sums       every wavefront computes each sum for itself (qm_block.hpp: wave_sum): lane l adds samples l, l + 64, ...
+//              in that order, a fixed butterfly adds the 64 partials.  All wavefronts get the same bits, the result
+//              does not depend on the run, and nothing has to cross wavefronts (the trace kernels have no LDS left
+//              for that).
 //   detrend,   elementwise, all threads of the workgroup (256 in the trace kernels, 64 in amp_window_kernel)
 //   taper
 //   filter     the recurrence is the serial part.  A cascade of S second-order sections over T samples is
@@ -21,25 +22,11 @@
 // compiled with contraction allowed, so a function without it would gain FMAs and lose the pinned bits
 // (tests/preprocess_ref.py: detrend_device_order, sosfilt).
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "qm_block.hpp"
 
 namespace qm {
 
 constexpr int kPreprocMaxSections = 8;
-
-// sum over i < n of f(i), the same bits in every lane of the wavefront and in every run
-template <typename F>
-__device__ __forceinline__ double wave_sum(int n, F f) {
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x & 63;
-    double acc = 0.0;
-    for (int i = lane; i < n; i += 64) acc += f(i);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
-    return acc;
-}
 
 __device__ __forceinline__ double lane_below(double v) {       // lane l <- lane l - 1 within a row of 16
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x111, 0xf, 0xf, false);

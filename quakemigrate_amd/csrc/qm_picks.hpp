@@ -4,13 +4,13 @@
 // Gaussian fitted to that run.
 //
 // One workgroup of four wavefronts per onset row, one launch for all rows of a call.  LDS holds the row (f64), one
-// 64-bit key per sample and the reductions' slots -- 16 T + 768 bytes, all of it dynamic: T <= kPicksLdsSamples.
-//   noise set  key[t] = the bits of row[t] where t lies in no window of the row's group and row[t] > 1, all ones
-//              elsewhere.  Positive doubles order like their bit patterns, so
-//   medians    are selected on the keys bit by bit: the k-th smallest key is the largest v with #(key < v) <= k,
-//              built from the top bit down in 64 counting passes.  The selection is exact and ties do not matter;
-//              (a + b) / 2, |x - med|, 1.4826 mad, med + mad * multiplier follow in NumPy's order without
-//              contraction -- the threshold has NumPy's bits.
+// 64-bit key per sample, the reductions' slots and the median's histogram -- 16 T + 768 + 1040 bytes (picks_lds_bytes),
+// all of it dynamic: T <= kPicksLdsSamples.  The workgroup's sums, maxima and the median: qm_block.hpp.
+//   noise set  key[t] = order_key(row[t]) where t lies in no window of the row's group and row[t] > 1, all ones (no
+//              finite value's key) elsewhere.
+//   medians    block_median over the keys, then over order_key(|row[t] - med|) formed on the fly where key[t] is a
+//              value's: eight radix passes each, exact, ties and all.  (a + b) / 2, |x - med|, 1.4826 mad,
+//              med + mad * multiplier follow in NumPy's order without contraction -- the threshold has NumPy's bits.
 //   peak       three reductions over [lo, hi): the maximum, its first index, the nearest samples not above the
 //              threshold on either side of it.
 //   fit        Levenberg-Marquardt on the 3x3 normal equations, analytic Jacobian, More's scaling (D = running
@@ -19,13 +19,11 @@
 //              workgroup's 256 threads and added in a fixed order (lane butterfly, then wavefront 0..3): the same bits
 //              in every thread and every run.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "qm_block.hpp"
 
 namespace qm {
 
-constexpr int kPicksLdsSamples = 10112;         // 16 bytes per sample + 768 bytes of slots <= 160 KB
+constexpr int kPicksLdsSamples = 10112;         // 16 bytes per sample + slots + histogram <= 160 KB: 240 bytes to spare
 constexpr int kPicksThreads = 256;
 constexpr int kPicksSlots = 12;                 // values per reduction, at most
 constexpr int kPicksMaxIter = 200;
@@ -48,93 +46,14 @@ struct PickArgs {
     double rate, mad_multiplier;
 };
 
-inline size_t picks_lds_bytes(int T) {
-    return (size_t)T * 16 + (size_t)2 * 4 * kPicksSlots * 8;
-}
-
-// The workgroup's reductions: v[0..N) of every thread combined with `op` -- lanes by butterfly, then the four
-// wavefronts in order -- and handed back to every thread.  One barrier per call: the slots alternate between two
-// sets, and a set is written again only after the barrier of the call in between.
-struct PickReduce {
-    unsigned long long *slots;      // [2][4][kPicksSlots]
-    int phase;
-
-    template <typename T, int N, typename Op>
-    __device__ __forceinline__ void run(T (&v)[N], Op op) {
-        static_assert(sizeof(T) == 8 && N <= kPicksSlots, "64-bit values, at most kPicksSlots of them");
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        unsigned long long *set = slots + (phase & 1) * 4 * kPicksSlots;
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) v[k] = op(v[k], __shfl_xor(v[k], m, 64));
-            if (lane == 0) __builtin_memcpy(&set[wave * kPicksSlots + k], &v[k], 8);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            T w[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) __builtin_memcpy(&w[q], &set[q * kPicksSlots + k], 8);
-            v[k] = op(op(op(w[0], w[1]), w[2]), w[3]);
-        }
-        ++phase;
-    }
-};
-
-struct PickAdd {
-    __device__ __forceinline__ double operator()(double a, double b) const {
-#pragma clang fp contract(off)
-        return a + b;
-    }
-    __device__ __forceinline__ long long operator()(long long a, long long b) const { return a + b; }
-};
-struct PickMax {
-    __device__ __forceinline__ double operator()(double a, double b) const { return a > b ? a : b; }
-    __device__ __forceinline__ long long operator()(long long a, long long b) const { return a > b ? a : b; }
-};
-struct PickMin {
-    __device__ __forceinline__ long long operator()(long long a, long long b) const { return a < b ? a : b; }
-    __device__ __forceinline__ unsigned long long operator()(unsigned long long a, unsigned long long b) const {
-        return a < b ? a : b;
-    }
-};
-
+using PickReduce = BlockReduce<kPicksSlots, kPicksThreads / 64>;
 constexpr unsigned long long kPickNoKey = ~0ull;
 
-// k-th smallest (k from 0) of the keys that are not kPickNoKey; there are more than k of them
-__device__ __forceinline__ unsigned long long pick_select(const unsigned long long *key, int T, long long k,
-                                                          PickReduce &red) {
-    unsigned long long v = 0;
-    for (int bit = 63; bit >= 0; --bit) {
-        const unsigned long long cand = v | (1ull << bit);
-        long long c[1] = {0};
-        for (int t = threadIdx.x; t < T; t += kPicksThreads) c[0] += key[t] < cand ? 1 : 0;
-        red.run(c, PickAdd());
-        if (c[0] <= k) v = cand;
-    }
-    return v;
+// all of the workgroup's LDS (the kernel declares none of its own): row, keys, slots, histogram
+constexpr size_t picks_lds_bytes(int T) {
+    return (size_t)T * 16 + (size_t)PickReduce::kWords * 8 + sizeof(MedianLds);
 }
-
-// median of the n > 0 keys (as doubles): NumPy's mean of the two middle values for an even count
-__device__ __forceinline__ double pick_median(const unsigned long long *key, int T, long long n, PickReduce &red) {
-#pragma clang fp contract(off)
-    const unsigned long long hi = pick_select(key, T, n / 2, red);
-    if (n & 1) return __longlong_as_double((long long)hi);
-    // the element below it: the largest key under `hi`, or `hi` itself where the value repeats
-    long long below[1] = {0};
-    unsigned long long best = 0;
-    for (int t = threadIdx.x; t < T; t += kPicksThreads) {
-        const unsigned long long q = key[t];
-        below[0] += q < hi ? 1 : 0;
-        if (q < hi && q > best) best = q;
-    }
-    long long b[1] = {(long long)best};              // (keys of positive doubles: below 2^63)
-    red.run(below, PickAdd());
-    red.run(b, PickMax());
-    const unsigned long long lo = below[0] < n / 2 ? hi : (unsigned long long)b[0];
-    return (__longlong_as_double((long long)lo) + __longlong_as_double((long long)hi)) / 2.0;
-}
+static_assert(picks_lds_bytes(kPicksLdsSamples) <= 160 * 1024, "the longest row must fit a workgroup's 160 KB of LDS");
 
 __device__ __forceinline__ bool pick_solve3(const double (&s)[6], const double (&rhs)[3], double (&q)[3]) {
     // Cholesky of the symmetric s = [s00 s10 s11 s20 s21 s22]
@@ -166,7 +85,7 @@ __device__ __forceinline__ double pick_cost(const double *row, int f0, int f1, d
         const double r = p[0] * exp(-(d * d) / (2.0 * (p[2] * p[2]))) - row[k];
         f[0] += r * r;
     }
-    red.run(f, PickAdd());
+    red.run(f, BlockAdd());
     return f[0];
 }
 
@@ -176,7 +95,8 @@ __global__ __launch_bounds__(kPicksThreads) void pick_phases_kernel(PickArgs a) 
     const int T = a.T, row_id = blockIdx.x, tid = threadIdx.x;
     double *row = reinterpret_cast<double *>(pick_lds);
     unsigned long long *key = reinterpret_cast<unsigned long long *>(pick_lds) + T;
-    PickReduce red{key + T, 0};
+    PickReduce red{key + T, kPicksThreads / 64, 0};
+    MedianLds &hist = *reinterpret_cast<MedianLds *>(red.slots + PickReduce::kWords);
 
     const double *x = a.onsets + (int64_t)row_id * T;
     const int lo = a.windows[3 * row_id], hi = a.windows[3 * row_id + 2];
@@ -189,7 +109,7 @@ __global__ __launch_bounds__(kPicksThreads) void pick_phases_kernel(PickArgs a) 
         row[t] = v;
         bad[0] += isfinite(v) ? 0 : 1;
     }
-    red.run(bad, PickAdd());                            // (its barrier: the row is in LDS)
+    red.run(bad, BlockAdd());                            // (its barrier: the row is in LDS)
     double thr = __builtin_nan("");
     if (bad[0] > 0) {
         status = kPickNonFinite;
@@ -199,7 +119,7 @@ __global__ __launch_bounds__(kPicksThreads) void pick_phases_kernel(PickArgs a) 
 #pragma clang fp contract(off)
         for (int t = tid; t < T; t += kPicksThreads) {
             const double v = row[t];
-            key[t] = v > 1.0 ? (unsigned long long)__double_as_longlong(v) : kPickNoKey;
+            key[t] = v > 1.0 ? order_key(v) : kPickNoKey;
         }
         __syncthreads();
         const int group = a.row_group[row_id];
@@ -211,15 +131,16 @@ __global__ __launch_bounds__(kPicksThreads) void pick_phases_kernel(PickArgs a) 
         __syncthreads();
         long long n[1] = {0};
         for (int t = tid; t < T; t += kPicksThreads) n[0] += key[t] != kPickNoKey ? 1 : 0;
-        red.run(n, PickAdd());
+        red.run(n, BlockAdd());
         if (n[0] > 0) {
-            const double med = pick_median(key, T, n[0], red);
-            __syncthreads();                            // (every thread has read the keys it replaces)
-            for (int t = tid; t < T; t += kPicksThreads)
-                if (key[t] != kPickNoKey)
-                    key[t] = (unsigned long long)__double_as_longlong(fabs(row[t] - med));
-            __syncthreads();
-            const double mad = 1.4826 * pick_median(key, T, n[0], red);
+            const double med = block_median(T, (unsigned)n[0], [&](int t, unsigned long long &q) {
+                q = key[t];
+                return q != kPickNoKey;
+            }, hist, red);
+            const double mad = 1.4826 * block_median(T, (unsigned)n[0], [&](int t, unsigned long long &q) {
+                q = order_key(fabs(row[t] - med));
+                return key[t] != kPickNoKey;
+            }, hist, red);
             thr = med + mad * a.mad_multiplier;
         }
     }
@@ -230,14 +151,14 @@ __global__ __launch_bounds__(kPicksThreads) void pick_phases_kernel(PickArgs a) 
     if (status == kPicked) {
         double top[1] = {-__builtin_inf()};
         for (int t = lo + tid; t < hi; t += kPicksThreads) top[0] = row[t] > top[0] ? row[t] : top[0];
-        red.run(top, PickMax());
+        red.run(top, BlockMax());
         if (!(top[0] > thr)) {                          // (an empty window, a NaN threshold: nothing above it)
             status = kPickNothingAbove;
         } else {
             long long first[1] = {hi};
             for (int t = lo + tid; t < hi; t += kPicksThreads)
                 if (row[t] == top[0] && t < first[0]) first[0] = t;
-            red.run(first, PickMin());
+            red.run(first, BlockMin());
             const int imax = (int)first[0];
             long long left[1] = {lo - 1}, right[1] = {hi};      // nearest samples not above the threshold
             for (int t = lo + tid; t < hi; t += kPicksThreads) {
@@ -245,8 +166,8 @@ __global__ __launch_bounds__(kPicksThreads) void pick_phases_kernel(PickArgs a) 
                 if (t < imax && t > left[0]) left[0] = t;
                 if (t > imax && t < right[0]) right[0] = t;
             }
-            red.run(left, PickMax());
-            red.run(right, PickMin());
+            red.run(left, BlockMax());
+            red.run(right, BlockMin());
             const int run0 = (int)left[0] + 1, run1 = (int)right[0];
             if (run1 - run0 < 2) {
                 status = kPickOneSample;
@@ -265,11 +186,11 @@ __global__ __launch_bounds__(kPicksThreads) void pick_phases_kernel(PickArgs a) 
         // samples of padding do not exceed the threshold (or lie outside the window: then they may)
         double top[1] = {-__builtin_inf()};
         for (int k = f0 + tid; k < f1; k += kPicksThreads) top[0] = row[k] > top[0] ? row[k] : top[0];
-        red.run(top, PickMax());
+        red.run(top, BlockMax());
         long long first[1] = {f1};
         for (int k = f0 + tid; k < f1; k += kPicksThreads)
             if (row[k] == top[0] && k < first[0]) first[0] = k;
-        red.run(first, PickMin());
+        red.run(first, BlockMin());
         const double rate = a.rate;
         double p[3] = {top[0], (double)first[0] / rate, a.halfwidth[row_id] / rate};
         double dmax[3] = {0.0, 0.0, 0.0};
@@ -291,7 +212,7 @@ __global__ __launch_bounds__(kPicksThreads) void pick_phases_kernel(PickArgs a) 
                 s[3] += jc * ja; s[4] += jc * jb; s[5] += jc * jc;
                 s[6] += ja * r; s[7] += jb * r; s[8] += jc * r;
             }
-            red.run(s, PickAdd());
+            red.run(s, BlockAdd());
             const double n0 = sqrt(s[0]), n1 = sqrt(s[2]), n2 = sqrt(s[5]);
             dmax[0] = n0 > dmax[0] ? n0 : dmax[0];
             dmax[1] = n1 > dmax[1] ? n1 : dmax[1];

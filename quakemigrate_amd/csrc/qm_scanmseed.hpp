@@ -41,9 +41,7 @@
 //   kSmsComposeChunk  1024   tiles per LDS pass of the compose kernel ("scanmseed_compose_chunk")
 //   kSmsMaxSamples    2^28   longest channel taken (5 n positions are indexed in 32 bits by the side arrays' rows)
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "qm_block.hpp"
 
 namespace qm {
 
@@ -122,22 +120,6 @@ __host__ __device__ __forceinline__ int sms_slot_word(int s) { return (s / 15) *
 
 #ifdef QM_TU_SCANMSEED
 __device__ __forceinline__ uint32_t sms_bswap(uint32_t v) { return __builtin_bswap32(v); }
-
-// inclusive prefix sum over the workgroup's kSmsThreads threads; `wsum`: 4 values, free again after the call
-template <typename T>
-__device__ __forceinline__ T sms_scan256(T v, T *wsum) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    if (lane == 63) wsum[wave] = v;
-    __syncthreads();
-    for (int q = 0; q < wave; ++q) v += wsum[q];
-    __syncthreads();
-    return v;
-}
 
 // ---- encode ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kSmsThreads) void sms_quantise_kernel(SmsQuantArgs a) {
@@ -344,7 +326,7 @@ __global__ __launch_bounds__(kSmsThreads) void sms_decode_kernel(SmsDecodeArgs a
         else if (code != 0) invalid |= 1 << i;
         mine += cn[i];
     }
-    const int incl = sms_scan256(mine, wsum);
+    const int incl = block_scan(mine, wsum);
     int at = incl - mine;                                       // differences before this thread's words
     if (tid == kSmsThreads - 1) total = incl;
     // the Python stops reading at the n-th difference: an invalid pair behind it is not looked at
@@ -374,7 +356,7 @@ __global__ __launch_bounds__(kSmsThreads) void sms_decode_kernel(SmsDecodeArgs a
     const int lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
     long long sum = 0;
     for (int i = lo; i < hi; ++i) sum += i ? diffs[i] : 0;      // (difference 0 is not used: sample 0 is x0)
-    long long run = x0 + sms_scan256(sum, wsum64) - sum;
+    long long run = x0 + block_scan(sum, wsum64) - sum;
     const int64_t base = a.rec_out[rec];
     const double factor = a.rec_factor ? a.rec_factor[rec] : 1.0;
     for (int i = lo; i < hi; ++i) {

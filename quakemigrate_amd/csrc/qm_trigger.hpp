@@ -9,12 +9,10 @@
 //   trig_smooth_kernel   tiles of kTrigSmoothTile outputs with a 2r halo and the r + 1 weights in LDS, both series in
 //                        one launch (blockIdx.y); halo indices by the periodic reflect rule d c b a | a b c d | d c b a
 //                        (period 2n: also right for n <= r); SciPy's symmetric summation order, no contraction: its bits
-//   trig_stat_kernel     one workgroup per chunk: exact selection of the middle order statistic by eight radix passes
-//                        (8-bit digits, histogram in LDS) over order-preserving 64-bit keys of the samples' bit
-//                        patterns, the chunk re-read from global memory (L2) on every pass; an even count takes the
-//                        largest key below the selected one as well (or the same value where it repeats); the MAD
-//                        passes form |x - med| on the fly.  Equal keys are the normal case (.scanmseed data are
-//                        quantised to 1e-5): a wavefront whose samples all fall into one bin adds once
+//   trig_stat_kernel     one workgroup per chunk: block_median (qm_block.hpp: eight radix passes over order-preserving
+//                        64-bit keys of the samples' bit patterns) with the chunk re-read from global memory (L2) on
+//                        every pass; the MAD passes form |x - med| on the fly.  Equal keys are the normal case
+//                        (.scanmseed data are quantised to 1e-5)
 //   trig_count_kernel    flag[i] = trig[i] >= thr[i / chunk]; run starts (flag[i] and not flag[i - 1]) and ends (flag[i]
 //                        and not flag[i + 1]) counted per workgroup of kTrigRunBlock samples, with the non-finite
 //                        samples of the two input series
@@ -34,9 +32,7 @@
 //   kTrigMergeThreads    256   candidates per pass of the merge loop ("trigger_merge_stride")
 //   kTrigMaxSamples     2^30   longest series taken (indices are 32-bit inside the kernels)
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "qm_block.hpp"
 
 namespace qm {
 
@@ -96,41 +92,8 @@ struct TrigPeakArgs {
     int64_t period, mw, mei;
 };
 
-// ---- device helpers -------------------------------------------------------------------------------------------------
-// doubles of either sign order like these keys (-0.0 just below +0.0)
-__device__ __forceinline__ unsigned long long trig_key(double v) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-__device__ __forceinline__ double trig_unkey(unsigned long long k) {
-    const unsigned long long u = (k >> 63) ? (k ^ (1ull << 63)) : ~k;
-    return __longlong_as_double((long long)u);
-}
-
-// sums / maxima over the workgroup (at most 16 wavefronts), handed back to every thread: lanes by butterfly, then the
-// wavefronts in order.  `slots`: 16 values, free again after the call's second barrier
-struct TrigSum {
-    __device__ __forceinline__ unsigned long long operator()(unsigned long long a, unsigned long long b) const {
-        return a + b;
-    }
-};
-struct TrigMax {
-    __device__ __forceinline__ unsigned long long operator()(unsigned long long a, unsigned long long b) const {
-        return a > b ? a : b;
-    }
-};
-template <typename Op>
-__device__ __forceinline__ unsigned long long trig_reduce(unsigned long long v, unsigned long long *slots, Op op) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = (blockDim.x + 63) >> 6;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = op(v, (unsigned long long)__shfl_xor((long long)v, m, 64));
-    if (lane == 0) slots[wave] = v;
-    __syncthreads();
-    unsigned long long r = slots[0];
-    for (int q = 1; q < waves; ++q) r = op(r, slots[q]);
-    __syncthreads();
-    return r;
-}
+// ---- device helpers (the workgroup's sums, scans and the median: qm_block.hpp) --------------------------------------
+using TrigRunReduce = BlockReduce<3, kTrigRunThreads / 64>;    // the run kernels' sums: three counts at most
 
 __device__ __forceinline__ bool trig_flag(const TrigRunArgs &a, int i) {
     return a.trig[i] >= a.thr[(unsigned)i / (unsigned)a.chunk];
@@ -165,98 +128,25 @@ __global__ __launch_bounds__(kTrigSmoothThreads) void trig_smooth_kernel(TrigSmo
 }
 
 // ---- chunk statistics -----------------------------------------------------------------------------------------------
-struct TrigStatLds {
-    unsigned hist[256];
-    unsigned wsum[4];
-    unsigned sel[2];
-    unsigned long long slots[16];
-};
-
-// the median of v[t] = x[t] (kDev = false) or |x[t] - med| (kDev = true), t in [0, m): NumPy's mean of the two middle
-// values for an even count
-template <bool kDev>
-__device__ __forceinline__ double trig_median(const double *x, int m, double med, TrigStatLds &s) {
-#pragma clang fp contract(off)
-    const int tid = threadIdx.x, lane = tid & 63, threads = blockDim.x;
-    auto key_at = [&](int t) { return trig_key(kDev ? fabs(x[t] - med) : x[t]); };
-    unsigned long long prefix = 0;
-    unsigned k = (unsigned)m / 2;                               // (from 0) among the keys that match the prefix
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        if (tid < 256) s.hist[tid] = 0;
-        __syncthreads();
-        const unsigned long long himask = shift == 56 ? 0ull : ~0ull << (shift + 8);
-        for (int t0 = 0; t0 < m; t0 += threads) {               // (the same trips for every thread: the ballots)
-            const int t = t0 + tid;
-            bool act = t < m;
-            unsigned bin = 0;
-            if (act) {
-                const unsigned long long q = key_at(t);
-                act = (q & himask) == prefix;
-                bin = (unsigned)(q >> shift) & 255u;
-            }
-            const unsigned long long mask = __ballot(act);
-            if (mask) {
-                const int leader = __builtin_ctzll(mask);
-                const unsigned b0 = (unsigned)__shfl((int)bin, leader, 64);
-                if (__all(!act || bin == b0)) {
-                    if (lane == leader) atomicAdd(&s.hist[b0], (unsigned)__popcll(mask));
-                } else if (act) {
-                    atomicAdd(&s.hist[bin], 1u);
-                }
-            }
-        }
-        __syncthreads();
-        // the bin that holds the k-th key: exclusive prefix <= k < inclusive prefix
-        unsigned c = 0, incl = 0;
-        if (tid < 256) {
-            c = incl = s.hist[tid];
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const unsigned o = (unsigned)__shfl_up((int)incl, d, 64);
-                if (lane >= d) incl += o;
-            }
-            if (lane == 63) s.wsum[tid >> 6] = incl;
-        }
-        __syncthreads();
-        if (tid < 256) {
-            for (int q = 0; q < (tid >> 6); ++q) incl += s.wsum[q];
-            const unsigned excl = incl - c;
-            if (excl <= k && k < incl) {
-                s.sel[0] = (unsigned)tid;
-                s.sel[1] = excl;
-            }
-        }
-        __syncthreads();
-        prefix |= (unsigned long long)s.sel[0] << shift;
-        k -= s.sel[1];
-    }
-    const unsigned long long hi = prefix;
-    if (m & 1) return trig_unkey(hi);
-    // the element below it: the largest key under `hi`, or `hi` itself where the value repeats
-    unsigned long long below = 0, best = 0;
-    for (int t = tid; t < m; t += threads) {
-        const unsigned long long q = key_at(t);
-        if (q < hi) {
-            ++below;
-            best = q > best ? q : best;
-        }
-    }
-    below = trig_reduce(below, s.slots, TrigSum());
-    best = trig_reduce(best, s.slots, TrigMax());
-    const unsigned long long lo = below < (unsigned long long)(m / 2) ? hi : best;
-    return (trig_unkey(lo) + trig_unkey(hi)) / 2.0;
-}
-
 __global__ __launch_bounds__(kTrigStatThreads) void trig_stat_kernel(TrigStatArgs a) {
 #pragma clang fp contract(off)
-    __shared__ TrigStatLds s;
+    using Reduce = BlockReduce<1, kTrigStatThreads / 64>;
+    __shared__ MedianLds s;
+    __shared__ unsigned long long slots[Reduce::kWords];
+    Reduce red{slots, (int)(blockDim.x >> 6), 0};
     const int64_t c0 = (int64_t)blockIdx.x * a.chunk;
     const int m = (int)(a.n - c0 < a.chunk ? a.n - c0 : a.chunk);
     const double *x = a.trig + c0;
-    const double med = trig_median<false>(x, m, 0.0, s);
+    const double med = block_median(m, (unsigned)m, [&](int t, unsigned long long &q) {
+        q = order_key(x[t]);
+        return true;
+    }, s, red);
     double thr;
     if (a.method == 1) {
-        const double mad = 1.4826 * trig_median<true>(x, m, med, s);
+        const double mad = 1.4826 * block_median(m, (unsigned)m, [&](int t, unsigned long long &q) {
+            q = order_key(fabs(x[t] - med));
+            return true;
+        }, s, red);
         thr = med + mad * a.value;
     } else {
         thr = med * a.value;
@@ -284,77 +174,61 @@ __device__ __forceinline__ void trig_edges(const TrigRunArgs &a, int i0, unsigne
 }
 
 __global__ __launch_bounds__(kTrigRunThreads) void trig_count_kernel(TrigRunArgs a) {
-    __shared__ unsigned long long slots[16];
+    __shared__ unsigned long long slots[TrigRunReduce::kWords];
+    TrigRunReduce red{slots, kTrigRunThreads / 64, 0};
     const int i0 = blockIdx.x * kTrigRunBlock + threadIdx.x * kTrigRunItems;
     unsigned starts, ends;
     trig_edges(a, i0, starts, ends);
-    unsigned long long bad = 0;
+    unsigned long long c[3] = {(unsigned long long)__popc(starts), (unsigned long long)__popc(ends), 0ull};
     for (int j = 0; j < kTrigRunItems; ++j) {
         const int i = i0 + j;
-        if (i < a.n) bad += (isfinite(a.raw[i]) ? 0 : 1) + (isfinite(a.raw[(int64_t)a.n + i]) ? 0 : 1);
+        if (i < a.n) c[2] += (isfinite(a.raw[i]) ? 0 : 1) + (isfinite(a.raw[(int64_t)a.n + i]) ? 0 : 1);
     }
-    const unsigned long long ns = trig_reduce((unsigned long long)__popc(starts), slots, TrigSum());
-    const unsigned long long ne = trig_reduce((unsigned long long)__popc(ends), slots, TrigSum());
-    bad = trig_reduce(bad, slots, TrigSum());
-    if (threadIdx.x == 0) {
-        a.counts[blockIdx.x] = (int32_t)ns;
-        a.counts[a.nblocks + blockIdx.x] = (int32_t)ne;
-        a.counts[2 * a.nblocks + blockIdx.x] = (int32_t)bad;
-    }
-}
-
-// inclusive prefix sum over the workgroup's kTrigRunThreads threads (four wavefronts); `wsum`: 4 values, free again
-// after the call
-__device__ __forceinline__ unsigned trig_scan256(unsigned v, unsigned *wsum) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned o = (unsigned)__shfl_up((int)v, d, 64);
-        if (lane >= d) v += o;
-    }
-    if (lane == 63) wsum[wave] = v;
-    __syncthreads();
-    for (int q = 0; q < wave; ++q) v += wsum[q];
-    __syncthreads();
-    return v;
+    red.run(c, BlockAdd());
+    if (threadIdx.x == 0)
+        for (int k = 0; k < 3; ++k) a.counts[k * a.nblocks + blockIdx.x] = (int32_t)c[k];
 }
 
 __global__ __launch_bounds__(kTrigRunThreads) void trig_scan_kernel(TrigRunArgs a) {
-    __shared__ unsigned wsum[4];
-    __shared__ unsigned long long slots[16];
+    __shared__ unsigned wsum[kTrigRunThreads / 64];
+    __shared__ unsigned long long slots[TrigRunReduce::kWords];
+    TrigRunReduce red{slots, kTrigRunThreads / 64, 0};
     unsigned carry_s = 0, carry_e = 0;
-    unsigned long long bad = 0;
+    unsigned long long bad[1] = {0};
     for (int b0 = 0; b0 < a.nblocks; b0 += kTrigRunThreads) {
         const int b = b0 + threadIdx.x;
         const unsigned cs = b < a.nblocks ? (unsigned)a.counts[b] : 0u;
         const unsigned ce = b < a.nblocks ? (unsigned)a.counts[a.nblocks + b] : 0u;
-        bad += b < a.nblocks ? (unsigned long long)a.counts[2 * a.nblocks + b] : 0ull;
-        const unsigned is = trig_scan256(cs, wsum), ie = trig_scan256(ce, wsum);
+        bad[0] += b < a.nblocks ? (unsigned long long)a.counts[2 * a.nblocks + b] : 0ull;
+        const unsigned is = block_scan(cs, wsum), ie = block_scan(ce, wsum);
         if (b < a.nblocks) {
             a.offsets[b] = (int32_t)(carry_s + is - cs);
             a.offsets[a.nblocks + b] = (int32_t)(carry_e + ie - ce);
         }
         // the tile's totals: the last thread's inclusive sums
-        carry_s += (unsigned)trig_reduce(threadIdx.x == kTrigRunThreads - 1 ? is : 0u, slots, TrigSum());
-        carry_e += (unsigned)trig_reduce(threadIdx.x == kTrigRunThreads - 1 ? ie : 0u, slots, TrigSum());
+        const bool last = threadIdx.x == kTrigRunThreads - 1;
+        unsigned long long total[2] = {last ? is : 0u, last ? ie : 0u};
+        red.run(total, BlockAdd());
+        carry_s += (unsigned)total[0];
+        carry_e += (unsigned)total[1];
     }
-    bad = trig_reduce(bad, slots, TrigSum());
+    red.run(bad, BlockAdd());
     if (threadIdx.x == 0) {
         a.totals[0] = carry_s;
         a.totals[1] = carry_e;
-        a.totals[2] = (int64_t)bad;
+        a.totals[2] = (int64_t)bad[0];
         a.totals[3] = 0;
     }
 }
 
 __global__ __launch_bounds__(kTrigRunThreads) void trig_compact_kernel(TrigRunArgs a) {
-    __shared__ unsigned wsum[4];
+    __shared__ unsigned wsum[kTrigRunThreads / 64];
     const int i0 = blockIdx.x * kTrigRunBlock + threadIdx.x * kTrigRunItems;
     unsigned starts, ends;
     trig_edges(a, i0, starts, ends);
     const unsigned cs = __popc(starts), ce = __popc(ends);
-    unsigned ps = a.offsets[blockIdx.x] + trig_scan256(cs, wsum) - cs;
-    unsigned pe = a.offsets[a.nblocks + blockIdx.x] + trig_scan256(ce, wsum) - ce;
+    unsigned ps = a.offsets[blockIdx.x] + block_scan(cs, wsum) - cs;
+    unsigned pe = a.offsets[a.nblocks + blockIdx.x] + block_scan(ce, wsum) - ce;
 #pragma unroll
     for (int j = 0; j < kTrigRunItems; ++j) {
         if (starts & (1u << j)) a.first[ps++] = i0 + j;
@@ -417,20 +291,17 @@ __device__ __forceinline__ TrigSeg trig_join(const TrigSeg &a, const TrigSeg &b)
     r.cnt = a.cnt + b.cnt;
     return r;
 }
-__device__ __forceinline__ TrigSeg trig_seg_up(const TrigSeg &v, int d) {
-    TrigSeg o;
-    o.ev = __shfl_up(v.ev, d, 64);
-    o.cnt = __shfl_up(v.cnt, d, 64);
-    o.val = __shfl_up(v.val, d, 64);
-    o.p = __shfl_up(v.p, d, 64);
-    o.mn = __shfl_up(v.mn, d, 64);
-    o.mx = __shfl_up(v.mx, d, 64);
-    return o;
+struct TrigJoin {
+    __device__ __forceinline__ TrigSeg operator()(const TrigSeg &a, const TrigSeg &b) const { return trig_join(a, b); }
+};
+__device__ __forceinline__ TrigSeg lane_up(const TrigSeg &v, int d) {      // (wave_scan's shuffle, per member)
+    return TrigSeg{lane_up(v.ev, d), lane_up(v.cnt, d), lane_up(v.val, d), lane_up(v.p, d), lane_up(v.mn, d),
+                   lane_up(v.mx, d)};
 }
 
 __global__ __launch_bounds__(kTrigMergeThreads) void trig_merge_kernel(TrigPeakArgs a) {
-    __shared__ unsigned wsum[4];
-    __shared__ TrigSeg wseg[4];
+    __shared__ unsigned wsum[kTrigMergeThreads / 64];
+    __shared__ TrigSeg wseg[kTrigMergeThreads / 64];
     __shared__ TrigSeg carry_slot;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     auto peak_time = [&](int k) { return a.cand[(int64_t)k * kTrigCandColumns + 2] * a.period; };
@@ -446,7 +317,7 @@ __global__ __launch_bounds__(kTrigMergeThreads) void trig_merge_kernel(TrigPeakA
         const unsigned sep = valid && k > 0 && separate(k) ? 1u : 0u;
         const bool ends = valid && (k == a.nc - 1 || separate(k + 1));
         TrigSeg v{};
-        v.ev = (k0 > 0 ? carry.ev : 0) + (int)trig_scan256(sep, wsum);
+        v.ev = (k0 > 0 ? carry.ev : 0) + (int)block_scan(sep, wsum);
         if (valid) {
             const int64_t *c = a.cand + (int64_t)k * kTrigCandColumns;
             v.cnt = 1;
@@ -457,11 +328,7 @@ __global__ __launch_bounds__(kTrigMergeThreads) void trig_merge_kernel(TrigPeakA
         } else {
             v.ev = 0x7fffffff;
         }
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const TrigSeg o = trig_seg_up(v, d);
-            if (lane >= d) v = trig_join(o, v);
-        }
+        v = wave_scan(v, TrigJoin());
         if (lane == 63) wseg[wave] = v;
         __syncthreads();
         TrigSeg acc = carry;

@@ -386,3 +386,47 @@ def designed_rows(t_samples=700, sampling_rate=50.0):
                 row_group=np.array([r["group"] for r in rows], dtype=np.int32),
                 halfwidth=np.array([r["halfwidth"] for r in rows]), sampling_rate=float(sampling_rate),
                 names=[r["name"] for r in rows], expected=np.array([r["expected"] for r in rows], dtype=np.int32))
+
+
+# -- noise sets at the median's edges ------------------------------------------------------------------------------
+NOISE_SIZES = (0, 1, 2, 3, 4, 255, 256, 257)
+NOISE_KINDS = ("distinct", "all equal", "two middle values equal", "middle value across the even split",
+               "last bit apart")
+
+
+def noise_values(n, kind, rng):
+    """``n`` values above 1, in sorted order, of one of ``NOISE_KINDS``."""
+    v = np.sort(1.0 + 0.25 * (1 + np.arange(n)) / (n + 1) + 1e-3 * rng.random(n))
+    if kind == "all equal":
+        v[:] = 1.75
+    elif kind == "two middle values equal" and n > 1:
+        v[n // 2 - 1] = v[n // 2]
+    elif kind == "middle value across the even split" and n > 1:
+        v[n // 4:n - n // 4] = v[n // 2]
+    elif kind == "last bit apart":
+        v = 1.5 + np.arange(n) * np.spacing(1.5)
+    return v
+
+
+def noise_set_rows(t_samples=331, window=(40, 70, 100), sampling_rate=50.0, seed=5):
+    """
+    One row per (size, kind) of ``NOISE_SIZES`` x ``NOISE_KINDS``, each a station of its own: the noise set -- the
+    samples above 1 outside the row's window -- has that size and those values at shuffled places, every other sample
+    is 0.5 (nothing in the window exceeds any threshold: status 1 throughout).  Returns a dict like ``family`` plus
+    ``names`` and ``noise`` (each row's values, sorted).
+    """
+    rng = np.random.default_rng(seed)
+    outside = np.concatenate([np.arange(window[0]), np.arange(window[2], t_samples)])
+    names, noise, rows = [], [], []
+    for n in NOISE_SIZES:
+        for kind in NOISE_KINDS:
+            y = np.full(t_samples, 0.5)
+            v = noise_values(n, kind, rng)
+            y[rng.permutation(outside)[:n]] = rng.permutation(v)
+            names.append(f"{n} {kind}")
+            noise.append(v)
+            rows.append(y)
+    n_rows = len(rows)
+    return dict(onsets=np.ascontiguousarray(np.stack(rows)),
+                windows=np.tile(np.array(window, dtype=np.int32), (n_rows, 1)), row_group=np.arange(n_rows, dtype=np.int32), halfwidth=np.full(n_rows, 5.0),
+                sampling_rate=float(sampling_rate), names=names, noise=noise)

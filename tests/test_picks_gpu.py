@@ -160,6 +160,22 @@ def test_designed_rows(engine, designed):
     assert max(dist.values()) <= RTOL, dist
 
 
+def test_small_and_tied_noise_sets_have_numpys_threshold_bits(engine):
+    """The median's selection at its edges (tests/picks_ref.py: noise_set_rows): noise sets of 0, 1, 2, 3, 4, 255, 256
+    and 257 samples -- one pass of the workgroup's 256 threads, and one sample past it -- of distinct values, equal
+    values, equal middle values, a middle value that repeats across the even split, and neighbouring bit patterns.
+    tests/test_picks_host.py pins the restatement on these rows to the formula on sorted values."""
+    d = pr.noise_set_rows()
+    want_picks, want_status = pr.pick_rows(d["onsets"], d["windows"], d["row_group"], d["sampling_rate"],
+                                           d["halfwidth"])
+    assert 64 <= d["onsets"].shape[1] <= 600 and len(d["names"]) == 40
+    got = call(engine, d)
+    assert_discrete(got, want_picks, want_status, d["names"])
+    empty = np.array([name.startswith("0 ") for name in d["names"]])
+    assert np.all(np.isnan(got[0][empty, 0])) and np.all(np.isfinite(got[0][~empty, 0]))
+    assert np.all(got[1] == 1)
+
+
 # -- 5. modes and layouts ------------------------------------------------------------------------------------------
 def test_given_thresholds_equal_the_mad_mode(engine, fam, fam_gpu):
     got = call(engine, fam, threshold_mode=1, thresholds=fam_gpu[0][:, 0].copy())

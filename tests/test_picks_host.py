@@ -51,6 +51,41 @@ def test_threshold_is_the_sorted_middle_formula(fam):
         assert 20 < np.count_nonzero(~keep) and noise.size < keep.sum()        # (windows and pads both bite)
 
 
+def test_noise_set_rows_have_the_thresholds_written_out_on_sorted_values():
+    """tests/picks_ref.py: noise_set_rows -- every size and kind of noise set is what its name says, and the
+    restatement's threshold has the bits of the sorted-middle formula on the values the row was built from."""
+    d = pr.noise_set_rows()
+    picks, status = pr.pick_rows(d["onsets"], d["windows"], d["row_group"], d["sampling_rate"], d["halfwidth"])
+    assert len(d["names"]) == len(pr.NOISE_SIZES) * len(pr.NOISE_KINDS) and np.all(status == pr.NOTHING_ABOVE)
+
+    def middle(v):                                      # (sorted)
+        n = len(v)
+        return v[n // 2] if n % 2 else (v[n // 2 - 1] + v[n // 2]) / 2
+
+    for r, (name, v) in enumerate(zip(d["names"], d["noise"])):
+        n, kind = len(v), name.partition(" ")[2]
+        lo, hi = d["windows"][r, 0], d["windows"][r, 2]
+        assert np.all(d["onsets"][r, lo:hi] == 0.5)
+        assert np.array_equal(np.sort(d["onsets"][r][d["onsets"][r] > 1]), v) and name.startswith(f"{n} "), name
+        assert np.all((d["onsets"][r] == 0.5) | (d["onsets"][r] > 1))
+        if n == 0:
+            assert np.isnan(picks[r, 0]), name
+            continue
+        med = middle(v)
+        want = med + (1.4826 * middle(np.sort(np.abs(v - med)))) * 8.0
+        assert want == picks[r, 0] and want > 1, name
+        if kind == "distinct" or kind == "last bit apart":
+            assert len(np.unique(v)) == n
+        if kind == "all equal":
+            assert len(np.unique(v)) == 1 and want == v[0]
+        if kind == "two middle values equal" and n > 1:
+            assert v[n // 2 - 1] == v[n // 2] and (n < 4 or len(np.unique(v)) == n - 1)
+        if kind == "middle value across the even split" and n > 1:
+            assert np.count_nonzero(v == v[n // 2]) == n - 2 * (n // 4) and med == v[n // 2]
+        if kind == "last bit apart":
+            assert np.all(np.diff(v.view(np.uint64)) == 1)
+
+
 def test_peak_is_the_run_around_the_first_maximum(fam):
     for r in range(len(fam["status"])):
         lo, hi = fam["windows"][r, 0], fam["windows"][r, 2]
