@@ -1,6 +1,6 @@
 // qm_amplitudes.hip -- the amplitude stage's host side: argument checks, staging, the two launches (kernels and their
 // notes: qm_amplitudes.hpp).  Records, filters, tapers and outputs are host arrays; the packed traces are the caller's,
-// on the host or on the device.  The engine works on a copy of them (d_amp_work) whenever a trace is filtered or the
+// on the host or on the device.  The engine works on a copy of them (amps.work) whenever a trace is filtered or the
 // traces come from the host; device traces without any filter are read where they are.
 #define QM_TU_AMPLITUDES 1
 #include "qm_engine.hpp"
@@ -106,41 +106,39 @@ int qm_engine_measure_amplitudes(qm_engine *e, const double *traces, int traces_
     if (n_taper_weights) coef.insert(coef.end(), taper_weights, taper_weights + n_taper_weights);
     const size_t nw = (size_t)n_windows;
     const bool copy = any_filter || !traces_on_device;
-    if (e->d_amp_meta.ensure(meta.size()) || e->d_amp_coef.ensure(std::max<size_t>(coef.size(), 1)) ||
-        e->d_amp_val.ensure(nw * kAmpColumns) || e->d_amp_idx.ensure(nw * 4))
+    if (e->amps.meta.ensure(meta.size()) || e->amps.coef.ensure(std::max<size_t>(coef.size(), 1)) ||
+        e->amps.val.ensure(nw * kAmpColumns) || e->amps.idx.ensure(nw * 4))
         return 1;
-    if (copy && e->d_amp_work.ensure((size_t)total_samples)) return 1;
-    if (scratch_doubles && e->d_amp_scratch.ensure((size_t)scratch_doubles)) return 1;
-    QM_HIP(copy_in(e->d_amp_meta.p, meta.data(), meta.size() * sizeof(int64_t), e->stream));
-    if (!coef.empty()) QM_HIP(copy_in(e->d_amp_coef.p, coef.data(), coef.size() * sizeof(double), e->stream));
+    if (copy && e->amps.work.ensure((size_t)total_samples)) return 1;
+    if (scratch_doubles && e->amps.scratch.ensure((size_t)scratch_doubles)) return 1;
+    QM_HIP(copy_in(e->amps.meta.p, meta.data(), meta.size() * sizeof(int64_t), e->stream));
+    if (!coef.empty()) QM_HIP(copy_in(e->amps.coef.p, coef.data(), coef.size() * sizeof(double), e->stream));
     if (copy) {
         if (traces_on_device)
-            QM_HIP(hipMemcpyAsync(e->d_amp_work.p, traces, (size_t)total_samples * sizeof(double),
+            QM_HIP(hipMemcpyAsync(e->amps.work.p, traces, (size_t)total_samples * sizeof(double),
                                   hipMemcpyDeviceToDevice, e->stream));
         else
-            QM_HIP(copy_in(e->d_amp_work.p, traces, (size_t)total_samples * sizeof(double), e->stream));
+            QM_HIP(copy_in(e->amps.work.p, traces, (size_t)total_samples * sizeof(double), e->stream));
     }
     AmpArgs a{};
-    a.work = copy ? e->d_amp_work.p : const_cast<double *>(traces);     // (read only where nothing is filtered)
-    a.traces = e->d_amp_meta.p;
-    a.tapers = e->d_amp_meta.p + n_trec;
-    a.windows = e->d_amp_meta.p + n_wrec0;
-    a.sos = e->d_amp_coef.p;
-    a.taper_w = e->d_amp_coef.p + n_coef;
-    a.scratch = e->d_amp_scratch.p;
-    a.values = e->d_amp_val.p;
-    a.index = e->d_amp_idx.p;
+    a.work = copy ? e->amps.work.p : const_cast<double *>(traces);     // (read only where nothing is filtered)
+    a.traces = e->amps.meta.p;
+    a.tapers = e->amps.meta.p + n_trec;
+    a.windows = e->amps.meta.p + n_wrec0;
+    a.sos = e->amps.coef.p;
+    a.taper_w = e->amps.coef.p + n_coef;
+    a.scratch = e->amps.scratch.p;
+    a.values = e->amps.val.p;
+    a.index = e->amps.idx.p;
     a.n_sections = n_sections; a.skew = e->cfg.preproc_skew;
     a.detrend_windows = detrend_windows; a.method = average_method; a.multiplier = prominence_multiplier;
-    QM_HIP(hipEventRecord(e->ev0, e->stream));
-    if (any_filter) {
-        const size_t lds = (size_t)std::min<int64_t>(longest_filtered, kPreprocLdsSamples) * sizeof(double);
-        if (launch_with_lds(e, amp_filter_kernel, (unsigned)n_traces, 256, lds, a)) return 1;
-    }
-    if (launch_with_lds(e, amp_window_kernel, (unsigned)n_windows, kAmpWindowThreads, amp_lds_bytes(longest_lds), a))
+    if (timed_launches(e, [&]() -> int {
+            const size_t lds = (size_t)std::min<int64_t>(longest_filtered, kPreprocLdsSamples) * sizeof(double);
+            if (any_filter && launch_with_lds(e, amp_filter_kernel, (unsigned)n_traces, 256, lds, a)) return 1;
+            return launch_with_lds(e, amp_window_kernel, (unsigned)n_windows, kAmpWindowThreads,
+                                   amp_lds_bytes(longest_lds), a);
+        }))
         return 1;
-    QM_HIP(hipEventRecord(e->ev1, e->stream));
-    e->timed = true;
     QM_HIP(copy_back(values, a.values, nw * kAmpColumns * sizeof(double), e->stream));
     QM_HIP(copy_back(index, a.index, nw * 4 * sizeof(int32_t), e->stream));
     if (filtered_out) QM_HIP(copy_back(filtered_out, a.work, (size_t)total_samples * sizeof(double), e->stream));

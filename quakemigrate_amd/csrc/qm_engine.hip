@@ -513,8 +513,8 @@ int combine(qm_engine *e, const SetView &in, CombineMode mode, int64_t node_offs
     // (tie_rule = 1 with a row of maxima per brick: the fold of the workgroups' own sets also leaves the largest z)
     double *o_z = nullptr;
     if (e->cfg.tie_rule && e->last.brick_rows > 0 && in.max == e->d_pmax.p && run_if == nullptr) {
-        if (e->d_tie_zext.ensure(in.n)) return 1;
-        o_z = e->d_tie_zext.p;
+        if (e->tie.zext.ensure(in.n)) return 1;
+        o_z = e->tie.zext.p;
     }
     hipLaunchKernelGGL(qm::combine_kernel, dim3((in.n + qm::kWave - 1) / qm::kWave),
                        dim3(qm::kCombineWaves * qm::kWave), 0,
@@ -566,7 +566,7 @@ int detect_core(qm_engine *e, const double *d_on, int T, int fsmp, int ns, int a
     StackLaunch s(d_on, T, fsmp, ns, available);
     if (screened) {
         if (combine(e, engine_sets(e, sets, ns), mode, e->node_offset, n_nodes_total, out, nullptr)) return 1;
-        s.run_if = e->d_flags.p;
+        s.run_if = e->sweep.flags.p;
     }
     if (stack_fold(e, s, mode, n_nodes_total, out).rc) return 1;
     // (d_pmax holds the float64 launch's sets for certain -- and they are those of a detect_partial, the only call
@@ -611,30 +611,30 @@ int refine_ties(qm_engine *e, const StackLaunch &launch, int64_t *o_idx, const d
     if (n > INT32_MAX / (2 * qm::kTieMaxSets)) return fail("tie_rule: %d samples in one launch are too many", n);
     const int max_pairs = qm::kTieMaxSets * n;
     const int max_cands = 4 * n + 65536;
-    if (e->d_tie_z.ensure(n) || e->d_tie_pairs.ensure(2 * (size_t)max_pairs) || e->d_tie_imin.ensure(n) ||
-        e->d_tie_count.ensure(4) || e->d_tie_emax.ensure(n) || e->d_tie_cands.ensure(2 * (size_t)max_cands) ||
-        e->d_tie_keys.ensure(max_cands))
+    if (e->tie.z.ensure(n) || e->tie.pairs.ensure(2 * (size_t)max_pairs) || e->tie.imin.ensure(n) ||
+        e->tie.count.ensure(4) || e->tie.emax.ensure(n) || e->tie.cands.ensure(2 * (size_t)max_cands) ||
+        e->tie.keys.ensure(max_cands))
         return 1;
     hipStream_t s = e->stream;
-    QM_HIP(hipMemsetAsync(e->d_tie_count.p, 0, 4 * sizeof(int32_t), s));
-    int2 *pairs = reinterpret_cast<int2 *>(e->d_tie_pairs.p);
+    QM_HIP(hipMemsetAsync(e->tie.count.p, 0, 4 * sizeof(int32_t), s));
+    int2 *pairs = reinterpret_cast<int2 *>(e->tie.pairs.p);
     // (brick maxima: the sample's largest z is already in the workgroups' few partial sets; the per-brick rows are
     // read once, for the candidates)
     // (... and the sample's largest z came out of the combine that preceded this call)
     const int rows = e->last.brick_rows;
-    if (rows > 0 && !zext) zext = e->d_tie_zext.p;
+    if (rows > 0 && !zext) zext = e->tie.zext.p;
     hipLaunchKernelGGL(qm::tie_pairs_kernel, dim3((n + 63) / 64), dim3(64, qm::kTieSetLanes), 0, s,
                        rows > 0 ? (const double *)e->d_bmax.p : (const double *)e->d_pmax.p, rows > 0 ? rows : sets,
                        (const double *)e->d_pmax.p + (int64_t)e->last.groups_lds * n,
-                       rows > 0 ? e->last.groups_direct : 0, n, (int64_t)n, e->d_tie_z.p, pairs,
-                       e->d_tie_count.p, max_pairs, e->d_tie_emax.p, e->d_tie_imin.p, e->d_tie_count.p + 1, zext);
+                       rows > 0 ? e->last.groups_direct : 0, n, (int64_t)n, e->tie.z.p, pairs,
+                       e->tie.count.p, max_pairs, e->tie.emax.p, e->tie.imin.p, e->tie.count.p + 1, zext);
     QM_HIP(hipGetLastError());
     // How many pairs there are is known on the device only, and nobody waits for it: the evaluation is
     // launched for what a generic step has (one pair per sample) with room to spare; workgroups beyond the
     // list return at once, a longer list is covered by the grid's stride.  The
     // counters travel to the host when somebody asks (qm_engine_get "tie_pairs", "tie_overflow_samples").
-    ++e->tie_refined_steps;
-    e->tie_counts_pending = true;
+    ++e->tie.refined_steps;
+    e->tie.counts_pending = true;
     qm::TieArgs a{};
     a.g = e->last.g;
     a.onsets = launch.onsets;
@@ -652,14 +652,14 @@ int refine_ties(qm_engine *e, const StackLaunch &launch, int64_t *o_idx, const d
     // workgroups per pair: ~2048 nodes each
     const int64_t per_set = (int64_t)e->n_nodes / std::max(1, e->last.groups_lds + e->last.groups_direct);
     a.chunks = rows > 0 ? 1 : (int)std::max<int64_t>(1, std::min<int64_t>(64, per_set / 2048));   // (rows: a brick)
-    a.zbest = e->d_tie_z.p;
+    a.zbest = e->tie.z.p;
     a.pairs = pairs;
-    a.n_pairs = e->d_tie_count.p;
-    a.emax = e->d_tie_emax.p;
-    a.imin = e->d_tie_imin.p;
-    a.cands = reinterpret_cast<int2 *>(e->d_tie_cands.p);
-    a.cand_keys = e->d_tie_keys.p;
-    a.n_cands = e->d_tie_count.p + 2;
+    a.n_pairs = e->tie.count.p;
+    a.emax = e->tie.emax.p;
+    a.imin = e->tie.imin.p;
+    a.cands = reinterpret_cast<int2 *>(e->tie.cands.p);
+    a.cand_keys = e->tie.keys.p;
+    a.n_cands = e->tie.count.p + 2;
     a.max_cands = max_cands;
     const unsigned grid = (unsigned)((int64_t)(n + 1024) * a.chunks);
     hipLaunchKernelGGL(qm::tie_eval_kernel<0>, dim3(grid), dim3(256), 0, s, a);
@@ -667,11 +667,11 @@ int refine_ties(qm_engine *e, const StackLaunch &launch, int64_t *o_idx, const d
     hipLaunchKernelGGL(qm::tie_eval_kernel<1>, dim3(grid), dim3(256), 0, s, a);   // (returns at once unless the list overflowed)
     if (o_key)
         hipLaunchKernelGGL(qm::tie_export_kernel, dim3((n + 255) / 256), dim3(256), 0, s,
-                           (const unsigned long long *)e->d_tie_emax.p, (const int32_t *)e->d_tie_imin.p, n,
+                           (const unsigned long long *)e->tie.emax.p, (const int32_t *)e->tie.imin.p, n,
                            e->node_offset, o_key, o_idx);
     else
         hipLaunchKernelGGL(qm::tie_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, s,
-                           (const int32_t *)e->d_tie_imin.p, n, e->node_offset, o_idx);
+                           (const int32_t *)e->tie.imin.p, n, e->node_offset, o_idx);
     QM_HIP(hipGetLastError());
     return 0;
 }
@@ -687,19 +687,6 @@ int check_step(qm_engine *e, int T, int fsmp, int lsmp, int available, int *n_sa
                     "would read past the onset rows (undefined behaviour in the reference)",
                     e->lut_max, lsmp);
     *n_samples = ns;
-    return 0;
-}
-
-// device-resident copy of the onsets (or the caller's device pointer)
-int stage_onsets(qm_engine *e, const double *onsets, int on_device, int T, const double **out) {
-    if (on_device) {
-        *out = onsets;
-        return 0;
-    }
-    const size_t n = (size_t)e->g.n_rows * T;
-    if (e->d_onsets.ensure(n)) return 1;
-    QM_HIP(copy_in(e->d_onsets.p, onsets, n * sizeof(double), e->stream));
-    *out = e->d_onsets.p;
     return 0;
 }
 
@@ -732,6 +719,88 @@ int finalize_sets(qm_engine *e, const SetView &in, int64_t n_nodes_total, const 
     if (stage_out(e, in.n, out_on_device, user, &st) || combine(e, in, kCombineFinal, 0, n_nodes_total, st, nullptr))
         return 1;
     return fetch_out(e, in.n, out_on_device, st, user);
+}
+
+// The read-outs that are no tunables: name, value and -- where the value is still on the device -- what brings it to
+// the host first (run under a DeviceGuard).  waves, lds_bytes, screen_pairs, screen_big, shift_waves and shift_lazy
+// shadow the tunable of the same name with the live value.
+struct Readout {
+    const char *name;
+    int64_t (*value)(const qm_engine *e);
+    int (*fetch)(qm_engine *e);
+};
+int fetch_tie_counts(qm_engine *e) {                    // (the last refinement's counters: now)
+    if (!e->tie.counts_pending) return 0;
+    int32_t h[2] = {0, 0};
+    QM_HIP(copy_back(h, e->tie.count.p, sizeof(h), e->stream));
+    e->tie.pairs_last = h[0];
+    e->tie.overflow_last = h[1];
+    e->tie.counts_pending = false;
+    return 0;
+}
+#define V(expr) [](const qm_engine *e) -> int64_t { return (expr); }
+const Readout kReadouts[] = {
+    {"waves", V(run_waves(e))}, {"lds_bytes", V(run_lds_bytes(e))},
+    {"screen_pairs", V(e->sweep.last_plan_jp)}, {"screen_big", V(e->sweep.last_plan_big)},
+    // (of the layout the last launch ran on, if shift-reuse and still this table's: a table change voids the layouts,
+    // invalidate_derived)
+    {"shift_waves", V(e->last.shift && e->last.shift->ok ? e->last.shift->nw : e->sh.ok ? e->sh.nw : e->cfg.shift_waves)},
+    // the screened detect
+    {"screened_steps", V(e->sweep.screened_steps), drain_flags}, {"fallback_steps", V(e->sweep.fallback_steps), drain_flags},
+    {"last_candidates", V(e->sweep.last_candidates), drain_flags}, {"screen_brick_nodes", V(e->screen.g.brick_nodes)},
+    // the last stacking launch and the shift-reuse layouts
+    {"last_kernel", V(e->last.family)}, {"last_kernel_j", V(e->last.j)}, {"steps_per_launch", V(e->last_batched)},
+    {"shift_tail_spl", V(e->last.tail_spl)}, {"shift_wide_tiles", V(e->last.wide_tiles)},
+    {"shift_ok", V(e->sh.built && e->sh.ok ? 1 : 0)}, {"shift_wide_ok", V(e->shw.built && e->shw.ok ? 1 : 0)},
+    {"shift_row_blocks", V(e->sh.ok ? e->sh.nblk : 0)}, {"shift_wide_row_blocks", V(e->shw.ok ? e->shw.nblk : 0)},
+    {"shift_brick_nodes", V(e->sh.ok ? e->sh.g.brick_nodes : 0)},
+    {"shift_wide_brick_nodes", V(e->shw.ok ? e->shw.g.brick_nodes : 0)},
+    {"shift_wide_bricks", V(e->sh.ok ? e->sh.n_list : 0)}, {"shift_wide_direct_bricks", V(e->shw.ok ? e->shw.n_list : 0)},
+    // 8-byte LDS operands fetched per add (x 1000); per add of a wide tile
+    {"shift_operands_per_add_x1000",
+     V(e->sh.ok && e->sh.group_rows > 0 ? (e->sh.quads * 4 * 1000) / (e->sh.group_rows * 32) : 0)},
+    {"shift_wide_operands_per_add_x1000",
+     V(e->shw.ok && e->shw.group_rows > 0 ? (e->shw.wquads * 4 * 1000) / (e->shw.group_rows * 48) : 0)},
+    {"pair_brick_nodes", V(e->pair.kt ? e->pair.g.brick_nodes : 0)}, {"pair_tile", V(e->pair.ok ? e->pair.kt : 0)},
+    {"pair_wide_bricks", V(e->pair.kt ? e->pair.n_list : 0)}, {"shift_lazy", V(e->last.lazy)},
+    // the stage kernels' constants
+    {"pick_lds_samples", V(qm::kPicksLdsSamples)}, {"amp_lds_samples", V(qm::kAmpLdsSamples)},
+    {"trigger_max_radius", V(qm::kTrigMaxRadius)}, {"trigger_smooth_tile", V(qm::kTrigSmoothTile)},
+    {"trigger_run_block", V(qm::kTrigRunBlock)}, {"trigger_merge_stride", V(qm::kTrigMergeThreads)},
+    {"scanmseed_tile", V(qm::kSmsTile)}, {"scanmseed_compose_chunk", V(qm::kSmsComposeChunk)},
+    // the near-tie refinement
+    {"tie_brick_rows", V(e->last.brick_rows)}, {"tie_refined_steps", V(e->tie.refined_steps)},
+    {"tie_overflow_samples", V(e->tie.overflow_last), fetch_tie_counts}, {"tie_pairs", V(e->tie.pairs_last), fetch_tie_counts},
+    // tables: parked ones, device bytes of the resident table's state and of the parked ones, the process's pool
+    {"table_hits", V(e->table_hits)}, {"table_misses", V(e->table_misses)}, {"table_evictions", V(e->table_evictions)},
+    {"table_digests", V(e->table_digests)}, {"table_bytes", V(e->device_bytes())},
+    {"tables_parked", V(std::count_if(e->slots.begin(), e->slots.end(), [](const TableSlot &sl) { return sl.used; }))},
+    {"tables_parked_bytes", [](const qm_engine *e) -> int64_t {
+         int64_t sum = 0;
+         for (const TableSlot &sl : e->slots) sum += sl.used ? (int64_t)sl.state.device_bytes() : 0;
+         return sum;
+     }},
+    {"pool_live_bytes", V(pool_live_bytes(e->device))},
+    // the resident table and the device
+    {"n_bricks", V(e->g.nbricks)},
+    {"n_wide_bricks", V(e->r2().n_list), [](qm_engine *e) { return e->have_lut ? plan_wide(e, eff_j(e)) : 0; }},
+    {"mean_span", [](const qm_engine *e) -> int64_t {   // mean delay span per (brick, row), samples
+         int64_t sum = 0;
+         const std::vector<int32_t> &totals = e->r2().h_total;
+         for (int32_t t : totals) sum += t;
+         return totals.empty() ? 0 : sum / ((int64_t)totals.size() * std::max(1, e->g.n_rows));
+     }},
+    {"n_cu", V(e->n_cu)}, {"n_nodes", V(e->n_nodes)}, {"n_rows", V(e->g.n_rows)},
+    {"nx", V(e->g.nx)}, {"ny", V(e->g.ny)}, {"nz", V(e->g.nz)},
+};
+#undef V
+
+// "<prefix><stage name>" of a stage clock: the last call's time for that stage
+template <int N>
+bool clock_readout(const StageClock<N> &clock, const std::string &prefix, const std::string &key, int64_t *v) {
+    for (int st = 0; st < N; ++st)
+        if (key == prefix + clock.names[st]) return *v = clock.ns[st], true;
+    return false;
 }
 
 }  // namespace
@@ -803,120 +872,28 @@ int qm_engine_config(qm_engine *e, const char *key, int64_t v) {
     return 0;
 }
 
-// In this order: the keys whose read-out is live (the resident table's brick shape, samples per lane and workgroup
-// shape; the last launch's or plan's shift_waves, shift_lazy, screen_pairs, screen_big), the read-outs that are no
-// tunables, the tunables as set (config_get).
+// In this order: the resident table's brick shape and samples per lane where there is a table, the read-outs of
+// kReadouts (above) and of the stage clocks, the tunables as set (config_get).
 int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
     if (!e || !key || !v) return fail("qm_engine_get: NULL argument");
     const std::string k(key);
-    if (e->have_lut && k == "brick_x") *v = e->g.bx;
-    else if (e->have_lut && k == "brick_y") *v = e->g.by;
-    else if (e->have_lut && k == "brick_z") *v = e->g.bz;
-    else if (e->have_lut && k == "samples_per_lane") *v = eff_j(e);
-    else if (k == "waves") *v = run_waves(e);
-    else if (k == "lds_bytes") *v = run_lds_bytes(e);
-    else if (k == "screened_steps" || k == "fallback_steps" || k == "last_candidates") {
-        DeviceGuard guard(e->device);
-        if (drain_flags(e)) return 1;
-        *v = k == "screened_steps" ? e->screened_steps
-             : k == "fallback_steps" ? e->fallback_steps : e->last_candidates;
+    if (e->have_lut && (k == "brick_x" || k == "brick_y" || k == "brick_z" || k == "samples_per_lane")) {
+        *v = k == "brick_x" ? e->g.bx : k == "brick_y" ? e->g.by : k == "brick_z" ? e->g.bz : eff_j(e);
+        return 0;
     }
-    else if (k == "screen_pairs") *v = e->last_plan_jp;
-    else if (k == "screen_big") *v = e->last_plan_big;
-    else if (k == "screen_brick_nodes") *v = e->screen.g.brick_nodes;
-    else if (k == "last_kernel") *v = e->last.family;
-    else if (k == "last_kernel_j") *v = e->last.j;
-    else if (k == "shift_ok") *v = e->sh.built && e->sh.ok ? 1 : 0;
-    else if (k == "shift_waves")                        // (of the layout the last launch ran on, if shift-reuse and
-        // still this table's: a table change voids the layouts, invalidate_derived)
-        *v = e->last.shift && e->last.shift->ok ? e->last.shift->nw : e->sh.ok ? e->sh.nw : e->cfg.shift_waves;
-    else if (k == "shift_lazy") *v = e->last.lazy;
-    else if (k == "shift_tail_spl") *v = e->last.tail_spl;
-    else if (k == "shift_wide_ok") *v = e->shw.built && e->shw.ok ? 1 : 0;
-    else if (k == "shift_wide_row_blocks") *v = e->shw.ok ? e->shw.nblk : 0;
-    else if (k == "shift_wide_tiles") *v = e->last.wide_tiles;
-    else if (k == "shift_wide_brick_nodes") *v = e->shw.ok ? e->shw.g.brick_nodes : 0;
-    else if (k == "shift_wide_direct_bricks") *v = e->shw.ok ? e->shw.n_list : 0;
-    else if (k == "shift_wide_operands_per_add_x1000")   // 8-byte LDS operands fetched per add of a wide tile (x 1000)
-        *v = e->shw.ok && e->shw.group_rows > 0 ? (e->shw.wquads * 4 * 1000) / (e->shw.group_rows * 48) : 0;
-    else if (k == "steps_per_launch") *v = e->last_batched;
-    else if (k == "pick_lds_samples") *v = qm::kPicksLdsSamples;
-    else if (k == "amp_lds_samples") *v = qm::kAmpLdsSamples;
-    else if (k == "trigger_max_radius") *v = qm::kTrigMaxRadius;
-    else if (k == "trigger_ns_smooth") *v = e->trg_ns[qm::kTrigSmooth];
-    else if (k == "trigger_ns_stats") *v = e->trg_ns[qm::kTrigStats];
-    else if (k == "trigger_ns_runs") *v = e->trg_ns[qm::kTrigRuns];
-    else if (k == "trigger_ns_compact") *v = e->trg_ns[qm::kTrigCompact];
-    else if (k == "trigger_ns_peaks") *v = e->trg_ns[qm::kTrigPeaks];
-    else if (k == "trigger_ns_merge") *v = e->trg_ns[qm::kTrigMerge];
-    else if (k == "trigger_smooth_tile") *v = qm::kTrigSmoothTile;
-    else if (k == "trigger_run_block") *v = qm::kTrigRunBlock;
-    else if (k == "trigger_merge_stride") *v = qm::kTrigMergeThreads;
-    else if (k == "scanmseed_tile") *v = qm::kSmsTile;
-    else if (k == "scanmseed_compose_chunk") *v = qm::kSmsComposeChunk;
-    else if (k == "scanmseed_ns_quantise") *v = e->sms_ns[qm::kSmsQuantise];
-    else if (k == "scanmseed_ns_scan") *v = e->sms_ns[qm::kSmsScan];
-    else if (k == "scanmseed_ns_compose") *v = e->sms_ns[qm::kSmsCompose];
-    else if (k == "scanmseed_ns_pack") *v = e->sms_ns[qm::kSmsPack];
-    else if (k == "scanmseed_ns_frame") *v = e->sms_ns[qm::kSmsFrame];
-    else if (k == "scanmseed_ns_decode") *v = e->sms_ns[qm::kSmsDecode];
-    else if (k == "tie_brick_rows") *v = e->last.brick_rows;
-
-    else if (k == "tie_refined_steps") *v = e->tie_refined_steps;
-    else if (k == "tie_overflow_samples" || k == "tie_pairs") {
-        if (e->tie_counts_pending) {                       // (the last refinement's counters: now)
+    for (const Readout &r : kReadouts) {
+        if (k != r.name) continue;
+        if (r.fetch) {
             DeviceGuard guard(e->device);
-            int32_t h[2] = {0, 0};
-            QM_HIP(copy_back(h, e->d_tie_count.p, sizeof(h), e->stream));
-            e->tie_pairs_last = h[0];
-            e->tie_overflow_last = h[1];
-            e->tie_counts_pending = false;
+            if (r.fetch(e)) return 1;
         }
-        *v = k == "tie_pairs" ? e->tie_pairs_last : e->tie_overflow_last;
+        *v = r.value(e);
+        return 0;
     }
-    else if (k == "table_hits") *v = e->table_hits;
-    else if (k == "table_misses") *v = e->table_misses;
-    else if (k == "table_evictions") *v = e->table_evictions;
-    else if (k == "table_digests") *v = e->table_digests;
-    else if (k == "tables_parked") {
-        *v = 0;
-        for (const TableSlot &sl : e->slots) *v += sl.used ? 1 : 0;
-    } else if (k == "table_bytes") {                     // device bytes of the resident table's state
-        *v = (int64_t)e->device_bytes();
-    } else if (k == "tables_parked_bytes") {
-        *v = 0;
-        for (const TableSlot &sl : e->slots) *v += sl.used ? (int64_t)sl.state.device_bytes() : 0;
-    }
-    else if (k == "pool_live_bytes") *v = (int64_t)pool_live_bytes(e->device);
-    else if (k == "shift_row_blocks") *v = e->sh.ok ? e->sh.nblk : 0;
-    else if (k == "shift_brick_nodes") *v = e->sh.ok ? e->sh.g.brick_nodes : 0;
-    else if (k == "shift_wide_bricks") *v = e->sh.ok ? e->sh.n_list : 0;
-    else if (k == "shift_operands_per_add_x1000")   // 8-byte LDS operands fetched per add (x 1000)
-        *v = e->sh.ok && e->sh.group_rows > 0
-                 ? (e->sh.quads * 4 * 1000) / (e->sh.group_rows * 32) : 0;
-    else if (k == "pair_brick_nodes") *v = e->pair.kt ? e->pair.g.brick_nodes : 0;
-    else if (k == "pair_wide_bricks") *v = e->pair.kt ? e->pair.n_list : 0;
-    else if (k == "pair_tile") *v = e->pair.ok ? e->pair.kt : 0;
-    else if (k == "n_bricks") *v = e->g.nbricks;
-    else if (k == "n_wide_bricks") {
-        if (e->have_lut) {
-            DeviceGuard guard(e->device);
-            if (plan_wide(e, eff_j(e))) return 1;
-        }
-        *v = e->r2().n_list;
-    } else if (k == "mean_span") {                     // mean delay span per (brick, row), samples
-        int64_t sum = 0;
-        const std::vector<int32_t> &totals = e->r2().h_total;
-        for (int32_t t : totals) sum += t;
-        *v = totals.empty() ? 0 : sum / ((int64_t)totals.size() * std::max(1, e->g.n_rows));
-    } else if (k == "n_cu") *v = e->n_cu;
-    else if (k == "n_nodes") *v = e->n_nodes;
-    else if (k == "n_rows") *v = e->g.n_rows;
-    else if (k == "nx") *v = e->g.nx;
-    else if (k == "ny") *v = e->g.ny;
-    else if (k == "nz") *v = e->g.nz;
-    else if (!config_get(e->cfg, key, v)) return fail("unknown key '%s'", key);
-    return 0;
+    if (clock_readout(e->trig.clock, "trigger_ns_", k, v) || clock_readout(e->sms.clock, "scanmseed_ns_", k, v) ||
+        config_get(e->cfg, key, v))
+        return 0;
+    return fail("unknown key '%s'", key);
 }
 
 int qm_engine_detect_partial(qm_engine *e, const double *log_onsets, int onsets_on_device,
@@ -927,7 +904,7 @@ int qm_engine_detect_partial(qm_engine *e, const double *log_onsets, int onsets_
     DeviceGuard guard(e->device);
     int ns = 0;
     const double *d_on = nullptr;
-    if (check_step(e, T, fsmp, lsmp, available, &ns) || stage_onsets(e, log_onsets, onsets_on_device, T, &d_on))
+    if (check_step(e, T, fsmp, lsmp, available, &ns) || !(d_on = stage_onsets(e, log_onsets, onsets_on_device, T)))
         return 1;
     return detect_core(e, d_on, T, fsmp, ns, available, kCombinePartial, 0,
                        OutSeries{d_part_max, d_part_sum, d_part_idx});
@@ -966,7 +943,7 @@ int qm_engine_detect(qm_engine *e, const double *log_onsets, int onsets_on_devic
     const double *d_on = nullptr;
     const OutSeries user{max_coa, max_norm_coa, max_coa_idx};
     OutSeries st;
-    if (check_step(e, T, fsmp, lsmp, available, &ns) || stage_onsets(e, log_onsets, onsets_on_device, T, &d_on) ||
+    if (check_step(e, T, fsmp, lsmp, available, &ns) || !(d_on = stage_onsets(e, log_onsets, onsets_on_device, T)) ||
         stage_out(e, ns, out_on_device, user, &st))
         return 1;
     if (detect_core(e, d_on, T, fsmp, ns, available, kCombineFinal, n_nodes_total, st)) return 1;
@@ -985,12 +962,8 @@ int qm_engine_detect_batch(qm_engine *e, const double *log_onsets, int onsets_on
     if (check_step(e, T, fsmp, lsmp, available, &ns)) return 1;
     if ((int64_t)n_steps * ns >= INT32_MAX) return fail("qm_engine_detect_batch: too many samples");
     const size_t per_step = (size_t)e->g.n_rows * T;
-    const double *d_on = log_onsets;
-    if (!onsets_on_device) {
-        if (e->d_onsets.ensure(per_step * n_steps)) return 1;
-        QM_HIP(copy_in(e->d_onsets.p, log_onsets, per_step * n_steps * sizeof(double), e->stream));
-        d_on = e->d_onsets.p;
-    }
+    const double *d_on = stage_onsets(e, log_onsets, onsets_on_device, T, n_steps);
+    if (!d_on) return 1;
     const int n_all = n_steps * ns;
     const OutSeries user{max_coa, max_norm_coa, max_coa_idx};
     OutSeries st;
@@ -1032,14 +1005,14 @@ int qm_engine_tie_partial(qm_engine *e, const double *log_onsets, int onsets_on_
                     "(call qm_engine_detect_partial for the step first, with no other launch, volume scan or "
                     "table change in between; the screened sweep leaves none)", ns);
     const double *d_on = nullptr;
-    if (stage_onsets(e, log_onsets, onsets_on_device, T, &d_on)) return 1;
+    if (!(d_on = stage_onsets(e, log_onsets, onsets_on_device, T))) return 1;
     // the grid's largest z per sample: the fold of the gathered maxima (rows [s][0] of [n_sets][3][ns])
-    if (e->d_tie_zgrid.ensure(ns)) return 1;
+    if (e->tie.zgrid.ensure(ns)) return 1;
     hipLaunchKernelGGL(qm::tie_zmax_kernel, dim3((ns + 255) / 256), dim3(256), 0, e->stream, d_packed, (int)n_sets,
-                       ns, 3 * (int64_t)ns, e->d_tie_zgrid.p);
+                       ns, 3 * (int64_t)ns, e->tie.zgrid.p);
     QM_HIP(hipGetLastError());
     return refine_ties(e, StackLaunch(d_on, T, fsmp, ns, available), reinterpret_cast<int64_t *>(d_tie_packed + ns),
-                       e->d_tie_zgrid.p, reinterpret_cast<unsigned long long *>(d_tie_packed));
+                       e->tie.zgrid.p, reinterpret_cast<unsigned long long *>(d_tie_packed));
 }
 
 // ... and folds the gathered outcomes [n_sets][2][n_samples] into the index series (device, in place).
@@ -1068,7 +1041,7 @@ int qm_engine_migrate(qm_engine *e, const double *log_onsets, int onsets_on_devi
     const double *d_on = nullptr;
     const OutSeries user{max_coa, max_norm_coa, max_coa_idx};
     OutSeries st;
-    if (check_step(e, T, fsmp, lsmp, available, &ns) || stage_onsets(e, log_onsets, onsets_on_device, T, &d_on) ||
+    if (check_step(e, T, fsmp, lsmp, available, &ns) || !(d_on = stage_onsets(e, log_onsets, onsets_on_device, T)) ||
         (want_scan && stage_out(e, ns, out_on_device, user, &st)))
         return 1;
     StackLaunch s(d_on, T, fsmp, ns, available);
@@ -1121,22 +1094,16 @@ int qm_engine_marginal(qm_engine *e, const double *log_onsets, int onsets_on_dev
     const double *d_on = nullptr;
     const OutSeries user{max_coa, max_norm_coa, max_coa_idx};
     OutSeries st;
-    if (stage_onsets(e, log_onsets, onsets_on_device, T, &d_on) ||
+    if (!(d_on = stage_onsets(e, log_onsets, onsets_on_device, T)) ||
         (want_scan && stage_out(e, ns, out_on_device, user, &st)))
         return 1;
-    double *d_map = coa_map;
-    if (!map_on_device) {
-        if (e->d_marg_out.ensure((size_t)e->n_nodes)) return 1;
-        d_map = e->d_marg_out.p;
-    }
+    const StagedOut<double> map = stage_host_out(e->d_marg_out, coa_map, map_on_device, (size_t)e->n_nodes);
+    if (!map.d) return 1;
     StackLaunch s(d_on, T, fsmp, ns, available);
     s.want_scan = want_scan;
-    s.kind = StackLaunch::Marginal{first_sample, end_sample, d_map};
-    if (stack_fold(e, s, kCombineFinal, n_nodes_total, st).rc) return 1;
-    if (!map_on_device) {
-        QM_HIP(copy_back(coa_map, d_map, (size_t)e->n_nodes * sizeof(double), e->stream));
-        QM_HIP(hipStreamSynchronize(e->stream));
-    }
+    s.kind = StackLaunch::Marginal{first_sample, end_sample, map.d};
+    if (stack_fold(e, s, kCombineFinal, n_nodes_total, st).rc || map.fetch(e)) return 1;
+    if (!map_on_device) QM_HIP(hipStreamSynchronize(e->stream));
     if (want_scan) return fetch_out(e, ns, out_on_device, st, user);
     return 0;
 }
@@ -1175,13 +1142,14 @@ int qm_engine_exp_correctly_rounded(qm_engine *e, const double *x, int64_t n, do
     if (!e || !x || !out) return fail("qm_engine_exp_correctly_rounded: NULL argument");
     if (n < 1) return 0;
     DeviceGuard guard(e->device);
-    if (e->d_fit_a.ensure((size_t)n) || e->d_fit_b.ensure((size_t)n)) return 1;
-    QM_HIP(copy_in(e->d_fit_a.p, x, (size_t)n * sizeof(double), e->stream));
-    hipLaunchKernelGGL(qm::exp_cr_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream,
-                       (const double *)e->d_fit_a.p, n, e->d_fit_b.p);
+    // (in and out through two of the locate fits' map-sized buffers: FitScratch says so)
+    const double *d_x = stage_in(e, e->fit.a, x, 0, (size_t)n);
+    if (!d_x) return 1;
+    const StagedOut<double> res = stage_host_out(e->fit.b, out, 0, (size_t)n);
+    if (!res.d) return 1;
+    hipLaunchKernelGGL(qm::exp_cr_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, d_x, n, res.d);
     QM_HIP(hipGetLastError());
-    QM_HIP(copy_back(out, e->d_fit_b.p, (size_t)n * sizeof(double), e->stream));
-    return 0;
+    return res.fetch(e);
 }
 
 int qm_engine_kernel_log(qm_engine *e, double *total_ms, int32_t *n_calls) {

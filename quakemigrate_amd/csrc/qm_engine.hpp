@@ -6,9 +6,10 @@
 //   qm_tables.hip    everything derived from ONE travel-time table: load, layout search, the kernels'
 //                    derived tables (round-2 offsets, paired, shift-reuse, screening), parked tables,
 //                    on-device serving
-//   qm_engine.hip    engine handle, tunables, the stacking launch (run_stack: plan_stack decides into a StackPlan,
-//                    issue_stack enqueues it, e->last keeps it), one core per launch kind and the step entry points
-//                    around them (detect / detect_batch / partial / finalize / migrate / marginal / find_max_coa)
+//   qm_engine.hip    engine handle, tunables, read-outs (one table: kReadouts), the stacking launch (run_stack:
+//                    plan_stack decides into a StackPlan, issue_stack enqueues it, e->last keeps it), one core per launch
+//                    kind and the step entry points around them (detect / detect_batch / partial / finalize / migrate /
+//                    marginal / find_max_coa)
 //   qm_screen.hip    the opt-in screened detect's launch sequence
 //   qm_stream.hip    the continuous detect pipeline (pinned ring, copies overlapped with compute), also over
 //                    several engines that hold the same table (replicas: launches round-robin)
@@ -27,6 +28,10 @@
 //                    peak-to-trough measurements out
 //   qm_compat.hip    the five reference-signature symbols (qmlib.h:28-44)
 //   qm_group.hip     engine groups: one process driving the boxes of a column partition on several devices
+// Whose scratch is whose: the stacking scratch and the serving grids are the engine's own members (folds, ties, streams
+// and groups read them); every other call family has a record below (the front-end stages', PickStage ... CallStaging)
+// whose comments name what is shared.  Host arrays pass through stage_in / stage_host_out, timed launches through
+// timed_launches, a sequence's per-stage times through StageClock.
 // Who frees what: nobody by name.  Device buffers, pinned host buffers and events are the owning handles below
 // (DevBuf, PinnedBuf, Event); the structs here hold them as members and have no release lists.  What a teardown
 // still does itself -- one wait, the right device, the order -- stands with the handles.
@@ -344,6 +349,127 @@ struct ResampleStage {
     int launch(qm_engine *e, const void *raw, double *out, int n_steps) const;
 };
 
+// The clock of a launch sequence of N stages: a pair of HIP events around each stage's launches, the elapsed times
+// once the call has synchronised.  `names`: the stages as the read-outs "<prefix>_ns_<name>" call them, defined beside
+// the stage enum.  A call goes begin, stage ..., its synchronise, collect.
+template <int N>
+struct StageClock {
+    const char *const (&names)[N];
+    std::vector<Event> ev;              // 2 per stage, made on first use
+    int64_t ns[N] = {};                 // the last collected call's stage times, 0: the stage did not run
+    bool ran[N] = {};                   // the stages bracketed since begin
+    bool on = true;
+    explicit StageClock(const char *const (&names_)[N]) : names(names_) {}
+    int ensure_events() {
+        while (ev.size() < 2 * (size_t)N) {
+            Event made;
+            QM_HIP(made.create());
+            ev.push_back(std::move(made));
+        }
+        return 0;
+    }
+    // on_ = false: nothing is recorded, every stage reads 0 after collect.  zero_now: the times read 0 from here on -- a
+    // call that fails before collect leaves zeros, not the previous call's times.
+    void begin(bool on_, bool zero_now) {
+        on = on_;
+        for (bool &r : ran) r = false;
+        if (zero_now) for (int64_t &t : ns) t = 0;
+    }
+    // `launches` (enqueue only) between the stage's two events on `stream`
+    template <typename F>
+    int stage(hipStream_t stream, int st, F &&launches) {
+        if (on) {
+            if (ensure_events()) return 1;
+            QM_HIP(hipEventRecord(ev[2 * st], stream));
+        }
+        launches();
+        QM_HIP(hipGetLastError());
+        if (on) {
+            QM_HIP(hipEventRecord(ev[2 * st + 1], stream));
+            ran[st] = true;
+        }
+        return 0;
+    }
+    // ... one kernel
+    template <typename... P, typename... A>
+    int launch(hipStream_t stream, int st, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, A... args) {
+        return stage(stream, st, [&] { hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...); });
+    }
+    // after the synchronise: every stage's time, 0 where it did not run
+    int collect() {
+        for (int st = 0; st < N; ++st) {
+            ns[st] = 0;
+            if (!ran[st]) continue;
+            float ms = 0.0f;
+            QM_HIP(hipEventElapsedTime(&ms, ev[2 * st], ev[2 * st + 1]));
+            ns[st] = (int64_t)((double)ms * 1e6);
+        }
+        return 0;
+    }
+};
+
+// The scratch of the stages behind the detect and of the engine's own sweeps, one record per call family: device
+// buffers that grow with the largest call seen, the family's counters and clocks.  Plain data -- the calls that fill
+// them are named with each record -- and nothing outside a family touches its record, except where a comment says so.
+struct PickStage {                      // qm_engine_pick_phases (qm_picks.hip)
+    DevBuf<double> val;                 // half-widths, thresholds, then the picks
+    DevBuf<int32_t> meta;               // windows, groups, then the status
+};
+struct AmplitudeStage {                 // qm_engine_measure_amplitudes (qm_amplitudes.hip)
+    DevBuf<double> work, scratch;       // the working copy of the packed traces, windows above the LDS limit
+    DevBuf<double> coef, val;           // sections and taper weights; the value table
+    DevBuf<int64_t> meta;               // trace records, taper table and window records
+    DevBuf<int32_t> idx;                // the index table
+};
+struct TriggerStage {                   // qm_engine_trigger / _trigger_resident (qm_trigger.hip)
+    DevBuf<double> x, par;              // the two series (raw, then smoothed), weights and thresholds
+    DevBuf<int32_t> cnt;                // the run kernels' counts ...
+    DevBuf<int64_t> tot;                // ... and totals
+    DevBuf<int32_t> run;                // sized once the candidate count is known: run starts and ends,
+    DevBuf<int64_t> cand;               // ... candidate and event tables,
+    DevBuf<double> val;                 // ... their values
+    StageClock<qm::kTrigStages> clock{qm::kTrigStageNames};     // "trigger_ns_<stage>": runs under cfg.trigger_timing
+};
+struct ScanmseedCodec {                 // qm_engine_scanmseed_encode / _decode (qm_scanmseed.hip)
+    DevBuf<int32_t> x;                  // the int32 series: quantised, copied in or decoded
+    DevBuf<double> f, fac;              // float64 series in or descaled out; decode's factors
+    DevBuf<uint8_t> bytes;              // count(p) and the words' codes
+    DevBuf<uint32_t> map, out;          // the tiles' maps; the records
+    DevBuf<int32_t> tile, rec;          // the tiles' entries and first words; first samples and counts (decode: sample counts)
+    DevBuf<unsigned long long> tot;     // totals and error slots
+    DevBuf<int64_t> off;                // decode's offsets
+    StageClock<qm::kSmsStages> clock{qm::kSmsStageNames};       // "scanmseed_ns_<stage>": always runs
+};
+struct TieScratch {                     // the near-tie refinement (refine_ties, qm_engine_tie_partial; qm_ties.hpp)
+    DevBuf<double> zext, zgrid, z;      // the largest z per sample left by the combine of the own sets; the GRID's (sharded)
+    DevBuf<int32_t> pairs, imin, count, cands;
+    DevBuf<unsigned long long> emax, keys;
+    int64_t refined_steps = 0, overflow_last = 0, pairs_last = 0;
+    bool counts_pending = false;        // the last refinement's counters are still on the device
+};
+struct ScreenScratch {                  // the screened detect's sweep (run_screen, drain_flags; qm_screen.hpp)
+    DevBuf<int32_t> counts, cells, work, flags;     // (work: also ensure_shift_tables' per-brick fit flags of a wide
+    DevBuf<int32_t> onq, cell, gmax, pm, sparams;   // layout, qm_tables.hip)
+    DevBuf<double> rowmax, ssum, cand_z;
+    DevBuf<int64_t> cand_idx;
+    int64_t screened_steps = 0, fallback_steps = 0, last_candidates = 0;
+    int last_plan_jp = 0, last_plan_big = 0;
+    PinnedBuf<int32_t> h_flags;             // pinned ring of per-step (flags, candidates) pairs
+    int flags_pending = 0, flags_head = 0;  // not yet folded into the counters
+};
+struct FitScratch {                     // qm_engine_locate_fits, _rbf_peak (qm_widen.hip): three map-sized work buffers,
+    DevBuf<double> a, b, c;             // ... (a, b: also qm_engine_exp_correctly_rounded's input and output)
+    DevBuf<double> part, val, win;      // reduction partials (also qm_engine_exp2f_max_error's), device-side scalars, windows
+    DevBuf<int64_t> pidx;
+};
+// Where the staged calls put host arrays on their way in and out.  Shared on purpose: a call is over when it returns.
+struct CallStaging {
+    DevBuf<double> sig;                 // in: qm_engine_preprocess' and _onsets' signals, qm_engine_pick_phases' onset rows
+    DevBuf<double> raw;                 // out: qm_engine_onsets' raw onsets
+    DevBuf<double> pre_out;             // out: qm_engine_preprocess' filtered and qm_engine_resample's resampled traces
+    DevBuf<double> rs_raw;              // in: qm_engine_resample's raw samples (bytes, in doubles)
+};
+
 struct qm_stream;                    // a continuous-detect pipeline on an engine (qm_stream.hip)
 
 // One stacking launch (StackLaunch below) as plan_stack decides it and issue_stack enqueues it (qm_engine.hip).
@@ -396,72 +522,34 @@ struct qm_engine : TableState {
 
     EngineConfig cfg;                   // the tunables (qm_config.hpp): written by config_set only
 
-    // per-step scratch of the screened detect (qm_screen.hpp) and its statistics
-    DevBuf<int32_t> d_scalar, d_counts, d_cells, d_work, d_flags;
-    DevBuf<int32_t> d_onq, d_cell, d_gmax, d_pm, d_sparams;
-    DevBuf<double> d_rowmax, d_ssum, d_cand_z;
-    DevBuf<int64_t> d_cand_idx;
-    int64_t screened_steps = 0, fallback_steps = 0, last_candidates = 0;
-    int last_plan_jp = 0, last_plan_big = 0;
-    PinnedBuf<int32_t> h_flags;             // pinned ring of per-step (flags, candidates) pairs
-    int flags_pending = 0, flags_head = 0;  // not yet folded into the counters
-    int last_batched = 1;                   // timesteps the last detect_batch put into one launch
-    StackPlan last;                                     // the last stacking launch (run_stack)
-    DevBuf<double> d_bmax;                              // its row of maxima per brick (StackPlan::brick_rows)
-    DevBuf<double> d_tie_zext;                          // the largest z per sample, left by the combine of the own sets
-    DevBuf<double> d_tie_zgrid;                         // sharded detects: the GRID's largest z per sample
-    DevBuf<double> d_tie_z;
-    DevBuf<int32_t> d_tie_pairs, d_tie_imin, d_tie_count, d_tie_cands;
-    DevBuf<unsigned long long> d_tie_emax, d_tie_keys;
-    int64_t tie_refined_steps = 0, tie_overflow_last = 0, tie_pairs_last = 0;
-    bool tie_counts_pending = false;        // the last refinement's counters are still on the device
+    DevBuf<int32_t> d_scalar;           // a few device-side counters of the table builds (qm_tables.hip)
+    int last_batched = 1;               // timesteps the last detect_batch put into one launch
+    StackPlan last;                     // the last stacking launch (run_stack)
 
     // float64 travel-time grids in seconds (optional; on-device table serving)
     DevBuf<double> d_grids;
     DevBuf<int32_t> d_rows, d_served;
     int gx = 0, gy = 0, gz = 0, g_rows = 0;
 
-    // the stages in front of the detect as the staged calls (qm_engine_resample / _preprocess / _onsets) last built
-    // them, and those calls' staging of host data: signals in, raw onsets, filtered or resampled traces out, raw
-    // samples in (bytes, in doubles); the log-onsets go through d_onsets
+    // the stacking scratch, read by folds, ties, streams and groups alike: log-onsets staged from the host (and
+    // qm_engine_onsets' output on its way there), the launch's partial sets and its row of maxima per brick (StackPlan::
+    // brick_rows), the packed three series and a host volume's chunk on their way out, the marginal map's tile sums, the map
+    DevBuf<double> d_onsets, d_pmax, d_psum, d_bmax, d_out_a, d_chunk, d_marg, d_marg_out;
+    DevBuf<int64_t> d_pidx;
+
+    // the stages in front of the detect as the staged calls (qm_engine_resample / _preprocess / _onsets) last built them
     ResampleStage rs_stage;
     PreprocStage pre_stage;
     OnsetStage on_stage;
-    DevBuf<double> d_sig, d_raw, d_pre_out, d_rs_raw;
-    // phase-pick stage scratch: half-widths, thresholds and picks; windows, groups and status
-    DevBuf<double> d_pick_val;
-    DevBuf<int32_t> d_pick_meta;
-    // amplitude stage scratch: the working copy of the packed traces, windows above the LDS limit; trace records, taper
-    // table and window records; sections and taper weights; the two output tables
-    DevBuf<double> d_amp_work, d_amp_scratch, d_amp_coef, d_amp_val;
-    DevBuf<int64_t> d_amp_meta;
-    DevBuf<int32_t> d_amp_idx;
-    // trigger stage scratch: the two series (raw, then smoothed), weights and thresholds, the run kernels' counts and
-    // totals; sized once the candidate count is known: run starts and ends, candidate and event tables, their values
-    DevBuf<double> d_trg_x, d_trg_par, d_trg_val;
-    DevBuf<int32_t> d_trg_cnt, d_trg_run;
-    DevBuf<int64_t> d_trg_tot, d_trg_cand;
-    std::vector<Event> trg_ev;              // cfg.trigger_timing: a pair of HIP events per stage of the trigger sequence
-    int64_t trg_ns[qm::kTrigStages] = {};   // ... the last call's stage times ("trigger_ns_<stage>"), 0: did not run
-
-    // .scanmseed codec scratch: the int32 series (quantised, copied in or decoded), float64 series in or descaled out,
-    // count(p) and the words' codes, the tiles' maps, entries and first words, totals and error slots, the records,
-    // their first samples and counts (decode: their sample counts), decode's offsets and factors
-    DevBuf<int32_t> d_sms_x, d_sms_tile, d_sms_rec;
-    DevBuf<double> d_sms_f, d_sms_fac;
-    DevBuf<uint8_t> d_sms_bytes;
-    DevBuf<uint32_t> d_sms_map, d_sms_out;
-    DevBuf<unsigned long long> d_sms_tot;
-    DevBuf<int64_t> d_sms_off;
-    std::vector<Event> sms_ev;              // a pair of HIP events per stage of the codec's sequences
-    int64_t sms_ns[qm::kSmsStages] = {};    // ... the last call's stage times ("scanmseed_ns_<stage>"), 0: did not run
-
-    // scratch
-    DevBuf<double> d_onsets, d_pmax, d_psum, d_out_a, d_chunk, d_marg, d_marg_out;
-    DevBuf<int64_t> d_pidx;
-    // locate fits: three map-sized work buffers, reduction partials, device-side scalars
-    DevBuf<double> d_fit_a, d_fit_b, d_fit_c, d_fit_part, d_fit_val, d_fit_win;
-    DevBuf<int64_t> d_fit_pidx;
+    // the scratch records above, one per call family
+    CallStaging staging;
+    PickStage picks;
+    AmplitudeStage amps;
+    TriggerStage trig;
+    ScanmseedCodec sms;
+    TieScratch tie;
+    ScreenScratch sweep;
+    FitScratch fit;
 };
 
 struct DeviceGuard {
@@ -508,6 +596,46 @@ int launch_with_lds(qm_engine *e, void (*kernel)(P...), unsigned blocks, unsigne
                                    (int)lds));
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), lds, e->stream, args...);
     QM_HIP(hipGetLastError());
+    return 0;
+}
+
+// Staging of a call's arrays.  In: the device pointer to read `n` elements of `src` from -- `src` itself where it is
+// on the device, else `buf`, grown and filled on e->stream; nullptr: that failed.
+// (bytes: what to copy where that is not n elements -- raw samples of either width in a buffer of doubles)
+template <typename T, typename U>
+const U *stage_in(qm_engine *e, DevBuf<T> &buf, const U *src, int on_device, size_t n, size_t bytes = 0) {
+    if (on_device) return src;
+    const auto fill = [&]() -> int {
+        if (buf.ensure(n)) return 1;
+        QM_HIP(copy_in(buf.p, src, bytes ? bytes : n * sizeof(T), e->stream));
+        return 0;
+    };
+    return fill() ? nullptr : reinterpret_cast<const U *>(buf.p);
+}
+// Out: where the kernels write the caller's `n` elements -- `user` itself on the device, else `buf` (d == nullptr:
+// growing it failed); fetch enqueues the copy back, the synchronise that follows stays with the call.
+template <typename T>
+struct StagedOut {
+    T *d = nullptr, *user = nullptr;    // user: the host destination, nullptr where there is none
+    size_t n = 0;
+    int fetch(qm_engine *e) const {
+        if (user) QM_HIP(copy_back(user, d, n * sizeof(T), e->stream));
+        return 0;
+    }
+};
+template <typename T>
+StagedOut<T> stage_host_out(DevBuf<T> &buf, T *user, int on_device, size_t n) {
+    if (on_device) return {user, nullptr, n};
+    return {buf.ensure(n) ? nullptr : buf.p, user, n};
+}
+// The engine's own event pair (qm_engine_last_kernel_ms) around `launches`, a callable in the error convention: the
+// call counts as timed only once the end event is recorded -- one that fails in between leaves e->timed as it was.
+template <typename F>
+int timed_launches(qm_engine *e, F &&launches) {
+    QM_HIP(hipEventRecord(e->ev0, e->stream));
+    if (launches()) return 1;
+    QM_HIP(hipEventRecord(e->ev1, e->stream));
+    e->timed = true;
     return 0;
 }
 
@@ -635,7 +763,10 @@ int scan_fold(qm_engine *e, const double *vol, int64_t stride, int ns, int64_t n
 int detect_core(qm_engine *e, const double *d_on, int T, int fsmp, int ns, int available, CombineMode mode,
                 int64_t n_nodes_total, const OutSeries &out);
 int check_step(qm_engine *e, int T, int fsmp, int lsmp, int available, int *n_samples);
-int stage_onsets(qm_engine *e, const double *onsets, int on_device, int T, const double **out);
+// the log-onsets of n_steps timesteps on the device: the caller's pointer or their copy in d_onsets; nullptr: failed
+inline const double *stage_onsets(qm_engine *e, const double *onsets, int on_device, int T, int n_steps = 1) {
+    return stage_in(e, e->d_onsets, onsets, on_device, (size_t)e->g.n_rows * T * n_steps);
+}
 // where the kernels write the caller's three series (on host: the engine's packed [3][n] buffer) ...
 int stage_out(qm_engine *e, int n, int out_on_device, const OutSeries &user, OutSeries *st);
 // ... and their copy back to the caller

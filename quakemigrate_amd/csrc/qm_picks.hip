@@ -30,37 +30,30 @@ int qm_engine_pick_phases(qm_engine *e, const double *onsets, int onsets_on_devi
     DeviceGuard guard(e->device);
     const size_t n = (size_t)n_rows, sig = n * t_samples;
     // one buffer of doubles (half-widths, thresholds, then the picks), one of integers (windows, groups, status)
-    if (e->d_pick_val.ensure(n * (2 + qm::kPicksColumns)) || e->d_pick_meta.ensure(n * 5)) return 1;
     std::vector<double> val(halfwidth, halfwidth + n);
     if (threshold_mode == 1) val.insert(val.end(), thresholds_in, thresholds_in + n);
     std::vector<int32_t> meta(windows, windows + 3 * n);
     meta.insert(meta.end(), row_group, row_group + n);
-    QM_HIP(copy_in(e->d_pick_val.p, val.data(), val.size() * sizeof(double), e->stream));
-    QM_HIP(copy_in(e->d_pick_meta.p, meta.data(), meta.size() * sizeof(int32_t), e->stream));
-    const double *d_on = onsets;
-    if (!onsets_on_device) {
-        if (e->d_sig.ensure(sig)) return 1;
-        QM_HIP(copy_in(e->d_sig.p, onsets, sig * sizeof(double), e->stream));
-        d_on = e->d_sig.p;
-    }
+    if (!stage_in(e, e->picks.val, val.data(), 0, n * (2 + qm::kPicksColumns), val.size() * sizeof(double)) ||
+        !stage_in(e, e->picks.meta, meta.data(), 0, n * 5, meta.size() * sizeof(int32_t)))
+        return 1;
+    const double *d_on = stage_in(e, e->staging.sig, onsets, onsets_on_device, sig);
+    if (!d_on) return 1;
     qm::PickArgs a{};
     a.onsets = d_on;
-    a.windows = e->d_pick_meta.p;
-    a.row_group = e->d_pick_meta.p + 3 * n;
-    a.status = e->d_pick_meta.p + 4 * n;
-    a.halfwidth = e->d_pick_val.p;
-    a.thresholds_in = threshold_mode == 1 ? e->d_pick_val.p + n : nullptr;
-    a.picks = e->d_pick_val.p + 2 * n;
+    a.windows = e->picks.meta.p;
+    a.row_group = e->picks.meta.p + 3 * n;
+    a.status = e->picks.meta.p + 4 * n;
+    a.halfwidth = e->picks.val.p;
+    a.thresholds_in = threshold_mode == 1 ? e->picks.val.p + n : nullptr;
+    a.picks = e->picks.val.p + 2 * n;
     a.n_rows = n_rows; a.T = t_samples; a.mode = threshold_mode;
     a.rate = sampling_rate; a.mad_multiplier = mad_multiplier;
     const size_t lds = qm::picks_lds_bytes(t_samples);
-    QM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&qm::pick_phases_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    QM_HIP(hipEventRecord(e->ev0, e->stream));
-    hipLaunchKernelGGL(qm::pick_phases_kernel, dim3((unsigned)n_rows), dim3(qm::kPicksThreads), lds, e->stream, a);
-    QM_HIP(hipGetLastError());
-    QM_HIP(hipEventRecord(e->ev1, e->stream));
-    e->timed = true;
+    if (timed_launches(e, [&] {
+            return launch_with_lds(e, qm::pick_phases_kernel, (unsigned)n_rows, qm::kPicksThreads, lds, a);
+        }))
+        return 1;
     QM_HIP(copy_back(picks, a.picks, n * qm::kPicksColumns * sizeof(double), e->stream));
     QM_HIP(copy_back(status, a.status, n * sizeof(int32_t), e->stream));
     QM_HIP(hipStreamSynchronize(e->stream));

@@ -77,22 +77,11 @@ int qm_engine_preprocess(qm_engine *e, const double *signals, int signals_on_dev
                            detrend, taper_left, n_left, taper_right, n_right, zero_phase))
         return 1;
     const size_t sig = (size_t)n_traces * t_samples;
-    const double *d_sig = signals;
-    if (!signals_on_device) {
-        if (e->d_sig.ensure(sig)) return 1;
-        QM_HIP(copy_in(e->d_sig.p, signals, sig * sizeof(double), e->stream));
-        d_sig = e->d_sig.p;
-    }
-    double *d_out = filtered;
-    if (!out_on_device) {
-        if (e->d_pre_out.ensure(sig)) return 1;
-        d_out = e->d_pre_out.p;
-    }
-    if (e->pre_stage.launch(e, d_sig, d_out, 1)) return 1;
-    if (!out_on_device) {
-        QM_HIP(copy_back(filtered, d_out, sig * sizeof(double), e->stream));
-        QM_HIP(hipStreamSynchronize(e->stream));
-    }
+    const double *d_sig = stage_in(e, e->staging.sig, signals, signals_on_device, sig);
+    if (!d_sig) return 1;
+    const StagedOut<double> out = stage_host_out(e->staging.pre_out, filtered, out_on_device, sig);
+    if (!out.d || e->pre_stage.launch(e, d_sig, out.d, 1) || out.fetch(e)) return 1;
+    if (!out_on_device) QM_HIP(hipStreamSynchronize(e->stream));
     return 0;
 }
 

@@ -136,25 +136,12 @@ int qm_engine_resample(qm_engine *e, const void *raw, int raw_dtype, int raw_on_
                  n_lowpass, n_sections_lp, detrend, taper_table, n_tapers, taper_weights, n_taper_weights))
         return 1;
     const size_t sig = (size_t)n_traces * t_samples;
-    const void *d_raw = raw;
-    if (!raw_on_device) {
-        if (e->d_rs_raw.ensure(rs.raw_step)) return 1;
-        QM_HIP(copy_in(e->d_rs_raw.p, raw, rs.raw_bytes, e->stream));
-        d_raw = e->d_rs_raw.p;
-    }
-    double *d_out = out;
-    if (!out_on_device) {
-        if (e->d_pre_out.ensure(sig)) return 1;
-        d_out = e->d_pre_out.p;
-    }
-    QM_HIP(hipEventRecord(e->ev0, e->stream));
-    if (rs.launch(e, d_raw, d_out, 1)) return 1;
-    QM_HIP(hipEventRecord(e->ev1, e->stream));
-    e->timed = true;
-    if (!out_on_device) {
-        QM_HIP(copy_back(out, d_out, sig * sizeof(double), e->stream));
-        QM_HIP(hipStreamSynchronize(e->stream));
-    }
+    const void *d_raw = stage_in(e, e->staging.rs_raw, raw, raw_on_device, rs.raw_step, rs.raw_bytes);
+    if (!d_raw) return 1;
+    // (the resampled traces leave through the pre-processing call's output buffer: CallStaging)
+    const StagedOut<double> res = stage_host_out(e->staging.pre_out, out, out_on_device, sig);
+    if (!res.d || timed_launches(e, [&] { return rs.launch(e, d_raw, res.d, 1); }) || res.fetch(e)) return 1;
+    if (!out_on_device) QM_HIP(hipStreamSynchronize(e->stream));
     return 0;
 }
 

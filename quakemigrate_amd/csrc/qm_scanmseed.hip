@@ -4,36 +4,6 @@
 #define QM_TU_SCANMSEED 1
 #include "qm_engine.hpp"
 
-// an event before (side 0) and after (side 1) a stage: "scanmseed_ns_<stage>"
-static int sms_mark(qm_engine *e, int stage, int side, bool (&ran)[qm::kSmsStages]) {
-    while (e->sms_ev.size() < 2 * (size_t)qm::kSmsStages) {
-        Event ev;
-        QM_HIP(ev.create());
-        e->sms_ev.push_back(std::move(ev));
-    }
-    QM_HIP(hipEventRecord(e->sms_ev[2 * stage + side], e->stream));
-    if (side) ran[stage] = true;
-    return 0;
-}
-#define QM_SMS_STAGE(stage, ...)                               \
-    do {                                                       \
-        if (sms_mark(e, stage, 0, ran)) return 1;              \
-        __VA_ARGS__;                                           \
-        QM_HIP(hipGetLastError());                             \
-        if (sms_mark(e, stage, 1, ran)) return 1;              \
-    } while (0)
-
-static int sms_times(qm_engine *e, const bool (&ran)[qm::kSmsStages]) {
-    for (int st = 0; st < qm::kSmsStages; ++st) {
-        e->sms_ns[st] = 0;
-        if (!ran[st]) continue;
-        float ms = 0.0f;
-        QM_HIP(hipEventElapsedTime(&ms, e->sms_ev[2 * st], e->sms_ev[2 * st + 1]));
-        e->sms_ns[st] = (int64_t)((double)ms * 1e6);
-    }
-    return 0;
-}
-
 static const char *const kSmsChannelNames[qm::kSmsChannels] = {"COA", "COA_N", "X", "Y", "Z"};
 constexpr unsigned long long kSmsNone = ~0ull;
 
@@ -63,104 +33,100 @@ int qm_engine_scanmseed_encode(qm_engine *e, const void *series, int series_dtyp
     const size_t N = (size_t)n, all = qm::kSmsChannels * N;
     const int tiles = (int)((N + qm::kSmsTile - 1) / qm::kSmsTile);
     const size_t all_tiles = (size_t)qm::kSmsChannels * tiles;
-    if (e->d_sms_bytes.ensure(2 * all) || e->d_sms_map.ensure(all_tiles * qm::kSmsMaxCount) ||
-        e->d_sms_tile.ensure(2 * all_tiles) || e->d_sms_tot.ensure(2 * qm::kSmsChannels + qm::kSmsErrSlots))
+    if (e->sms.bytes.ensure(2 * all) || e->sms.map.ensure(all_tiles * qm::kSmsMaxCount) ||
+        e->sms.tile.ensure(2 * all_tiles) || e->sms.tot.ensure(2 * qm::kSmsChannels + qm::kSmsErrSlots))
         return 1;
-    unsigned long long *d_tot = e->d_sms_tot.p, *d_err = d_tot + 2 * qm::kSmsChannels;
+    unsigned long long *d_tot = e->sms.tot.p, *d_err = d_tot + 2 * qm::kSmsChannels;
     QM_HIP(hipMemsetAsync(d_err, 0xff, qm::kSmsErrSlots * sizeof(unsigned long long), e->stream));
 
-    bool ran[qm::kSmsStages] = {};
-    const int32_t *d_x = nullptr;
+    // the stage clock always runs, and it rewrites its six times only at the end of a call that gets as far as
+    // collect(): a refused call leaves the times of the call before
+    auto &clock = e->sms.clock;
+    clock.begin(true, false);
+    hipStream_t s = e->stream;
     const bool is_float = series_dtype == 1;
+    const double *d_in = nullptr;                       // float64: the series to quantise into sms.x
+    const int32_t *d_x = nullptr;
     if (is_float) {
-        const double *d_in = static_cast<const double *>(series);
-        if (!series_on_device) {
-            if (e->d_sms_f.ensure(all)) return 1;
-            QM_HIP(copy_in(e->d_sms_f.p, series, all * sizeof(double), e->stream));
-            d_in = e->d_sms_f.p;
-        }
-        if (e->d_sms_x.ensure(all)) return 1;
-        QM_HIP(hipEventRecord(e->ev0, e->stream));
-        qm::SmsQuantArgs q{};
-        q.in = d_in; q.out = e->d_sms_x.p; q.n = (int)n; q.err = d_err;
-        for (int c = 0; c < qm::kSmsChannels; ++c) {
-            q.factor[c] = factors[c];
-            q.clip[c] = clips[c];
-        }
-        const unsigned blocks = (unsigned)std::min<size_t>((N + qm::kSmsThreads - 1) / qm::kSmsThreads, 4096);
-        QM_SMS_STAGE(qm::kSmsQuantise, hipLaunchKernelGGL(qm::sms_quantise_kernel, dim3(blocks, qm::kSmsChannels),
-                                                           dim3(qm::kSmsThreads), 0, e->stream, q));
-        d_x = e->d_sms_x.p;
-    } else if (series_on_device) {
-        d_x = static_cast<const int32_t *>(series);
-        QM_HIP(hipEventRecord(e->ev0, e->stream));
+        d_in = stage_in(e, e->sms.f, static_cast<const double *>(series), series_on_device, all);
+        d_x = d_in && !e->sms.x.ensure(all) ? e->sms.x.p : nullptr;
     } else {
-        if (e->d_sms_x.ensure(all)) return 1;
-        QM_HIP(copy_in(e->d_sms_x.p, series, all * sizeof(int32_t), e->stream));
-        d_x = e->d_sms_x.p;
-        QM_HIP(hipEventRecord(e->ev0, e->stream));
+        d_x = stage_in(e, e->sms.x, static_cast<const int32_t *>(series), series_on_device, all);
     }
+    if (!d_x) return 1;
 
     qm::SmsEncodeArgs a{};
     a.x = d_x; a.n = (int)n; a.tiles = tiles;
-    a.count = e->d_sms_bytes.p; a.codes = e->d_sms_bytes.p + all;
-    a.map = e->d_sms_map.p;
-    a.entry = e->d_sms_tile.p; a.word0 = e->d_sms_tile.p + all_tiles;
+    a.count = e->sms.bytes.p; a.codes = e->sms.bytes.p + all;
+    a.map = e->sms.map.p;
+    a.entry = e->sms.tile.p; a.word0 = e->sms.tile.p + all_tiles;
     a.totals = d_tot; a.err = d_err;
-    QM_SMS_STAGE(qm::kSmsScan, hipLaunchKernelGGL(qm::sms_scan_kernel, dim3((unsigned)tiles, qm::kSmsChannels),
-                                                   dim3(qm::kSmsThreads), 0, e->stream, a));
-    QM_SMS_STAGE(qm::kSmsCompose, hipLaunchKernelGGL(qm::sms_compose_kernel, dim3(qm::kSmsChannels),
-                                                      dim3(qm::kSmsThreads), 0, e->stream, a));
     unsigned long long h[2 * qm::kSmsChannels + qm::kSmsErrSlots];
-    QM_HIP(copy_back(h, d_tot, sizeof(h), e->stream));
-    const unsigned long long *h_err = h + 2 * qm::kSmsChannels;
-    auto where = [&](unsigned long long at, const char **ch, long long *pos) {
-        *ch = kSmsChannelNames[at / N];
-        *pos = (long long)(at % N);
+    size_t R = 0;
+    const dim3 per_tile((unsigned)tiles, qm::kSmsChannels), threads(qm::kSmsThreads);
+    const auto sequence = [&]() -> int {
+        if (is_float) {
+            qm::SmsQuantArgs q{};
+            q.in = d_in; q.out = e->sms.x.p; q.n = (int)n; q.err = d_err;
+            for (int c = 0; c < qm::kSmsChannels; ++c) {
+                q.factor[c] = factors[c];
+                q.clip[c] = clips[c];
+            }
+            const unsigned blocks = (unsigned)std::min<size_t>((N + qm::kSmsThreads - 1) / qm::kSmsThreads, 4096);
+            if (clock.launch(s, qm::kSmsQuantise, qm::sms_quantise_kernel, dim3(blocks, qm::kSmsChannels), threads, 0, q))
+                return 1;
+        }
+        if (clock.launch(s, qm::kSmsScan, qm::sms_scan_kernel, per_tile, threads, 0, a) ||
+            clock.launch(s, qm::kSmsCompose, qm::sms_compose_kernel, dim3(qm::kSmsChannels), threads, 0, a))
+            return 1;
+        QM_HIP(copy_back(h, d_tot, sizeof(h), s));
+        const unsigned long long *h_err = h + 2 * qm::kSmsChannels;
+        auto where = [&](unsigned long long at, const char **ch, long long *pos) {
+            *ch = kSmsChannelNames[at / N];
+            *pos = (long long)(at % N);
+        };
+        const char *ch;
+        long long pos;
+        if (h_err[qm::kSmsErrNaN] != kSmsNone) {
+            where(h_err[qm::kSmsErrNaN], &ch, &pos);
+            return fail("%s: channel %s, sample %lld is NaN: not quantised (NumPy's cast to int32 is platform-defined there)",
+                        what, ch, pos);
+        }
+        if (h_err[qm::kSmsErrRange] != kSmsNone) {
+            where(h_err[qm::kSmsErrRange], &ch, &pos);
+            return fail("%s: channel %s, sample %lld: the scaled value is outside int32: not quantised (NumPy's cast to "
+                        "int32 is platform-defined there)", what, ch, pos);
+        }
+        if (h_err[qm::kSmsErrDiff] != kSmsNone) {
+            where(h_err[qm::kSmsErrDiff], &ch, &pos);
+            return fail("%s: channel %s, sample %lld: difference does not fit 30 bits: not STEIM2-encodable", what, ch,
+                        pos);
+        }
+        int64_t total = 0;
+        for (int c = 0; c < qm::kSmsChannels; ++c) {
+            a.rec_off[c] = (int)total;
+            a.words[c] = (int)h[c];
+            total += (int64_t)h[qm::kSmsChannels + c];
+        }
+        a.rec_off[qm::kSmsChannels] = (int)total;
+        if (total > max_records)
+            return fail("%s: %lld records, the output has room for %lld (max_records)", what, (long long)total,
+                        (long long)max_records);
+        R = (size_t)total;
+        if (e->sms.out.ensure(R * qm::kSmsRecU32) || e->sms.rec.ensure(2 * R)) return 1;
+        a.out = e->sms.out.p;
+        a.rec_first = e->sms.rec.p;
+        a.rec_count = e->sms.rec.p + R;
+        QM_HIP(hipMemsetAsync(a.out, 0, R * qm::kSmsRecLen, s));
+        return clock.launch(s, qm::kSmsPack, qm::sms_pack_kernel, per_tile, threads, 0, a) ||
+               clock.launch(s, qm::kSmsFrame, qm::sms_frame_kernel, dim3((unsigned)R), dim3(64), 0, a);
     };
-    const char *ch;
-    long long pos;
-    if (h_err[qm::kSmsErrNaN] != kSmsNone) {
-        where(h_err[qm::kSmsErrNaN], &ch, &pos);
-        return fail("%s: channel %s, sample %lld is NaN: not quantised (NumPy's cast to int32 is platform-defined there)",
-                    what, ch, pos);
-    }
-    if (h_err[qm::kSmsErrRange] != kSmsNone) {
-        where(h_err[qm::kSmsErrRange], &ch, &pos);
-        return fail("%s: channel %s, sample %lld: the scaled value is outside int32: not quantised (NumPy's cast to "
-                    "int32 is platform-defined there)", what, ch, pos);
-    }
-    if (h_err[qm::kSmsErrDiff] != kSmsNone) {
-        where(h_err[qm::kSmsErrDiff], &ch, &pos);
-        return fail("%s: channel %s, sample %lld: difference does not fit 30 bits: not STEIM2-encodable", what, ch,
-                    pos);
-    }
-    int64_t total = 0;
-    for (int c = 0; c < qm::kSmsChannels; ++c) {
-        a.rec_off[c] = (int)total;
-        a.words[c] = (int)h[c];
-        total += (int64_t)h[qm::kSmsChannels + c];
-    }
-    a.rec_off[qm::kSmsChannels] = (int)total;
-    if (total > max_records)
-        return fail("%s: %lld records, the output has room for %lld (max_records)", what, (long long)total,
-                    (long long)max_records);
-    const size_t R = (size_t)total;
-    if (e->d_sms_out.ensure(R * qm::kSmsRecU32) || e->d_sms_rec.ensure(2 * R)) return 1;
-    a.out = e->d_sms_out.p;
-    a.rec_first = e->d_sms_rec.p;
-    a.rec_count = e->d_sms_rec.p + R;
-    QM_HIP(hipMemsetAsync(a.out, 0, R * qm::kSmsRecLen, e->stream));
-    QM_SMS_STAGE(qm::kSmsPack, hipLaunchKernelGGL(qm::sms_pack_kernel, dim3((unsigned)tiles, qm::kSmsChannels),
-                                                   dim3(qm::kSmsThreads), 0, e->stream, a));
-    QM_SMS_STAGE(qm::kSmsFrame, hipLaunchKernelGGL(qm::sms_frame_kernel, dim3((unsigned)R), dim3(64), 0, e->stream, a));
-    QM_HIP(hipEventRecord(e->ev1, e->stream));
-    e->timed = true;
+    if (timed_launches(e, sequence)) return 1;
     QM_HIP(copy_back(records, a.out, R * qm::kSmsRecLen, e->stream));
     QM_HIP(copy_back(rec_first, a.rec_first, R * sizeof(int32_t), e->stream));
     QM_HIP(copy_back(rec_count, a.rec_count, R * sizeof(int32_t), e->stream));
     QM_HIP(hipStreamSynchronize(e->stream));
-    if (sms_times(e, ran)) return 1;
+    if (clock.collect()) return 1;
     for (int c = 0; c < qm::kSmsChannels; ++c) n_records[c] = (int64_t)h[qm::kSmsChannels + c];
     return 0;
 }
@@ -190,33 +156,35 @@ int qm_engine_scanmseed_decode(qm_engine *e, const uint8_t *records, int64_t n_r
     DeviceGuard guard(e->device);
     const size_t R = (size_t)n_records, NT = (size_t)n_total;
     const bool want_f = out_f64 != nullptr;
-    if (e->d_sms_out.ensure(R * qm::kSmsRecU32) || e->d_sms_rec.ensure(R) || e->d_sms_off.ensure(R) ||
-        e->d_sms_tot.ensure(2 * qm::kSmsChannels + qm::kSmsErrSlots))
+    if (e->sms.out.ensure(R * qm::kSmsRecU32) || e->sms.rec.ensure(R) || e->sms.off.ensure(R) ||
+        e->sms.tot.ensure(2 * qm::kSmsChannels + qm::kSmsErrSlots))
         return 1;
-    if (want_f && e->d_sms_fac.ensure(R)) return 1;
-    if (!out_on_device && (e->d_sms_x.ensure(NT) || (want_f && e->d_sms_f.ensure(NT)))) return 1;
-    unsigned long long *d_err = e->d_sms_tot.p + 2 * qm::kSmsChannels;
+    if (want_f && e->sms.fac.ensure(R)) return 1;
+    const StagedOut<int32_t> ints = stage_host_out(e->sms.x, out, out_on_device, NT);
+    StagedOut<double> floats;                           // (no out_f64: nothing staged, floats.d stays NULL)
+    if (!ints.d || (want_f && !(floats = stage_host_out(e->sms.f, out_f64, out_on_device, NT)).d)) return 1;
+    unsigned long long *d_err = e->sms.tot.p + 2 * qm::kSmsChannels;
     QM_HIP(hipMemsetAsync(d_err, 0xff, qm::kSmsErrSlots * sizeof(unsigned long long), e->stream));
-    QM_HIP(copy_in(e->d_sms_out.p, records, R * qm::kSmsRecLen, e->stream));
-    QM_HIP(copy_in(e->d_sms_rec.p, rec_samples, R * sizeof(int32_t), e->stream));
-    QM_HIP(copy_in(e->d_sms_off.p, rec_offset, R * sizeof(int64_t), e->stream));
-    if (want_f) QM_HIP(copy_in(e->d_sms_fac.p, rec_factor, R * sizeof(double), e->stream));
+    QM_HIP(copy_in(e->sms.out.p, records, R * qm::kSmsRecLen, e->stream));
+    QM_HIP(copy_in(e->sms.rec.p, rec_samples, R * sizeof(int32_t), e->stream));
+    QM_HIP(copy_in(e->sms.off.p, rec_offset, R * sizeof(int64_t), e->stream));
+    if (want_f) QM_HIP(copy_in(e->sms.fac.p, rec_factor, R * sizeof(double), e->stream));
 
     qm::SmsDecodeArgs a{};
-    a.rec = e->d_sms_out.p; a.rec_n = e->d_sms_rec.p; a.rec_out = e->d_sms_off.p;
-    a.rec_factor = want_f ? e->d_sms_fac.p : nullptr;
-    a.out = out_on_device ? out : e->d_sms_x.p;
-    a.outf = !want_f ? nullptr : out_on_device ? out_f64 : e->d_sms_f.p;
+    a.rec = e->sms.out.p; a.rec_n = e->sms.rec.p; a.rec_out = e->sms.off.p;
+    a.rec_factor = want_f ? e->sms.fac.p : nullptr;
+    a.out = ints.d;
+    a.outf = floats.d;
     a.err = d_err;
-    bool ran[qm::kSmsStages] = {};
-    QM_HIP(hipEventRecord(e->ev0, e->stream));
-    QM_SMS_STAGE(qm::kSmsDecode, hipLaunchKernelGGL(qm::sms_decode_kernel, dim3((unsigned)R), dim3(qm::kSmsThreads), 0,
-                                                     e->stream, a));
-    QM_HIP(hipEventRecord(e->ev1, e->stream));
-    e->timed = true;
+    auto &clock = e->sms.clock;
+    clock.begin(true, false);                           // (as in encode: always on, times rewritten by collect() only)
+    if (timed_launches(e, [&] {
+            return clock.launch(e->stream, qm::kSmsDecode, qm::sms_decode_kernel, dim3((unsigned)R), dim3(qm::kSmsThreads), 0, a);
+        }))
+        return 1;
     unsigned long long h_err[qm::kSmsErrSlots];
     QM_HIP(copy_back(h_err, d_err, sizeof(h_err), e->stream));
-    if (sms_times(e, ran)) return 1;
+    if (clock.collect()) return 1;
     const unsigned long long bad = h_err[qm::kSmsErrDecode];
     if (bad != kSmsNone) {
         const long long r = (long long)(bad / 4);
@@ -226,11 +194,8 @@ int qm_engine_scanmseed_decode(qm_engine *e, const uint8_t *records, int64_t n_r
             default: return fail("%s: record %lld: STEIM2 reverse integration constant mismatch", what, r);
         }
     }
-    if (!out_on_device) {
-        QM_HIP(copy_back(out, e->d_sms_x.p, NT * sizeof(int32_t), e->stream));
-        if (want_f) QM_HIP(copy_back(out_f64, e->d_sms_f.p, NT * sizeof(double), e->stream));
-        QM_HIP(hipStreamSynchronize(e->stream));
-    }
+    if (ints.fetch(e) || floats.fetch(e)) return 1;
+    if (!out_on_device) QM_HIP(hipStreamSynchronize(e->stream));
     return 0;
 }
 

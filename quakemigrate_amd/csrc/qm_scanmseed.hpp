@@ -63,6 +63,7 @@ enum SmsErr : int { kSmsErrNaN = 0, kSmsErrRange, kSmsErrDiff, kSmsErrDecode, kS
 enum SmsDecodeKind : int { kSmsBadCode = 0, kSmsShort = 1, kSmsMismatch = 2 };
 // the stages "scanmseed_ns_<stage>" times: encode's five launches, the decode launch
 enum SmsStage : int { kSmsQuantise = 0, kSmsScan, kSmsCompose, kSmsPack, kSmsFrame, kSmsDecode, kSmsStages };
+inline constexpr const char *const kSmsStageNames[kSmsStages] = {"quantise", "scan", "compose", "pack", "frame", "decode"};
 
 struct SmsQuantArgs {
     const double *in;               // [5][n]

@@ -6,14 +6,14 @@
 
 // fold the per-step outcomes that have reached the host into the counters (synchronises)
 int drain_flags(qm_engine *e) {
-    if (e->flags_pending == 0) return 0;
+    if (e->sweep.flags_pending == 0) return 0;
     QM_HIP(hipStreamSynchronize(e->stream));
-    for (; e->flags_pending > 0; --e->flags_pending) {
-        const int32_t *f = e->h_flags.p + 2 * e->flags_head;
-        if (f[0] != 0) ++e->fallback_steps;
-        else ++e->screened_steps;
-        e->last_candidates = f[1];
-        e->flags_head = (e->flags_head + 1) % kFlagRing;
+    for (; e->sweep.flags_pending > 0; --e->sweep.flags_pending) {
+        const int32_t *f = e->sweep.h_flags.p + 2 * e->sweep.flags_head;
+        if (f[0] != 0) ++e->sweep.fallback_steps;
+        else ++e->sweep.screened_steps;
+        e->sweep.last_candidates = f[1];
+        e->sweep.flags_head = (e->sweep.flags_head + 1) % kFlagRing;
     }
     return 0;
 }
@@ -57,11 +57,11 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
     const int JP = plan.jp;
     if (JP == 0) return 0;
     if (ensure_screen_tables(e, plan)) return 1;
-    e->last_plan_jp = plan.jp;
-    e->last_plan_big = plan.big ? 1 : 0;
+    e->sweep.last_plan_jp = plan.jp;
+    e->sweep.last_plan_big = plan.big ? 1 : 0;
     const ScreenLayout &L = e->screen;                  // the sweep's bricks, those that do not fit: direct kernel
     const qm::GridDesc &g = L.g;
-    if (e->h_flags.ensure(2 * kFlagRing, hipHostMallocDefault)) return 1;
+    if (e->sweep.h_flags.ensure(2 * kFlagRing, hipHostMallocDefault)) return 1;
     const int KT = 128 * JP;
     const int ntiles = (ns + KT - 1) / KT;
     const int64_t ns_pad = (int64_t)ntiles * KT;
@@ -77,13 +77,13 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
                      : 0;
     const int sets = groups_direct + 1;
     constexpr int kGroupsPerBlock = 32;
-    if (e->d_onq.ensure((size_t)S * T) || e->d_rowmax.ensure(S) || e->d_sparams.ensure(4) ||
-        e->d_cell.ensure((size_t)g.nbricks * ns_pad) ||
-        e->d_gmax.ensure((size_t)std::max(1, groups) * ns_pad) || e->d_pm.ensure(ns) || e->d_ssum.ensure((size_t)std::max(1, groups) * ns) ||
-        e->d_counts.ensure(ns) || e->d_cells.ensure((size_t)ns * qm::kScreenSlots) ||
-        e->d_work.ensure((size_t)ns * qm::kScreenSlots) ||
-        e->d_flags.ensure(4) || e->d_cand_z.ensure((size_t)ns * qm::kScreenSlots) ||
-        e->d_cand_idx.ensure((size_t)ns * qm::kScreenSlots))
+    if (e->sweep.onq.ensure((size_t)S * T) || e->sweep.rowmax.ensure(S) || e->sweep.sparams.ensure(4) ||
+        e->sweep.cell.ensure((size_t)g.nbricks * ns_pad) ||
+        e->sweep.gmax.ensure((size_t)std::max(1, groups) * ns_pad) || e->sweep.pm.ensure(ns) || e->sweep.ssum.ensure((size_t)std::max(1, groups) * ns) ||
+        e->sweep.counts.ensure(ns) || e->sweep.cells.ensure((size_t)ns * qm::kScreenSlots) ||
+        e->sweep.work.ensure((size_t)ns * qm::kScreenSlots) ||
+        e->sweep.flags.ensure(4) || e->sweep.cand_z.ensure((size_t)ns * qm::kScreenSlots) ||
+        e->sweep.cand_idx.ensure((size_t)ns * qm::kScreenSlots))
         return 1;
     const size_t need = (size_t)sets * ns;
     if (e->d_pmax.ensure(need) || e->d_psum.ensure(need) || e->d_pidx.ensure(need)) return 1;
@@ -91,19 +91,19 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     if (timing_events(e, &ev_begin, &ev_end)) return 1;
     hipStream_t s = e->stream;
-    QM_HIP(hipMemsetAsync(e->d_counts.p, 0, (size_t)ns * sizeof(int32_t), s));
-    QM_HIP(hipMemsetAsync(e->d_flags.p, 0, 4 * sizeof(int32_t), s));
+    QM_HIP(hipMemsetAsync(e->sweep.counts.p, 0, (size_t)ns * sizeof(int32_t), s));
+    QM_HIP(hipMemsetAsync(e->sweep.flags.p, 0, 4 * sizeof(int32_t), s));
     // this step's fixed-point scale (device-side: max |L| -> k) and the quantised log-onsets
     hipLaunchKernelGGL(qm::screen_rowmax_kernel, dim3(S), dim3(256), 0, s, d_onsets, T,
-                       e->d_rowmax.p);
+                       e->sweep.rowmax.p);
     hipLaunchKernelGGL(qm::screen_quantise_kernel, dim3(S), dim3(256), 0, s, d_onsets, T, S,
-                       available, (const double *)e->d_rowmax.p, e->d_onq.p,
-                       reinterpret_cast<qm::ScreenParams *>(e->d_sparams.p), e->d_flags.p);
+                       available, (const double *)e->sweep.rowmax.p, e->sweep.onq.p,
+                       reinterpret_cast<qm::ScreenParams *>(e->sweep.sparams.p), e->sweep.flags.p);
     QM_HIP(hipGetLastError());
 
     qm::ScreenArgs a{};
     a.g = g;
-    a.onsets_q = e->d_onq.p;
+    a.onsets_q = e->sweep.onq.p;
     a.rel = L.rel.p;
     a.brick_meta = L.meta.p;
     a.brick_total = L.total.p;
@@ -113,11 +113,11 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
     a.ntiles = ntiles;
     a.ngroups = groups;
     a.window_bytes = plan.window_bytes(e);
-    a.params = reinterpret_cast<const qm::ScreenParams *>(e->d_sparams.p);
-    a.cell_max = e->d_cell.p;
-    a.group_max = e->d_gmax.p;
+    a.params = reinterpret_cast<const qm::ScreenParams *>(e->sweep.sparams.p);
+    a.cell_max = e->sweep.cell.p;
+    a.group_max = e->sweep.gmax.p;
     a.ns_pad = ns_pad;
-    a.part_sum = e->d_ssum.p;
+    a.part_sum = e->sweep.ssum.p;
     QM_HIP(hipEventRecord(ev_begin, s));               // the timing log brackets the sweep kernel
     if (groups > 0) {
         const size_t lds = (size_t)plan.lds_bytes(e);
@@ -159,13 +159,13 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
     }
     const unsigned tcols = (unsigned)((ns + 63) / 64);
     hipLaunchKernelGGL(qm::screen_peak_kernel, dim3(tcols), dim3(256), 0, s,
-                       (const int32_t *)e->d_gmax.p, ns_pad, ns, groups, e->d_pm.p);
+                       (const int32_t *)e->sweep.gmax.p, ns_pad, ns, groups, e->sweep.pm.p);
     hipLaunchKernelGGL(qm::screen_candidates_kernel,
                        dim3(tcols, (unsigned)std::max(1, (groups + kGroupsPerBlock - 1) / kGroupsPerBlock)),
-                       dim3(256), 0, s, (const int32_t *)e->d_cell.p, (const int32_t *)e->d_gmax.p,
-                       ns_pad, ns, g.nbricks, groups, kGroupsPerBlock, (const int32_t *)e->d_pm.p,
-                       reinterpret_cast<const qm::ScreenParams *>(e->d_sparams.p), e->d_counts.p,
-                       e->d_cells.p, e->d_work.p, e->d_flags.p);
+                       dim3(256), 0, s, (const int32_t *)e->sweep.cell.p, (const int32_t *)e->sweep.gmax.p,
+                       ns_pad, ns, g.nbricks, groups, kGroupsPerBlock, (const int32_t *)e->sweep.pm.p,
+                       reinterpret_cast<const qm::ScreenParams *>(e->sweep.sparams.p), e->sweep.counts.p,
+                       e->sweep.cells.p, e->sweep.work.p, e->sweep.flags.p);
     QM_HIP(hipGetLastError());
     qm::RefineArgs r{};
     r.g = g;
@@ -175,15 +175,15 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
     r.fsmp = fsmp;
     r.n_samples = ns;
     r.z_scale = 1.4426950408889634074 / (double)available;
-    r.cells = e->d_cells.p;
-    r.work = e->d_work.p;
-    r.flags = e->d_flags.p;
-    r.cand_z = e->d_cand_z.p;
-    r.cand_idx = e->d_cand_idx.p;
+    r.cells = e->sweep.cells.p;
+    r.work = e->sweep.work.p;
+    r.flags = e->sweep.flags.p;
+    r.cand_z = e->sweep.cand_z.p;
+    r.cand_idx = e->sweep.cand_idx.p;
     hipLaunchKernelGGL(qm::screen_refine_kernel, dim3((unsigned)(8 * e->n_cu)), dim3(256), 0, s, r);
     hipLaunchKernelGGL(qm::screen_collect_kernel, dim3((ns + 63) / 64), dim3(256), 0, s,
-                       (const int32_t *)e->d_counts.p, (const double *)e->d_cand_z.p,
-                       (const int64_t *)e->d_cand_idx.p, (const double *)e->d_ssum.p, groups, ns,
+                       (const int32_t *)e->sweep.counts.p, (const double *)e->sweep.cand_z.p,
+                       (const int64_t *)e->sweep.cand_idx.p, (const double *)e->sweep.ssum.p, groups, ns,
                        e->d_pmax.p + (size_t)groups_direct * ns,
                        e->d_pidx.p + (size_t)groups_direct * ns,
                        e->d_psum.p + (size_t)groups_direct * ns);
@@ -191,10 +191,10 @@ int run_screen(qm_engine *e, const double *d_onsets, int T, int fsmp, int ns, in
     e->timed = !e->cfg.log_timing;
     // the outcome travels to the host asynchronously (statistics only: the decision to redo the
     // step in float64 is taken on the device, see detect_core)
-    if (e->flags_pending == kFlagRing && drain_flags(e)) return 1;
-    QM_HIP(hipMemcpyAsync(e->h_flags.p + 2 * ((e->flags_head + e->flags_pending) % kFlagRing),
-                          e->d_flags.p, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    ++e->flags_pending;
+    if (e->sweep.flags_pending == kFlagRing && drain_flags(e)) return 1;
+    QM_HIP(hipMemcpyAsync(e->sweep.h_flags.p + 2 * ((e->sweep.flags_head + e->sweep.flags_pending) % kFlagRing),
+                          e->sweep.flags.p, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    ++e->sweep.flags_pending;
     *n_sets = sets;
     *screened = true;
     return 0;
@@ -208,12 +208,12 @@ int qm_exp2f_max_error(qm_engine *e, float lo, float hi, double *max_rel_error) 
         return fail("qm_exp2f_max_error: need lo <= hi of one sign");
     DeviceGuard guard(e->device);
     constexpr int kBlocks = 4096;
-    if (e->d_fit_part.ensure(kBlocks)) return 1;
+    if (e->fit.part.ensure(kBlocks)) return 1;
     hipLaunchKernelGGL(qm::exp2f_error_kernel, dim3(kBlocks), dim3(256), 0, e->stream, lo, hi,
-                       e->d_fit_part.p);
+                       e->fit.part.p);
     QM_HIP(hipGetLastError());
     std::vector<double> h(kBlocks);
-    QM_HIP(copy_back(h.data(), e->d_fit_part.p, kBlocks * sizeof(double), e->stream));
+    QM_HIP(copy_back(h.data(), e->fit.part.p, kBlocks * sizeof(double), e->stream));
     QM_HIP(hipStreamSynchronize(e->stream));
     *max_rel_error = *std::max_element(h.begin(), h.end());
     return 0;

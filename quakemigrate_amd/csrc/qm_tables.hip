@@ -334,7 +334,7 @@ static int build_shift_tables(qm_engine *e, ShiftLayout &L, bool wide, bool wide
         if (L.raw.ensure(4 * br) || L.meta.ensure(4 * nvb * sb + 1024) ||
             L.total.ensure(nvb) || L.fit.ensure(nvb) || e->d_scalar.ensure(12))
             return 1;
-        if (wide && (L.wmeta.ensure(4 * nvb * sb + 1024) || L.wtotal.ensure(nvb) || e->d_work.ensure(nvb))) return 1;
+        if (wide && (L.wmeta.ensure(4 * nvb * sb + 1024) || L.wtotal.ensure(nvb) || e->sweep.work.ensure(nvb))) return 1;
         QM_HIP(hipMemsetAsync(e->d_scalar.p, 0, 12 * sizeof(int32_t), e->stream));
         hipLaunchKernelGGL(qm::brick_minmax_kernel, dim3(g.nbricks), dim3(64), 0, e->stream, g,
                            e->d_lut.p, reinterpret_cast<int4 *>(L.raw.p), e->d_scalar.p);
@@ -361,12 +361,12 @@ static int build_shift_tables(qm_engine *e, ShiftLayout &L, bool wide, bool wide
             QM_HIP(hipMemsetAsync(tally_d, 0, sizeof(tally), e->stream));
             hipLaunchKernelGGL(qm::shift_need_kernel, dim3((unsigned)nvb), dim3(256), 0, e->stream, g,
                                e->d_lut.p, reinterpret_cast<const int4 *>(L.raw.p),
-                               reinterpret_cast<int4 *>(L.wmeta.p), L.wtotal.p, e->d_work.p, tally_d,
+                               reinterpret_cast<int4 *>(L.wmeta.p), L.wtotal.p, e->sweep.work.p, tally_d,
                                blocks ? qm::kShiftPlane : qm::kShiftLdsBytes8 / 2, nblk, sb, 1);   // (a half holds
                                // 2 x kShiftPlane bytes, as for the two-plane blocks: the launch's 163712 bytes)
             QM_HIP(hipGetLastError());
             fitw.resize(nvb);
-            QM_HIP(copy_back(fitw.data(), e->d_work.p, nvb * sizeof(int32_t), e->stream));
+            QM_HIP(copy_back(fitw.data(), e->sweep.work.p, nvb * sizeof(int32_t), e->stream));
             QM_HIP(copy_back(tally, tally_d, sizeof(tally), e->stream));
             QM_HIP(hipStreamSynchronize(e->stream));
             L.wquads = (int64_t)tally[0];

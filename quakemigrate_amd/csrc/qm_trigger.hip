@@ -4,26 +4,6 @@
 #define QM_TU_TRIGGER 1
 #include "qm_engine.hpp"
 
-// "trigger_timing": an event before (side 0) and after (side 1) a stage of the sequence
-static int trig_mark(qm_engine *e, int stage, int side, bool (&ran)[qm::kTrigStages]) {
-    if (!e->cfg.trigger_timing) return 0;
-    while (e->trg_ev.size() < 2 * (size_t)qm::kTrigStages) {
-        Event ev;
-        QM_HIP(ev.create());
-        e->trg_ev.push_back(std::move(ev));
-    }
-    QM_HIP(hipEventRecord(e->trg_ev[2 * stage + side], e->stream));
-    if (side) ran[stage] = true;
-    return 0;
-}
-#define QM_TRIG_STAGE(stage, ...)                              \
-    do {                                                       \
-        if (trig_mark(e, stage, 0, ran)) return 1;             \
-        __VA_ARGS__;                                           \
-        QM_HIP(hipGetLastError());                             \
-        if (trig_mark(e, stage, 1, ran)) return 1;             \
-    } while (0)
-
 // the two public calls: `resident` -- the series are on the engine's GPU already (device to device on the stream)
 static int trigger_run(qm_engine *e, const char *what, bool resident, const double *coa, const double *coa_n, int64_t n,
                        const qm_trigger_params *p, int64_t max_events, int64_t *n_candidates, int64_t *n_events,
@@ -62,10 +42,10 @@ static int trigger_run(qm_engine *e, const char *what, bool resident, const doub
     const int chunk = dynamic ? (int)std::min<int64_t>(p->chunk_samples, n) : (int)n;
     const size_t n_chunks = (N + chunk - 1) / chunk;
     const int nblocks = (int)((N + qm::kTrigRunBlock - 1) / qm::kTrigRunBlock);
-    if (e->d_trg_x.ensure(smooth ? 4 * N : 2 * N) || e->d_trg_par.ensure((size_t)r + 1 + n_chunks) ||
-        e->d_trg_cnt.ensure(5 * (size_t)nblocks) || e->d_trg_tot.ensure(4))
+    if (e->trig.x.ensure(smooth ? 4 * N : 2 * N) || e->trig.par.ensure((size_t)r + 1 + n_chunks) ||
+        e->trig.cnt.ensure(5 * (size_t)nblocks) || e->trig.tot.ensure(4))
         return 1;
-    double *d_raw = e->d_trg_x.p, *d_w = e->d_trg_par.p, *d_thr = e->d_trg_par.p + r + 1;
+    double *d_raw = e->trig.x.p, *d_w = e->trig.par.p, *d_thr = e->trig.par.p + r + 1;
     if (resident) {
         QM_HIP(hipMemcpyAsync(d_raw, coa, N * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
         QM_HIP(hipMemcpyAsync(d_raw + N, coa_n, N * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
@@ -76,94 +56,89 @@ static int trigger_run(qm_engine *e, const char *what, bool resident, const doub
     if (smooth) QM_HIP(copy_in(d_w, p->smooth_weights, ((size_t)r + 1) * sizeof(double), e->stream));
     if (!dynamic) QM_HIP(copy_in(d_thr, &p->threshold_value, sizeof(double), e->stream));
 
-    bool ran[qm::kTrigStages] = {};
-    for (int64_t &ns : e->trg_ns) ns = 0;
-    QM_HIP(hipEventRecord(e->ev0, e->stream));
-    const double *d_series = d_raw;
-    if (smooth) {
-        qm::TrigSmoothArgs a{d_raw, d_w, d_raw + 2 * N, (int)n, r};
-        const size_t lds = qm::trig_smooth_lds_bytes(r);
-        QM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&qm::trig_smooth_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const unsigned tiles = (unsigned)((N + qm::kTrigSmoothTile - 1) / qm::kTrigSmoothTile);
-        QM_TRIG_STAGE(qm::kTrigSmooth, hipLaunchKernelGGL(qm::trig_smooth_kernel, dim3(tiles, 2),
-                                                           dim3(qm::kTrigSmoothThreads), lds, e->stream, a));
-        d_series = d_raw + 2 * N;
-    }
-    const double *d_coa = d_series, *d_coa_n = d_series + N;
-    const double *d_trig = p->trigger_on ? d_coa_n : d_coa;
-    if (dynamic) {
-        qm::TrigStatArgs a{d_trig, d_thr, (int)n, chunk, p->threshold_method, p->threshold_value};
-        const int threads = chunk <= qm::kTrigStatSmall ? 256 : qm::kTrigStatThreads;
-        QM_TRIG_STAGE(qm::kTrigStats, hipLaunchKernelGGL(qm::trig_stat_kernel, dim3((unsigned)n_chunks), dim3(threads),
-                                                          0, e->stream, a));
-    }
-    qm::TrigRunArgs ra{};
-    ra.raw = d_raw; ra.trig = d_trig; ra.thr = d_thr;
-    ra.n = (int)n; ra.chunk = chunk; ra.nblocks = nblocks;
-    ra.counts = e->d_trg_cnt.p; ra.offsets = e->d_trg_cnt.p + 3 * (size_t)nblocks; ra.totals = e->d_trg_tot.p;
-    QM_TRIG_STAGE(qm::kTrigRuns,
-                  hipLaunchKernelGGL(qm::trig_count_kernel, dim3((unsigned)nblocks), dim3(qm::kTrigRunThreads), 0,
-                                     e->stream, ra);
-                  hipLaunchKernelGGL(qm::trig_scan_kernel, dim3(1), dim3(qm::kTrigRunThreads), 0, e->stream, ra));
-    int64_t totals[4] = {0, 0, 0, 0};
-    QM_HIP(copy_back(totals, e->d_trg_tot.p, sizeof(totals), e->stream));
-    if (totals[2] > 0)
-        return fail("%s: %lld non-finite samples in the two series (the reference would trigger nothing on NaN "
-                    "thresholds)", what, (long long)totals[2]);
-    if (totals[0] != totals[1])
-        return fail("%s: %lld run starts, %lld run ends", what, (long long)totals[0], (long long)totals[1]);
-    const int64_t nc = totals[0];
-    if (candidates && nc > max_candidates)
-        return fail("%s: %lld candidates, the candidate table has room for %lld", what, (long long)nc,
-                    (long long)max_candidates);
-    int64_t ne = 0;
-    if (nc > 0) {
-        const size_t C = (size_t)nc;
-        if (e->d_trg_run.ensure(2 * C) || e->d_trg_cand.ensure((qm::kTrigCandColumns + qm::kTrigEventInts) * C) ||
-            e->d_trg_val.ensure((1 + qm::kTrigEventValues) * C))
+    // the stage clock runs under "trigger_timing" only, and its times read 0 from here on: a call that fails below
+    // leaves zeros, not the call before's times
+    auto &clock = e->trig.clock;
+    clock.begin(e->cfg.trigger_timing != 0, true);
+    hipStream_t s = e->stream;
+    int64_t nc = 0, ne = 0;
+    const auto sequence = [&]() -> int {
+        const double *d_series = d_raw;
+        if (smooth) {
+            qm::TrigSmoothArgs a{d_raw, d_w, d_raw + 2 * N, (int)n, r};
+            const size_t lds = qm::trig_smooth_lds_bytes(r);
+            QM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&qm::trig_smooth_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            const unsigned tiles = (unsigned)((N + qm::kTrigSmoothTile - 1) / qm::kTrigSmoothTile);
+            if (clock.launch(s, qm::kTrigSmooth, qm::trig_smooth_kernel, dim3(tiles, 2), dim3(qm::kTrigSmoothThreads), lds, a))
+                return 1;
+            d_series = d_raw + 2 * N;
+        }
+        const double *d_coa = d_series, *d_coa_n = d_series + N;
+        const double *d_trig = p->trigger_on ? d_coa_n : d_coa;
+        if (dynamic) {
+            qm::TrigStatArgs a{d_trig, d_thr, (int)n, chunk, p->threshold_method, p->threshold_value};
+            const int threads = chunk <= qm::kTrigStatSmall ? 256 : qm::kTrigStatThreads;
+            if (clock.launch(s, qm::kTrigStats, qm::trig_stat_kernel, dim3((unsigned)n_chunks), dim3(threads), 0, a)) return 1;
+        }
+        qm::TrigRunArgs ra{};
+        ra.raw = d_raw; ra.trig = d_trig; ra.thr = d_thr;
+        ra.n = (int)n; ra.chunk = chunk; ra.nblocks = nblocks;
+        ra.counts = e->trig.cnt.p; ra.offsets = e->trig.cnt.p + 3 * (size_t)nblocks; ra.totals = e->trig.tot.p;
+        const dim3 run_blocks((unsigned)nblocks), run_threads(qm::kTrigRunThreads);
+        if (clock.stage(s, qm::kTrigRuns, [&] {
+                hipLaunchKernelGGL(qm::trig_count_kernel, run_blocks, run_threads, 0, s, ra);
+                hipLaunchKernelGGL(qm::trig_scan_kernel, dim3(1), run_threads, 0, s, ra);
+            }))
             return 1;
-        ra.first = e->d_trg_run.p;
-        ra.last = e->d_trg_run.p + C;
-        QM_TRIG_STAGE(qm::kTrigCompact, hipLaunchKernelGGL(qm::trig_compact_kernel, dim3((unsigned)nblocks),
-                                                            dim3(qm::kTrigRunThreads), 0, e->stream, ra));
+        int64_t totals[4] = {0, 0, 0, 0};
+        QM_HIP(copy_back(totals, e->trig.tot.p, sizeof(totals), s));
+        if (totals[2] > 0)
+            return fail("%s: %lld non-finite samples in the two series (the reference would trigger nothing on NaN "
+                        "thresholds)", what, (long long)totals[2]);
+        if (totals[0] != totals[1])
+            return fail("%s: %lld run starts, %lld run ends", what, (long long)totals[0], (long long)totals[1]);
+        nc = totals[0];
+        if (candidates && nc > max_candidates)
+            return fail("%s: %lld candidates, the candidate table has room for %lld", what, (long long)nc,
+                        (long long)max_candidates);
+        if (nc == 0) return 0;
+        const size_t C = (size_t)nc;
+        if (e->trig.run.ensure(2 * C) || e->trig.cand.ensure((qm::kTrigCandColumns + qm::kTrigEventInts) * C) ||
+            e->trig.val.ensure((1 + qm::kTrigEventValues) * C))
+            return 1;
+        ra.first = e->trig.run.p;
+        ra.last = e->trig.run.p + C;
+        if (clock.launch(s, qm::kTrigCompact, qm::trig_compact_kernel, run_blocks, run_threads, 0, ra)) return 1;
         qm::TrigPeakArgs pa{};
         pa.coa = d_coa; pa.coa_n = d_coa_n; pa.trig = d_trig;
         pa.first = ra.first; pa.last = ra.last;
-        pa.cand = e->d_trg_cand.p; pa.ev_i = e->d_trg_cand.p + qm::kTrigCandColumns * C;
-        pa.cval = e->d_trg_val.p; pa.ev_f = e->d_trg_val.p + C;
-        pa.totals = e->d_trg_tot.p;
+        pa.cand = e->trig.cand.p; pa.ev_i = e->trig.cand.p + qm::kTrigCandColumns * C;
+        pa.cval = e->trig.val.p; pa.ev_f = e->trig.val.p + C;
+        pa.totals = e->trig.tot.p;
         pa.nc = (int)nc; pa.period = p->period_ns; pa.mw = p->mw_ns; pa.mei = p->mei_ns;
-        QM_TRIG_STAGE(qm::kTrigPeaks, hipLaunchKernelGGL(qm::trig_peak_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256),
-                                                          0, e->stream, pa));
-        QM_TRIG_STAGE(qm::kTrigMerge, hipLaunchKernelGGL(qm::trig_merge_kernel, dim3(1), dim3(qm::kTrigMergeThreads), 0,
-                                                          e->stream, pa));
-        QM_HIP(copy_back(&ne, e->d_trg_tot.p + 3, sizeof(ne), e->stream));
-    }
-    QM_HIP(hipEventRecord(e->ev1, e->stream));
-    e->timed = true;
+        if (clock.launch(s, qm::kTrigPeaks, qm::trig_peak_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, pa) ||
+            clock.launch(s, qm::kTrigMerge, qm::trig_merge_kernel, dim3(1), dim3(qm::kTrigMergeThreads), 0, pa))
+            return 1;
+        QM_HIP(copy_back(&ne, e->trig.tot.p + 3, sizeof(ne), s));
+        return 0;
+    };
+    if (timed_launches(e, sequence)) return 1;
     if (ne > max_events)
         return fail("%s: %lld events, the event tables have room for %lld (max_events)", what, (long long)ne,
                     (long long)max_events);
     if (ne > 0) {
         const size_t C = (size_t)nc;
-        QM_HIP(copy_back(events_i, e->d_trg_cand.p + qm::kTrigCandColumns * C,
-                         (size_t)ne * qm::kTrigEventInts * sizeof(int64_t), e->stream));
-        QM_HIP(copy_back(events_f, e->d_trg_val.p + C, (size_t)ne * qm::kTrigEventValues * sizeof(double),
-                         e->stream));
+        QM_HIP(copy_back(events_i, e->trig.cand.p + qm::kTrigCandColumns * C,
+                         (size_t)ne * qm::kTrigEventInts * sizeof(int64_t), s));
+        QM_HIP(copy_back(events_f, e->trig.val.p + C, (size_t)ne * qm::kTrigEventValues * sizeof(double), s));
     }
     if (candidates && nc > 0)
-        QM_HIP(copy_back(candidates, e->d_trg_cand.p, (size_t)nc * qm::kTrigCandColumns * sizeof(int64_t),
-                         e->stream));
-    if (thresholds) QM_HIP(copy_back(thresholds, d_thr, n_chunks * sizeof(double), e->stream));
-    if (smoothed && smooth) QM_HIP(copy_back(smoothed, d_raw + 2 * N, 2 * N * sizeof(double), e->stream));
-    QM_HIP(hipStreamSynchronize(e->stream));
-    for (int st = 0; st < qm::kTrigStages; ++st) {
-        if (!ran[st]) continue;
-        float ms = 0.0f;
-        QM_HIP(hipEventElapsedTime(&ms, e->trg_ev[2 * st], e->trg_ev[2 * st + 1]));
-        e->trg_ns[st] = (int64_t)((double)ms * 1e6);
-    }
+        QM_HIP(copy_back(candidates, e->trig.cand.p, (size_t)nc * qm::kTrigCandColumns * sizeof(int64_t), s));
+    if (thresholds) QM_HIP(copy_back(thresholds, d_thr, n_chunks * sizeof(double), s));
+    if (smoothed && smooth) QM_HIP(copy_back(smoothed, d_raw + 2 * N, 2 * N * sizeof(double), s));
+    QM_HIP(hipStreamSynchronize(s));
+    if (clock.collect()) return 1;
     *n_candidates = nc;
     *n_events = ne;
     return 0;

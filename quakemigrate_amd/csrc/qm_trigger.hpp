@@ -52,6 +52,7 @@ constexpr int kTrigEventValues = 3;             // TRIG_COA, COA, COA_NORM
 // the stages of a call, as "trigger_timing" times them: smoothing, chunk statistics, run count + scan, compaction,
 // peaks, merge
 enum TrigStage : int { kTrigSmooth = 0, kTrigStats, kTrigRuns, kTrigCompact, kTrigPeaks, kTrigMerge, kTrigStages };
+inline constexpr const char *const kTrigStageNames[kTrigStages] = {"smooth", "stats", "runs", "compact", "peaks", "merge"};
 
 inline size_t trig_smooth_lds_bytes(int r) { return ((size_t)kTrigSmoothTile + 3 * (size_t)r + 1) * sizeof(double); }
 

@@ -96,11 +96,7 @@ int OnsetStage::launch(qm_engine *e, const double *signals, double *raw_onsets, 
     // one workgroup per trace; the transformed trace lives in LDS if it fits (20 480 samples)
     const size_t lds = (size_t)a.T * sizeof(double);
     const int in_lds = lds <= 160 * 1024 ? 1 : 0;
-    if (in_lds)
-        QM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&qm::stalta_sums_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(qm::stalta_sums_kernel, dim3(a.n_traces), dim3(256), in_lds ? lds : 0, e->stream, a, in_lds);
-    QM_HIP(hipGetLastError());
+    if (launch_with_lds(e, qm::stalta_sums_kernel, (unsigned)a.n_traces, 256, in_lds ? lds : 0, a, in_lds)) return 1;
     const size_t out = (size_t)a.n_rows * a.T;
     hipLaunchKernelGGL(qm::onset_rows_kernel, dim3((unsigned)((out + 255) / 256)), dim3(256), 0, e->stream, a);
     QM_HIP(hipGetLastError());
@@ -123,28 +119,15 @@ int qm_engine_onsets(qm_engine *e, const double *signals, int signals_on_device,
     // engine's stream before it enqueues its kernels, and keeps doing so)
     QM_HIP(hipStreamSynchronize(e->stream));
     const size_t sig = (size_t)n_traces * t_samples, out = (size_t)n_rows * t_samples;
-    const double *d_sig = signals;
-    if (!signals_on_device) {
-        if (e->d_sig.ensure(sig)) return 1;
-        QM_HIP(copy_in(e->d_sig.p, signals, sig * sizeof(double), e->stream));
-        d_sig = e->d_sig.p;
-    }
-    double *d_log = log_onsets, *d_raw = raw_onsets;
-    if (!out_on_device) {
-        if (e->d_onsets.ensure(out)) return 1;
-        d_log = e->d_onsets.p;
-        if (raw_onsets) {
-            if (e->d_raw.ensure(out)) return 1;
-            d_raw = e->d_raw.p;
-        }
-    }
-    if (e->on_stage.launch(e, d_sig, d_raw, d_log, 1)) return 1;
-    if (!out_on_device) {
-        QM_HIP(copy_back(log_onsets, d_log, out * sizeof(double), e->stream));
-        if (raw_onsets)
-            QM_HIP(copy_back(raw_onsets, d_raw, out * sizeof(double), e->stream));
-        QM_HIP(hipStreamSynchronize(e->stream));
-    }
+    const double *d_sig = stage_in(e, e->staging.sig, signals, signals_on_device, sig);
+    if (!d_sig) return 1;
+    // (the log-onsets leave through the detect's onset buffer; no raw onsets wanted: nothing staged, raw.d stays NULL)
+    const StagedOut<double> log = stage_host_out(e->d_onsets, log_onsets, out_on_device, out);
+    if (!log.d) return 1;
+    StagedOut<double> raw;
+    if (raw_onsets && !(raw = stage_host_out(e->staging.raw, raw_onsets, out_on_device, out)).d) return 1;
+    if (e->on_stage.launch(e, d_sig, raw.d, log.d, 1) || log.fetch(e) || raw.fetch(e)) return 1;
+    if (!out_on_device) QM_HIP(hipStreamSynchronize(e->stream));
     return 0;
 }
 
@@ -160,24 +143,24 @@ int qm_engine_locate_fits(qm_engine *e, const double *coa_map, int map_on_device
     DeviceGuard guard(e->device);
     const int64_t n = (int64_t)nx * ny * nz;
     constexpr int NB = qm::kFitBlocks, BS = qm::kFitBlock;
-    if (e->d_fit_a.ensure((size_t)n) || e->d_fit_b.ensure((size_t)n) ||
-        e->d_fit_c.ensure((size_t)n) || e->d_fit_part.ensure((size_t)NB * 6) ||
-        e->d_fit_pidx.ensure(NB) || e->d_fit_val.ensure(32) || e->d_fit_win.ensure(343 + 125))
+    if (e->fit.a.ensure((size_t)n) || e->fit.b.ensure((size_t)n) ||
+        e->fit.c.ensure((size_t)n) || e->fit.part.ensure((size_t)NB * 6) ||
+        e->fit.pidx.ensure(NB) || e->fit.val.ensure(32) || e->fit.win.ensure(343 + 125))
         return 1;
     hipStream_t s = e->stream;
     const double *d_in = coa_map;
     if (!map_on_device) {
-        QM_HIP(copy_in(e->d_fit_c.p, coa_map, (size_t)n * sizeof(double), s));
-        d_in = e->d_fit_c.p;
+        QM_HIP(copy_in(e->fit.c.p, coa_map, (size_t)n * sizeof(double), s));
+        d_in = e->fit.c.p;
     }
-    double *val = e->d_fit_val.p;
+    double *val = e->fit.val.p;
     // device scalars: 0 map max, 1 map argmax, 2 pass-1 max, 3 -, 4 pass-2 max, 5 -,
     // 6 smoothed mean, 7 smoothed argmax, 8..11 first moments, 12..17 second moments, 18 -
     auto argmax = [&](const double *m, double *out_v, double *out_i) -> int {
         hipLaunchKernelGGL(qm::argmax_partial_kernel, dim3(NB), dim3(BS), 0, s, m, n,
-                           e->d_fit_part.p, e->d_fit_pidx.p);
-        hipLaunchKernelGGL(qm::argmax_final_kernel, dim3(1), dim3(BS), 0, s, e->d_fit_part.p,
-                           e->d_fit_pidx.p, NB, out_v, out_i);
+                           e->fit.part.p, e->fit.pidx.p);
+        hipLaunchKernelGGL(qm::argmax_final_kernel, dim3(1), dim3(BS), 0, s, e->fit.part.p,
+                           e->fit.pidx.p, NB, out_v, out_i);
         QM_HIP(hipGetLastError());
         return 0;
     };
@@ -199,15 +182,15 @@ int qm_engine_locate_fits(qm_engine *e, const double *coa_map, int map_on_device
     };
 
     // (1) coa_map / nanmax(coa_map)                                       scan.py:721
-    double *d_norm = (norm_map && out_on_device) ? norm_map : e->d_fit_a.p;
+    double *d_norm = (norm_map && out_on_device) ? norm_map : e->fit.a.p;
     if (argmax(d_in, val + 0, val + 1)) return 1;
     hipLaunchKernelGGL(qm::divide_kernel, dim3(NB), dim3(BS), 0, s, d_in, (const double *)val, n,
                        d_norm);
     if (argmax(d_norm, val + 18, val + 1)) return 1;
 
     // (2) _gaufilt3d: filter, normalise, filter mirrored, normalise        scan.py:1033-1041
-    double *d_smooth = (smoothed_map && out_on_device) ? smoothed_map : e->d_fit_b.p;
-    double *d_tmp = e->d_fit_c.p;           // the staged input is dead once d_norm exists
+    double *d_smooth = (smoothed_map && out_on_device) ? smoothed_map : e->fit.b.p;
+    double *d_tmp = e->fit.c.p;           // the staged input is dead once d_norm exists
     if (smooth(d_norm, d_tmp, d_smooth, false, nullptr)) return 1;
     if (argmax(d_smooth, val + 2, val + 3)) return 1;
     // second pass: its first axis divides by the pass-1 maximum (the filter is linear)
@@ -233,36 +216,36 @@ int qm_engine_locate_fits(qm_engine *e, const double *coa_map, int map_on_device
                        (const double *)(val + 4), n, d_smooth);
     if (argmax(d_smooth, val + 18, val + 7)) return 1;
     hipLaunchKernelGGL(qm::sum_partial_kernel, dim3(NB), dim3(BS), 0, s,
-                       (const double *)d_smooth, n, e->d_fit_part.p);
+                       (const double *)d_smooth, n, e->fit.part.p);
     hipLaunchKernelGGL(qm::sums_final_kernel, dim3(1), dim3(BS), 0, s,
-                       (const double *)e->d_fit_part.p, NB, 1, 1.0 / (double)n, val + 6);
+                       (const double *)e->fit.part.p, NB, 1, 1.0 / (double)n, val + 6);
 
     // (3) _covfit3d on the normalised (unsmoothed) map                     scan.py:973-999
     hipLaunchKernelGGL(qm::moments_partial_kernel<0>, dim3(NB), dim3(BS), 0, s,
                        (const double *)d_norm, nx, ny, nz, cov_thresh, node_spacing[0],
                        node_spacing[1], node_spacing[2], (const double *)nullptr,
-                       e->d_fit_part.p);
+                       e->fit.part.p);
     hipLaunchKernelGGL(qm::sums_final_kernel, dim3(4), dim3(BS), 0, s,
-                       (const double *)e->d_fit_part.p, NB, 4, 1.0, val + 8);
+                       (const double *)e->fit.part.p, NB, 4, 1.0, val + 8);
     hipLaunchKernelGGL(qm::moments_partial_kernel<1>, dim3(NB), dim3(BS), 0, s,
                        (const double *)d_norm, nx, ny, nz, cov_thresh, node_spacing[0],
                        node_spacing[1], node_spacing[2], (const double *)(val + 8),
-                       e->d_fit_part.p);
+                       e->fit.part.p);
     hipLaunchKernelGGL(qm::sums_final_kernel, dim3(6), dim3(BS), 0, s,
-                       (const double *)e->d_fit_part.p, NB, 6, 1.0, val + 12);
+                       (const double *)e->fit.part.p, NB, 6, 1.0, val + 12);
     hipLaunchKernelGGL(qm::moments_scale_kernel, dim3(1), dim3(64), 0, s, val + 12,
                        (const double *)(val + 8));
 
     // (4) the windows the Gaussian (7^3, smoothed map) and spline (5^3, normalised map) fits use
     hipLaunchKernelGGL(qm::window_kernel, dim3(2), dim3(256), 0, s, (const double *)d_smooth, nx,
-                       ny, nz, 7, (const double *)(val + 7), e->d_fit_win.p);
+                       ny, nz, 7, (const double *)(val + 7), e->fit.win.p);
     hipLaunchKernelGGL(qm::window_kernel, dim3(1), dim3(128), 0, s, (const double *)d_norm, nx,
-                       ny, nz, 5, (const double *)(val + 1), e->d_fit_win.p + 343);
+                       ny, nz, 5, (const double *)(val + 1), e->fit.win.p + 343);
     QM_HIP(hipGetLastError());
 
     double h[32], w[343 + 125];
     QM_HIP(copy_back(h, val, sizeof(h), s));
-    QM_HIP(copy_back(w, e->d_fit_win.p, sizeof(w), s));
+    QM_HIP(copy_back(w, e->fit.win.p, sizeof(w), s));
     if (norm_map && !out_on_device)
         QM_HIP(copy_back(norm_map, d_norm, (size_t)n * sizeof(double), s));
     if (smoothed_map && !out_on_device)
@@ -293,21 +276,21 @@ int qm_engine_rbf_peak(qm_engine *e, const double *weights, int32_t n, int32_t u
     const int m = (n - 1) * upscale + 1;
     const int64_t fine = (int64_t)m * m * m;
     constexpr int NB = qm::kFitBlocks, BS = qm::kFitBlock;
-    if (e->d_fit_a.ensure((size_t)fine) || e->d_fit_win.ensure(9 * 9 * 9) ||
-        e->d_fit_part.ensure((size_t)NB * 6) || e->d_fit_pidx.ensure(NB) || e->d_fit_val.ensure(32))
+    if (e->fit.a.ensure((size_t)fine) || e->fit.win.ensure(9 * 9 * 9) ||
+        e->fit.part.ensure((size_t)NB * 6) || e->fit.pidx.ensure(NB) || e->fit.val.ensure(32))
         return 1;
     hipStream_t s = e->stream;
-    QM_HIP(copy_in(e->d_fit_win.p, weights, (size_t)n * n * n * sizeof(double), s));
+    QM_HIP(copy_in(e->fit.win.p, weights, (size_t)n * n * n * sizeof(double), s));
     hipLaunchKernelGGL(qm::rbf_dense_kernel, dim3((unsigned)((fine + BS - 1) / BS)), dim3(BS), 0, s,
-                       (const double *)e->d_fit_win.p, (int)n, m, (double)(n - 1) / (double)(m - 1),
-                       e->d_fit_a.p);
+                       (const double *)e->fit.win.p, (int)n, m, (double)(n - 1) / (double)(m - 1),
+                       e->fit.a.p);
     hipLaunchKernelGGL(qm::argmax_partial_kernel, dim3(NB), dim3(BS), 0, s,
-                       (const double *)e->d_fit_a.p, fine, e->d_fit_part.p, e->d_fit_pidx.p);
-    hipLaunchKernelGGL(qm::argmax_final_kernel, dim3(1), dim3(BS), 0, s, e->d_fit_part.p,
-                       e->d_fit_pidx.p, NB, e->d_fit_val.p, e->d_fit_val.p + 1);
+                       (const double *)e->fit.a.p, fine, e->fit.part.p, e->fit.pidx.p);
+    hipLaunchKernelGGL(qm::argmax_final_kernel, dim3(1), dim3(BS), 0, s, e->fit.part.p,
+                       e->fit.pidx.p, NB, e->fit.val.p, e->fit.val.p + 1);
     QM_HIP(hipGetLastError());
     double h[2];
-    QM_HIP(copy_back(h, e->d_fit_val.p, sizeof(h), s));
+    QM_HIP(copy_back(h, e->fit.val.p, sizeof(h), s));
     QM_HIP(hipStreamSynchronize(s));
     if (h[1] < 0) return fail("qm_engine_rbf_peak: the interpolant holds no finite value");
     *peak_value = h[0];

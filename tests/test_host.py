@@ -962,7 +962,7 @@ def test_owning_handles_free_everything_once(tmp_path):
     """tools/ownership_check.cpp over csrc/qm_engine.hpp alone, pool, pinned memory and events replaced by counting
     stubs, under AddressSanitizer (with its leak check) and UBSan: the handles' moves and releases, TableState's
     device_bytes() against what is out, swaps and drops of parked tables, a deleted and an abandoned qm_engine, the
-    stage records -- every block freed once, nothing left out, one wait per teardown."""
+    stage records, the scratch records with both stage clocks' events -- every block freed once, nothing left out, one wait per teardown."""
     import shutil
     import subprocess
 
@@ -978,5 +978,6 @@ def test_owning_handles_free_everything_once(tmp_path):
     assert out.returncode == 0, out.stdout + out.stderr
     lines = out.stdout.splitlines()
     assert lines[-1] == "ownership_check: ok"
-    assert [line.split(":")[0] for line in lines[:-1]] == ["handles", "TableState", "qm_engine", "stage records"]
+    assert [line.split(":")[0] for line in lines[:-1]] == ["handles", "TableState", "qm_engine", "stage records",
+                                                            "scratch records"]
 

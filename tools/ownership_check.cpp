@@ -154,21 +154,48 @@ static void stage_records(PreprocStage &pre, OnsetStage &on, ResampleStage &rs) 
     CHECK(!rs.meta.ensure(22) && !rs.coef.ensure(26) && !rs.scratch.ensure(402));
 }
 
+// every buffer of every scratch record (58 pool blocks, the pinned flag ring) and the events of both stage clocks (24)
+static void scratch_records(CallStaging &st, PickStage &pk, AmplitudeStage &am, TriggerStage &tr, ScanmseedCodec &sm,
+                            TieScratch &ti, ScreenScratch &sw, FitScratch &fi) {
+    size_t k = 300;
+    CHECK(!st.sig.ensure(++k) && !st.raw.ensure(++k) && !st.pre_out.ensure(++k) && !st.rs_raw.ensure(++k));
+    CHECK(!pk.val.ensure(++k) && !pk.meta.ensure(++k));
+    CHECK(!am.work.ensure(++k) && !am.scratch.ensure(++k) && !am.coef.ensure(++k) && !am.val.ensure(++k) &&
+          !am.meta.ensure(++k) && !am.idx.ensure(++k));
+    CHECK(!tr.x.ensure(++k) && !tr.par.ensure(++k) && !tr.cnt.ensure(++k) && !tr.tot.ensure(++k) && !tr.run.ensure(++k) &&
+          !tr.cand.ensure(++k) && !tr.val.ensure(++k));
+    CHECK(!sm.x.ensure(++k) && !sm.f.ensure(++k) && !sm.fac.ensure(++k) && !sm.bytes.ensure(++k) && !sm.map.ensure(++k) &&
+          !sm.out.ensure(++k) && !sm.tile.ensure(++k) && !sm.rec.ensure(++k) && !sm.tot.ensure(++k) && !sm.off.ensure(++k));
+    CHECK(!ti.zext.ensure(++k) && !ti.zgrid.ensure(++k) && !ti.z.ensure(++k) && !ti.pairs.ensure(++k) &&
+          !ti.imin.ensure(++k) && !ti.count.ensure(++k) && !ti.cands.ensure(++k) && !ti.emax.ensure(++k) &&
+          !ti.keys.ensure(++k));
+    CHECK(!sw.counts.ensure(++k) && !sw.cells.ensure(++k) && !sw.work.ensure(++k) && !sw.flags.ensure(++k) &&
+          !sw.onq.ensure(++k) && !sw.cell.ensure(++k) && !sw.gmax.ensure(++k) && !sw.pm.ensure(++k) &&
+          !sw.sparams.ensure(++k) && !sw.rowmax.ensure(++k) && !sw.ssum.ensure(++k) && !sw.cand_z.ensure(++k) &&
+          !sw.cand_idx.ensure(++k));
+    CHECK(!sw.h_flags.ensure(2 * kFlagRing, hipHostMallocDefault));
+    CHECK(!fi.a.ensure(++k) && !fi.b.ensure(++k) && !fi.c.ensure(++k) && !fi.part.ensure(++k) && !fi.val.ensure(++k) &&
+          !fi.win.ensure(++k) && !fi.pidx.ensure(++k));
+    CHECK(k == 300 + 58);
+    CHECK(!tr.clock.ensure_events() && !sm.clock.ensure_events());
+    CHECK(tr.clock.ev.size() == 2 * qm::kTrigStages && sm.clock.ev.size() == 2 * qm::kSmsStages);
+}
+
 static void fill_engine(qm_engine *e) {
     fill_table(*e, 100);
     e->slots.emplace_back();
     fill_table(e->slots.back().state, 200);
     CHECK(!e->d_onsets.ensure(900) && !e->d_pmax.ensure(390) && !e->d_pidx.ensure(390) && !e->d_out_a.ensure(390) &&
-          !e->d_tie_keys.ensure(7) && !e->d_trg_cand.ensure(12) && !e->d_digest.ensure(1));
+          !e->d_digest.ensure(1));
     stage_records(e->pre_stage, e->on_stage, e->rs_stage);
-    CHECK(!e->h_flags.ensure(2 * kFlagRing, hipHostMallocDefault));
+    scratch_records(e->staging, e->picks, e->amps, e->trig, e->sms, e->tie, e->sweep, e->fit);
     CHECK(e->ev0.create() == hipSuccess && e->ev1.create() == hipSuccess);
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < 2; ++i) {
         Event ev;
         CHECK(ev.create() == hipSuccess);
-        (i < 2 ? e->ev_log : e->trg_ev).push_back(std::move(ev));
+        e->ev_log.push_back(std::move(ev));
     }
-    CHECK(g_pool.live.size() == 2 * 36 + 7 + 8 && g_pinned.live.size() == 1 && g_events.live.size() == 6);
+    CHECK(g_pool.live.size() == 2 * 36 + 5 + 8 + 58 && g_pinned.live.size() == 1 && g_events.live.size() == 4 + 24);
 }
 
 // a create path that gives up half-way: what the engine holds by then goes back, behind one wait
@@ -258,6 +285,26 @@ int main() {
     }
     CHECK(nothing_out() && g_waits == 1);
     std::printf("stage records: out of scope with nothing out\n");
+
+    {
+        g_waits = 0;
+        PoolReleaseScope one_wait;
+        {
+            CallStaging st;
+            PickStage pk;
+            AmplitudeStage am;
+            TriggerStage tr;
+            ScanmseedCodec sm;
+            TieScratch ti;
+            ScreenScratch sw;
+            FitScratch fi;
+            scratch_records(st, pk, am, tr, sm, ti, sw, fi);
+            CHECK(g_pool.live.size() == 58 && g_pinned.live.size() == 1 && g_events.live.size() == 24);
+        }
+        CHECK(nothing_out() && g_waits == 0);
+    }
+    CHECK(nothing_out() && g_waits == 1);
+    std::printf("scratch records: out of scope with nothing out\n");
 
     CHECK(g_pool.handed_out == g_pool.taken_back && g_pinned.handed_out == g_pinned.taken_back &&
           g_events.handed_out == g_events.taken_back);
