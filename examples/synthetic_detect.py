@@ -9,7 +9,11 @@ coalescence series -- the hot-path side of ``QuakeScan.detect()``
     fused migrate + find_max_coa per timestep (the path) --> max_coa, max_coa_n, argmax
     quantise + STEIM2 (row f4) --> <year>_<julday>.scanmseed, as the reference writes it
 
-Run:  python examples/synthetic_detect.py [out_dir]
+With ``--lut 1d`` the grids themselves come from the GPU: eikonal sections of a 1-D velocity model per station and
+phase, swept round the stations (row f8, ``quakemigrate_amd.traveltimes.compute_traveltimes``), and go from there
+into the table serving without a host round trip.
+
+Run:  python examples/synthetic_detect.py [out_dir] [--lut 1d]
 """
 
 import datetime as dt
@@ -27,9 +31,10 @@ from quakemigrate_amd.core import lib  # noqa: E402
 
 
 def run(out_dir, grid=(24, 20, 12), spacing=0.5, n_stations=6, rate=50, timestep=6.0,
-        n_steps=4, seed=3, steps_per_launch=1):
+        n_steps=4, seed=3, steps_per_launch=1, lut="homogeneous"):
     """``steps_per_launch`` > 1: the onset rows of that many timesteps are stacked by ONE launch
-    (``Engine.detect_batch``) -- what fills the GPU on grids of this size; same series."""
+    (``Engine.detect_batch``) -- what fills the GPU on grids of this size; same series.
+    ``lut``: "homogeneous" (NumPy grids, uploaded) or "1d" (a three-layer model, computed on the device)."""
     import torch
 
     rng = np.random.default_rng(seed)
@@ -43,7 +48,20 @@ def run(out_dir, grid=(24, 20, 12), spacing=0.5, n_stations=6, rate=50, timestep
     grids = [d / 5.0 for d in dist] + [d / 2.9 for d in dist]          # P rows, then S rows
     eng = lib.Engine(0)
     eng.set_stream(torch.cuda.current_stream().cuda_stream)
-    eng.set_traveltime_grids(grids)
+    if lut == "1d":
+        from quakemigrate_amd import traveltimes as tt
+
+        vmod = {"Depth": [0.0, 1.5, 4.0], "Vp": [4.2, 5.0, 6.1], "Vs": [2.4, 2.9, 3.5]}
+        names = [f"ST{i:02d}" for i in range(n_stations)]
+        table = tt.compute_traveltimes(eng, (0.0, 0.0, 0.0), (spacing,) * 3, grid, dict(zip(names, st)), "1d",
+                                       vmod=vmod, section_dx=spacing / 5, device=True)
+        served = [table[s]["P"] for s in names] + [table[s]["S"] for s in names]
+        grids = [g.cpu().numpy() for g in served]                      # (for the synthetic arrivals below only)
+    elif lut == "homogeneous":
+        served = grids
+    else:
+        raise ValueError(f"lut must be 'homogeneous' or '1d', got {lut!r}")
+    eng.set_traveltime_grids(served)
     eng.serve(rate, np.arange(2 * n_stations))                          # all available
     lut_max = eng.lut_max
     # ---- windowing as QuakeScan does: pre/post pad around every timestep -------------------
@@ -97,7 +115,13 @@ def run(out_dir, grid=(24, 20, 12), spacing=0.5, n_stations=6, rate=50, timestep
 
 
 if __name__ == "__main__":
-    res = run(sys.argv[1] if len(sys.argv) > 1 else "synthetic_detect_out")
+    argv = sys.argv[1:]
+    lut = "homogeneous"
+    if "--lut" in argv:
+        at = argv.index("--lut")
+        lut = argv[at + 1]
+        del argv[at:at + 2]
+    res = run(argv[0] if argv else "synthetic_detect_out", lut=lut)
     for node, t in res["truth"]:
         k = int(np.argmax(res["coa"][max(0, t - 10): t + 10])) + max(0, t - 10)
         print(f"event at node {node}, sample {t}: peak coalescence {res['coa'][k]:.2f} at sample "

@@ -233,7 +233,11 @@ int qm_engine_synchronize(qm_engine *e);
  * the .scanmseed codec's compile-time constants (csrc/qm_scanmseed.hpp): scanmseed_tile (positions per workgroup of
  * the chain kernels), scanmseed_compose_chunk, and the last codec call's stage times in nanoseconds:
  * scanmseed_ns_quantise, scanmseed_ns_scan, scanmseed_ns_compose, scanmseed_ns_pack, scanmseed_ns_frame (encode),
- * scanmseed_ns_decode (0: the stage did not run). */
+ * scanmseed_ns_decode (0: the stage did not run);
+ * the travel-time stage's compile-time constants (csrc/qm_traveltimes.hpp): tt_lds_nodes (the largest section whose
+ * tau qm_engine_tt_sections keeps in LDS), tt_section_threads, tt_grid_blocks and tt_grid_threads (the launch grid of
+ * the two per-node kernels, which stride over it), and the last call's launch time in nanoseconds: tt_ns_homogeneous,
+ * tt_ns_sections, tt_ns_sweep. */
 int qm_engine_config(qm_engine *e, const char *key, int64_t value);
 int qm_engine_get(qm_engine *e, const char *key, int64_t *value);
 
@@ -608,6 +612,61 @@ int qm_engine_measure_amplitudes(qm_engine *e, const double *traces, int traces_
                                  const int64_t *window_records, int detrend_windows, int average_method,
                                  double prominence_multiplier, double *values /*[n_windows][4]*/,
                                  int32_t *index /*[n_windows][4]*/, double *filtered_out);
+
+/* Travel-time tables on the device -- the float64 grids in seconds that qm_engine_grids_set and qm_engine_serve work
+ * from, computed where they live: the reference's compute_traveltimes (quakemigrate/lut/create_lut.py) for the two
+ * methods that need no external program.  The rules on arrays: tests/traveltimes_ref.py; the kernels and what bounds
+ * them: csrc/qm_traveltimes.hpp.  All arithmetic is float64 without contraction, IEEE divide and square root: every
+ * output has the bits of the NumPy restatement.  A grid is ll_corner [3], node_spacing [3] (> 0), node_count [3]; node
+ * (ix, iy, iz) lies at ll_corner[j] + index * node_spacing[j] (Grid3D.grid_xyz) and is element (ix ny + iy) nz + iz
+ * of its row.  Units are the caller's: one unit of length throughout, seconds per that unit.  Parameter arrays are
+ * host arrays; out_on_device says where the outputs are.  Every call synchronises and leaves its launch's time in
+ * "tt_ns_homogeneous" / "tt_ns_sections" / "tt_ns_sweep" (qm_engine_get, nanoseconds) and qm_engine_last_kernel_ms.
+ *
+ * qm_engine_tt_homogeneous (create_lut.py:241-265): row_params [n_rows][4] = station x, y, z, velocity; out
+ * [n_rows][nodes] = sqrt(dx dx + dy dy + dz dz) / v, the sum taken left to right.
+ *
+ * qm_engine_tt_sections: |grad T| = s(z) on n_sections (distance, depth) sections of nr x nz nodes of spacing h, node
+ * (i, k) at distance i h and depth k h below the section's first row, element i nz + k.  slowness [n_sections][nz]:
+ * per depth row; source [n_sections][2]: the source's depth zs below the first row -- the source sits in column 0 --
+ * and the slowness s0 there.  The scheme is the multiplicatively factored first-order upwind one, T = T0 tau with
+ * T0 = s0 rho, rho = sqrt(x x + z z) from the source: a node takes the smallest candidate over its available
+ * neighbours (finite tau) -- per horizontal neighbour (i - sx, k), sx = +-1, ax = T0 sx / h + T0x, bx = T0 sx tau_a / h,
+ * the same in z; the two-sided candidate is the larger root of (ax tau - bx)^2 + (az tau - bz)^2 = s[k]^2, kept where
+ * sx (ax tau - bx) >= 0 and sz (az tau - bz) >= 0 (the only causality tests); the one-sided ones are
+ * (bx + sx s[k]) / ax where sx ax > 0 and the result is > 0 -- and only where that is below its value by more than
+ * tol times the value (tol = 2^-40 stops the creep in the last bits; 0: strict).  Columns 0 and 1 of the two rows
+ * that bracket zs (floor(zs / h) and the next) are frozen at tau = (s0 + s[k]) / (2 s0), the node at the source at
+ * tau = 1.  Gauss-Seidel sweeps in the orderings (+,+) (-,+) (-,-) (+,-) of (i, k) make a round; rounds repeat until
+ * one accepts nothing.  One workgroup per section runs every anti-diagonal of a sweep in parallel, which reads what
+ * the serial i-outer / k-inner loop reads: the values are that loop's.  tau lives in LDS up to "tt_lds_nodes" nodes
+ * (qm_engine_get), above that -- or with force_scratch = 1 -- in engine scratch: the same bits.  T [n_sections][nr][nz]
+ * f64, rounds [n_sections] i32 (rounds run, the last, idle one included), status [n_sections] i32 (0 settled, 1 not
+ * settled in max_iters rounds), all three on the side out_on_device says.  Refused: a NULL argument, n_sections < 1,
+ * nr or nz < 2, h or a slowness not finite and > 0 (the section and row are named), a source outside the section's
+ * rows or in its last row's cell below (named), tol outside [0, 1), max_iters < 1; and, with the outputs written, a
+ * section that max_iters rounds did not settle (named).
+ *
+ * qm_engine_tt_sweep (create_lut.py:471-474, 504-513, 746-762): row_params [n_rows][4] = station x, y, the origin x0,
+ * z0 of the row's section; row_section [n_rows]: which of the n_sections sections [n_sections][nr][nz] (host or
+ * device: a caller's own, NonLinLoc's for instance, or qm_engine_tt_sections') the row is swept from.  Per node
+ * d = sqrt(dx dx + dy dy), z, and then _bilinear_interpolate literally: i, k = floor((d - x0) / h), floor((z - z0) / h);
+ * fractions np.remainder(d, h) / h and np.remainder(z, h) / h -- of the coordinates, not of the offsets from the origin:
+ * the reference's rule, which names the cell of the floor only where x0 and z0 are multiples of h --; c0 = c00 (1 - xd)
+ * + c10 xd, c1 = c01 (1 - xd) + c11 xd, c0 (1 - zd) + c1 zd.  out [n_rows][nodes].  Refused besides the arguments: a
+ * node whose four corners are not all inside its section -- NumPy would raise, or wrap a negative index --, with the
+ * row and its first such node named; the other nodes of out are written, such nodes hold NaN. */
+int qm_engine_tt_homogeneous(qm_engine *e, const double *ll_corner, const double *node_spacing,
+                             const int32_t *node_count, int32_t n_rows, const double *row_params /*[n_rows][4]*/,
+                             double *out, int out_on_device);
+int qm_engine_tt_sections(qm_engine *e, int32_t n_sections, int32_t nr, int32_t nz, double h,
+                          const double *slowness /*[n_sections][nz]*/, const double *source /*[n_sections][2]*/,
+                          double tol, int32_t max_iters, int force_scratch, double *T, int32_t *rounds,
+                          int32_t *status, int out_on_device);
+int qm_engine_tt_sweep(qm_engine *e, const double *ll_corner, const double *node_spacing, const int32_t *node_count,
+                       int32_t n_rows, const double *row_params /*[n_rows][4]*/, const int32_t *row_section,
+                       const double *sections, int sections_on_device, int32_t n_sections, int32_t nr, int32_t nz,
+                       double h, double *out, int out_on_device);
 
 /* Trigger on the device -- the step between the detect sweep and the location: what Trigger._trigger_batch does to
  * the coalescence series of a batch (quakemigrate/signal/trigger.py:318-638; the rules on arrays:

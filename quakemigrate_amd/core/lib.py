@@ -125,6 +125,12 @@ qmlib.qm_engine_pick_phases.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32
 qmlib.qm_engine_measure_amplitudes.argtypes = [_vp, _vp, ctypes.c_int, c_int64, c_int32, c_i64Pt, c_dPt, c_int32,
                                                c_int32, c_i32Pt, c_int32, c_dPt, c_int64, c_int32, c_i64Pt,
                                                ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, _vp, _vp]
+qmlib.qm_engine_tt_homogeneous.argtypes = [_vp, c_dPt, c_dPt, c_i32Pt, c_int32, c_dPt, _vp, ctypes.c_int]
+qmlib.qm_engine_tt_sections.argtypes = [_vp, c_int32, c_int32, c_int32, ctypes.c_double, c_dPt, c_dPt, ctypes.c_double,
+                                        c_int32, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int]
+qmlib.qm_engine_tt_sweep.argtypes = [_vp, c_dPt, c_dPt, c_i32Pt, c_int32, c_dPt, c_i32Pt, _vp, ctypes.c_int, c_int32,
+                                     c_int32, c_int32, ctypes.c_double, _vp, ctypes.c_int]
+
 
 class TriggerParams(ctypes.Structure):
     """``qm_trigger_params`` (include/qmhip.h)."""
@@ -904,6 +910,103 @@ class Engine:
             float(prominence_multiplier), _host(values), _host(index),
             _host(filtered) if want_filtered else _vp(None)))
         return (values, index, filtered) if want_filtered else (values, index)
+
+    # -- travel-time tables (create_lut.py's compute_traveltimes on the GPU) ----
+    @staticmethod
+    def _tt_grid(ll_corner, node_spacing, node_count):
+        ll = np.ascontiguousarray(ll_corner, dtype=np.float64).reshape(-1)
+        sp = np.ascontiguousarray(node_spacing, dtype=np.float64).reshape(-1)
+        nc = np.ascontiguousarray(node_count, dtype=np.int32).reshape(-1)
+        if not len(ll) == len(sp) == len(nc) == 3:
+            raise ValueError("ll_corner, node_spacing and node_count have three entries each")
+        return ll, sp, nc
+
+    def _tt_out(self, shape, device, dtype=np.float64):
+        """A new output array: a torch tensor on this engine's GPU (``device``) or a NumPy array."""
+        if not device:
+            return np.zeros(shape, dtype=dtype)
+        import torch
+
+        where = torch.device("cuda", self.device)
+        out = torch.empty(shape, dtype=torch.float64 if dtype == np.float64 else torch.int32, device=where)
+        torch.cuda.synchronize(where)                   # (the allocator's stream is not the engine's)
+        return out
+
+    def traveltimes_homogeneous(self, ll_corner, node_spacing, node_count, stations_xyz, velocities, device=False):
+        """
+        Travel-time grids of a homogeneous medium (``_compute_homogeneous``, create_lut.py:241-265; include/qmhip.h:
+        ``qm_engine_tt_homogeneous``).  One row per entry of ``stations_xyz`` (n_rows, 3) and ``velocities``
+        (n_rows,).  Returns (n_rows, nx, ny, nz) float64 seconds: a NumPy array, or with ``device`` a torch tensor on
+        this engine's GPU.
+        """
+        ll, sp, nc = self._tt_grid(ll_corner, node_spacing, node_count)
+        xyz = np.ascontiguousarray(stations_xyz, dtype=np.float64).reshape(-1, 3)
+        vel = np.ascontiguousarray(velocities, dtype=np.float64).reshape(-1)
+        if len(vel) != len(xyz):
+            raise ValueError(f"{len(xyz)} stations, {len(vel)} velocities: one row each")
+        rows = np.ascontiguousarray(np.column_stack([xyz, vel]))
+        out = self._tt_out((len(rows),) + tuple(int(n) for n in nc), device)
+        p, dev = self._ptr(out, np.float64)
+        _check(qmlib.qm_engine_tt_homogeneous(self._h, ll, sp, nc, len(rows), rows.reshape(-1), p, dev))
+        return out
+
+    def traveltime_sections(self, slowness, source_depth, nr, h, source_slowness=None, tol=2.0 ** -40, max_iters=64,
+                            force_scratch=False, device=False):
+        """
+        Eikonal travel-time sections of 1-D models (include/qmhip.h: ``qm_engine_tt_sections``).  ``slowness``
+        (n_sections, nz): per depth row of spacing ``h``; ``source_depth`` (n_sections,): below the first row;
+        ``source_slowness``: at the source, by default interpolated linearly between the rows.  Returns
+        ``(T (n_sections, nr, nz), rounds, status)``, NumPy arrays or with ``device`` torch tensors on this
+        engine's GPU.  A section that ``max_iters`` rounds do not settle raises.
+        """
+        slowness = np.ascontiguousarray(np.atleast_2d(slowness), dtype=np.float64)
+        n_sec, nz = (int(v) for v in slowness.shape)
+        zs = np.ascontiguousarray(source_depth, dtype=np.float64).reshape(-1)
+        if len(zs) != n_sec:
+            raise ValueError(f"{n_sec} sections, {len(zs)} source depths")
+        if source_slowness is None:
+            depth = np.arange(nz) * float(h)
+            source_slowness = [np.interp(zs[s], depth, slowness[s]) for s in range(n_sec)]
+        s0 = np.ascontiguousarray(source_slowness, dtype=np.float64).reshape(-1)
+        if len(s0) != n_sec:
+            raise ValueError(f"{n_sec} sections, {len(s0)} source slownesses")
+        source = np.ascontiguousarray(np.column_stack([zs, s0]))
+        T = self._tt_out((n_sec, int(nr), nz), device)
+        rounds, status = self._tt_out(n_sec, device, np.int32), self._tt_out(n_sec, device, np.int32)
+        (pt, dev), (pr, _), (ps, _) = self._ptr(T, np.float64), self._ptr(rounds, np.int32), self._ptr(status, np.int32)
+        _check(qmlib.qm_engine_tt_sections(self._h, n_sec, int(nr), nz, float(h), slowness.reshape(-1),
+                                           source.reshape(-1), float(tol), int(max_iters), 1 if force_scratch else 0,
+                                           pt, pr, ps, dev))
+        return T, rounds, status
+
+    def sweep_sections(self, sections, ll_corner, node_spacing, node_count, stations_xy, row_section, origins, h,
+                       device=False):
+        """
+        (distance, depth) sections swept round their stations over a 3-D grid by the reference's bilinear rule
+        (create_lut.py:471-474, 504-513, 746-762; include/qmhip.h: ``qm_engine_tt_sweep``).  ``sections``
+        (n_sections, nr, nz): a NumPy array -- a caller's own, NonLinLoc's for instance -- or a tensor on this engine's
+        GPU (:meth:`traveltime_sections`'); per row ``stations_xy`` (n_rows, 2), ``row_section`` (n_rows,) and
+        ``origins`` (n_rows, 2), the section's ``(x0, z0)``; ``h``: the sections' spacing.  Returns (n_rows, nx, ny, nz)
+        like :meth:`traveltimes_homogeneous`.  A node outside its section raises.
+        """
+        ll, sp, nc = self._tt_grid(ll_corner, node_spacing, node_count)
+        if not hasattr(sections, "data_ptr"):           # (anything but a tensor: an array, nested lists)
+            sections = np.ascontiguousarray(sections, dtype=np.float64)
+        if len(sections.shape) != 3:
+            raise ValueError(f"sections of shape {tuple(sections.shape)}: (n_sections, nr, nz) expected")
+        n_sec, nr, nz = (int(v) for v in sections.shape)
+        psec, dev_sec = self._ptr(sections, np.float64)
+        xy = np.ascontiguousarray(stations_xy, dtype=np.float64).reshape(-1, 2)
+        org = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 2)
+        row_section = np.ascontiguousarray(row_section, dtype=np.int32).reshape(-1)
+        if not len(xy) == len(org) == len(row_section):
+            raise ValueError(f"{len(xy)} stations, {len(org)} origins, {len(row_section)} section indices: one row each")
+        rows = np.ascontiguousarray(np.column_stack([xy, org]))
+        out = self._tt_out((len(rows),) + tuple(int(n) for n in nc), device)
+        p, dev = self._ptr(out, np.float64)
+        _check(qmlib.qm_engine_tt_sweep(self._h, ll, sp, nc, len(rows), rows.reshape(-1), row_section, psec, dev_sec,
+                                        n_sec, nr, nz, float(h), p, dev))
+        return out
 
     TRIGGER_METHODS = {"static": 0, "mad": 1, "median_ratio": 2}
 

@@ -768,6 +768,8 @@ const Readout kReadouts[] = {
     {"trigger_max_radius", V(qm::kTrigMaxRadius)}, {"trigger_smooth_tile", V(qm::kTrigSmoothTile)},
     {"trigger_run_block", V(qm::kTrigRunBlock)}, {"trigger_merge_stride", V(qm::kTrigMergeThreads)},
     {"scanmseed_tile", V(qm::kSmsTile)}, {"scanmseed_compose_chunk", V(qm::kSmsComposeChunk)},
+    {"tt_lds_nodes", V(qm::kTtLdsNodes)}, {"tt_section_threads", V(qm::kTtSectionThreads)},
+    {"tt_grid_blocks", V(qm::kTtGridBlocks)}, {"tt_grid_threads", V(qm::kTtGridThreads)},
     // the near-tie refinement
     {"tie_brick_rows", V(e->last.brick_rows)}, {"tie_refined_steps", V(e->tie.refined_steps)},
     {"tie_overflow_samples", V(e->tie.overflow_last), fetch_tie_counts}, {"tie_pairs", V(e->tie.pairs_last), fetch_tie_counts},
@@ -891,6 +893,7 @@ int qm_engine_get(qm_engine *e, const char *key, int64_t *v) {
         return 0;
     }
     if (clock_readout(e->trig.clock, "trigger_ns_", k, v) || clock_readout(e->sms.clock, "scanmseed_ns_", k, v) ||
+        clock_readout(e->tt.clock, "tt_ns_", k, v) ||
         config_get(e->cfg, key, v))
         return 0;
     return fail("unknown key '%s'", key);

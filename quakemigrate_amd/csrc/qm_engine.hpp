@@ -26,6 +26,8 @@
 //                    records of a .scanmseed file (encode, decode)
 //   qm_amplitudes.hip  the row after the picks: local-magnitude amplitudes, filtered traces and time windows in,
 //                    peak-to-trough measurements out
+//   qm_traveltimes.hip  the table the engine is built around: travel-time grids for a homogeneous medium, eikonal
+//                    sections of 1-D models and their sweep round the stations
 //   qm_compat.hip    the five reference-signature symbols (qmlib.h:28-44)
 //   qm_group.hip     engine groups: one process driving the boxes of a column partition on several devices
 // Whose scratch is whose: the stacking scratch and the serving grids are the engine's own members (folds, ties, streams
@@ -68,6 +70,7 @@
 #include "qm_trigger.hpp"
 #include "qm_amplitudes.hpp"
 #include "qm_scanmseed.hpp"
+#include "qm_traveltimes.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -440,6 +443,14 @@ struct ScanmseedCodec {                 // qm_engine_scanmseed_encode / _decode 
     DevBuf<int64_t> off;                // decode's offsets
     StageClock<qm::kSmsStages> clock{qm::kSmsStageNames};       // "scanmseed_ns_<stage>": always runs
 };
+struct TravelTimeStage {                // qm_engine_tt_homogeneous / _tt_sections / _tt_sweep (qm_traveltimes.hip)
+    DevBuf<double> par;                 // row parameters; the sections' slowness rows and sources
+    DevBuf<double> sec, out;            // a host caller's sections on their way in; grids or sections on their way out
+    DevBuf<double> tau;                 // the solver's tau of sections above the LDS limit: [n_sections][nr * nz]
+    DevBuf<int32_t> meta;               // the sweep's row -> section; the solver's rounds and status
+    DevBuf<unsigned long long> bad;     // the sweep's first node outside its section, per row
+    StageClock<qm::kTtStages> clock{qm::kTtStageNames};         // "tt_ns_<stage>": always runs
+};
 struct TieScratch {                     // the near-tie refinement (refine_ties, qm_engine_tie_partial; qm_ties.hpp)
     DevBuf<double> zext, zgrid, z;      // the largest z per sample left by the combine of the own sets; the GRID's (sharded)
     DevBuf<int32_t> pairs, imin, count, cands;
@@ -547,6 +558,7 @@ struct qm_engine : TableState {
     AmplitudeStage amps;
     TriggerStage trig;
     ScanmseedCodec sms;
+    TravelTimeStage tt;
     TieScratch tie;
     ScreenScratch sweep;
     FitScratch fit;
