@@ -186,6 +186,27 @@ def test_strict_iteration_has_the_restatements_bits(engine):
         assert np.array_equal(bits(got[0]), bits(T))
 
 
+def test_diagonals_longer_than_one_pass_of_the_workgroup(engine):
+    """515 x 514: the longest diagonals (514 nodes, two of them per sweep) exceed the workgroup's 512 threads, so the
+    kernel's walk along a diagonal (``ip += threads``) takes its second trip; the largest diagonal of the other cases
+    has 125 nodes.  Above the LDS limit: the scratch form.
+    Two sections in one launch, the gradient and the low-velocity model, the source between rows.  The restatement
+    settles in 7 and 8 rounds (about 4 s on a CPU); the kernel's time is printed (``-s``)."""
+    nr, nz = 515, 514
+    threads = engine.get("tt_section_threads")
+    assert min(nr, nz) > threads
+    assert nr * nz > engine.get("tt_lds_nodes")
+    slowness, zs, s0 = section_inputs(nz, names=("gradient", "low_velocity"), depths=[7.4 * H])
+    assert slowness.shape == (2, nz)
+    T, rounds, status = tr.solve_sections(slowness, zs, s0, nr, H)
+    got_T, got_rounds, got_status = engine.traveltime_sections(slowness, zs, nr, H, source_slowness=s0)
+    print(f"\n{nr} x {nz}, 2 sections: rounds {rounds.tolist()}, status {status.tolist()}, kernel "
+          f"{engine.get('tt_ns_sections') / 1e6:.1f} ms")
+    assert np.array_equal(got_status, status) and not status.any()
+    assert np.array_equal(got_rounds, rounds)
+    assert np.array_equal(bits(got_T), bits(T))
+
+
 def test_sections_refusals(engine, lib):
     nr, nz = 67, 45
     slowness, zs, s0 = section_inputs(nz, names=("gradient", "low_velocity"), depths=[7.4 * H])
