@@ -11,8 +11,8 @@
 //                    kind and the step entry points around them (detect / detect_batch / partial / finalize / migrate /
 //                    marginal / find_max_coa)
 //   qm_screen.hip    the opt-in screened detect's launch sequence
-//   qm_stream.hip    the continuous detect pipeline (pinned ring, copies overlapped with compute), also over
-//                    several engines that hold the same table (replicas: launches round-robin)
+//   qm_stream.hip    the continuous detect pipeline: one lane per engine (StreamLane: pinned ring, copies overlapped
+//                    with compute), launches round-robin over the lanes; a stream on one engine is the one-lane case
 //   qm_widen.hip     the rows next to the path: onset stage (OnsetStage), locate fits, RBF peak
 //   qm_preproc.hip   the row before the onset stage: detrend, taper, zero-phase band-pass of the component traces
 //                    (PreprocStage)
@@ -130,8 +130,8 @@ void event_destroy(hipEvent_t ev);
 //               un-keyed replacement, a stream's release, a stage's undo, a group's parts and its lead: one wait each.
 //   the device  the scope's end and pool_free wait for the CURRENT device: every owner is torn down under a DeviceGuard
 //               of its device (a group: each part under its own, the lead's buffers under the lead's).
-//   the order   an engine's streams are orphaned -- they release what they hold and forget the engine -- before the
-//               engine's own buffers go; an orphaned qm_stream destroyed later holds nothing and frees nothing.
+//   the order   an engine's stream lanes are orphaned -- they release what they hold and forget the engine -- before
+//               the engine's own buffers go; a qm_stream destroyed later finds such a lane empty and frees nothing.
 // release() is for giving something up EARLY, on purpose, while its owner lives on.
 struct PoolMem {
     static hipError_t get(void **out, size_t bytes, unsigned) { return pool_alloc(out, bytes); }
@@ -481,7 +481,7 @@ struct CallStaging {
     DevBuf<double> rs_raw;              // in: qm_engine_resample's raw samples (bytes, in doubles)
 };
 
-struct qm_stream;                    // a continuous-detect pipeline on an engine (qm_stream.hip)
+struct StreamLane;                   // a continuous-detect pipeline's ring on one engine (qm_stream.hip)
 
 // One stacking launch (StackLaunch below) as plan_stack decides it and issue_stack enqueues it (qm_engine.hip).
 // qm_engine::last is the plan of the last launch enqueued, assigned whole by run_stack: the only description of
@@ -513,7 +513,7 @@ struct StackPlan {
 
 struct qm_engine : TableState {
     int device = 0;
-    std::vector<qm_stream *> streams;   // pipelines alive on this engine: orphaned when it is destroyed
+    std::vector<StreamLane *> streams;  // pipelines' lanes alive on this engine: orphaned when it is destroyed
     int n_cu = 256;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;

@@ -37,21 +37,27 @@
 // The stages in front of the detect are the records of qm_engine.hpp (ResampleStage, PreprocStage, OnsetStage): the
 // stream builds its own, steps_per_launch times over, where the stage is set, launches them slot by slot and
 // releases them with its slots.  Nothing here checks a stage's arrays or fills a kernel's arguments.
+//
+// Two records: a StreamLane is one engine's ring and does what it is told (fill, launch, pop, build or undo a stage,
+// release); a qm_stream, the C ABI's handle, owns one lane per engine and keeps what belongs to the whole stream --
+// the launches in push order, the kind of input, which stages are set.  Launch j goes to lane j mod n; a stream on
+// one engine (qm_stream_create) is the one-lane case of a stream over replicas (qm_stream_create_replicas).
 #include "qm_engine.hpp"
 
 #include <deque>
 
 
-struct qm_stream {
-    qm_engine *e = nullptr;
+// what the pushes carry, one kind per stream: log-onsets [n_rows][T]; with an onset stage the component traces
+// [n_traces][T], from which the slot's log-onsets are made on the device; with a resampling stage as well the
+// packed raw samples, from which the slot's traces are made
+enum Feed { kNothingYet = 0, kLogOnsets = 1, kSignals = 2, kRaw = 3, kFeeds = 4 };
+
+struct StreamLane {
+    qm_engine *e = nullptr;             // (nullptr: orphaned by qm_engine_destroy -- the lane holds nothing any more)
     int n_rows = 0, T = 0, fsmp = 0, lsmp = 0, available = 0, ns = 0, K = 1, depth = 2;
     int64_t n_nodes_total = 0;
     uint64_t table_serial = 0;          // the table the stream was made on (TableState::serial)
     hipStream_t copy_stream = nullptr;
-    // what the pushes carry, one kind per stream: log-onsets [n_rows][T]; with an onset stage the component traces
-    // [n_traces][T], from which the slot's log-onsets are made on the device; with a resampling stage as well the
-    // packed raw samples, from which the slot's traces are made
-    enum Feed { kNothingYet = 0, kLogOnsets = 1, kSignals = 2, kRaw = 3, kFeeds = 4 };
     struct Slot {
         struct In {
             PinnedBuf<double> h;        // pinned [K][step_words[feed]] (the signals': given up at the first raw step)
@@ -68,28 +74,28 @@ struct qm_stream {
     std::vector<Slot> slots;
     std::deque<int> order;              // slots in flight, oldest first
     int fill_slot = 0, fill_n = 0;      // slot being filled, steps pushed into it so far
-    int64_t launched_steps = 0, popped_steps = 0, launches = 0;
+    int64_t launched_steps = 0, launches = 0;
     PinnedBuf<unsigned long long> h_stamp;   // ("stream_stamps") pinned [2][4096]
     bool pulled = false;                // the last launch's inputs were pulled by a kernel (no copy command)
-    int feed = kNothingYet;
     size_t step_words[kFeeds] = {};     // a timestep of each kind in doubles, as a slot holds it (raw bytes: rounded up)
     size_t step_bytes[kFeeds] = {};     // ... in bytes, as it is pushed
     // the stages (qm_engine.hpp), K times over: qm_stream_set_onset_stage builds `pre` and `on`,
     // qm_stream_set_resample_stage `rs`
-    bool staged = false, resampled = false;
     PreprocStage pre;
     OnsetStage on;
     ResampleStage rs;
-    // A stream over replicas (qm_stream_create_replicas) holds no slots of its own: one ordinary stream per
-    // engine (a LANE, registered on that engine like any other stream) and the launches in push order.  Launch j
-    // goes to lane j mod n; the entry points dispatch to the replicas_* functions below.
-    std::vector<qm_stream *> lanes;
+};
+
+struct qm_stream {
+    std::vector<std::unique_ptr<StreamLane>> lanes;    // one per engine, at least one (registered on that engine)
     struct Launch {
         int lane = 0;
         int left = 0;                   // steps not yet popped
     };
-    std::deque<Launch> launched;        // oldest first
+    std::deque<Launch> launched;        // every lane's launches in push order, oldest first
     int cur = 0;                        // the lane being filled
+    int feed = kNothingYet;             // the kind of the steps pushed so far
+    bool staged = false, resampled = false;     // the onset stage, the resampling stage: on every lane or on none
 };
 
 namespace {
@@ -115,21 +121,17 @@ __global__ __launch_bounds__(256) void pull_kernel(const pull2 *__restrict__ src
 // ("stream_stamps": the GPU's own clock before and behind every launch of a stream, digested at its destruction)
 __global__ void stamp_kernel(unsigned long long *slot) { *slot = wall_clock64(); }
 
-int alive(const qm_stream *s, const char *what) {
-    if (!s) return fail("%s: NULL argument", what);
-    if (!s->e) return fail("%s: the stream's engine has been destroyed", what);
-    return 0;
-}
+// ---- a lane: one engine's ring.  The engine's device is current in all of these. ------------------------------
 
 // every slot's buffers for one kind of input, K timesteps each (s->step_words[feed] is set)
-int alloc_inputs(qm_stream *s, int feed, const char *what) {
+int alloc_inputs(StreamLane *s, int feed, const char *what) {
     const size_t words = (size_t)s->K * s->step_words[feed];
     hipError_t r = hipSuccess;
-    for (qm_stream::Slot &sl : s->slots) {
-        qm_stream::Slot::In &in = sl.in[feed];
+    for (StreamLane::Slot &sl : s->slots) {
+        StreamLane::Slot::In &in = sl.in[feed];
         if (r == hipSuccess) r = in.h.alloc(words, hipHostMallocDefault);
         if (r == hipSuccess) r = in.d.alloc(words);
-        if (r == hipSuccess && feed == qm_stream::kRaw)         // (the bytes a step's int32s leave over)
+        if (r == hipSuccess && feed == kRaw)            // (the bytes a step's int32s leave over)
             std::memset(in.h.p, 0, words * sizeof(double));
     }
     if (r != hipSuccess)
@@ -138,8 +140,8 @@ int alloc_inputs(qm_stream *s, int feed, const char *what) {
     return 0;
 }
 
-// everything the stream holds on its engine's device goes back (the engine's device is current)
-void release_stream(qm_stream *s) {
+// everything the lane holds on its engine's device goes back
+void release_lane(StreamLane *s) {
     (void)hipStreamSynchronize(s->e->stream);
     if (s->h_stamp.p) {
         // launch i: [begin_i, end_i]; gap_i = begin_i - end_(i-1)   (wall_clock64: 100 MHz)
@@ -163,7 +165,7 @@ void release_stream(qm_stream *s) {
     if (s->copy_stream) (void)hipStreamSynchronize(s->copy_stream);
     {
         PoolReleaseScope one_wait;
-        for (qm_stream::Slot &sl : s->slots) sl = qm_stream::Slot{};
+        for (StreamLane::Slot &sl : s->slots) sl = StreamLane::Slot{};
         s->rs = ResampleStage{};
         s->pre = PreprocStage{};
         s->on = OnsetStage{};
@@ -173,10 +175,27 @@ void release_stream(qm_stream *s) {
     s->order.clear();
 }
 
-// H2D, the launch and D2H of the slot being filled: enqueue only
-int launch_slot(qm_stream *s) {
+// A timestep of the stream's kind into the slot being filled, which has room (fill_n < K).  0, or 2: that slot is the
+// lane's oldest launch and holds results that have not been popped.
+int fill(StreamLane *s, const void *step, int feed, const char *what) {
+    StreamLane::Slot &sl = s->slots[s->fill_slot];
+    if (s->fill_n == 0 && sl.in_flight) {
+        (void)fail("%s: all %d slots hold results that have not been popped", what, s->depth);
+        return 2;
+    }
+    // (the slot's previous H2D has finished: its launch's results were popped)
+    if (feed == kRaw && sl.in[kSignals].h.p)            // the first raw step: the ring's pinned slots hold raw bytes
+        for (StreamLane::Slot &other : s->slots)        // from here on, the signals' pinned buffers are given up
+            other.in[kSignals].h.release();
+    host_copy(sl.in[feed].h.p + (size_t)s->fill_n * s->step_words[feed], step, s->step_bytes[feed]);
+    ++s->fill_n;
+    return 0;
+}
+
+// H2D, the launch and D2H of the slot being filled, which holds steps of kind `feed`: enqueue only
+int launch_slot(StreamLane *s, int feed) {
     qm_engine *e = s->e;
-    qm_stream::Slot &sl = s->slots[s->fill_slot];
+    StreamLane::Slot &sl = s->slots[s->fill_slot];
     const int n = s->fill_n;
     // (not the row count alone -- another table of the same shape, e.g. a table_select switch or a
     // foreign load on the shared default engine, would be stacked and normalised as if it were the stream's)
@@ -186,9 +205,9 @@ int launch_slot(qm_stream *s) {
                     (unsigned long long)(e->have_lut ? e->serial : 0), e->have_lut ? e->g.n_rows : 0,
                     (unsigned long long)s->table_serial, s->n_rows);
     const size_t kns = (size_t)s->K * s->ns;
-    const size_t words = (size_t)n * s->step_words[s->feed];
-    const double *h_in = sl.in[s->feed].h.p;
-    double *d_in = sl.in[s->feed].d.p;
+    const size_t words = (size_t)n * s->step_words[feed];
+    const double *h_in = sl.in[feed].h.p;
+    double *d_in = sl.in[feed].d.p;
     const bool pull = e->cfg.stream_pull > 0 || (e->cfg.stream_pull < 0 && words * sizeof(double) <= kPullBytes);
     // ("stream_stamps" = 1, measurement: the GPU's clock before and behind every launch -- two one-thread kernels;
     // the digest goes to stderr when the stream is destroyed.  What found round 6's one-off stall: tools/diag_stream.py)
@@ -213,12 +232,12 @@ int launch_slot(qm_stream *s) {
         QM_HIP(hipStreamWaitEvent(e->stream, sl.copied, 0));
     }
     s->pulled = pull;
-    double *d_sig = sl.in[qm_stream::kSignals].d.p, *d_on = sl.in[qm_stream::kLogOnsets].d.p;
+    double *d_sig = sl.in[kSignals].d.p, *d_on = sl.in[kLogOnsets].d.p;
     // raw samples -> the n steps' traces at the scan rate, straight into the slot's signals
-    if (s->feed == qm_stream::kRaw && s->rs.launch(e, d_in, d_sig, n)) return 1;
+    if (feed == kRaw && s->rs.launch(e, d_in, d_sig, n)) return 1;
     // waveforms -> log-onsets, all on the engine's stream: the n steps' traces filtered in place, then the onset
     // kernels, straight into the slot's log-onsets
-    if (s->feed == qm_stream::kRaw || s->feed == qm_stream::kSignals)
+    if (feed == kRaw || feed == kSignals)
         if (s->pre.launch(e, d_sig, d_sig, n) || s->on.launch(e, d_sig, nullptr, d_on, n)) return 1;
     // The results are a few KB per timestep: the combine kernel writes them STRAIGHT into the slot's
     // pinned host buffer (pinned memory is device-accessible under one address; the event behind the
@@ -243,111 +262,142 @@ int launch_slot(qm_stream *s) {
     return 0;
 }
 
-// A stage that did not come about, on this stream or on a later lane -- the onset stage (feed = kSignals) or the
-// resampling stage (kRaw): what it took goes back and the stream is what it was before (the engine's device is
-// current; the error text stays).  Returns 1.
-int stage_undo(qm_stream *s, int feed) {
+// the next `take` timesteps of the lane's oldest launch, which has that many left; waits for the launch
+int pop_oldest(StreamLane *s, int take, double *max_coa, double *max_norm_coa, int64_t *max_coa_idx) {
+    StreamLane::Slot &sl = s->slots[s->order.front()];
+    QM_HIP(hipEventSynchronize(sl.done));
+    const size_t ns = (size_t)s->ns, kns = (size_t)s->K * ns;
+    const double *src = sl.h_out.p + (size_t)sl.taken * ns;
+    std::memcpy(max_coa, src, (size_t)take * ns * sizeof(double));
+    std::memcpy(max_norm_coa, src + kns, (size_t)take * ns * sizeof(double));
+    std::memcpy(max_coa_idx, src + 2 * kns, (size_t)take * ns * sizeof(int64_t));
+    sl.taken += take;
+    if (sl.taken == sl.n) {
+        sl.in_flight = false;
+        s->order.pop_front();
+    }
+    return 0;
+}
+
+// A stage that did not come about, on this lane or on a later one -- the onset stage (feed = kSignals) or the
+// resampling stage (kRaw): what it took goes back and the lane is what it was before (the error text stays).
+void stage_undo(StreamLane *s, int feed) {
     PoolReleaseScope one_wait;
-    for (qm_stream::Slot &sl : s->slots) sl.in[feed] = {};
-    if (feed == qm_stream::kRaw) {
+    for (StreamLane::Slot &sl : s->slots) sl.in[feed] = {};
+    if (feed == kRaw) {
         s->rs = ResampleStage{};
-        s->resampled = false;
     } else {
         s->pre = PreprocStage{};
         s->on = OnsetStage{};
-        s->staged = false;
     }
-    return 1;
 }
 
-// ---- replicas: one pipeline over several engines that hold the same table -----------------------------------
+// ---- the stream: one pipeline over its lanes ------------------------------------------------------------------
 // Launches go round the lanes in push order, so a lane's next slot is in flight only when all n x depth launches
 // are un-popped -- and then the oldest launch is on that lane: "pop the oldest launch, push again" still frees it.
 
-// a stage on every lane or on none: the lanes before the one that refused give it back
-template <typename Set>
-int replicas_stage(qm_stream *s, int feed, Set set) {
-    for (qm_stream *lane : s->lanes)
-        if (set(lane)) {
-            for (qm_stream *before : s->lanes) {
-                if (before == lane) break;
-                DeviceGuard guard(before->e->device);
-                stage_undo(before, feed);
-            }
-            return 1;
-        }
-    (feed == qm_stream::kRaw ? s->resampled : s->staged) = true;
+int alive(const qm_stream *s, const char *what) {
+    if (!s) return fail("%s: NULL argument", what);
+    for (const auto &lane : s->lanes)
+        if (!lane->e) return fail("%s: the stream's engine has been destroyed", what);
     return 0;
 }
 
-int replicas_alive(const qm_stream *s, const char *what) {
-    for (const qm_stream *lane : s->lanes)
-        if (alive(lane, what)) return 1;
-    return 0;
-}
-
-// the current lane launched `steps` timesteps (a push that filled its slot, or a flush): record them, next lane
-void replicas_launched(qm_stream *s, int64_t steps) {
-    s->launched.push_back({s->cur, (int)steps});
-    s->cur = (s->cur + 1) % (int)s->lanes.size();
-}
-
-int replicas_flush(qm_stream *s) {
-    if (replicas_alive(s, "qm_stream_flush")) return 1;
-    qm_stream *lane = s->lanes[s->cur];
-    const int64_t before = lane->launched_steps;
-    if (qm_stream_flush(lane)) return 1;
-    if (lane->launched_steps != before) replicas_launched(s, lane->launched_steps - before);
-    return 0;
-}
-
-int replicas_push(qm_stream *s, const void *step, int feed, const char *what) {
-    if (replicas_alive(s, what)) return 1;
-    // (a full slot whose launch failed -- the table changed under the stream -- goes out first, as on one engine;
-    // then this timestep goes to the next lane, not behind it on the same one)
-    if (s->lanes[s->cur]->fill_n >= s->lanes[s->cur]->K && replicas_flush(s)) return 1;
-    qm_stream *lane = s->lanes[s->cur];
-    const int64_t before = lane->launched_steps;
-    const int rc = feed == qm_stream::kRaw ? qm_stream_push_raw(lane, step)
-                   : feed == qm_stream::kSignals ? qm_stream_push_signals(lane, static_cast<const double *>(step))
-                                                 : qm_stream_push(lane, static_cast<const double *>(step));
-    if (lane->launched_steps != before) replicas_launched(s, lane->launched_steps - before);
-    return rc;
-}
-
-int replicas_pending(const qm_stream *s, int64_t *launched_not_popped) {
+// launched and not yet popped, over all lanes
+int64_t waiting(const qm_stream *s) {
     int64_t n = 0;
-    for (const qm_stream *lane : s->lanes) n += lane->launched_steps - lane->popped_steps;
-    *launched_not_popped = n;
-    return s->lanes[s->cur]->fill_n;
+    for (const qm_stream::Launch &l : s->launched) n += l.left;
+    return n;
 }
 
-int replicas_pop(qm_stream *s, int32_t n_steps, double *max_coa, double *max_norm_coa, int64_t *max_coa_idx) {
-    if (replicas_alive(s, "qm_stream_pop")) return 1;
-    int64_t waiting = 0;
-    const int filling = replicas_pending(s, &waiting);
-    if (n_steps < 0 || n_steps > waiting)
-        return fail("qm_stream_pop: %d steps asked for, %lld launched and not yet popped (%d pushed into "
-                    "a launch that has not gone out: qm_stream_flush)", n_steps, (long long)waiting, filling);
-    const size_t ns = (size_t)s->lanes[0]->ns;
-    for (int k = 0; k < n_steps;) {
-        qm_stream::Launch &l = s->launched.front();
-        const int take = std::min(n_steps - k, l.left);
-        if (qm_stream_pop(s->lanes[l.lane], take, max_coa + k * ns, max_norm_coa + k * ns, max_coa_idx + k * ns))
-            return 1;
-        k += take;
-        l.left -= take;
-        if (l.left == 0) s->launched.pop_front();
+// "before the first push" is over: something has been pushed into or launched from a lane
+bool pushed_to(const qm_stream *s) {
+    return std::any_of(s->lanes.begin(), s->lanes.end(),
+                       [](const auto &lane) { return lane->fill_n > 0 || lane->launched_steps > 0; });
+}
+
+// the lane being filled sends what its slot holds (its device is current); the next lane is filled from here on
+int send(qm_stream *s) {
+    StreamLane *lane = s->lanes[s->cur].get();
+    const int n = lane->fill_n;
+    if (launch_slot(lane, s->feed)) return 1;
+    s->launched.push_back({s->cur, n});
+    s->cur = (s->cur + 1) % (int)s->lanes.size();
+    return 0;
+}
+
+// ... the same from outside a lane's device; nothing to send is fine
+int flush(qm_stream *s) {
+    StreamLane *lane = s->lanes[s->cur].get();
+    if (lane->fill_n == 0) return 0;
+    DeviceGuard guard(lane->e->device);
+    return send(s);
+}
+
+// a stage on every lane or on none: where a lane refuses, it and the lanes before it give back what they took
+template <typename Build>
+int stage_every_lane(qm_stream *s, int feed, Build build) {
+    for (size_t i = 0; i < s->lanes.size(); ++i) {
+        DeviceGuard guard(s->lanes[i]->e->device);
+        if (!build(s->lanes[i].get())) continue;
+        for (size_t j = 0; j <= i; ++j) {
+            DeviceGuard undo(s->lanes[j]->e->device);
+            stage_undo(s->lanes[j].get(), feed);
+        }
+        return 1;
     }
+    (feed == kRaw ? s->resampled : s->staged) = true;
+    return 0;
+}
+
+// One lane per engine, on tables the caller has found equal; `what` is the entry point's name.
+int create(qm_engine *const *engines, int n_engines, const char *what, int32_t t_samples, int32_t fsmp, int32_t lsmp,
+           int32_t available, int64_t n_nodes_total, int32_t steps_per_launch, int32_t depth, qm_stream **out) {
+    if (steps_per_launch < 1 || steps_per_launch > 4096)
+        return fail("%s: steps_per_launch must be in 1..4096 (got %d)", what, steps_per_launch);
+    if (depth < 2 || depth > 64) return fail("%s: depth must be in 2..64 (got %d)", what, depth);
+    // (destroyed as any stream is if a step below fails: a lane not yet on its engine's list, which destroy does not mind)
+    std::unique_ptr<qm_stream, decltype(&qm_stream_destroy)> s(new qm_stream(), qm_stream_destroy);
+    for (int r = 0; r < n_engines; ++r) {
+        qm_engine *e = engines[r];
+        int ns = 0;
+        if (check_step(e, t_samples, fsmp, lsmp, available, &ns)) return 1;
+        if ((int64_t)steps_per_launch * ns >= INT32_MAX) return fail("%s: too many samples per launch", what);
+        DeviceGuard guard(e->device);
+        s->lanes.emplace_back(new StreamLane());
+        StreamLane *lane = s->lanes.back().get();
+        lane->e = e;
+        lane->n_rows = e->g.n_rows;
+        lane->table_serial = e->serial;
+        lane->T = t_samples; lane->fsmp = fsmp; lane->lsmp = lsmp; lane->available = available; lane->ns = ns;
+        lane->K = steps_per_launch; lane->depth = depth;
+        lane->n_nodes_total = n_nodes_total > 0 ? n_nodes_total : e->n_nodes;
+        // (the copy stream is taken at the first launch that copies: slots that are pulled never need one)
+        lane->slots.resize((size_t)depth);
+        lane->step_words[kLogOnsets] = (size_t)lane->n_rows * lane->T;
+        lane->step_bytes[kLogOnsets] = lane->step_words[kLogOnsets] * sizeof(double);
+        const size_t out_bytes = 3 * (size_t)lane->K * ns * sizeof(double);
+        for (StreamLane::Slot &sl : lane->slots) {
+            hipError_t err = sl.h_out.alloc(out_bytes / sizeof(double), hipHostMallocDefault);
+            for (Event *ev : {&sl.copied, &sl.done})
+                if (err == hipSuccess) err = ev->create(hipEventDisableTiming);
+            if (err != hipSuccess)
+                return fail("%s: %s (%d steps of %zu bytes of results per slot, %d slots)", what,
+                            hipGetErrorString(err), lane->K, out_bytes / lane->K, depth);
+        }
+        if (alloc_inputs(lane, kLogOnsets, what)) return 1;
+        e->streams.push_back(lane);
+    }
+    *out = s.release();
     return 0;
 }
 
 }  // namespace
 
 void streams_orphan(qm_engine *e) {
-    for (qm_stream *s : e->streams) {
-        release_stream(s);
-        s->e = nullptr;
+    for (StreamLane *lane : e->streams) {
+        release_lane(lane);
+        lane->e = nullptr;
     }
     e->streams.clear();
 }
@@ -358,38 +408,8 @@ int qm_stream_create(qm_engine *e, int32_t t_samples, int32_t fsmp, int32_t lsmp
                      int64_t n_nodes_total, int32_t steps_per_launch, int32_t depth, qm_stream **out) {
     if (!e || !out) return fail("qm_stream_create: NULL argument");
     *out = nullptr;
-    if (steps_per_launch < 1 || steps_per_launch > 4096)
-        return fail("qm_stream_create: steps_per_launch must be in 1..4096 (got %d)", steps_per_launch);
-    if (depth < 2 || depth > 64) return fail("qm_stream_create: depth must be in 2..64 (got %d)", depth);
-    int ns = 0;
-    if (check_step(e, t_samples, fsmp, lsmp, available, &ns)) return 1;
-    if ((int64_t)steps_per_launch * ns >= INT32_MAX) return fail("qm_stream_create: too many samples per launch");
-    DeviceGuard guard(e->device);
-    // (destroyed as any stream is if a step below fails; not yet on the engine's list, which destroy does not mind)
-    std::unique_ptr<qm_stream, decltype(&qm_stream_destroy)> s(new qm_stream(), qm_stream_destroy);
-    s->e = e;
-    s->n_rows = e->g.n_rows;
-    s->table_serial = e->serial;
-    s->T = t_samples; s->fsmp = fsmp; s->lsmp = lsmp; s->available = available; s->ns = ns;
-    s->K = steps_per_launch; s->depth = depth;
-    s->n_nodes_total = n_nodes_total > 0 ? n_nodes_total : e->n_nodes;
-    // (the copy stream is taken at the first launch that copies: slots that are pulled never need one)
-    s->slots.resize((size_t)depth);
-    s->step_words[qm_stream::kLogOnsets] = (size_t)s->n_rows * s->T;
-    s->step_bytes[qm_stream::kLogOnsets] = s->step_words[qm_stream::kLogOnsets] * sizeof(double);
-    const size_t out_bytes = 3 * (size_t)s->K * ns * sizeof(double);
-    for (qm_stream::Slot &sl : s->slots) {
-        hipError_t r = sl.h_out.alloc(out_bytes / sizeof(double), hipHostMallocDefault);
-        for (Event *ev : {&sl.copied, &sl.done})
-            if (r == hipSuccess) r = ev->create(hipEventDisableTiming);
-        if (r != hipSuccess)
-            return fail("qm_stream_create: %s (%d steps of %zu bytes of results per slot, %d slots)",
-                        hipGetErrorString(r), s->K, out_bytes / s->K, depth);
-    }
-    if (alloc_inputs(s.get(), qm_stream::kLogOnsets, "qm_stream_create")) return 1;
-    e->streams.push_back(s.get());
-    *out = s.release();
-    return 0;
+    return create(&e, 1, "qm_stream_create", t_samples, fsmp, lsmp, available, n_nodes_total, steps_per_launch, depth,
+                  out);
 }
 
 int qm_stream_create_replicas(qm_engine *const *engines, int32_t n_engines, int32_t t_samples, int32_t fsmp,
@@ -421,84 +441,61 @@ int qm_stream_create_replicas(qm_engine *const *engines, int32_t n_engines, int3
         if (qm_engine_table_digest(engines[r], &d)) return 1;
         if (d != d0) return fail("qm_stream_create_replicas: replica %d holds another table than replica 0", r);
     }
-    std::unique_ptr<qm_stream, decltype(&qm_stream_destroy)> s(new qm_stream(), qm_stream_destroy);
-    for (int r = 0; r < n_engines; ++r) {
-        qm_stream *lane = nullptr;
-        if (qm_stream_create(engines[r], t_samples, fsmp, lsmp, available, n_nodes_total, steps_per_launch, depth,
-                             &lane))
-            return 1;
-        s->lanes.push_back(lane);
-    }
-    *out = s.release();
-    return 0;
+    return create(engines, n_engines, "qm_stream_create_replicas", t_samples, fsmp, lsmp, available, n_nodes_total,
+                  steps_per_launch, depth, out);
 }
 
 void qm_stream_destroy(qm_stream *s) {
     if (!s) return;
-    for (qm_stream *lane : s->lanes) qm_stream_destroy(lane);   // (a replicated stream: its lanes, orphaned or not)
-    if (s->e) {                                         // (else: orphaned by qm_engine_destroy)
-        DeviceGuard guard(s->e->device);
-        release_stream(s);
-        auto &list = s->e->streams;
-        list.erase(std::remove(list.begin(), list.end(), s), list.end());
+    for (const auto &lane : s->lanes) {
+        if (!lane->e) continue;                         // (orphaned by qm_engine_destroy: released there)
+        DeviceGuard guard(lane->e->device);
+        release_lane(lane.get());
+        auto &list = lane->e->streams;
+        list.erase(std::remove(list.begin(), list.end(), lane.get()), list.end());
     }
     delete s;
 }
 
-// a timestep into the slot being filled: log-onsets, (an onset stage) signals or (a resampling stage as well) raw
+// a timestep into the lane being filled: log-onsets, (an onset stage) signals or (a resampling stage as well) raw
 // samples -- one kind per stream
 static int push_step(qm_stream *s, const void *step, int feed, const char *what) {
     if (!step || !s) return fail("%s: NULL argument", what);
-    const bool replicated = !s->lanes.empty();          // (the kind of input is the whole stream's, not a lane's)
-    if (!replicated && alive(s, what)) return 1;
-    if (feed == qm_stream::kSignals && !s->staged)
+    if (alive(s, what)) return 1;
+    if (feed == kSignals && !s->staged)
         return fail("qm_stream_push_signals: the stream has no onset stage (qm_stream_set_onset_stage)");
-    if (feed == qm_stream::kRaw && !s->resampled)
+    if (feed == kRaw && !s->resampled)
         return fail("qm_stream_push_raw: the stream has no resampling stage (qm_stream_set_resample_stage)");
-    if (feed == qm_stream::kSignals && s->resampled)
+    if (feed == kSignals && s->resampled)
         return fail("qm_stream_push_signals: this stream takes raw traces (qm_stream_push_raw): one stream, one kind of "
                     "input");
-    if (s->feed != qm_stream::kNothingYet && s->feed != feed)
+    if (s->feed != kNothingYet && s->feed != feed)
         return fail("%s: this stream takes %s: one stream, one kind of input", what,
-                    s->feed == qm_stream::kRaw       ? "raw traces (qm_stream_push_raw)"
-                    : s->feed == qm_stream::kSignals ? "signals (qm_stream_push_signals)"
-                                                     : "log-onsets (qm_stream_push)");
-    if (replicated) {
-        const int rc = replicas_push(s, step, feed, what);
-        if (rc == 0) s->feed = feed;
-        return rc;
-    }
-    DeviceGuard guard(s->e->device);
+                    s->feed == kRaw       ? "raw traces (qm_stream_push_raw)"
+                    : s->feed == kSignals ? "signals (qm_stream_push_signals)"
+                                          : "log-onsets (qm_stream_push)");
     // A full slot whose launch FAILED (the table changed under the stream, no memory, a refused step) is still
     // waiting to go out: it goes first, or this call fails as that one did -- never a copy past the slot's
     // K timesteps (the next push used to write one timestep behind the pinned buffer and launch
-    // K + 1 of them).
-    if (s->fill_n >= s->K && launch_slot(s)) return 1;
-    qm_stream::Slot &sl = s->slots[s->fill_slot];
-    if (s->fill_n == 0 && sl.in_flight) {
-        (void)fail("%s: all %d slots hold results that have not been popped", what, s->depth);
-        return 2;
-    }
+    // K + 1 of them).  This timestep then goes to the next lane, not behind it on the same one.
+    if (s->lanes[s->cur]->fill_n >= s->lanes[s->cur]->K && flush(s)) return 1;
+    StreamLane *lane = s->lanes[s->cur].get();
+    DeviceGuard guard(lane->e->device);
+    if (const int rc = fill(lane, step, feed, what)) return rc;
     s->feed = feed;
-    // (the slot's previous H2D has finished: its launch's results were popped)
-    if (feed == qm_stream::kRaw && sl.in[qm_stream::kSignals].h.p)  // the first raw step: the ring's pinned slots hold
-        for (qm_stream::Slot &other : s->slots)         // raw bytes from here on, the signals' pinned buffers are given up
-            other.in[qm_stream::kSignals].h.release();
-    host_copy(sl.in[feed].h.p + (size_t)s->fill_n * s->step_words[feed], step, s->step_bytes[feed]);
-    if (++s->fill_n < s->K) return 0;
-    return launch_slot(s);
+    return lane->fill_n < lane->K ? 0 : send(s);
 }
 
 int qm_stream_push(qm_stream *s, const double *log_onsets) {
-    return push_step(s, log_onsets, qm_stream::kLogOnsets, "qm_stream_push");
+    return push_step(s, log_onsets, kLogOnsets, "qm_stream_push");
 }
 
 int qm_stream_push_signals(qm_stream *s, const double *signals) {
-    return push_step(s, signals, qm_stream::kSignals, "qm_stream_push_signals");
+    return push_step(s, signals, kSignals, "qm_stream_push_signals");
 }
 
 int qm_stream_push_raw(qm_stream *s, const void *raw) {
-    return push_step(s, raw, qm_stream::kRaw, "qm_stream_push_raw");
+    return push_step(s, raw, kRaw, "qm_stream_push_raw");
 }
 
 int qm_stream_set_resample_stage(qm_stream *s, int32_t n_traces, const int64_t *records, const double *sos_lp,
@@ -509,32 +506,24 @@ int qm_stream_set_resample_stage(qm_stream *s, int32_t n_traces, const int64_t *
     if (!s) return fail("%s: NULL argument", what);
     if (!s->staged) return fail("%s: the stream has no onset stage (qm_stream_set_onset_stage comes first)", what);
     if (s->resampled) return fail("%s: the stream has its resampling stage already (it is set once)", what);
-    if (s->feed != qm_stream::kNothingYet || s->fill_n > 0 || s->launched_steps > 0)
-        return fail("%s: the stage is set before the first push", what);
-    if (!s->lanes.empty())
-        return replicas_stage(s, qm_stream::kRaw, [&](qm_stream *lane) {
-            return qm_stream_set_resample_stage(lane, n_traces, records, sos_lp, n_lowpass, n_sections_lp, detrend,
-                                                taper_table, n_tapers, taper_weights, n_taper_weights, t_samples,
-                                                raw_dtype, total_raw_samples);
-        });
+    if (pushed_to(s)) return fail("%s: the stage is set before the first push", what);
     if (alive(s, what)) return 1;
-    if (t_samples != s->T || n_traces != s->pre.n_traces)
+    const StreamLane *lead = s->lanes[0].get();
+    if (t_samples != lead->T || n_traces != lead->pre.n_traces)
         return fail("%s: %d traces of %d samples, the onset stage takes %d of %d", what, n_traces, t_samples,
-                    s->pre.n_traces, s->T);
+                    lead->pre.n_traces, lead->T);
     if (total_raw_samples > 0 &&
-        (double)s->K * (double)ResampleStage::step_doubles(raw_dtype, total_raw_samples) * 8.0 >= 0x1p40)
+        (double)lead->K * (double)ResampleStage::step_doubles(raw_dtype, total_raw_samples) * 8.0 >= 0x1p40)
         return fail("%s: too many raw samples per launch", what);
-    qm_engine *e = s->e;
-    DeviceGuard guard(e->device);
-    if (s->rs.build(e, what, s->K, raw_dtype, total_raw_samples, n_traces, t_samples, records, sos_lp, n_lowpass,
-                    n_sections_lp, detrend, taper_table, n_tapers, taper_weights, n_taper_weights))
-        return stage_undo(s, qm_stream::kRaw);
-    // (the signals' pinned buffers are given up at the first qm_stream_push_raw: until then nothing is lost)
-    s->step_words[qm_stream::kRaw] = s->rs.raw_step;
-    s->step_bytes[qm_stream::kRaw] = s->rs.raw_bytes;
-    if (alloc_inputs(s, qm_stream::kRaw, what)) return stage_undo(s, qm_stream::kRaw);
-    s->resampled = true;
-    return 0;
+    return stage_every_lane(s, kRaw, [&](StreamLane *lane) {
+        if (lane->rs.build(lane->e, what, lane->K, raw_dtype, total_raw_samples, n_traces, t_samples, records, sos_lp,
+                           n_lowpass, n_sections_lp, detrend, taper_table, n_tapers, taper_weights, n_taper_weights))
+            return 1;
+        // (the signals' pinned buffers are given up at the first qm_stream_push_raw: until then nothing is lost)
+        lane->step_words[kRaw] = lane->rs.raw_step;
+        lane->step_bytes[kRaw] = lane->rs.raw_bytes;
+        return alloc_inputs(lane, kRaw, what);
+    });
 }
 
 int qm_stream_set_onset_stage(qm_stream *s, int32_t n_traces, const int32_t *trace_row, const int32_t *trace_filter,
@@ -545,81 +534,54 @@ int qm_stream_set_onset_stage(qm_stream *s, int32_t n_traces, const int32_t *tra
     const char *what = "qm_stream_set_onset_stage";
     if (!s) return fail("%s: NULL argument", what);
     if (s->staged) return fail("%s: the stream has its onset stage already (it is set once)", what);
-    if (s->feed != qm_stream::kNothingYet || s->fill_n > 0 || s->launched_steps > 0)
-        return fail("%s: the stage is set before the first push", what);
-    if (!s->lanes.empty())
-        return replicas_stage(s, qm_stream::kSignals, [&](qm_stream *lane) {
-            return qm_stream_set_onset_stage(lane, n_traces, trace_row, trace_filter, sos, n_filters, n_sections, detrend,
-                                             taper_left, n_left, taper_right, n_right, nsta, nlta, transform, position,
-                                             taper_pad, min_onset_value);
-        });
+    if (pushed_to(s)) return fail("%s: the stage is set before the first push", what);
     if (alive(s, what)) return 1;
-    if ((int64_t)s->K * n_traces * s->T >= INT32_MAX || (int64_t)s->K * s->n_rows * s->T >= INT32_MAX)
+    const StreamLane *lead = s->lanes[0].get();
+    if ((int64_t)lead->K * n_traces * lead->T >= INT32_MAX || (int64_t)lead->K * lead->n_rows * lead->T >= INT32_MAX)
         return fail("%s: too many samples per launch", what);
-    qm_engine *e = s->e;
-    DeviceGuard guard(e->device);
-    if (s->pre.build(e, what, s->K, n_traces, s->T, trace_filter, sos, n_filters, n_sections, detrend, taper_left, n_left,
-                     taper_right, n_right, /*zero_phase=*/1) ||
-        s->on.build(e, what, s->K, n_traces, s->T, trace_row, s->n_rows, nsta, nlta, transform, position, taper_pad,
-                    min_onset_value))
-        return stage_undo(s, qm_stream::kSignals);
-    s->step_words[qm_stream::kSignals] = (size_t)n_traces * s->T;
-    s->step_bytes[qm_stream::kSignals] = s->step_words[qm_stream::kSignals] * sizeof(double);
-    if (alloc_inputs(s, qm_stream::kSignals, what)) return stage_undo(s, qm_stream::kSignals);
-    s->staged = true;
-    return 0;
+    return stage_every_lane(s, kSignals, [&](StreamLane *lane) {
+        if (lane->pre.build(lane->e, what, lane->K, n_traces, lane->T, trace_filter, sos, n_filters, n_sections, detrend,
+                            taper_left, n_left, taper_right, n_right, /*zero_phase=*/1) ||
+            lane->on.build(lane->e, what, lane->K, n_traces, lane->T, trace_row, lane->n_rows, nsta, nlta, transform,
+                           position, taper_pad, min_onset_value))
+            return 1;
+        lane->step_words[kSignals] = (size_t)n_traces * lane->T;
+        lane->step_bytes[kSignals] = lane->step_words[kSignals] * sizeof(double);
+        return alloc_inputs(lane, kSignals, what);
+    });
 }
 
 int qm_stream_flush(qm_stream *s) {
-    if (s && !s->lanes.empty()) return replicas_flush(s);
     if (alive(s, "qm_stream_flush")) return 1;
-    if (s->fill_n == 0) return 0;
-    DeviceGuard guard(s->e->device);
-    return launch_slot(s);
+    return flush(s);
+}
+
+int qm_stream_pending(qm_stream *s, int32_t *launched_not_popped, int32_t *pushed_not_launched) {
+    if (alive(s, "qm_stream_pending")) return 1;
+    if (launched_not_popped) *launched_not_popped = (int32_t)waiting(s);
+    if (pushed_not_launched) *pushed_not_launched = s->lanes[s->cur]->fill_n;
+    return 0;
 }
 
 int qm_stream_pop(qm_stream *s, int32_t n_steps, double *max_coa, double *max_norm_coa,
                   int64_t *max_coa_idx) {
     if (!max_coa || !max_norm_coa || !max_coa_idx) return fail("qm_stream_pop: NULL argument");
-    if (s && !s->lanes.empty()) return replicas_pop(s, n_steps, max_coa, max_norm_coa, max_coa_idx);
     if (alive(s, "qm_stream_pop")) return 1;
-    if (n_steps < 0 || n_steps > s->launched_steps - s->popped_steps)
+    if (n_steps < 0 || n_steps > waiting(s))
         return fail("qm_stream_pop: %d steps asked for, %lld launched and not yet popped (%d pushed into "
-                    "a launch that has not gone out: qm_stream_flush)", n_steps,
-                    (long long)(s->launched_steps - s->popped_steps), s->fill_n);
-    DeviceGuard guard(s->e->device);
-    const size_t ns = (size_t)s->ns, kns = (size_t)s->K * ns;
+                    "a launch that has not gone out: qm_stream_flush)", n_steps, (long long)waiting(s),
+                    s->lanes[s->cur]->fill_n);
+    const size_t ns = (size_t)s->lanes[0]->ns;
     for (int k = 0; k < n_steps;) {
-        qm_stream::Slot &sl = s->slots[s->order.front()];
-        QM_HIP(hipEventSynchronize(sl.done));
-        const int take = std::min(n_steps - k, sl.n - sl.taken);
-        const double *src = sl.h_out.p + (size_t)sl.taken * ns;
-        std::memcpy(max_coa + (size_t)k * ns, src, (size_t)take * ns * sizeof(double));
-        std::memcpy(max_norm_coa + (size_t)k * ns, src + kns, (size_t)take * ns * sizeof(double));
-        std::memcpy(max_coa_idx + (size_t)k * ns, src + 2 * kns, (size_t)take * ns * sizeof(int64_t));
+        qm_stream::Launch &l = s->launched.front();
+        StreamLane *lane = s->lanes[l.lane].get();
+        const int take = std::min(n_steps - k, l.left);
+        DeviceGuard guard(lane->e->device);
+        if (pop_oldest(lane, take, max_coa + k * ns, max_norm_coa + k * ns, max_coa_idx + k * ns)) return 1;
         k += take;
-        sl.taken += take;
-        s->popped_steps += take;
-        if (sl.taken == sl.n) {
-            sl.in_flight = false;
-            s->order.pop_front();
-        }
+        l.left -= take;
+        if (l.left == 0) s->launched.pop_front();
     }
-    return 0;
-}
-
-int qm_stream_pending(qm_stream *s, int32_t *launched_not_popped, int32_t *pushed_not_launched) {
-    if (s && !s->lanes.empty()) {
-        if (replicas_alive(s, "qm_stream_pending")) return 1;
-        int64_t waiting = 0;
-        const int filling = replicas_pending(s, &waiting);
-        if (launched_not_popped) *launched_not_popped = (int32_t)waiting;
-        if (pushed_not_launched) *pushed_not_launched = filling;
-        return 0;
-    }
-    if (alive(s, "qm_stream_pending")) return 1;
-    if (launched_not_popped) *launched_not_popped = (int32_t)(s->launched_steps - s->popped_steps);
-    if (pushed_not_launched) *pushed_not_launched = s->fill_n;
     return 0;
 }
 

@@ -344,6 +344,128 @@ def test_closing_the_replicas_first(lib, stream_case):
     sd.close()
 
 
+def _script(lib, eng, stream_case):
+    """One fixed sequence of stream calls on ``eng`` (depth 2, three steps per launch).  Returns the log -- per
+    operation its name, what it returned, its error text and ``pending()`` behind it -- and the popped timesteps.
+    Two things in an error text belong to the handle, not to the protocol, and are levelled: the constructor's own
+    function name, and the tables' serial numbers (``#7``), which are unique in the process."""
+    import re
+
+    from quakemigrate_amd.stream import StreamingDetector
+
+    c0, wins = stream_case
+    T = wins[0].shape[1]
+    log, popped = [], []
+
+    def text(exc):
+        return re.sub(r"#\d+", "#n", str(exc).replace("qm_stream_create_replicas", "qm_stream_create"))
+
+    def do(name, call, sd=None):
+        value = err = pend = None
+        try:
+            value = call()
+        except lib.QMHipError as exc:
+            err = text(exc)
+        if isinstance(value, tuple):                    # a pop: the series go to `popped`, their count to the log
+            popped.extend((value[0][j], value[1][j], value[2][j]) for j in range(len(value[0])))
+            value = len(value[0])
+        if sd is not None:
+            try:
+                pend = sd.pending()
+            except lib.QMHipError as exc:
+                pend = text(exc)
+        log.append((name, value, err, pend))
+
+    assert not eng.select_table("A")
+    eng.load_lut(c0.traveltimes)
+    do("create, too many steps per launch",
+       lambda: StreamingDetector(eng, ROWS, T, c0.fsmp, c0.lsmp, c0.available, depth=2, steps_per_launch=5000) and None)
+    sd = StreamingDetector(eng, ROWS, T, c0.fsmp, c0.lsmp, c0.available, depth=2, steps_per_launch=3)
+    for j in range(6):
+        do(f"fill the ring {j}", lambda: sd.push(wins[j]), sd)
+    do("refused push", lambda: sd.push(wins[6]), sd)
+    do("partial pop", lambda: sd.pop(2), sd)
+    do("refused push, slot partly popped", lambda: sd.push(wins[6]), sd)
+    do("pop that frees a slot", lambda: sd.pop(1), sd)
+    do("push 6", lambda: sd.push(wins[6]), sd)
+    do("push 7", lambda: sd.push(wins[7]), sd)
+    do("over-pop", lambda: sd.pop(4), sd)
+    do("flush a partly filled launch", sd.flush, sd)
+    do("flush nothing", sd.flush, sd)
+    do("pop 5", lambda: sd.pop(5), sd)
+    do("push 8", lambda: sd.push(wins[8]), sd)
+    do("push 9", lambda: sd.push(wins[9]), sd)
+    assert not eng.select_table("B")
+    eng.load_lut(np.ascontiguousarray(c0.traveltimes[::-1]))    # same shape, other delays
+    do("table changed: the filling push", lambda: sd.push(wins[10]), sd)
+    do("table changed: the next push", lambda: sd.push(wins[0]), sd)
+    do("table changed: flush", sd.flush, sd)
+    assert eng.select_table("A")
+    do("recovery: push", lambda: sd.push(wins[0]), sd)
+    do("recovery: push again", lambda: sd.push(wins[1]), sd)
+    do("recovery: flush", sd.flush, sd)
+    do("recovery: pop", lambda: sd.pop(5), sd)
+    do("push before the engine closes", lambda: sd.push(wins[2]), sd)
+    eng.close()
+    do("engine closed: push", lambda: sd.push(wins[3]), sd)
+    do("engine closed: flush", sd.flush, sd)
+    do("engine closed: pop", lambda: sd.pop(1), sd)
+    sd.close()
+    sd.close()
+    return log, popped
+
+
+def test_one_script_two_handles(lib, stream_case):
+    """A stream on ``Engine(0)`` and one on ``EngineReplicas([0])`` are the same thing: after every operation of one
+    script -- the ring filled, a refused push, a partial pop, a pop that frees a slot, an over-pop, a flush of a partly
+    filled launch, a table change under the stream with its refusals and the recovery, the engine closed first -- the
+    return value, ``pending()`` and any error's text are the same, and all popped series are equal."""
+    single = _reference(lib, stream_case, 3, 0)[0]
+    log_e, popped_e = _script(lib, lib.Engine(0), stream_case)
+    log_r, popped_r = _script(lib, lib.EngineReplicas([0]), stream_case)
+    for e, r in zip(log_e, log_r):
+        assert e == r
+    assert len(log_e) == len(log_r)
+    _same(popped_r, popped_e)
+    _same(popped_e, single[:8] + [single[j] for j in (8, 9, 10, 0, 1)])
+    # the script is what it says it is: the refusals refuse, and for the reasons named
+    by_name = {name: (value, err, pend) for name, value, err, pend in log_e}
+    assert "steps_per_launch must be in 1..4096" in by_name["create, too many steps per launch"][1]
+    assert by_name["refused push"] == (False, None, (6, 0))
+    assert by_name["refused push, slot partly popped"] == (False, None, (4, 0))
+    assert by_name["push 7"] == (True, None, (3, 2))
+    assert "4 steps asked for, 3 launched" in by_name["over-pop"][1] and by_name["over-pop"][2] == (3, 2)
+    assert by_name["flush a partly filled launch"] == (None, None, (5, 0))
+    for name in ("table changed: the filling push", "table changed: the next push", "table changed: flush"):
+        assert "changed under the stream" in by_name[name][1] and by_name[name][2] == (0, 3), name
+    assert by_name["recovery: push again"] == (True, None, (3, 2))
+    assert by_name["recovery: pop"] == (5, None, (0, 0))
+    for name in ("engine closed: push", "engine closed: flush", "engine closed: pop"):
+        assert "destroyed" in by_name[name][1] and "destroyed" in by_name[name][2], name
+
+
+def test_a_stage_on_every_lane_or_on_none(lib, stream_case):
+    """A lane whose engine is gone refuses the onset stage; the lane before it keeps nothing of it."""
+    from quakemigrate_amd.preprocess import OnsetStage
+    from quakemigrate_amd.stream import StreamingDetector
+
+    c0, wins = stream_case
+    T = wins[0].shape[1]
+    stage = OnsetStage(filters={"P": (2.0, 16.0, 2)}, sta_lta_windows={"P": (0.2, 1.0)}, trace_row=tuple(range(ROWS)),
+                       trace_phase=tuple("P" * ROWS), row_phase=tuple("P" * ROWS), taper_pad=20)
+    rep = lib.EngineReplicas([0, 0])
+    rep.load_lut(c0.traveltimes)
+    sd = StreamingDetector(rep, ROWS, T, c0.fsmp, c0.lsmp, c0.available, depth=2, steps_per_launch=3)
+    rep.replicas[1].close()
+    lib.release_cached_memory()
+    before = rep.replicas[0].get("pool_live_bytes")
+    with pytest.raises(lib.QMHipError, match="destroyed"):
+        sd.set_onset_stage(stage, sampling_rate=50)
+    assert rep.replicas[0].get("pool_live_bytes") == before
+    sd.close()
+    rep.close()
+
+
 @pytest.mark.parametrize("cfg", [{"tie_rule": 1}, {"screen": 1}], ids=["tie_rule", "screen"])
 def test_near_ties_with_tie_rule_and_screen(lib, oracle, cfg):
     from quakemigrate_amd.stream import StreamingDetector
