@@ -11,9 +11,10 @@ coalescence series -- the hot-path side of ``QuakeScan.detect()``
 
 With ``--lut 1d`` the grids themselves come from the GPU: eikonal sections of a 1-D velocity model per station and
 phase, swept round the stations (row f8, ``quakemigrate_amd.traveltimes.compute_traveltimes``), and go from there
-into the table serving without a host round trip.
+into the table serving without a host round trip.  With ``--lut 3d`` the same 1-D model carries a smooth slow anomaly
+and is solved as a 3-D velocity model on the grid's own nodes (row f9, ``method="3d"``).
 
-Run:  python examples/synthetic_detect.py [out_dir] [--lut 1d]
+Run:  python examples/synthetic_detect.py [out_dir] [--lut 1d | --lut 3d]
 """
 
 import datetime as dt
@@ -34,7 +35,8 @@ def run(out_dir, grid=(24, 20, 12), spacing=0.5, n_stations=6, rate=50, timestep
         n_steps=4, seed=3, steps_per_launch=1, lut="homogeneous"):
     """``steps_per_launch`` > 1: the onset rows of that many timesteps are stacked by ONE launch
     (``Engine.detect_batch``) -- what fills the GPU on grids of this size; same series.
-    ``lut``: "homogeneous" (NumPy grids, uploaded) or "1d" (a three-layer model, computed on the device)."""
+    ``lut``: "homogeneous" (NumPy grids, uploaded), "1d" (a three-layer model, computed on the device) or "3d" (that
+    model with a smooth velocity anomaly, solved on the grid's nodes on the device)."""
     import torch
 
     rng = np.random.default_rng(seed)
@@ -48,19 +50,27 @@ def run(out_dir, grid=(24, 20, 12), spacing=0.5, n_stations=6, rate=50, timestep
     grids = [d / 5.0 for d in dist] + [d / 2.9 for d in dist]          # P rows, then S rows
     eng = lib.Engine(0)
     eng.set_stream(torch.cuda.current_stream().cuda_stream)
-    if lut == "1d":
+    if lut in ("1d", "3d"):
         from quakemigrate_amd import traveltimes as tt
 
         vmod = {"Depth": [0.0, 1.5, 4.0], "Vp": [4.2, 5.0, 6.1], "Vs": [2.4, 2.9, 3.5]}
         names = [f"ST{i:02d}" for i in range(n_stations)]
-        table = tt.compute_traveltimes(eng, (0.0, 0.0, 0.0), (spacing,) * 3, grid, dict(zip(names, st)), "1d",
-                                       vmod=vmod, section_dx=spacing / 5, device=True)
+        if lut == "1d":
+            table = tt.compute_traveltimes(eng, (0.0, 0.0, 0.0), (spacing,) * 3, grid, dict(zip(names, st)), "1d",
+                                           vmod=vmod, section_dx=spacing / 5, device=True)
+        else:
+            # the 1-D model, 12 % slower in a smooth body a third of the way into the grid
+            centre = [0.35 * (n - 1) * spacing for n in grid]
+            body = np.exp(-((gx - centre[0]) ** 2 + (gy - centre[1]) ** 2 + (gz - centre[2]) ** 2) / (2 * 1.5 ** 2))
+            velocity = {ph: tt.model_velocity(vmod, ph, gz) * (1.0 - 0.12 * body) for ph in ("P", "S")}
+            table = tt.compute_traveltimes(eng, (0.0, 0.0, 0.0), (spacing,) * 3, grid, dict(zip(names, st)), "3d",
+                                           velocity=velocity, device=True)
         served = [table[s]["P"] for s in names] + [table[s]["S"] for s in names]
         grids = [g.cpu().numpy() for g in served]                      # (for the synthetic arrivals below only)
     elif lut == "homogeneous":
         served = grids
     else:
-        raise ValueError(f"lut must be 'homogeneous' or '1d', got {lut!r}")
+        raise ValueError(f"lut must be 'homogeneous', '1d' or '3d', got {lut!r}")
     eng.set_traveltime_grids(served)
     eng.serve(rate, np.arange(2 * n_stations))                          # all available
     lut_max = eng.lut_max

@@ -236,8 +236,10 @@ int qm_engine_synchronize(qm_engine *e);
  * scanmseed_ns_decode (0: the stage did not run);
  * the travel-time stage's compile-time constants (csrc/qm_traveltimes.hpp): tt_lds_nodes (the largest section whose
  * tau qm_engine_tt_sections keeps in LDS), tt_section_threads, tt_grid_blocks and tt_grid_threads (the launch grid of
- * the two per-node kernels, which stride over it), and the last call's launch time in nanoseconds: tt_ns_homogeneous,
- * tt_ns_sections, tt_ns_sweep. */
+ * the two per-node kernels, which stride over it), tt_plane_threads (a workgroup of qm_engine_tt_eikonal3d's plane
+ * launch, one node at most per thread) and tt_plane_max_rows (the most rows it takes in one call), and the last call's
+ * launch time in nanoseconds: tt_ns_homogeneous, tt_ns_sections, tt_ns_sweep, tt_ns_eikonal3d (first launch to last,
+ * the per-round flag read-backs included). */
 int qm_engine_config(qm_engine *e, const char *key, int64_t value);
 int qm_engine_get(qm_engine *e, const char *key, int64_t *value);
 
@@ -621,7 +623,8 @@ int qm_engine_measure_amplitudes(qm_engine *e, const double *traces, int traces_
  * (ix, iy, iz) lies at ll_corner[j] + index * node_spacing[j] (Grid3D.grid_xyz) and is element (ix ny + iy) nz + iz
  * of its row.  Units are the caller's: one unit of length throughout, seconds per that unit.  Parameter arrays are
  * host arrays; out_on_device says where the outputs are.  Every call synchronises and leaves its launch's time in
- * "tt_ns_homogeneous" / "tt_ns_sections" / "tt_ns_sweep" (qm_engine_get, nanoseconds) and qm_engine_last_kernel_ms.
+ * "tt_ns_homogeneous" / "tt_ns_sections" / "tt_ns_sweep" / "tt_ns_eikonal3d" (qm_engine_get, nanoseconds) and
+ * qm_engine_last_kernel_ms.
  *
  * qm_engine_tt_homogeneous (create_lut.py:241-265): row_params [n_rows][4] = station x, y, z, velocity; out
  * [n_rows][nodes] = sqrt(dx dx + dy dy + dz dz) / v, the sum taken left to right.
@@ -655,7 +658,36 @@ int qm_engine_measure_amplitudes(qm_engine *e, const double *traces, int traces_
  * the reference's rule, which names the cell of the floor only where x0 and z0 are multiples of h --; c0 = c00 (1 - xd)
  * + c10 xd, c1 = c01 (1 - xd) + c11 xd, c0 (1 - zd) + c1 zd.  out [n_rows][nodes].  Refused besides the arguments: a
  * node whose four corners are not all inside its section -- NumPy would raise, or wrap a negative index --, with the
- * row and its first such node named; the other nodes of out are written, such nodes hold NaN. */
+ * row and its first such node named; the other nodes of out are written, such nodes hold NaN.
+ *
+ * qm_engine_tt_eikonal3d: |grad T| = s(x, y, z) on the grid's own nodes, one solve per row -- what the reference
+ * leaves to scikit-fmm (1dfmm) and NonLinLoc (3-D models); the rules on arrays: tests/traveltimes3d_ref.py.
+ * row_params [n_rows][4] = source x, y, z and the slowness s0 at the source; row_model [n_rows]: which of the n_models
+ * volumes slowness [n_models][nodes] (host or device) the row is solved in.  The scheme is qm_engine_tt_sections' with
+ * one axis more: T = T0 tau, T0 = s0 rho, rho = sqrt(dx dx + dy dy + dz dz) from the source, d = (ll + index spacing)
+ * - source per axis.  Per axis d and side sg = +1 (the neighbour at index - 1), -1 (at index + 1): a = T0 sg / h_d +
+ * dT0/dd, b = T0 sg tau_nb / h_d.  A node takes the smallest candidate over its available neighbours (finite tau), one
+ * neighbour at most per axis, in this order: the 6 one-sided ones (b + sg s) / a, kept where sg a > 0 and the result
+ * is > 0, axis x side +1, x side -1, y, z; the 12 two-sided ones, axes (x, y), (x, z), (y, z), sides (+,+) (+,-)
+ * (-,+) (-,-), the larger root of sum (a tau - b)^2 = s^2 -- qa = sum a a, qb = sum a b, qc = sum b b - s s, every sum
+ * left to right, (qb + sqrt(qb qb - qa qc)) / qa -- kept where the discriminant is >= 0 and sg (a tau - b) >= 0 on both
+ * axes; the 8 three-sided ones, the same with three terms, sides of x outermost -- and only where that is below its
+ * value by more than tol times the value.  The eight nodes of the cell that holds the source (per axis
+ * floor((src - ll) / h), clipped to n - 2) are frozen at tau = (s0 + s_node) / (2 s0), a node at the source at 1; out
+ * is T0 tau, 0 where T0 = 0.  Gauss-Seidel sweeps in the eight orderings itertools.product((+1, -1), repeat=3) of
+ * (x, y, z) make a round; rounds repeat until one accepts nothing in the row.  One launch per plane i' + j' + k' = d
+ * of a sweep (indices counted from the far end of an axis the ordering runs backwards), all rows in it: a node's six
+ * neighbours lie in the planes d - 1 and d + 1, so the plane at once reads what the serial x-outer / z-inner loop
+ * reads, and the values are that loop's.  8 (nx + ny + nz - 2) launches per round, then the host reads the rows'
+ * "accepted something" flags: the one synchronisation per round.  out [n_rows][nodes] f64 on the side out_on_device
+ * says; rounds, status [n_rows] i32, HOST arrays: a row's rounds run (the last, idle one included; a settled row's
+ * further rounds, run for the others, change nothing and are not counted), 0 settled / 1 not settled in max_iters.
+ * Deviations from the reference's _eikonal_fmm: first order, not scikit-fmm's second-order march -- the values differ
+ * by the schemes' discretisation errors --; the source is the station's true position, not the nearest node.
+ * Refused, by name: a NULL argument, an axis shorter than 2 nodes, more than "tt_plane_max_rows" rows, a source
+ * outside [ll, ur], s0 or a slowness not finite and > 0 (model and node named, host or device input alike),
+ * row_model outside [0, n_models), tol outside [0, 1), max_iters < 1; and, with the outputs written, a row that
+ * max_iters rounds did not settle ("row R: not settled after N rounds"). */
 int qm_engine_tt_homogeneous(qm_engine *e, const double *ll_corner, const double *node_spacing,
                              const int32_t *node_count, int32_t n_rows, const double *row_params /*[n_rows][4]*/,
                              double *out, int out_on_device);
@@ -667,6 +699,11 @@ int qm_engine_tt_sweep(qm_engine *e, const double *ll_corner, const double *node
                        int32_t n_rows, const double *row_params /*[n_rows][4]*/, const int32_t *row_section,
                        const double *sections, int sections_on_device, int32_t n_sections, int32_t nr, int32_t nz,
                        double h, double *out, int out_on_device);
+int qm_engine_tt_eikonal3d(qm_engine *e, const double *ll_corner, const double *node_spacing, const int32_t *node_count,
+                           int32_t n_rows, const double *row_params /*[n_rows][4]*/, const int32_t *row_model,
+                           int32_t n_models, const double *slowness /*[n_models][nodes]*/, int slowness_on_device,
+                           double tol, int32_t max_iters, double *out, int out_on_device, int32_t *rounds,
+                           int32_t *status);
 
 /* Trigger on the device -- the step between the detect sweep and the location: what Trigger._trigger_batch does to
  * the coalescence series of a batch (quakemigrate/signal/trigger.py:318-638; the rules on arrays:

@@ -130,6 +130,8 @@ qmlib.qm_engine_tt_sections.argtypes = [_vp, c_int32, c_int32, c_int32, ctypes.c
                                         c_int32, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int]
 qmlib.qm_engine_tt_sweep.argtypes = [_vp, c_dPt, c_dPt, c_i32Pt, c_int32, c_dPt, c_i32Pt, _vp, ctypes.c_int, c_int32,
                                      c_int32, c_int32, ctypes.c_double, _vp, ctypes.c_int]
+qmlib.qm_engine_tt_eikonal3d.argtypes = [_vp, c_dPt, c_dPt, c_i32Pt, c_int32, c_dPt, c_i32Pt, c_int32, _vp, ctypes.c_int,
+                                         ctypes.c_double, c_int32, _vp, ctypes.c_int, c_i32Pt, c_i32Pt]
 
 
 class TriggerParams(ctypes.Structure):
@@ -1007,6 +1009,45 @@ class Engine:
         _check(qmlib.qm_engine_tt_sweep(self._h, ll, sp, nc, len(rows), rows.reshape(-1), row_section, psec, dev_sec,
                                         n_sec, nr, nz, float(h), p, dev))
         return out
+
+    def traveltimes_eikonal3d(self, ll_corner, node_spacing, node_count, sources_xyz, source_slowness, slowness,
+                              row_model, tol=2.0 ** -40, max_iters=64, device=True):
+        """
+        Eikonal travel-time grids of 3-D slowness volumes, solved on the grid's own nodes (include/qmhip.h:
+        ``qm_engine_tt_eikonal3d``): a first-order factored sweep, one solve per row.  ``sources_xyz`` (n_rows, 3):
+        anywhere inside the grid, not snapped to a node; ``source_slowness`` (n_rows,): at the source; ``slowness``
+        (n_models, nx, ny, nz) -- a single (nx, ny, nz) volume will do --: a NumPy array or a tensor on this engine's
+        GPU; ``row_model`` (n_rows,): the row's volume.  Returns ``(grids (n_rows, nx, ny, nz), rounds, status)``: the
+        grids float64 seconds, with ``device`` a torch tensor on this engine's GPU, else a NumPy array; ``rounds`` and
+        ``status`` NumPy int32 arrays.  A row that ``max_iters`` rounds do not settle raises.
+        """
+        ll, sp, nc = self._tt_grid(ll_corner, node_spacing, node_count)
+        shape = tuple(int(n) for n in nc)
+        if not hasattr(slowness, "data_ptr"):
+            slowness = np.ascontiguousarray(slowness, dtype=np.float64)
+        if tuple(slowness.shape) == shape:
+            slowness = slowness.reshape((1,) + shape)
+        if len(slowness.shape) != 4 or tuple(slowness.shape[1:]) != shape:
+            raise ValueError(f"slowness of shape {tuple(slowness.shape)}: (n_models,) + {shape} expected")
+        pslow, dev_slow = self._ptr(slowness, np.float64)
+        if dev_slow and hasattr(slowness, "is_cuda"):
+            import torch
+
+            torch.cuda.synchronize(slowness.device)     # (whatever wrote the volumes ran on torch's stream, not the engine's)
+        xyz = np.ascontiguousarray(sources_xyz, dtype=np.float64).reshape(-1, 3)
+        s0 = np.ascontiguousarray(source_slowness, dtype=np.float64).reshape(-1)
+        row_model = np.ascontiguousarray(row_model, dtype=np.int32).reshape(-1)
+        if not len(xyz) == len(s0) == len(row_model):
+            raise ValueError(f"{len(xyz)} sources, {len(s0)} source slownesses, {len(row_model)} model indices: one "
+                             "row each")
+        rows = np.ascontiguousarray(np.column_stack([xyz, s0]))
+        out = self._tt_out((len(rows),) + shape, device)
+        rounds, status = np.zeros(len(rows), dtype=np.int32), np.zeros(len(rows), dtype=np.int32)
+        p, dev = self._ptr(out, np.float64)
+        _check(qmlib.qm_engine_tt_eikonal3d(self._h, ll, sp, nc, len(rows), rows.reshape(-1), row_model,
+                                            int(slowness.shape[0]), pslow, dev_slow, float(tol), int(max_iters), p, dev,
+                                            rounds, status))
+        return out, rounds, status
 
     TRIGGER_METHODS = {"static": 0, "mad": 1, "median_ratio": 2}
 

@@ -770,6 +770,7 @@ const Readout kReadouts[] = {
     {"scanmseed_tile", V(qm::kSmsTile)}, {"scanmseed_compose_chunk", V(qm::kSmsComposeChunk)},
     {"tt_lds_nodes", V(qm::kTtLdsNodes)}, {"tt_section_threads", V(qm::kTtSectionThreads)},
     {"tt_grid_blocks", V(qm::kTtGridBlocks)}, {"tt_grid_threads", V(qm::kTtGridThreads)},
+    {"tt_plane_threads", V(qm::kTtPlaneThreads)}, {"tt_plane_max_rows", V(qm::kTtPlaneMaxRows)},
     // the near-tie refinement
     {"tie_brick_rows", V(e->last.brick_rows)}, {"tie_refined_steps", V(e->tie.refined_steps)},
     {"tie_overflow_samples", V(e->tie.overflow_last), fetch_tie_counts}, {"tie_pairs", V(e->tie.pairs_last), fetch_tie_counts},

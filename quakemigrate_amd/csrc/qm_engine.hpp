@@ -443,12 +443,17 @@ struct ScanmseedCodec {                 // qm_engine_scanmseed_encode / _decode 
     DevBuf<int64_t> off;                // decode's offsets
     StageClock<qm::kSmsStages> clock{qm::kSmsStageNames};       // "scanmseed_ns_<stage>": always runs
 };
-struct TravelTimeStage {                // qm_engine_tt_homogeneous / _tt_sections / _tt_sweep (qm_traveltimes.hip)
+struct TravelTimeStage {                // qm_engine_tt_homogeneous / _tt_sections / _tt_sweep / _tt_eikonal3d (qm_traveltimes.hip)
+    // (every call fills what it uses before it launches and reads it back before it returns: nothing here is carried
+    // from one call to the next, whichever of the four it is -- only the sizes grow)
     DevBuf<double> par;                 // row parameters; the sections' slowness rows and sources
-    DevBuf<double> sec, out;            // a host caller's sections on their way in; grids or sections on their way out
+    DevBuf<double> sec, out;            // a host caller's sections (eikonal3d: slowness volumes) on their way in; grids or
+                                        // sections on their way out (eikonal3d: a host caller's tau lives here, in place)
     DevBuf<double> tau;                 // the solver's tau of sections above the LDS limit: [n_sections][nr * nz]
-    DevBuf<int32_t> meta;               // the sweep's row -> section; the solver's rounds and status
-    DevBuf<unsigned long long> bad;     // the sweep's first node outside its section, per row
+    DevBuf<int32_t> meta;               // the sweep's row -> section; the solver's rounds and status; eikonal3d: row ->
+                                        // model, the sources' cells [n_rows][3], two sets of row flags
+    DevBuf<unsigned long long> bad;     // the sweep's first node outside its section, per row; eikonal3d: slot 0, the first
+                                        // slowness that is not finite and positive
     StageClock<qm::kTtStages> clock{qm::kTtStageNames};         // "tt_ns_<stage>": always runs
 };
 struct TieScratch {                     // the near-tie refinement (refine_ties, qm_engine_tie_partial; qm_ties.hpp)

@@ -191,4 +191,128 @@ int qm_engine_tt_sweep(qm_engine *e, const double *ll_corner, const double *node
     return 0;
 }
 
+int qm_engine_tt_eikonal3d(qm_engine *e, const double *ll_corner, const double *node_spacing, const int32_t *node_count,
+                           int32_t n_rows, const double *row_params, const int32_t *row_model, int32_t n_models,
+                           const double *slowness, int slowness_on_device, double tol, int32_t max_iters, double *out,
+                           int out_on_device, int32_t *rounds, int32_t *status) {
+    using namespace qm;
+    const char *what = "qm_engine_tt_eikonal3d";
+    if (!e || !ll_corner || !node_spacing || !node_count || !row_params || !row_model || !slowness || !out || !rounds ||
+        !status)
+        return fail("%s: NULL argument", what);
+    for (int j = 0; j < 3; ++j)
+        if (node_count[j] < 2) return fail("%s: axis %d: %d nodes (at least 2)", what, j, node_count[j]);
+    TtGrid g{};
+    if (tt_check_grid(what, ll_corner, node_spacing, node_count, n_rows, &g)) return 1;
+    if (n_rows > kTtPlaneMaxRows) return fail("%s: %d rows (at most %d in one call)", what, n_rows, kTtPlaneMaxRows);
+    if (n_models < 1) return fail("%s: n_models = %d", what, n_models);
+    if (!(tol >= 0.0) || !(tol < 1.0)) return fail("%s: tol %g (0 <= tol < 1)", what, tol);
+    if (max_iters < 1) return fail("%s: max_iters = %d", what, max_iters);
+    const size_t R = (size_t)n_rows, n_slow = (size_t)n_models * (size_t)g.nodes;
+    // row -> model, the source's cell, the two sets of row flags: the first one's "previous round" is all rows live
+    std::vector<int32_t> meta(6 * R, 0);
+    for (size_t r = 0; r < R; ++r) {
+        const double *p = row_params + 4 * r;
+        for (int j = 0; j < 3; ++j) {
+            const double ur = g.ll[j] + (double)(g.n[j] - 1) * g.sp[j];
+            if (!(p[j] >= g.ll[j] && p[j] <= ur))
+                return fail("%s: row %d: source at (%g, %g, %g) outside the grid: axis %d spans [%g, %g]", what, (int)r,
+                            p[0], p[1], p[2], j, g.ll[j], ur);
+            // the cell that holds the source: floor((src - ll) / h), clipped to n - 2
+            const double c = std::floor((p[j] - g.ll[j]) / g.sp[j]);
+            meta[R + 3 * r + j] = (int32_t)std::min(std::max(c, 0.0), (double)(g.n[j] - 2));
+        }
+        if (!std::isfinite(p[3]) || !(p[3] > 0.0))
+            return fail("%s: row %d: slowness %g at the source (finite, > 0)", what, (int)r, p[3]);
+        if (row_model[r] < 0 || row_model[r] >= n_models)
+            return fail("%s: row %d: model %d of %d", what, (int)r, row_model[r], n_models);
+        meta[r] = row_model[r];
+        meta[4 * R + r] = 1;
+    }
+    DeviceGuard guard(e->device);
+    auto &tt = e->tt;
+    TtEikonalArgs a{};
+    a.g = g;
+    a.rows = stage_in(e, tt.par, row_params, 0, 4 * R);
+    a.row_model = stage_in(e, tt.meta, meta.data(), 0, meta.size());
+    a.slow = stage_in(e, tt.sec, slowness, slowness_on_device, n_slow);
+    const StagedOut<double> grids = stage_host_out(tt.out, out, out_on_device, (size_t)g.total);
+    if (!a.rows || !a.row_model || !a.slow || !grids.d || tt.bad.ensure(1)) return 1;
+    a.cell = a.row_model + R;
+    a.tau = grids.d;
+    a.tol = tol;
+    int32_t *const flags[2] = {tt.meta.p + 4 * R, tt.meta.p + 5 * R};
+
+    // the volumes, wherever they came from: the first element that is not finite and positive is refused by name
+    QM_HIP(hipMemsetAsync(tt.bad.p, 0xff, sizeof(unsigned long long), e->stream));
+    hipLaunchKernelGGL(tt_slowness_check_kernel, dim3(tt_grid_blocks((long long)std::min<size_t>(n_slow, INT32_MAX))),
+                       dim3(kTtGridThreads), 0, e->stream, a.slow, (unsigned long long)n_slow, tt.bad.p);
+    QM_HIP(hipGetLastError());
+    unsigned long long h_bad = kTtNone;
+    QM_HIP(copy_back(&h_bad, tt.bad.p, sizeof(h_bad), e->stream));
+    QM_HIP(hipStreamSynchronize(e->stream));
+    if (h_bad != kTtNone) {
+        double v = 0.0;
+        QM_HIP(copy_back(&v, a.slow + h_bad, sizeof(v), e->stream));
+        QM_HIP(hipStreamSynchronize(e->stream));
+        return fail("%s: model %d: slowness %g at node %lld (finite, > 0)", what, (int)(h_bad / (size_t)g.nodes), v,
+                    (long long)(h_bad % (size_t)g.nodes));
+    }
+
+    std::vector<int32_t> h_flag(R), h_rounds(R, 0), h_status(R, 1);
+    const unsigned node_blocks = tt_grid_blocks(g.nodes);
+    const auto solve = [&]() -> int {
+        hipLaunchKernelGGL(tt_eikonal_init_kernel, dim3(node_blocks), dim3(kTtGridThreads), 0, e->stream, a);
+        size_t open = R;
+        for (int round = 0; round < max_iters && open; ++round) {
+            a.live = flags[round & 1];
+            a.flag = flags[(round & 1) ^ 1];
+            QM_HIP(hipMemsetAsync(a.flag, 0, R * sizeof(int32_t), e->stream));
+            for (int o = 0; o < 8; ++o) {               // itertools.product((+1, -1), repeat=3) over (x, y, z)
+                TtPlane p{};
+                p.rev[0] = (o >> 2) & 1; p.rev[1] = (o >> 1) & 1; p.rev[2] = o & 1;
+                for (p.d = 0; p.d < g.n[0] + g.n[1] + g.n[2] - 2; ++p.d) {
+                    // the plane's rectangle: i' from lo0 to hi0, over those j' from lo1 to hi1
+                    const int hi0 = std::min(g.n[0] - 1, p.d);
+                    p.lo0 = std::max(0, p.d - (g.n[1] - 1) - (g.n[2] - 1));
+                    p.lo1 = std::max(0, p.d - hi0 - (g.n[2] - 1));
+                    p.n0 = hi0 - p.lo0 + 1;
+                    p.n1 = std::min(g.n[1] - 1, p.d - p.lo0) - p.lo1 + 1;
+                    const unsigned cells = (unsigned)p.n0 * (unsigned)p.n1;
+                    hipLaunchKernelGGL(tt_eikonal_plane_kernel, dim3((cells + kTtPlaneThreads - 1) / kTtPlaneThreads,
+                                                                     (unsigned)R),
+                                       dim3(kTtPlaneThreads), 0, e->stream, a, p);
+                }
+            }
+            QM_HIP(hipGetLastError());
+            // the round's one synchronisation: the row flags, through the pinned staging
+            QM_HIP(copy_back(h_flag.data(), a.flag, R * sizeof(int32_t), e->stream));
+            for (size_t r = 0; r < R; ++r) {
+                if (!h_status[r]) continue;
+                ++h_rounds[r];
+                if (!h_flag[r]) {
+                    h_status[r] = 0;
+                    --open;
+                }
+            }
+        }
+        hipLaunchKernelGGL(tt_eikonal_finish_kernel, dim3(node_blocks), dim3(kTtGridThreads), 0, e->stream, a);
+        return 0;
+    };
+    tt.clock.begin(true, false);
+    if (timed_launches(e, [&]() -> int {
+            int rc = 0;
+            return tt.clock.stage(e->stream, kTtEikonal3d, [&] { rc = solve(); }) || rc;
+        }))
+        return 1;
+    if (grids.fetch(e)) return 1;
+    QM_HIP(hipStreamSynchronize(e->stream));
+    if (tt.clock.collect()) return 1;
+    std::copy(h_rounds.begin(), h_rounds.end(), rounds);
+    std::copy(h_status.begin(), h_status.end(), status);
+    for (size_t r = 0; r < R; ++r)
+        if (h_status[r] != 0) return fail("%s: row %d: not settled after %d rounds (max_iters)", what, (int)r, max_iters);
+    return 0;
+}
+
 }  // extern "C"

@@ -1,23 +1,34 @@
 # -*- coding: utf-8 -*-
 """
 Travel-time tables computed on the GPU -- the reference's ``compute_traveltimes``
-(``quakemigrate/lut/create_lut.py``) for the two methods that need no external program:
+(``quakemigrate/lut/create_lut.py``) without an external program:
 
 * ``"homogeneous"`` (create_lut.py:241-265);
+* ``"3d"``: a 3-D velocity model given per phase on the grid's own nodes -- what the reference reaches only through
+  NonLinLoc and ``read_nlloc``, its own ``"3dfmm"`` being ``NotImplementedError`` (create_lut.py:214-217) --, and
+  ``"1d"`` with ``solver="grid"``: a 1-D model spread over the grid's depths, the reference's ``1dfmm`` path
+  (create_lut.py:298-317) with the engine's solver in scikit-fmm's place.  Both solve ``|grad T| = s`` on the grid's
+  nodes (``Engine.traveltimes_eikonal3d``), one solve per station and phase, stations inside the grid (the
+  reference's own condition for ``1dfmm``, :306-313).  This is a FIRST-ORDER factored sweep, not scikit-fmm's
+  second-order fast march: the two solve the same equation and their values differ by the schemes' discretisation
+  errors (measured here against closed forms: profiles/traveltimes3d_accuracy.txt), and the source is the station's
+  true position unless ``snap_to_node`` moves it to the node ``_eikonal_fmm`` picks.  There is no fixture from
+  ``1dfmm``: scikit-fmm is not among this project's dependencies, so nothing here was compared with it;
 * ``"1d"``: a 1-D velocity model, along the structure of the reference's ``1dnlloc`` path (create_lut.py:389-513): a
   2-D travel-time section per station and phase in (horizontal distance, depth), swept round the station over the
   3-D grid by ``_bilinear_interpolate`` (:746-762).  The section comes from the engine's eikonal solver
   (``Engine.traveltime_sections``) instead of NonLinLoc's ``Grid2Time``.  A 1-D model is axisymmetric about the
   station, so the section is the whole problem; the station need not sit on a node or inside the grid.
 
-This module is the host side: the velocity model's rows, the planner of the sections (pure NumPy) and
+This module is the host side: the velocity model's rows, the planner of the sections, the slowness at a station of a
+3-D model (:func:`trilinear`), the reference's nearest node (:func:`nearest_node`) -- all pure NumPy -- and
 :func:`compute_traveltimes`, which returns ``{station: {phase: grid}}`` -- the shape of ``lut.traveltimes``.  With
 ``device=True`` the grids are torch tensors on the engine's GPU, which ``Engine.set_traveltime_grids`` and
 ``MigrationScan(device_serving=True)`` take without a host round trip.
 
 Coordinates are grid coordinates in one unit of length (the reference converts to km for NonLinLoc; nothing here
 depends on the unit), depths positive down, velocities in that unit per second.  Not here: projections and the LUT
-pickle (pyproj), NonLinLoc files, ``1dfmm``'s 3-D march, 3-D models.
+pickle (pyproj), NonLinLoc files, bit parity with ``1dfmm`` (another scheme).
 """
 
 import numpy as np
@@ -109,24 +120,132 @@ def _stations(stations):
     return names, xyz
 
 
+def _grid(ll_corner, node_spacing, node_count):
+    ll = np.asarray(ll_corner, dtype=np.float64).reshape(3)
+    sp = np.asarray(node_spacing, dtype=np.float64).reshape(3)
+    nc = np.asarray([int(n) for n in node_count], dtype=np.int64).reshape(3)
+    return ll, sp, nc
+
+
+def trilinear(volume, ll_corner, node_spacing, node_count, xyz):
+    """``volume`` (nx, ny, nz), a NumPy array or a device tensor, at the points ``xyz`` (n, 3) inside the grid.  Per
+    axis the cell is ``floor((p - ll) / h)`` clipped to ``[0, n - 2]`` and the fraction ``f = (p - ll) / h - cell``;
+    with ``c`` the cell's eight corners the value is the one expression
+
+        ((c000 (1 - fz) + c001 fz) (1 - fy) + (c010 (1 - fz) + c011 fz) fy) (1 - fx)
+        + ((c100 (1 - fz) + c101 fz) (1 - fy) + (c110 (1 - fz) + c111 fz) fy) fx
+
+    in float64 on the host; where a fraction comes out as 0 or 1 it is the corner's value exactly."""
+    ll, sp, nc = _grid(ll_corner, node_spacing, node_count)
+    if tuple(volume.shape) != tuple(nc):
+        raise ValueError(f"a volume of shape {tuple(volume.shape)} on a grid of {tuple(nc)} nodes")
+    out = []
+    for p in np.asarray(xyz, dtype=np.float64).reshape(-1, 3):
+        q = (p - ll) / sp
+        cell = np.clip(np.floor(q), 0, nc - 2).astype(np.int64)
+        fx, fy, fz = q - cell
+        c = volume[cell[0]:cell[0] + 2, cell[1]:cell[1] + 2, cell[2]:cell[2] + 2]
+        c = np.asarray(c.cpu() if hasattr(c, "cpu") else c, dtype=np.float64)
+        out.append(((c[0, 0, 0] * (1 - fz) + c[0, 0, 1] * fz) * (1 - fy)
+                    + (c[0, 1, 0] * (1 - fz) + c[0, 1, 1] * fz) * fy) * (1 - fx)
+                   + ((c[1, 0, 0] * (1 - fz) + c[1, 0, 1] * fz) * (1 - fy)
+                      + (c[1, 1, 0] * (1 - fz) + c[1, 1, 1] * fz) * fy) * fx)
+    return np.array(out, dtype=np.float64)
+
+
+def nearest_node(ll_corner, node_spacing, node_count, xyz):
+    """The node the reference's ``_eikonal_fmm`` moves a station to (create_lut.py:379-384): the smallest
+    ``|dx| + |dy| + |dz|``, the lowest flat index among equals.  Returns ``(indices (n, 3), coordinates (n, 3))``."""
+    ll, sp, nc = _grid(ll_corner, node_spacing, node_count)
+    gx, gy, gz = (ll[j] + (np.arange(nc[j]) * sp[j]) for j in range(3))
+    idx = []
+    for p in np.asarray(xyz, dtype=np.float64).reshape(-1, 3):
+        far = np.abs(gx - p[0])[:, None, None] + np.abs(gy - p[1])[None, :, None] + np.abs(gz - p[2])[None, None, :]
+        idx.append(np.unravel_index(np.argmin(far), far.shape))
+    idx = np.array(idx, dtype=np.int64).reshape(-1, 3)
+    return idx, np.column_stack([gx[idx[:, 0]], gy[idx[:, 1]], gz[idx[:, 2]]])
+
+
+def _require_inside(ll_corner, node_spacing, node_count, names, xyz, what):
+    """The grid solver's condition, the reference's own for ``1dfmm`` (create_lut.py:306-313)."""
+    ll, sp, nc = _grid(ll_corner, node_spacing, node_count)
+    ur = ll + ((nc - 1) * sp)
+    for name, p in zip(names, xyz):
+        if (p < ll).any() or (p > ur).any():
+            raise ValueError(f"{what}: station {name} at {tuple(p)} lies outside the grid {tuple(ll)} .. {tuple(ur)}; "
+                             "the solver on the grid's own nodes needs every station inside it (method '1d' with "
+                             "solver='sections' does not)")
+
+
+def _solve_on_grid(engine, ll_corner, node_spacing, node_count, xyz, n_ph, s0, slowness, tol, max_iters, device):
+    """One row per source and phase, phase ``j``'s rows in model ``j`` of ``slowness``."""
+    grids, _, _ = engine.traveltimes_eikonal3d(ll_corner, node_spacing, node_count, np.repeat(xyz, n_ph, axis=0), s0,
+                                               slowness, np.tile(np.arange(n_ph), len(xyz)), tol=tol,
+                                               max_iters=max_iters, device=device)
+    return grids
+
+
 def compute_traveltimes(engine, ll_corner, node_spacing, node_count, stations, method, phases=("P", "S"), vp=None,
                         vs=None, vmod=None, section_dx=0.1, block_model=False, device=True, tol=2.0 ** -40,
-                        max_iters=64):
+                        max_iters=64, velocity=None, solver="sections", snap_to_node=False):
     """
     Travel-time grids for every station and phase, computed on ``engine``'s GPU.
 
     ``stations``: ``{name: (x, y, z)}`` or a sequence of ``(name, x, y, z)``, in grid coordinates.  ``method``:
-    ``"homogeneous"`` (``vp`` / ``vs``) or ``"1d"`` (``vmod``: see :func:`model_velocity`; ``section_dx``: the
-    sections' spacing, the reference's ``nlloc_dx``; ``block_model``).  Returns ``{station: {phase: grid}}`` with
-    grids of shape ``node_count`` in seconds -- torch tensors on the engine's GPU (views of one tensor) with
-    ``device``, else NumPy arrays.
+
+    * ``"homogeneous"`` (``vp`` / ``vs``);
+    * ``"1d"`` (``vmod``: see :func:`model_velocity`; ``block_model``) with ``solver="sections"`` (the default;
+      ``section_dx``: the sections' spacing, the reference's ``nlloc_dx``) or ``solver="grid"``: the model spread over
+      the grid's depths by :func:`model_velocity` and solved on the grid's own nodes, stations inside the grid;
+    * ``"3d"`` (``velocity``: ``{"P": array, "S": array}`` of shape ``node_count``, NumPy arrays or tensors on the
+      engine's GPU): solved on the grid's own nodes, stations inside the grid; the slowness at a station is ``1 /``
+      :func:`trilinear` of the velocity there.
+
+    ``snap_to_node`` (the two grid solves): move each station to the node the reference's ``_eikonal_fmm`` picks
+    (:func:`nearest_node`) before solving; by default the source is the station's true position.  Returns
+    ``{station: {phase: grid}}`` with grids of shape ``node_count`` in seconds -- torch tensors on the engine's GPU
+    (views of one tensor) with ``device``, else NumPy arrays.
     """
     names, xyz = _stations(stations)
     phases = list(phases)
     if not names or not phases:
         raise ValueError("no stations or no phases")
     n_ph = len(phases)
-    if method == "homogeneous":
+    if method == "1d" and solver not in ("sections", "grid"):
+        raise ValueError(f"'{solver}' is not a solver of method '1d': 'sections' or 'grid'")
+    if method == "3d":
+        velocity = velocity or {}
+        shape = tuple(int(n) for n in node_count)
+        for ph in phases:
+            if velocity.get(ph) is None:
+                raise ValueError(f"method '3d' needs velocity[{ph!r}] for phase {ph}")
+            if tuple(velocity[ph].shape) != shape:
+                raise ValueError(f"velocity[{ph!r}] has shape {tuple(velocity[ph].shape)}, the grid {shape}")
+        _require_inside(ll_corner, node_spacing, node_count, names, xyz, "method '3d'")
+        at = nearest_node(ll_corner, node_spacing, node_count, xyz)[1] if snap_to_node else xyz
+        s0 = 1.0 / np.column_stack([trilinear(velocity[ph], ll_corner, node_spacing, node_count, at) for ph in phases])
+        if all(hasattr(velocity[ph], "data_ptr") for ph in phases):
+            import torch
+
+            slowness = torch.stack([1.0 / velocity[ph].to(torch.float64) for ph in phases]).contiguous()
+        else:
+            slowness = np.stack([1.0 / np.asarray(velocity[ph].cpu() if hasattr(velocity[ph], "cpu") else velocity[ph],
+                                                  dtype=np.float64) for ph in phases])
+        grids = _solve_on_grid(engine, ll_corner, node_spacing, node_count, at, n_ph, s0.reshape(-1), slowness, tol,
+                               max_iters, device)
+    elif method == "1d" and solver == "grid":
+        if vmod is None:
+            raise ValueError("method '1d' needs vmod")
+        _require_inside(ll_corner, node_spacing, node_count, names, xyz, "method '1d' with solver='grid'")
+        ll, sp, nc = _grid(ll_corner, node_spacing, node_count)
+        depths = ll[2] + (np.arange(nc[2]) * sp[2])
+        at = nearest_node(ll_corner, node_spacing, node_count, xyz)[1] if snap_to_node else xyz
+        s0 = np.column_stack([1.0 / model_velocity(vmod, ph, at[:, 2], block_model) for ph in phases])
+        slowness = np.stack([np.broadcast_to(1.0 / model_velocity(vmod, ph, depths, block_model), tuple(nc))
+                             for ph in phases])
+        grids = _solve_on_grid(engine, ll_corner, node_spacing, node_count, at, n_ph, s0.reshape(-1), slowness, tol,
+                               max_iters, device)
+    elif method == "homogeneous":
         velocity = {"P": vp, "S": vs}
         for ph in phases:
             if velocity.get(ph) is None:
@@ -152,6 +271,6 @@ def compute_traveltimes(engine, ll_corner, node_spacing, node_count, stations, m
                                       np.arange(len(names) * n_ph), np.repeat(origins, n_ph, axis=0), section_dx,
                                       device=device)
     else:
-        raise ValueError(f"'{method}' is not a valid method here: 'homogeneous' or '1d' ('1dfmm' and '1dnlloc' stay "
-                         "with the reference's create_lut)")
+        raise ValueError(f"'{method}' is not a valid method here: 'homogeneous', '1d' (solver='sections' or 'grid') or "
+                         "'3d' ('1dfmm' and '1dnlloc' stay with the reference's create_lut)")
     return {name: {ph: grids[i * n_ph + j] for j, ph in enumerate(phases)} for i, name in enumerate(names)}
