@@ -443,8 +443,8 @@ int qm_engine_onsets(qm_engine *e, const double *signals, int signals_on_device,
 
 /* Pre-processing on the device -- the step upstream of the onset stage: what STALTAOnset.calculate_onsets does to
  * every component trace before the STA/LTA (stalta.py:137-211, :353-489) for gap-free traces of the full timespan
- * (the reference's default, full_timespan = True, allow_gaps = False; resampling, gappy traces and the envelope
- * transforms stay with the caller).  Per trace, one workgroup:
+ * (the reference's default, full_timespan = True, allow_gaps = False; gappy traces: qm_engine_preprocess_segments
+ * below, resampling: qm_engine_resample; the envelope transforms stay with the caller).  Per trace, one workgroup:
  *   1. detrend = 1: the least-squares line over t = 0..T-1 is subtracted in its centred form,
  *      y = x - (mean(x) + slope (t - mean(t))), slope = sum (t - mean t)(x - mean x) / sum (t - mean t)^2,
  *      then the mean of y (the reference detrends "linear", then "constant").  The sums are fixed-order
@@ -463,6 +463,43 @@ int qm_engine_preprocess(qm_engine *e, const double *signals, int signals_on_dev
                          int32_t n_sections, int detrend, const double *taper_left, int32_t n_left,
                          const double *taper_right, int32_t n_right, int zero_phase, double *filtered,
                          int out_on_device);
+
+/* Pre-processing of GAPPY traces on the device -- what STALTAOnset.calculate_onsets does with allow_gaps = True or
+ * full_timespan = False (stalta.py:137-211, :442-461): every trace SEGMENT is detrended, tapered and filtered on its
+ * own, a second taper takes the filter's transients off each segment, and the gaps and the window's ends are filled
+ * with sqrt(finfo(float).tiny) before the STA/LTA runs over the full-length trace.  signals / filtered: f64
+ * [n_traces][t_samples] in window layout, host or device (filtered may be signals on the device); a segment is samples
+ * [first, first + n) of its trace's row, and samples outside every segment are never read.  The caller plans the work
+ * (Python: quakemigrate_amd.preprocess.plan_segments): records [n_segments][8] int64, per segment
+ *    0 trace                 its row
+ *    1 first, 2 n            its samples, n >= 1
+ *    3 fill_before           filtered[first - fill_before .. first) = fill_value
+ *    4 fill_after            filtered[first + n .. first + n + fill_after) = fill_value
+ *    5 w_offset, 6 m         its taper: w = taper_weights + w_offset, w[0 .. m) the weights of the first m samples,
+ *                            w[m .. 2 m) of the last m
+ *    7                       0
+ * Per record, one workgroup -- the segments of a trace are conditioned in parallel, no workgroup waits on another --
+ * with y = x[first .. first + n):
+ *   1. detrend = 1: qm_engine_preprocess' step 1 over y (the same fixed-order sums; slope 0 where n == 1).
+ *   2. y[k] *= w[k], y[n - m + k] *= w[m + k] for k < m.
+ *   3. the cascade sos[trace_filter[trace]] over y, forward and with zero_phase = 1 backward as well:
+ *      scipy.signal.sosfilt's bits, as in qm_engine_preprocess; "preproc_skew" = 0 selects the plain form here too.
+ *   4. second_taper = 1: step 2 again with the same weights (the reference calls taper(type="cosine",
+ *      max_percentage=0.05) twice on traces of one length).
+ *   5. filtered[first .. first + n) = y, then the record's two fills.
+ * y lives in LDS up to 20 480 samples, else in place in its output row: the same bits.  With one record per trace,
+ * n = t_samples, no fill and second_taper = 0 the result is qm_engine_preprocess' of the same weights, bit for bit.
+ * Refused, with the output untouched: what qm_engine_preprocess refuses, n_segments < 1, a record whose trace is out
+ * of range, n < 1, a negative fill, a range [first - fill_before, first + n + fill_after) that leaves [0, t_samples),
+ * weights that leave taper_weights, 2 m > n, field 7 non-zero, a fill_value that is not finite, and a trace whose
+ * records' ranges do not tile [0, t_samples) exactly once (an overlap, a hole, a trace without a record).
+ * qm_engine_last_kernel_ms reports the launch. */
+int qm_engine_preprocess_segments(qm_engine *e, const double *signals, int signals_on_device, int32_t n_traces,
+                                  int32_t t_samples, const int32_t *trace_filter, const double *sos,
+                                  int32_t n_filters, int32_t n_sections, int detrend, int zero_phase,
+                                  const int64_t *records, int32_t n_segments, const double *taper_weights,
+                                  int64_t n_taper_weights, int second_taper, double fill_value, double *filtered,
+                                  int out_on_device);
 
 /* Resampling on the device -- the step upstream of the pre-processing: what util.resample does to every raw trace of
  * a timestep (quakemigrate/util.py:404-604): upsampling by linear interpolation with constant pads at the window's
@@ -880,6 +917,26 @@ int qm_stream_set_resample_stage(qm_stream *s, int32_t n_traces, const int64_t *
                                  int64_t n_taper_weights, int32_t t_samples, int raw_dtype,
                                  int64_t total_raw_samples);
 int qm_stream_push_raw(qm_stream *s, const void *raw);
+/* Gappy waveforms in: with the segment feed on top of its onset stage the stream takes a timestep's component traces
+ * in window layout TOGETHER WITH their segment layout -- it changes from timestep to timestep, so it travels with the
+ * push -- through qm_stream_push_segments: signals host f64 [n_traces][t_samples], records [n_segments][8] and
+ * taper_weights as qm_engine_preprocess_segments takes them.  A step is three parts in one pinned slot -- n_traces x
+ * t_samples doubles, 8 x max_segments int64, max_taper_weights doubles -- which one pull or copy moves, bits
+ * unchanged; records the push does not use are padded with n = 0.  A slot's launch becomes pull or copy ->
+ * qm_engine_preprocess_segments' kernel over the slot's (step, record)s, from the slot's buffer into the slot's
+ * signals -> qm_engine_onsets' kernels -> the fused detect: every timestep's bits are those of the three staged calls
+ * (filters, detrend and zero phase are the onset stage's; its tapers are not used).  qm_stream_set_segment_feed is
+ * called once, after qm_stream_set_onset_stage and before the first push; a stage that fails -- over replicas: on any
+ * lane -- leaves the stream as it was.  The push checks the records on the caller's thread: refused, with the stream
+ * unchanged, are what qm_engine_preprocess_segments refuses in them, n_segments > max_segments and n_taper_weights >
+ * max_taper_weights.  Refused too: a feed without an onset stage, with a resampling stage (and that stage after the
+ * feed), a second one, one after a push, max_segments < 1, max_taper_weights < 0, a fill_value that is not finite,
+ * qm_stream_push_segments without the feed, and any other push mixed with it on one stream.  Over replicas the feed
+ * and the pushes go lane by lane.  qm_stream_push_segments returns what qm_stream_push returns. */
+int qm_stream_set_segment_feed(qm_stream *s, int32_t max_segments, int64_t max_taper_weights, int second_taper,
+                               double fill_value);
+int qm_stream_push_segments(qm_stream *s, const double *signals, const int64_t *records, int32_t n_segments,
+                            const double *taper_weights, int64_t n_taper_weights);
 /* One pipeline over several engines that hold the SAME table (checked by digest): the continuous stream split by
  * time, not by grid.  Launch j (K timesteps) runs on engine j mod n_engines, each engine with
  * `depth` slots of its own; qm_stream_pop returns timesteps in push order.  Same qm_stream handle: push / flush /
@@ -894,7 +951,7 @@ int qm_stream_create_replicas(qm_engine *const *engines, int32_t n_engines, int3
 
 /* Duration (ms, HIP events on the engine stream) of the stacking kernel(s) of
  * the most recent detect / migrate call, or of the kernel of a more recent
- * qm_engine_pick_phases or qm_engine_resample, or of the two launches of a more recent
+ * qm_engine_pick_phases, qm_engine_resample or qm_engine_preprocess_segments, or of the two launches of a more recent
  * qm_engine_measure_amplitudes; negative if none.  Synchronises. */
 int qm_engine_last_kernel_ms(qm_engine *e, double *ms);
 

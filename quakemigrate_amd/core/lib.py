@@ -117,6 +117,9 @@ qmlib.qm_engine_onsets.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32, c_i
 qmlib.qm_engine_preprocess.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32, c_i32Pt, c_dPt, c_int32, c_int32,
                                        ctypes.c_int, c_dPt, c_int32, c_dPt, c_int32, ctypes.c_int, _vp,
                                        ctypes.c_int]
+qmlib.qm_engine_preprocess_segments.argtypes = [_vp, _vp, ctypes.c_int, c_int32, c_int32, c_i32Pt, c_dPt, c_int32,
+                                                c_int32, ctypes.c_int, ctypes.c_int, c_i64Pt, c_int32, c_dPt, c_int64,
+                                                ctypes.c_int, ctypes.c_double, _vp, ctypes.c_int]
 qmlib.qm_engine_resample.argtypes = [_vp, _vp, ctypes.c_int, ctypes.c_int, c_int64, c_int32, c_i64Pt, c_dPt, c_int32,
                                      c_int32, ctypes.c_int, c_i32Pt, c_int32, c_dPt, c_int64, c_int32, _vp,
                                      ctypes.c_int]
@@ -169,6 +172,8 @@ qmlib.qm_stream_set_onset_stage.argtypes = [_vp, c_int32, c_i32Pt, c_i32Pt, c_dP
 qmlib.qm_stream_push_raw.argtypes = [_vp, _vp]
 qmlib.qm_stream_set_resample_stage.argtypes = [_vp, c_int32, c_i64Pt, c_dPt, c_int32, c_int32, ctypes.c_int, c_i32Pt,
                                                c_int32, c_dPt, c_int64, c_int32, ctypes.c_int, c_int64]
+qmlib.qm_stream_set_segment_feed.argtypes = [_vp, c_int32, c_int64, ctypes.c_int, ctypes.c_double]
+qmlib.qm_stream_push_segments.argtypes = [_vp, _vp, c_i64Pt, c_int32, c_dPt, c_int64]
 qmlib.qm_stream_flush.argtypes = [_vp]
 qmlib.qm_stream_pop.argtypes = [_vp, c_int32, _vp, _vp, _vp]
 qmlib.qm_stream_pending.argtypes = [_vp, ctypes.POINTER(c_int32), ctypes.POINTER(c_int32)]
@@ -226,6 +231,16 @@ def _pack_by_records(traces, offsets, lengths, total, dtype, refuse):
         refuse(i, x, x.ndim == 1 and len(x) == n and off >= 0 and off + n <= total)
         packed[off:off + n] = x
     return packed
+
+
+def segment_arrays(records, taper_weights):
+    """A timestep's segment records (n_segments, 8) int64 and taper weights, contiguous and flat, as the C ABI takes
+    them (:func:`quakemigrate_amd.preprocess.plan_segments` makes them)."""
+    records = np.ascontiguousarray(records, dtype=np.int64)
+    if records.ndim != 2 or records.shape[1] != 8:
+        raise ValueError(f"records of shape {records.shape}: (n_segments, 8) expected")
+    weights = np.ascontiguousarray([] if taper_weights is None else taper_weights, dtype=np.float64).reshape(-1)
+    return records, weights
 
 
 def resample_arrays(stage, t_samples=None):
@@ -792,6 +807,38 @@ class Engine:
         _check(qmlib.qm_engine_preprocess(
             self._h, ps, dev_s, n_traces, t_samples, trace_filter, sos.reshape(-1), int(sos.shape[0]),
             int(sos.shape[1]), 1 if detrend else 0, left, len(left), right, len(right), 1 if zero_phase else 0,
+            po, dev_o))
+        return out
+
+    def preprocess_segments(self, signals, trace_filter, sos, records, taper_weights, detrend=True, zero_phase=True,
+                            second_taper=True, fill_value=None, out=None):
+        """
+        Pre-processing of gappy traces on the GPU (what ``STALTAOnset.calculate_onsets`` does with ``allow_gaps=True``
+        or ``full_timespan=False``, stalta.py:137-211, :442-461; include/qmhip.h: ``qm_engine_preprocess_segments``):
+        every segment detrended, tapered and filtered on its own, tapered again behind the filter (``second_taper``),
+        gaps and the window's ends set to ``fill_value`` (``None``: the reference's ``sqrt(finfo(float).tiny)``).
+
+        ``signals`` (n_traces, T) in window layout, host or device like :meth:`preprocess`; ``trace_filter`` and
+        ``sos`` as there; ``records`` (n_segments, 8) int64 and ``taper_weights`` from
+        :func:`quakemigrate_amd.preprocess.plan_segments`.  Returns the filtered traces (``out``, host or device -- it
+        may be ``signals`` on the device --, or a new host array).
+        """
+        from quakemigrate_amd.preprocess import GAP_FILL_VALUE
+
+        n_traces, t_samples = (int(v) for v in signals.shape)
+        trace_filter = np.ascontiguousarray(trace_filter, dtype=np.int32)
+        if trace_filter.shape != (n_traces,):
+            raise ValueError(f"trace_filter of shape {trace_filter.shape} for {n_traces} traces")
+        sos = _sections(sos)
+        records, weights = segment_arrays(records, taper_weights)
+        ps, dev_s = self._ptr(signals, np.float64)
+        if out is None:
+            out = np.zeros((n_traces, t_samples))
+        po, dev_o = self._ptr(out, np.float64, n_traces * t_samples)
+        _check(qmlib.qm_engine_preprocess_segments(
+            self._h, ps, dev_s, n_traces, t_samples, trace_filter, sos.reshape(-1), int(sos.shape[0]),
+            int(sos.shape[1]), 1 if detrend else 0, 1 if zero_phase else 0, records.reshape(-1), len(records), weights,
+            len(weights), 1 if second_taper else 0, GAP_FILL_VALUE if fill_value is None else float(fill_value),
             po, dev_o))
         return out
 
@@ -1564,6 +1611,9 @@ class EngineReplicas:
 
     def preprocess(self, *args, **kwargs):
         return self.lead.preprocess(*args, **kwargs)
+
+    def preprocess_segments(self, *args, **kwargs):
+        return self.lead.preprocess_segments(*args, **kwargs)
 
     def resample(self, *args, **kwargs):
         return self.lead.resample(*args, **kwargs)

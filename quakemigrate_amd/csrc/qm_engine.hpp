@@ -15,7 +15,7 @@
 //                    with compute), launches round-robin over the lanes; a stream on one engine is the one-lane case
 //   qm_widen.hip     the rows next to the path: onset stage (OnsetStage), locate fits, RBF peak
 //   qm_preproc.hip   the row before the onset stage: detrend, taper, zero-phase band-pass of the component traces
-//                    (PreprocStage)
+//                    (PreprocStage), and its segmented form for gappy traces (SegmentStage)
 //   qm_resample.hip  the row before that: raw traces, each at its own rate and length, upsampled and decimated to the
 //                    scan rate (ResampleStage)
 //                    -- each of the three: the stage's record below (checks, device arrays, launch), shared by the
@@ -324,6 +324,30 @@ struct PreprocStage {
               const double *taper_left, int32_t n_left, const double *taper_right, int32_t n_right, int zero_phase);
     int launch(qm_engine *e, const double *in, double *out, int n_steps) const;
 };
+// The pre-processing of gappy traces (qm_preproc.hpp: segments_kernel): what PreprocStage holds, and the segment
+// records and taper weights of ONE call.  A stream's records travel with its pushes, so its stage holds neither:
+// adopt() borrows the filters of the stream's PreprocStage -- which outlives it, both are the lane's -- and launch
+// takes where the slot keeps each step's records and weights.
+struct SegmentStage {
+    DevBuf<double> coef;                // sos, then the call's taper weights
+    DevBuf<int32_t> meta;               // trace_filter [n_traces]
+    DevBuf<int64_t> rec;                // the call's records [n_segments][8]
+    qm::SegmentArgs args{};
+    int n_traces = 0;                   // of one timestep
+    int max_n = 0;                      // the longest segment a launch may meet: sizes the LDS
+    int build(qm_engine *e, const char *what, int32_t n_traces, int32_t t_samples, const int32_t *trace_filter,
+              const double *sos, int32_t n_filters, int32_t n_sections, int detrend, int zero_phase,
+              const int64_t *records, int32_t n_segments, const double *taper_weights, int64_t n_taper_weights,
+              int second_taper, double fill_value);
+    void adopt(const PreprocStage &pre, int32_t max_segments, int second_taper, double fill_value);
+    // step k reads in + k in_step, its records at rec + k rec_step, its weights at w + k w_step, writes out + k out_step
+    int launch(qm_engine *e, const double *in, int64_t in_step, const int64_t *rec, int64_t rec_step, const double *w,
+               int64_t w_step, double *out, int64_t out_step, int n_steps) const;
+};
+// What the segment calls refuse in a timestep's records [n_segments][8] (include/qmhip.h: qm_engine_preprocess_segments),
+// on the caller's thread; defined in qm_preproc.hip.
+int check_segment_records(const char *what, int32_t n_traces, int32_t t_samples, const int64_t *records,
+                          int32_t n_segments, int64_t n_taper_weights);
 struct OnsetStage {
     DevBuf<int32_t> meta;               // trace_row [repeat][n_traces] (step k's rows k * n_rows on), nsta, nlta [repeat][n_rows]
     DevBuf<double> sta, lta;            // [repeat][n_traces][T] scratch of the two kernels
@@ -480,9 +504,11 @@ struct FitScratch {                     // qm_engine_locate_fits, _rbf_peak (qm_
 };
 // Where the staged calls put host arrays on their way in and out.  Shared on purpose: a call is over when it returns.
 struct CallStaging {
-    DevBuf<double> sig;                 // in: qm_engine_preprocess' and _onsets' signals, qm_engine_pick_phases' onset rows
+    DevBuf<double> sig;                 // in: qm_engine_preprocess', _preprocess_segments' and _onsets' signals,
+                                        // qm_engine_pick_phases' onset rows
     DevBuf<double> raw;                 // out: qm_engine_onsets' raw onsets
-    DevBuf<double> pre_out;             // out: qm_engine_preprocess' filtered and qm_engine_resample's resampled traces
+    DevBuf<double> pre_out;             // out: qm_engine_preprocess' and _preprocess_segments' filtered and
+                                        // qm_engine_resample's resampled traces
     DevBuf<double> rs_raw;              // in: qm_engine_resample's raw samples (bytes, in doubles)
 };
 
@@ -553,9 +579,11 @@ struct qm_engine : TableState {
     DevBuf<double> d_onsets, d_pmax, d_psum, d_bmax, d_out_a, d_chunk, d_marg, d_marg_out;
     DevBuf<int64_t> d_pidx;
 
-    // the stages in front of the detect as the staged calls (qm_engine_resample / _preprocess / _onsets) last built them
+    // the stages in front of the detect as the staged calls (qm_engine_resample / _preprocess / _preprocess_segments /
+    // _onsets) last built them
     ResampleStage rs_stage;
     PreprocStage pre_stage;
+    SegmentStage seg_stage;
     OnsetStage on_stage;
     // the scratch records above, one per call family
     CallStaging staging;

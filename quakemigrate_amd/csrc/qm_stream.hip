@@ -24,6 +24,13 @@
 //   caller's thread : qm_stream_push_raw   CPU copy of a step's packed raw samples, pinned
 //   engine's stream : pull or copy as above, then the resampling kernel (qm_resample.hpp) over the slot's
 //                     (step, trace)s -- its output IS the slot's device signals -- and the sequence above
+//   -- or, with the segment feed on top of the onset stage (qm_stream_set_segment_feed), GAPPY traces cross the bus
+//   with their layout, which changes from timestep to timestep and so travels with the push:
+//   caller's thread : qm_stream_push_segments   checks the step's segment records, CPU copy of its three parts --
+//                     traces, records (padded with n = 0 to max_segments), taper weights -- into ONE pinned step
+//   engine's stream : pull or copy as above (one move for the three parts: bits), then the segment kernel
+//                     (qm_preproc.hpp) over the slot's (step, record)s, from the slot's buffer into the slot's signals,
+//                     the onset kernels and the fused detect as above
 //   caller's thread : qm_stream_pop    waits for the launch's event, CPU copy of a step's three series
 //
 // Round 4 drove a pipeline like this from Python (three D2H copies, three events and NumPy staging per
@@ -49,8 +56,17 @@
 
 // what the pushes carry, one kind per stream: log-onsets [n_rows][T]; with an onset stage the component traces
 // [n_traces][T], from which the slot's log-onsets are made on the device; with a resampling stage as well the
-// packed raw samples, from which the slot's traces are made
-enum Feed { kNothingYet = 0, kLogOnsets = 1, kSignals = 2, kRaw = 3, kFeeds = 4 };
+// packed raw samples, from which the slot's traces are made; or, with the segment feed on top of the onset stage,
+// gappy component traces with their segment records and taper weights, from which the slot's traces are made
+enum Feed { kNothingYet = 0, kLogOnsets = 1, kSignals = 2, kRaw = 3, kSegments = 4, kFeeds = 5 };
+
+// what a step of the segment feed brings beside its signals (qm_stream_push_segments, checked there)
+struct SegmentStep {
+    const int64_t *records;
+    int32_t n_segments;
+    const double *weights;
+    int64_t n_weights;
+};
 
 struct StreamLane {
     qm_engine *e = nullptr;             // (nullptr: orphaned by qm_engine_destroy -- the lane holds nothing any more)
@@ -60,7 +76,7 @@ struct StreamLane {
     hipStream_t copy_stream = nullptr;
     struct Slot {
         struct In {
-            PinnedBuf<double> h;        // pinned [K][step_words[feed]] (the signals': given up at the first raw step)
+            PinnedBuf<double> h;        // pinned [K][step_words[feed]] (the signals': given up at the first raw or segment step)
             DevBuf<double> d;           // device, the same (the signals': filtered in place)
         } in[kFeeds];                   // by Feed: log-onsets from create on, signals and raw samples from their stage on
         PinnedBuf<double> h_out;        // pinned [3][K * ns]: max_coa, max_norm_coa, indices (int64 bits) --
@@ -80,10 +96,15 @@ struct StreamLane {
     size_t step_words[kFeeds] = {};     // a timestep of each kind in doubles, as a slot holds it (raw bytes: rounded up)
     size_t step_bytes[kFeeds] = {};     // ... in bytes, as it is pushed
     // the stages (qm_engine.hpp), K times over: qm_stream_set_onset_stage builds `pre` and `on`,
-    // qm_stream_set_resample_stage `rs`
+    // qm_stream_set_resample_stage `rs`; qm_stream_set_segment_feed has `seg` adopt `pre`'s filters
     PreprocStage pre;
     OnsetStage on;
     ResampleStage rs;
+    SegmentStage seg;
+    // a step of the segment feed: [n_traces * T] signals, [seg_max][8] records, [seg_w_max] taper weights
+    size_t seg_sig = 0;
+    int32_t seg_max = 0;
+    int64_t seg_w_max = 0;
 };
 
 struct qm_stream {
@@ -96,6 +117,7 @@ struct qm_stream {
     int cur = 0;                        // the lane being filled
     int feed = kNothingYet;             // the kind of the steps pushed so far
     bool staged = false, resampled = false;     // the onset stage, the resampling stage: on every lane or on none
+    bool segmented = false;                     // ... the segment feed
 };
 
 namespace {
@@ -131,7 +153,8 @@ int alloc_inputs(StreamLane *s, int feed, const char *what) {
         StreamLane::Slot::In &in = sl.in[feed];
         if (r == hipSuccess) r = in.h.alloc(words, hipHostMallocDefault);
         if (r == hipSuccess) r = in.d.alloc(words);
-        if (r == hipSuccess && feed == kRaw)            // (the bytes a step's int32s leave over)
+        if (r == hipSuccess && (feed == kRaw || feed == kSegments))    // (the bytes a step's int32s leave over; the
+                                                                        // weights a step does not bring)
             std::memset(in.h.p, 0, words * sizeof(double));
     }
     if (r != hipSuccess)
@@ -168,6 +191,7 @@ void release_lane(StreamLane *s) {
         for (StreamLane::Slot &sl : s->slots) sl = StreamLane::Slot{};
         s->rs = ResampleStage{};
         s->pre = PreprocStage{};
+        s->seg = SegmentStage{};
         s->on = OnsetStage{};
     }
     if (s->copy_stream) park_stream(s->e->device, s->copy_stream);
@@ -177,17 +201,30 @@ void release_lane(StreamLane *s) {
 
 // A timestep of the stream's kind into the slot being filled, which has room (fill_n < K).  0, or 2: that slot is the
 // lane's oldest launch and holds results that have not been popped.
-int fill(StreamLane *s, const void *step, int feed, const char *what) {
+int fill(StreamLane *s, const void *step, int feed, const char *what, const SegmentStep *seg) {
     StreamLane::Slot &sl = s->slots[s->fill_slot];
     if (s->fill_n == 0 && sl.in_flight) {
         (void)fail("%s: all %d slots hold results that have not been popped", what, s->depth);
         return 2;
     }
     // (the slot's previous H2D has finished: its launch's results were popped)
-    if (feed == kRaw && sl.in[kSignals].h.p)            // the first raw step: the ring's pinned slots hold raw bytes
-        for (StreamLane::Slot &other : s->slots)        // from here on, the signals' pinned buffers are given up
-            other.in[kSignals].h.release();
-    host_copy(sl.in[feed].h.p + (size_t)s->fill_n * s->step_words[feed], step, s->step_bytes[feed]);
+    if ((feed == kRaw || feed == kSegments) && sl.in[kSignals].h.p)     // the first raw or segment step: the ring's
+        for (StreamLane::Slot &other : s->slots)        // pinned slots hold those from here on, the signals' pinned
+            other.in[kSignals].h.release();             // buffers are given up
+    double *dst = sl.in[feed].h.p + (size_t)s->fill_n * s->step_words[feed];
+    if (feed == kSegments) {
+        // the step's three parts; records it does not use are padding (n = 0), weights it does not bring are never read
+        host_copy(dst, step, s->seg_sig * sizeof(double));
+        int64_t *rec = reinterpret_cast<int64_t *>(dst + s->seg_sig);
+        const size_t used = (size_t)seg->n_segments * qm::kSegmentFields;
+        std::memcpy(rec, seg->records, used * sizeof(int64_t));
+        std::memset(rec + used, 0, ((size_t)s->seg_max * qm::kSegmentFields - used) * sizeof(int64_t));
+        if (seg->n_weights > 0)
+            std::memcpy(dst + s->seg_sig + (size_t)s->seg_max * qm::kSegmentFields, seg->weights,
+                        (size_t)seg->n_weights * sizeof(double));
+    } else {
+        host_copy(dst, step, s->step_bytes[feed]);
+    }
     ++s->fill_n;
     return 0;
 }
@@ -239,6 +276,16 @@ int launch_slot(StreamLane *s, int feed) {
     // kernels, straight into the slot's log-onsets
     if (feed == kRaw || feed == kSignals)
         if (s->pre.launch(e, d_sig, d_sig, n) || s->on.launch(e, d_sig, nullptr, d_on, n)) return 1;
+    // gappy waveforms -> log-onsets: every record's segment conditioned from the slot's buffer into the slot's signals,
+    // the gaps filled, then the onset kernels as above
+    if (feed == kSegments) {
+        const int64_t step = (int64_t)s->step_words[feed];
+        const double *d_w = d_in + s->seg_sig + (size_t)s->seg_max * qm::kSegmentFields;
+        if (s->seg.launch(e, d_in, step, reinterpret_cast<const int64_t *>(d_in + s->seg_sig), step, d_w, step, d_sig,
+                          (int64_t)s->seg_sig, n) ||
+            s->on.launch(e, d_sig, nullptr, d_on, n))
+            return 1;
+    }
     // The results are a few KB per timestep: the combine kernel writes them STRAIGHT into the slot's
     // pinned host buffer (pinned memory is device-accessible under one address; the event behind the
     // launch makes them visible to the host) -- no D2H copy command, no third stream.  (With a copy on a
@@ -279,13 +326,17 @@ int pop_oldest(StreamLane *s, int take, double *max_coa, double *max_norm_coa, i
     return 0;
 }
 
-// A stage that did not come about, on this lane or on a later one -- the onset stage (feed = kSignals) or the
-// resampling stage (kRaw): what it took goes back and the lane is what it was before (the error text stays).
+// A stage that did not come about, on this lane or on a later one -- the onset stage (feed = kSignals), the
+// resampling stage (kRaw) or the segment feed (kSegments): what it took goes back and the lane is what it was before
+// (the error text stays).
 void stage_undo(StreamLane *s, int feed) {
     PoolReleaseScope one_wait;
     for (StreamLane::Slot &sl : s->slots) sl.in[feed] = {};
     if (feed == kRaw) {
         s->rs = ResampleStage{};
+    } else if (feed == kSegments) {
+        s->seg = SegmentStage{};
+        s->seg_sig = 0; s->seg_max = 0; s->seg_w_max = 0;
     } else {
         s->pre = PreprocStage{};
         s->on = OnsetStage{};
@@ -346,7 +397,7 @@ int stage_every_lane(qm_stream *s, int feed, Build build) {
         }
         return 1;
     }
-    (feed == kRaw ? s->resampled : s->staged) = true;
+    (feed == kRaw ? s->resampled : feed == kSegments ? s->segmented : s->staged) = true;
     return 0;
 }
 
@@ -459,7 +510,7 @@ void qm_stream_destroy(qm_stream *s) {
 
 // a timestep into the lane being filled: log-onsets, (an onset stage) signals or (a resampling stage as well) raw
 // samples -- one kind per stream
-static int push_step(qm_stream *s, const void *step, int feed, const char *what) {
+static int push_step(qm_stream *s, const void *step, int feed, const char *what, const SegmentStep *seg = nullptr) {
     if (!step || !s) return fail("%s: NULL argument", what);
     if (alive(s, what)) return 1;
     if (feed == kSignals && !s->staged)
@@ -469,11 +520,15 @@ static int push_step(qm_stream *s, const void *step, int feed, const char *what)
     if (feed == kSignals && s->resampled)
         return fail("qm_stream_push_signals: this stream takes raw traces (qm_stream_push_raw): one stream, one kind of "
                     "input");
+    if (feed == kSignals && s->segmented)
+        return fail("qm_stream_push_signals: this stream takes gappy traces (qm_stream_push_segments): one stream, one "
+                    "kind of input");
     if (s->feed != kNothingYet && s->feed != feed)
         return fail("%s: this stream takes %s: one stream, one kind of input", what,
-                    s->feed == kRaw       ? "raw traces (qm_stream_push_raw)"
-                    : s->feed == kSignals ? "signals (qm_stream_push_signals)"
-                                          : "log-onsets (qm_stream_push)");
+                    s->feed == kRaw        ? "raw traces (qm_stream_push_raw)"
+                    : s->feed == kSegments ? "gappy traces (qm_stream_push_segments)"
+                    : s->feed == kSignals  ? "signals (qm_stream_push_signals)"
+                                           : "log-onsets (qm_stream_push)");
     // A full slot whose launch FAILED (the table changed under the stream, no memory, a refused step) is still
     // waiting to go out: it goes first, or this call fails as that one did -- never a copy past the slot's
     // K timesteps (the next push used to write one timestep behind the pinned buffer and launch
@@ -481,7 +536,7 @@ static int push_step(qm_stream *s, const void *step, int feed, const char *what)
     if (s->lanes[s->cur]->fill_n >= s->lanes[s->cur]->K && flush(s)) return 1;
     StreamLane *lane = s->lanes[s->cur].get();
     DeviceGuard guard(lane->e->device);
-    if (const int rc = fill(lane, step, feed, what)) return rc;
+    if (const int rc = fill(lane, step, feed, what, seg)) return rc;
     s->feed = feed;
     return lane->fill_n < lane->K ? 0 : send(s);
 }
@@ -506,6 +561,8 @@ int qm_stream_set_resample_stage(qm_stream *s, int32_t n_traces, const int64_t *
     if (!s) return fail("%s: NULL argument", what);
     if (!s->staged) return fail("%s: the stream has no onset stage (qm_stream_set_onset_stage comes first)", what);
     if (s->resampled) return fail("%s: the stream has its resampling stage already (it is set once)", what);
+    if (s->segmented)
+        return fail("%s: this stream takes gappy traces (qm_stream_set_segment_feed): one stream, one kind of input", what);
     if (pushed_to(s)) return fail("%s: the stage is set before the first push", what);
     if (alive(s, what)) return 1;
     const StreamLane *lead = s->lanes[0].get();
@@ -549,6 +606,55 @@ int qm_stream_set_onset_stage(qm_stream *s, int32_t n_traces, const int32_t *tra
         lane->step_bytes[kSignals] = lane->step_words[kSignals] * sizeof(double);
         return alloc_inputs(lane, kSignals, what);
     });
+}
+
+int qm_stream_set_segment_feed(qm_stream *s, int32_t max_segments, int64_t max_taper_weights, int second_taper,
+                               double fill_value) {
+    const char *what = "qm_stream_set_segment_feed";
+    if (!s) return fail("%s: NULL argument", what);
+    if (!s->staged) return fail("%s: the stream has no onset stage (qm_stream_set_onset_stage comes first)", what);
+    if (s->segmented) return fail("%s: the stream has its segment feed already (it is set once)", what);
+    if (s->resampled)
+        return fail("%s: this stream takes raw traces (qm_stream_set_resample_stage): one stream, one kind of input", what);
+    if (pushed_to(s)) return fail("%s: the feed is set before the first push", what);
+    if (alive(s, what)) return 1;
+    if (max_segments < 1) return fail("%s: max_segments must be at least 1 (got %d)", what, max_segments);
+    if (max_taper_weights < 0)
+        return fail("%s: max_taper_weights must be at least 0 (got %lld)", what, (long long)max_taper_weights);
+    if (!std::isfinite(fill_value)) return fail("%s: fill_value %g is not finite", what, fill_value);
+    const StreamLane *lead = s->lanes[0].get();
+    const double words = (double)lead->pre.n_traces * lead->T + 8.0 * max_segments + (double)max_taper_weights;
+    if ((double)lead->K * words * 8.0 >= 0x1p40 || (int64_t)lead->K * max_segments >= INT32_MAX)
+        return fail("%s: too many segments or taper weights per launch", what);
+    return stage_every_lane(s, kSegments, [&](StreamLane *lane) {
+        lane->seg.adopt(lane->pre, max_segments, second_taper, fill_value);
+        lane->seg_sig = (size_t)lane->pre.n_traces * lane->T;
+        lane->seg_max = max_segments;
+        lane->seg_w_max = max_taper_weights;
+        lane->step_words[kSegments] = lane->seg_sig + (size_t)max_segments * qm::kSegmentFields + (size_t)max_taper_weights;
+        lane->step_bytes[kSegments] = lane->step_words[kSegments] * sizeof(double);
+        return alloc_inputs(lane, kSegments, what);
+    });
+}
+
+int qm_stream_push_segments(qm_stream *s, const double *signals, const int64_t *records, int32_t n_segments,
+                            const double *taper_weights, int64_t n_taper_weights) {
+    const char *what = "qm_stream_push_segments";
+    if (!s || !signals || !records) return fail("%s: NULL argument", what);
+    if (!s->segmented) return fail("%s: the stream has no segment feed (qm_stream_set_segment_feed)", what);
+    if (alive(s, what)) return 1;
+    // the records, on the caller's thread: the kernel takes them as they are
+    const StreamLane *lead = s->lanes[0].get();
+    if (n_taper_weights < 0 || (n_taper_weights > 0 && !taper_weights))
+        return fail("%s: %lld taper weights without their array", what, (long long)n_taper_weights);
+    if (n_segments > lead->seg_max)
+        return fail("%s: %d segments, the feed was set for up to %d (max_segments)", what, n_segments, lead->seg_max);
+    if (n_taper_weights > lead->seg_w_max)
+        return fail("%s: %lld taper weights, the feed was set for up to %lld (max_taper_weights)", what,
+                    (long long)n_taper_weights, (long long)lead->seg_w_max);
+    if (check_segment_records(what, lead->pre.n_traces, lead->T, records, n_segments, n_taper_weights)) return 1;
+    const SegmentStep seg{records, n_segments, taper_weights, n_taper_weights};
+    return push_step(s, signals, kSegments, what, &seg);
 }
 
 int qm_stream_flush(qm_stream *s) {

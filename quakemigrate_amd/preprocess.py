@@ -9,8 +9,11 @@ and :class:`ResampleStage`, the plan that brings a timestep's raw traces to the 
 The reference's ``STALTAOnset.calculate_onsets`` (quakemigrate/signal/onsets/stalta.py:137-211, :353-489) does this
 per timestep and component trace on the host: linear detrend, demean, 5 % cosine taper, zero-phase Butterworth
 band-pass, STA/LTA.  The device stage covers its default case -- gap-free traces of the full timespan
-(``full_timespan=True, allow_gaps=False``).  Gappy traces (their second taper and tiny-float padding,
-stalta.py:442-461) and the ``env`` / ``env_squared`` transforms stay on the host plugin path.
+(``full_timespan=True, allow_gaps=False``) -- and, with ``OnsetStage(fill_gaps=True)`` and :func:`plan_segments`,
+gappy traces as ``allow_gaps=True`` / ``full_timespan=False`` treat them (stalta.py:442-461): every segment
+conditioned on its own, a second taper, the gaps and the window's ends filled with ``sqrt(finfo(float).tiny)``
+(``Engine.preprocess_segments``, ``StreamingDetector.push_segments``).  The ``env`` / ``env_squared`` transforms stay
+on the host plugin path.
 
 Before that the reference brings every raw trace to the scan rate (``util.resample``, quakemigrate/util.py:404-604):
 integer decimation behind a detrend, a cosine taper and a zero-phase low-pass, and -- for rates that do not divide --
@@ -99,6 +102,58 @@ def cosine_taper_sides(npts, max_percentage=0.05):
     return left, np.ascontiguousarray(left[::-1])
 
 
+# the columns of a segment's record (include/qmhip.h: qm_engine_preprocess_segments)
+SEGMENT_FIELDS = ("trace", "first", "n", "fill_before", "fill_after", "w_offset", "m", "reserved")
+# what the reference pads gaps and the window's ends with (stalta.py:455-461): 2**-511
+GAP_FILL_VALUE = float(np.sqrt(np.finfo(float).tiny))
+
+
+def plan_segments(t_samples, n_traces, segments, taper_percentage=0.05):
+    """
+    The records and taper weights of a timestep's gappy traces, as ``Engine.preprocess_segments`` and
+    ``qm_stream_push_segments`` take them.  ``segments``: a list of ``(trace, first, n)`` -- samples
+    ``[first, first + n)`` of row ``trace`` of the (n_traces, t_samples) window hold data --, the segments of one
+    trace in ascending order with at least one sample between two of them.  Returns ``(records, taper_weights)``:
+    records (n_segments, 8) int64 in the order given (columns: ``SEGMENT_FIELDS``), their ``fill_before`` /
+    ``fill_after`` set so that each trace's records tile the window -- a segment fills up to its predecessor, or from
+    sample 0, and the trace's last one to the window's end --, ``m = int(taper_percentage * n)`` with the weights of
+    :func:`cosine_taper_sides`, one set per distinct length.  ``ValueError`` for a segment outside the window,
+    overlapping or touching segments or segments out of order, and a trace without a segment.
+    """
+    T, n_traces = int(t_samples), int(n_traces)
+    segments = [tuple(int(v) for v in seg) for seg in segments]
+    records = np.zeros((len(segments), len(SEGMENT_FIELDS)), dtype=np.int64)
+    tapers, weights, n_weights = {}, [], 0
+    last = {}                                           # trace -> index of its latest record
+    for i, (tr, first, n) in enumerate(segments):
+        if not 0 <= tr < n_traces:
+            raise ValueError(f"segment {i}: trace {tr} out of range ({n_traces} traces)")
+        if n < 1 or first < 0 or first + n > T:
+            raise ValueError(f"segment {i}: samples [{first}, {first + n}) of trace {tr} leave the window of {T} "
+                             "(at least one sample, inside it)")
+        start = 0
+        if tr in last:
+            prev = records[last[tr]]
+            start = int(prev[1] + prev[2])
+            if first <= start:
+                raise ValueError(f"segment {i}: samples [{first}, {first + n}) of trace {tr} overlap, touch or precede "
+                                 f"the trace's segment before them, which ends at {start} (segments of a trace go in "
+                                 "ascending order, a gap between them)")
+        if n not in tapers:
+            left, right = cosine_taper_sides(n, taper_percentage)
+            tapers[n] = (n_weights, len(left))
+            weights += [left, right]
+            n_weights += 2 * len(left)
+        records[i] = (tr, first, n, first - start, 0, tapers[n][0], tapers[n][1], 0)
+        last[tr] = i
+    for tr in range(n_traces):
+        if tr not in last:
+            raise ValueError(f"trace {tr} has no segment (a trace without data is not part of the stage)")
+        r = records[last[tr]]
+        r[4] = T - (r[1] + r[2])
+    return records, (np.concatenate(weights) if weights else np.zeros(0))
+
+
 _TRANSFORMS = {"energy": 0, "abs": 1}
 _POSITIONS = {"classic": 0, "centred": 1, "recursive": 2}
 
@@ -118,6 +173,9 @@ class OnsetStage:
     transform : "energy" or "abs";  position : "classic", "centred" or "recursive".
     taper_pad : samples of the onset's taper windows, < 0 for none;  min_onset_value : the clip.
     detrend, taper_percentage : the pre-processing's linear detrend + demean and its cosine taper.
+    fill_gaps : the traces come in segments (the reference's ``allow_gaps=True`` / ``full_timespan=False``): every
+        segment is conditioned on its own and tapered a second time behind the filter, gaps and the window's ends
+        are filled with ``sqrt(finfo(float).tiny)`` (:func:`plan_segments`, ``StreamingDetector.push_segments``).
 
     Two stages compare equal when they describe the same kernels' inputs: a pipeline is rebuilt when the stage
     changes (``MigrationScan.continuous_compute``).
@@ -134,6 +192,7 @@ class OnsetStage:
     min_onset_value: float = 0.4
     detrend: bool = True
     taper_percentage: float = 0.05
+    fill_gaps: bool = False
 
     def __post_init__(self):
         object.__setattr__(self, "filters", {k: tuple(v) for k, v in dict(self.filters).items()})
@@ -157,7 +216,7 @@ class OnsetStage:
     def __hash__(self):
         return hash((tuple(self.filters.items()), tuple(self.sta_lta_windows.items()), self.trace_row,
                      self.trace_phase, self.row_phase, self.transform, self.position, self.taper_pad,
-                     self.min_onset_value, self.detrend, self.taper_percentage))
+                     self.min_onset_value, self.detrend, self.taper_percentage, self.fill_gaps))
 
     @property
     def n_traces(self):
@@ -171,13 +230,15 @@ class OnsetStage:
         """The stage as the C ABI takes it, for windows of ``t_samples`` samples at ``sampling_rate`` Hz: a dict
         with ``trace_row``, ``trace_filter``, ``sos`` (n_filters, n_sections, 6), ``taper_left``, ``taper_right``,
         ``nsta``, ``nlta`` (samples, as the reference counts them: ``int(round(seconds * rate)) + 1``, stalta.py:394-396),
-        ``transform``, ``position`` (their integer codes), ``taper_pad``, ``min_onset_value`` and ``detrend``."""
+        ``transform``, ``position`` (their integer codes), ``taper_pad``, ``min_onset_value`` and ``detrend``; with
+        ``fill_gaps`` also ``second_taper`` = 1 and ``fill_value`` = ``sqrt(finfo(float).tiny)``."""
         phases = list(self.filters)
         sos = np.stack([butter_bandpass_sos(*self.filters[ph][:2], sampling_rate, self.filters[ph][2])
                         for ph in phases])
         left, right = cosine_taper_sides(t_samples, self.taper_percentage)
         windows = np.array([[int(round(w * int(sampling_rate))) + 1 for w in self.sta_lta_windows[ph]]
                             for ph in self.row_phase], dtype=np.int32).reshape(-1, 2)
+        gaps = {"second_taper": 1, "fill_value": GAP_FILL_VALUE} if self.fill_gaps else {}
         return {
             "trace_row": np.array(self.trace_row, dtype=np.int32),
             "trace_filter": np.array([phases.index(ph) for ph in self.trace_phase], dtype=np.int32),
@@ -187,6 +248,7 @@ class OnsetStage:
             "transform": _TRANSFORMS[self.transform], "position": _POSITIONS[self.position],
             "taper_pad": int(self.taper_pad), "min_onset_value": float(self.min_onset_value),
             "detrend": 1 if self.detrend else 0,
+            **gaps,
         }
 
 

@@ -306,9 +306,16 @@ class MigrationScan:
         (``StreamingDetector(..., onset_stage=...)``, ``qm_stream_push_signals``) instead of on the host per
         timestep: ``signals`` are the resampled, not yet filtered, full-timespan traces of the available rows in
         availability order, (n_traces, T) float64; the stage (``quakemigrate_amd.preprocess.OnsetStage``) names
-        their filters, windows and row layout.  The device stage covers gap-free traces of the full timespan only
-        (the reference's default, ``full_timespan=True, allow_gaps=False``): gappy traces (their second taper and
-        tiny-float padding, stalta.py:442-461), the ``env`` transforms and -- in this loop -- resampling (the
+        their filters, windows and row layout.  That 3-tuple is the reference's default, gap-free traces of the full
+        timespan (``full_timespan=True, allow_gaps=False``).  Gappy traces (``allow_gaps=True`` /
+        ``full_timespan=False``: every segment conditioned on its own, a second taper, tiny-float padding,
+        stalta.py:442-461) run on the GPU as well: ``device_stage`` returns ``(signals, stage, onset_data, segments)``
+        with ``stage.fill_gaps`` set, ``signals`` in window layout and ``segments`` the list of ``(trace, first, n)``
+        that hold data (``quakemigrate_amd.preprocess.plan_segments``); the pipeline is then made on the segment feed
+        (``qm_stream_push_segments``) with room for ``4 * n_traces`` segments, and a timestep with more than that
+        drains the pipeline and goes through ``calculate_onsets``, as a ``None`` does.  Which channels pass
+        ``check_availability`` -- the reference's flatline test on the filtered segments included -- stays the
+        plugin's decision.  The ``env`` transforms and -- in this loop -- resampling (the
         device's resampling stage, ``StreamingDetector(resample_stage=...)``, takes a plan of the timestep's raw
         traces; which ones a timestep has, and at what times, is the plugin's ``Stream`` bookkeeping) stay on the host
         plugin path -- ``device_stage`` returns ``None`` for a timestep it cannot describe and ``calculate_onsets`` is
@@ -391,6 +398,19 @@ class MigrationScan:
             try:
                 data = archive.read_waveform_data(w_beg, w_end)
                 staged = device_stage(data) if device_stage is not None else None
+                segments = None
+                if staged is not None and len(staged) == 4:     # gappy waveforms in, where their segments fit the feed
+                    segments = list(staged[3])
+                    if not staged[1].fill_gaps:
+                        raise ValueError("device_stage: segments go with a stage that fills gaps "
+                                         "(OnsetStage(fill_gaps=True))")
+                    if len(segments) > 4 * staged[1].n_traces:
+                        staged = None
+                    else:
+                        staged = staged[:3]
+                elif staged is not None and getattr(staged[1], "fill_gaps", False):
+                    raise ValueError("device_stage: a stage that fills gaps needs the timestep's segments "
+                                     "(signals, stage, onset_data, segments)")
                 if staged is not None:                   # waveforms in: the onsets are made in the launch
                     signals, stage, onset_data = staged
                     onsets = None
@@ -443,10 +463,15 @@ class MigrationScan:
                 k = steps_per_launch if steps_per_launch else (8 if eng.n_nodes <= 1_000_000 else 1)
                 state["stream"] = StreamingDetector(eng, n_onsets, t_samples, fsmp, lsmp, avail,
                                                     depth=depth, steps_per_launch=k, onset_stage=stage,
-                                                    sampling_rate=onset_data.sampling_rate)
+                                                    sampling_rate=onset_data.sampling_rate,
+                                                    max_segments=(4 * stage.n_traces if stage is not None
+                                                                  and stage.fill_gaps else None))
                 state["key"] = key
             stream = state["stream"]
             push, window = (stream.push, onsets) if stage is None else (stream.push_signals, signals)
+            if stage is not None and stage.fill_gaps:
+                gappy = (signals, segments)
+                push, window = (lambda pair: stream.push_segments(*pair)), gappy
             while not push(window):
                 emit(min(stream.k, stream.pending()[0]))
             pending.append((_shift(data.starttime, self.pre_pad), onset_data))

@@ -55,11 +55,18 @@ class StreamingDetector:
         ``raw_dtype``: what the raw samples are, int32 (as miniSEED holds them) or float64.  A slot's launch then
         starts with the resampling kernel, every timestep's bits those of ``Engine.resample`` in front of the calls
         above.
+    max_segments : with an onset stage whose ``fill_gaps`` is set (or whose dict holds ``second_taper`` /
+        ``fill_value``), the stream takes GAPPY traces with their segment layout (``push_segments``): up to this many
+        segments per timestep (``None``: 4 per trace).  A slot's launch is then the segment kernel -- every segment
+        conditioned on its own, tapered twice, gaps filled -> onsets -> fused detect, every timestep's bits those of
+        ``Engine.preprocess_segments`` in front of ``Engine.onsets`` and ``Engine.detect``.
+    max_taper_weights : room for a timestep's taper weights; ``None``: ``ceil(2 * taper_percentage * n_traces *
+        t_samples)``, which suffices for any layout, since sum 2 int(p n_s) <= 2 p n_traces T.
     """
 
     def __init__(self, engine, n_rows, t_samples, fsmp, lsmp, available, n_nodes_total=None,
                  depth=2, device=None, steps_per_launch=1, onset_stage=None, sampling_rate=None,
-                 resample_stage=None, raw_dtype=np.int32):
+                 resample_stage=None, raw_dtype=np.int32, max_segments=None, max_taper_weights=None):
         if engine.n_rows is None:
             raise _lib.QMHipError("no travel-time table resident: call load_lut first")
         if int(n_rows) != engine.n_rows:
@@ -87,13 +94,23 @@ class StreamingDetector:
         self._finalizer = weakref.finalize(self, _qm.qm_stream_destroy, h)
         self.n_traces = None
         self.raw_dtype = self._raw_records = self.total_raw_samples = None
+        self.max_segments = self.max_taper_weights = None
+        self.taper_percentage = 0.05
         if onset_stage is not None:
-            self.set_onset_stage(onset_stage, sampling_rate)
+            self.taper_percentage = float(getattr(onset_stage, "taper_percentage", 0.05))
+            gaps = self.set_onset_stage(onset_stage, sampling_rate)
+            if gaps is not None:
+                self.set_segment_feed(max_segments, max_taper_weights, *gaps)
+            elif max_segments is not None:
+                raise ValueError("max_segments: the onset stage does not fill gaps (OnsetStage(fill_gaps=True))")
+        elif max_segments is not None:
+            raise ValueError("max_segments goes with an onset stage that fills gaps")
         if resample_stage is not None:
             self.set_resample_stage(resample_stage, raw_dtype)
 
     def set_onset_stage(self, onset_stage, sampling_rate=None):
-        """Once, before the first push (``qm_stream_set_onset_stage``)."""
+        """Once, before the first push (``qm_stream_set_onset_stage``).  Returns ``(second_taper, fill_value)`` of a
+        stage that fills gaps -- what :meth:`set_segment_feed` takes -- and ``None`` of any other."""
         if hasattr(onset_stage, "arrays"):
             if sampling_rate is None:
                 raise ValueError("an OnsetStage needs the sampling_rate of the windows")
@@ -114,6 +131,27 @@ class StreamingDetector:
             int(a.get("detrend", 1)), left, len(left), right, len(right), nsta, nlta, int(a["transform"]),
             int(a["position"]), int(a["taper_pad"]), float(a["min_onset_value"])))
         self.n_traces = len(trace_row)
+        if "fill_value" in a or "second_taper" in a:
+            from quakemigrate_amd.preprocess import GAP_FILL_VALUE
+
+            return int(a.get("second_taper", 1)), float(a.get("fill_value", GAP_FILL_VALUE))
+        return None
+
+    def set_segment_feed(self, max_segments=None, max_taper_weights=None, second_taper=1, fill_value=None):
+        """Once, after the onset stage and before the first push (``qm_stream_set_segment_feed``)."""
+        from quakemigrate_amd.preprocess import GAP_FILL_VALUE
+
+        if self.n_traces is None:                       # (the library's own refusal)
+            raise _lib.QMHipError("qm_stream_set_segment_feed: the stream has no onset stage "
+                                  "(qm_stream_set_onset_stage comes first)")
+        if max_segments is None:
+            max_segments = 4 * self.n_traces
+        if max_taper_weights is None:
+            max_taper_weights = int(np.ceil(2.0 * self.taper_percentage * self.n_traces * self.t_samples))
+        _lib._check(_qm.qm_stream_set_segment_feed(
+            self._h, int(max_segments), int(max_taper_weights), int(second_taper),
+            GAP_FILL_VALUE if fill_value is None else float(fill_value)))
+        self.max_segments, self.max_taper_weights = int(max_segments), int(max_taper_weights)
 
     def set_resample_stage(self, resample_stage, raw_dtype=np.int32):
         """Once, after the onset stage and before the first push (``qm_stream_set_resample_stage``)."""
@@ -167,6 +205,26 @@ class StreamingDetector:
         _lib._check(rc)
         return True
 
+    def push_segments(self, window, segments, taper_weights=None):
+        """One timestep's gappy component traces (n_traces, t_samples) in window layout with their layout into a
+        pipeline with the segment feed: ``segments`` is a list of ``(trace, first, n)``, planned here
+        (:func:`quakemigrate_amd.preprocess.plan_segments` with the stage's taper percentage), or -- with
+        ``taper_weights`` -- the (n_segments, 8) records themselves.  Returns like :meth:`push`."""
+        w = np.ascontiguousarray(window, dtype=np.float64)
+        if self.n_traces is not None and w.shape != (self.n_traces, self.t_samples):
+            raise ValueError(f"window of shape {w.shape}, the stage takes {(self.n_traces, self.t_samples)}")
+        if taper_weights is None:
+            from quakemigrate_amd.preprocess import plan_segments
+
+            segments, taper_weights = plan_segments(self.t_samples, w.shape[0], segments, self.taper_percentage)
+        records, weights = _lib.segment_arrays(segments, taper_weights)
+        rc = _qm.qm_stream_push_segments(self._h, w.ctypes.data_as(ctypes.c_void_p), records.reshape(-1), len(records),
+                                         weights, len(weights))
+        if rc == 2:
+            return False
+        _lib._check(rc)
+        return True
+
     def flush(self):
         _lib._check(_qm.qm_stream_flush(self._h))
 
@@ -191,7 +249,8 @@ class StreamingDetector:
         """
         ``windows``: iterable of float64 arrays, one per timestep: (n_rows, t_samples), already logged --
         or, on a stream with an onset stage, (n_traces, t_samples) resampled component traces -- or, with a
-        resampling stage as well, the timestep's raw traces as :meth:`push_raw` takes them.  Returns a list of ``(max_coa, max_norm_coa, max_coa_idx)`` NumPy triples (or
+        resampling stage as well, the timestep's raw traces as :meth:`push_raw` takes them -- or, on a stream with the
+        segment feed, ``(traces, segments)`` pairs as :meth:`push_segments` takes them.  Returns a list of ``(max_coa, max_norm_coa, max_coa_idx)`` NumPy triples (or
         calls ``on_result(step, triple)`` and returns the number of steps).
         """
         results = []
@@ -211,6 +270,8 @@ class StreamingDetector:
         push = self.push if self.n_traces is None else self.push_signals
         if self._raw_records is not None:
             push = self.push_raw
+        if self.max_segments is not None:
+            push = lambda pair: self.push_segments(*pair)     # noqa: E731
         for w in windows:
             while not push(w):
                 take(min(self.k, self.pending()[0]))     # the oldest launch's timesteps
