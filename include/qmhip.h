@@ -882,17 +882,27 @@ int qm_stream_flush(qm_stream *s);
 int qm_stream_pop(qm_stream *s, int32_t n_steps, double *max_coa, double *max_norm_coa,
                   int64_t *max_coa_idx);
 int qm_stream_pending(qm_stream *s, int32_t *launched_not_popped, int32_t *pushed_not_launched);
-/* Waveforms in: with an onset stage the stream takes a timestep's resampled component traces (host f64
- * [n_traces][t_samples]) through qm_stream_push_signals instead of its log-onsets, and a slot's launch becomes
- * pull or copy of the signals -> qm_engine_preprocess's kernel (zero-phase) over the slot's (step, trace)s ->
- * qm_engine_onsets' kernels over its (step, trace)s and (step, row)s -> the fused detect: every timestep's bits are
- * those of the three staged calls.  The arguments are those of qm_engine_preprocess and qm_engine_onsets (n_rows is
- * the resident table's); every array is copied to the device here, so no launch waits on a host buffer.
- * qm_stream_set_onset_stage is called once, before the first push.  A stream takes signals or log-onsets, never both:
- * refused are a second stage, a stage after a push, qm_stream_push_signals without a stage, qm_stream_push after
- * qm_stream_push_signals and the reverse, a trace_row entry out of range or a row without a trace, and what
- * qm_engine_preprocess refuses.  Over replicas the stage and the pushes go lane by lane like everything else.
- * qm_stream_push_signals returns what qm_stream_push returns; flush / pop / pending are unchanged. */
+/* What crosses the bus is ONE KIND OF INPUT per stream, and a slot's launch is the part of one chain that kind still
+ * needs -- pull or copy of the input -> (signals made on the device) -> (conditioning) -> (onsets) -> fused detect:
+ *   log-onsets     qm_stream_push             no stage: taken from creation on
+ *   signals        qm_stream_push_signals     the onset stage        qm_stream_set_onset_stage
+ *   raw traces     qm_stream_push_raw         the resampling stage   qm_stream_set_resample_stage, on the onset stage
+ *   gappy traces   qm_stream_push_segments    the segment feed       qm_stream_set_segment_feed, on the onset stage
+ * The rules are the same for every kind (csrc/qm_stream.hip: kFeedTable), and every refusal leaves the stream as it was:
+ *   - a set call is refused when the stage it stands on is not set ("... comes first"), when its own is set already
+ *     ("it is set once"), when the other stage on the onset stage is set ("this stream takes ..."), and after the
+ *     first push -- launched or not ("... is set before the first push");
+ *   - a push is refused when its stage is not set ("the stream has no ..."), when a stage stands on its own (signals,
+ *     once the resampling stage or the segment feed is set), and when the stream has taken a step of another kind;
+ *   - every array of a set call is copied to the device there, so no launch waits on a host buffer; a stage that
+ *     fails -- over replicas: on any lane -- leaves the stream as it was; stage and pushes go lane by lane;
+ *   - every push returns what qm_stream_push returns; flush / pop / pending do not depend on the kind.
+ *
+ * Waveforms in: a timestep's resampled component traces (host f64 [n_traces][t_samples]).  A slot's launch is
+ * qm_engine_preprocess's kernel (zero-phase) over the slot's (step, trace)s -> qm_engine_onsets' kernels over its
+ * (step, trace)s and (step, row)s -> the fused detect: every timestep's bits are those of the three staged calls.  The
+ * arguments are those of qm_engine_preprocess and qm_engine_onsets (n_rows is the resident table's).  Refused too: a
+ * trace_row entry out of range or a row without a trace, and what qm_engine_preprocess refuses. */
 int qm_stream_set_onset_stage(qm_stream *s, int32_t n_traces, const int32_t *trace_row,
                               const int32_t *trace_filter, const double *sos, int32_t n_filters,
                               int32_t n_sections, int detrend, const double *taper_left,
@@ -900,39 +910,28 @@ int qm_stream_set_onset_stage(qm_stream *s, int32_t n_traces, const int32_t *tra
                               const int32_t *nsta, const int32_t *nlta, int transform, int position,
                               int32_t taper_pad, double min_onset_value);
 int qm_stream_push_signals(qm_stream *s, const double *signals);
-/* Raw waveforms in: with a resampling stage on top of its onset stage the stream takes a timestep's packed raw
- * traces (host, total_raw_samples int32 or float64 samples, laid out as the records say) through qm_stream_push_raw,
- * and a slot's launch becomes pull or copy of the raw bytes -> qm_engine_resample's kernel over the slot's
- * (step, trace)s -> the sequence of qm_stream_set_onset_stage: every timestep's bits are those of the staged calls.
- * The arguments are qm_engine_resample's; every array is copied to the device here, and the ring's pinned slots are
- * sized for the raw bytes (the signals' pinned buffers go at the first qm_stream_push_raw).  A stage that fails --
- * over replicas: on any lane -- leaves the stream as it was.  qm_stream_set_resample_stage is called once, after qm_stream_set_onset_stage and before
- * the first push; t_samples must be the stream's and n_traces the onset stage's.  Refused: a stage without an onset
- * stage, a second one, one after a push, qm_stream_push_raw without the stage, qm_stream_push_signals or
- * qm_stream_push mixed with qm_stream_push_raw on one stream, and what qm_engine_resample refuses.  Over replicas
- * the stage and the pushes go lane by lane.  qm_stream_push_raw returns what qm_stream_push returns. */
+/* Raw waveforms in: a timestep's packed raw traces (host, total_raw_samples int32 or float64 samples, laid out as the
+ * records say).  A slot's launch starts with qm_engine_resample's kernel over the slot's (step, trace)s, which makes
+ * the signals; then as above.  The arguments are qm_engine_resample's; t_samples must be the stream's and n_traces the
+ * onset stage's.  The ring's pinned slots are sized for the raw bytes (the signals' pinned buffers go at the first
+ * qm_stream_push_raw).  Refused too: what qm_engine_resample refuses. */
 int qm_stream_set_resample_stage(qm_stream *s, int32_t n_traces, const int64_t *records, const double *sos_lp,
                                  int32_t n_lowpass, int32_t n_sections_lp, int detrend,
                                  const int32_t *taper_table, int32_t n_tapers, const double *taper_weights,
                                  int64_t n_taper_weights, int32_t t_samples, int raw_dtype,
                                  int64_t total_raw_samples);
 int qm_stream_push_raw(qm_stream *s, const void *raw);
-/* Gappy waveforms in: with the segment feed on top of its onset stage the stream takes a timestep's component traces
- * in window layout TOGETHER WITH their segment layout -- it changes from timestep to timestep, so it travels with the
- * push -- through qm_stream_push_segments: signals host f64 [n_traces][t_samples], records [n_segments][8] and
- * taper_weights as qm_engine_preprocess_segments takes them.  A step is three parts in one pinned slot -- n_traces x
- * t_samples doubles, 8 x max_segments int64, max_taper_weights doubles -- which one pull or copy moves, bits
- * unchanged; records the push does not use are padded with n = 0.  A slot's launch becomes pull or copy ->
- * qm_engine_preprocess_segments' kernel over the slot's (step, record)s, from the slot's buffer into the slot's
- * signals -> qm_engine_onsets' kernels -> the fused detect: every timestep's bits are those of the three staged calls
- * (filters, detrend and zero phase are the onset stage's; its tapers are not used).  qm_stream_set_segment_feed is
- * called once, after qm_stream_set_onset_stage and before the first push; a stage that fails -- over replicas: on any
- * lane -- leaves the stream as it was.  The push checks the records on the caller's thread: refused, with the stream
- * unchanged, are what qm_engine_preprocess_segments refuses in them, n_segments > max_segments and n_taper_weights >
- * max_taper_weights.  Refused too: a feed without an onset stage, with a resampling stage (and that stage after the
- * feed), a second one, one after a push, max_segments < 1, max_taper_weights < 0, a fill_value that is not finite,
- * qm_stream_push_segments without the feed, and any other push mixed with it on one stream.  Over replicas the feed
- * and the pushes go lane by lane.  qm_stream_push_segments returns what qm_stream_push returns. */
+/* Gappy waveforms in: a timestep's component traces in window layout TOGETHER WITH their segment layout -- it changes
+ * from timestep to timestep, so it travels with the push: signals host f64 [n_traces][t_samples], records
+ * [n_segments][8] and taper_weights as qm_engine_preprocess_segments takes them.  A step is three parts in one pinned
+ * slot -- n_traces x t_samples doubles, 8 x max_segments int64, max_taper_weights doubles -- which one pull or copy
+ * moves, bits unchanged; records the push does not use are padded with n = 0.  A slot's launch starts with
+ * qm_engine_preprocess_segments' kernel over the slot's (step, record)s, from the slot's buffer into the slot's signals
+ * (filters, detrend and zero phase are the onset stage's; its tapers are not used); then the onset kernels and the
+ * detect.  The signals' pinned buffers go at the first push, as with raw traces.  Refused too: max_segments < 1,
+ * max_taper_weights < 0, a fill_value that is not finite; and by the push, which checks the records on the caller's
+ * thread: what qm_engine_preprocess_segments refuses in them, n_segments > max_segments and n_taper_weights >
+ * max_taper_weights. */
 int qm_stream_set_segment_feed(qm_stream *s, int32_t max_segments, int64_t max_taper_weights, int second_taper,
                                double fill_value);
 int qm_stream_push_segments(qm_stream *s, const double *signals, const int64_t *records, int32_t n_segments,

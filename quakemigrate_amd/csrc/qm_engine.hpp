@@ -326,8 +326,9 @@ struct PreprocStage {
 };
 // The pre-processing of gappy traces (qm_preproc.hpp: segments_kernel): what PreprocStage holds, and the segment
 // records and taper weights of ONE call.  A stream's records travel with its pushes, so its stage holds neither:
-// adopt() borrows the filters of the stream's PreprocStage -- which outlives it, both are the lane's -- and launch
-// takes where the slot keeps each step's records and weights.
+// adopt() borrows the filters of the stream's PreprocStage -- which outlives it, both are the lane's -- and lays out
+// the STEP the stream's slots hold, `repeat` of them per launch: [sig_words] signals, [max_segments][8] records,
+// [max_weights] taper weights, all 8-byte words.  pack() writes one on the host, the slot form of launch reads them.
 struct SegmentStage {
     DevBuf<double> coef;                // sos, then the call's taper weights
     DevBuf<int32_t> meta;               // trace_filter [n_traces]
@@ -335,11 +336,24 @@ struct SegmentStage {
     qm::SegmentArgs args{};
     int n_traces = 0;                   // of one timestep
     int max_n = 0;                      // the longest segment a launch may meet: sizes the LDS
+    size_t sig_words = 0;               // a stream's step (adopt): its signals ...
+    int32_t max_segments = 0;           // ... the records it has room for ...
+    int64_t max_weights = 0;            // ... and the taper weights
+    size_t step_words() const { return sig_words + (size_t)max_segments * qm::kSegmentFields + (size_t)max_weights; }
+    size_t step_bytes() const { return step_words() * sizeof(double); }
     int build(qm_engine *e, const char *what, int32_t n_traces, int32_t t_samples, const int32_t *trace_filter,
               const double *sos, int32_t n_filters, int32_t n_sections, int detrend, int zero_phase,
               const int64_t *records, int32_t n_segments, const double *taper_weights, int64_t n_taper_weights,
               int second_taper, double fill_value);
-    void adopt(const PreprocStage &pre, int32_t max_segments, int second_taper, double fill_value);
+    // refuses a step too large for a launch of `repeat` of them; max_segments >= 1, max_taper_weights >= 0
+    int adopt(const char *what, int repeat, const PreprocStage &pre, int32_t max_segments, int64_t max_taper_weights,
+              int second_taper, double fill_value);
+    // one step into dst [step_words()], on the host: n_segments <= max_segments records, the unused ones padded with
+    // n = 0; n_weights <= max_weights weights, the words behind them left alone (no record reads them)
+    void pack(double *dst, const double *signals, const int64_t *records, int32_t n_segments, const double *weights,
+              int64_t n_weights) const;
+    // n_steps packed steps on the device -> their signals [n_steps][sig_words]
+    int launch(qm_engine *e, const double *d_steps, double *d_signals, int n_steps) const;
     // step k reads in + k in_step, its records at rec + k rec_step, its weights at w + k w_step, writes out + k out_step
     int launch(qm_engine *e, const double *in, int64_t in_step, const int64_t *rec, int64_t rec_step, const double *w,
                int64_t w_step, double *out, int64_t out_step, int n_steps) const;
@@ -369,6 +383,8 @@ struct ResampleStage {
     static size_t step_doubles(int raw_dtype, int64_t total_raw_samples) {
         return ((size_t)total_raw_samples * (raw_dtype == qm::kRawInt32 ? 4 : 8) + 7) / 8;
     }
+    size_t step_words() const { return raw_step; }      // a stream's step, under the names SegmentStage answers to
+    size_t step_bytes() const { return raw_bytes; }
     int build(qm_engine *e, const char *what, int repeat, int raw_dtype, int64_t total_raw_samples, int32_t n_traces,
               int32_t t_samples, const int64_t *records, const double *sos_lp, int32_t n_lowpass, int32_t n_sections_lp,
               int detrend, const int32_t *taper_table, int32_t n_tapers, const double *taper_weights,

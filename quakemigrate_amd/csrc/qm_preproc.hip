@@ -2,8 +2,8 @@
 // (qm_engine.hpp) is the stage: build checks the caller's arrays and puts them on the device, launch runs the kernel over
 // the (step, trace)s of a launch.  qm_engine_preprocess is the staged call on the engine's record; the pipeline
 // (qm_stream.hip) holds a record of its own.  SegmentStage is the same for gappy traces -- one workgroup per segment
-// record -- with qm_engine_preprocess_segments beside it; check_segment_records is what both it and the stream's
-// push refuse in a timestep's records.
+// record -- with qm_engine_preprocess_segments beside it and, for the stream, the layout of a pushed step (adopt, pack,
+// the slot form of launch); check_segment_records is what both refuse in a timestep's records.
 #define QM_TU_PREPROC 1
 #include "qm_engine.hpp"
 
@@ -151,7 +151,15 @@ int SegmentStage::build(qm_engine *e, const char *what, int32_t n_traces_, int32
     return 0;
 }
 
-void SegmentStage::adopt(const PreprocStage &pre, int32_t max_segments, int second_taper, double fill_value) {
+int SegmentStage::adopt(const char *what, int repeat, const PreprocStage &pre, int32_t max_segments_,
+                        int64_t max_taper_weights, int second_taper, double fill_value) {
+    const double words = (double)pre.n_traces * pre.args.T + (double)qm::kSegmentFields * max_segments_ +
+                         (double)max_taper_weights;
+    if ((double)repeat * words * 8.0 >= 0x1p40 || (int64_t)repeat * max_segments_ >= INT32_MAX)
+        return fail("%s: too many segments or taper weights per launch", what);
+    sig_words = (size_t)pre.n_traces * pre.args.T;
+    max_segments = max_segments_;
+    max_weights = max_taper_weights;
     n_traces = pre.n_traces;
     max_n = pre.args.T;                                 // (a step's layout is not known before it is pushed)
     args = qm::SegmentArgs{};
@@ -161,6 +169,24 @@ void SegmentStage::adopt(const PreprocStage &pre, int32_t max_segments, int seco
     args.detrend = pre.args.detrend; args.zero_phase = pre.args.zero_phase;
     args.second_taper = second_taper ? 1 : 0;
     args.fill_value = fill_value;
+    return 0;
+}
+
+void SegmentStage::pack(double *dst, const double *signals, const int64_t *records, int32_t n_segments,
+                        const double *weights, int64_t n_weights) const {
+    host_copy(dst, signals, sig_words * sizeof(double));
+    int64_t *rec_dst = reinterpret_cast<int64_t *>(dst + sig_words);
+    const size_t used = (size_t)n_segments * qm::kSegmentFields, room = (size_t)max_segments * qm::kSegmentFields;
+    std::memcpy(rec_dst, records, used * sizeof(int64_t));
+    std::memset(rec_dst + used, 0, (room - used) * sizeof(int64_t));
+    if (n_weights > 0) std::memcpy(dst + sig_words + room, weights, (size_t)n_weights * sizeof(double));
+}
+
+int SegmentStage::launch(qm_engine *e, const double *d_steps, double *d_signals, int n_steps) const {
+    const int64_t step = (int64_t)step_words();
+    const double *d_rec = d_steps + sig_words;
+    return launch(e, d_steps, step, reinterpret_cast<const int64_t *>(d_rec), step,
+                  d_rec + (size_t)max_segments * qm::kSegmentFields, step, d_signals, (int64_t)sig_words, n_steps);
 }
 
 int SegmentStage::launch(qm_engine *e, const double *in, int64_t in_step, const int64_t *records, int64_t rec_step,

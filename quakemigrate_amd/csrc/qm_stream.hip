@@ -5,33 +5,35 @@
 // Timesteps are independent given their onsets, so the hot-path part of that loop is a pipeline over
 // a ring of `depth` slots, each holding `steps_per_launch` timesteps:
 //
-//   caller's thread : qm_stream_push   CPU copy of a step's log-onsets into the slot's PINNED input
+//   caller's thread : a push            CPU copy of a step's input into the slot's PINNED input
 //   copy stream     : H2D of the slot's inputs                 (overlaps the previous launch's kernel)
 //                     -- or, for slots of up to kPullBytes (the example-sized grids, one timestep per launch: a
 //                     step is a fraction of a millisecond and the wait for another stream's copy costs a quarter
 //                     of it), NO copy command at all: a small kernel on the engine's stream PULLS the pinned
 //                     input over the bus into the slot's device buffer, in order before the detect launch
-//   engine's stream : ONE fused-detect launch for the slot's K steps (qm_engine_detect_batch); its
-//                     combine kernel writes the results, packed as [3][K x n_samples] float64, STRAIGHT
-//                     into the slot's pinned host buffer (a few KB per timestep; no D2H command)
-//   -- or, with an onset stage (qm_stream_set_onset_stage), WAVEFORMS cross the bus instead of log-onsets:
-//   caller's thread : qm_stream_push_signals   CPU copy of a step's resampled component traces, pinned
-//   engine's stream : pull or copy as above, then the pre-processing kernel (detrend, taper, zero-phase band-pass;
-//                     qm_preproc.hpp) over the slot's (step, trace)s, the two onset kernels over its (step, trace)s and
-//                     (step, row)s -- their output IS the slot's device log-onsets -- and the fused detect as above
-//   -- or, with a resampling stage on top of that (qm_stream_set_resample_stage), the RAW traces cross the bus, each
-//   at its own rate and length, int32 as miniSEED holds them or float64:
-//   caller's thread : qm_stream_push_raw   CPU copy of a step's packed raw samples, pinned
-//   engine's stream : pull or copy as above, then the resampling kernel (qm_resample.hpp) over the slot's
-//                     (step, trace)s -- its output IS the slot's device signals -- and the sequence above
-//   -- or, with the segment feed on top of the onset stage (qm_stream_set_segment_feed), GAPPY traces cross the bus
-//   with their layout, which changes from timestep to timestep and so travels with the push:
-//   caller's thread : qm_stream_push_segments   checks the step's segment records, CPU copy of its three parts --
-//                     traces, records (padded with n = 0 to max_segments), taper weights -- into ONE pinned step
-//   engine's stream : pull or copy as above (one move for the three parts: bits), then the segment kernel
-//                     (qm_preproc.hpp) over the slot's (step, record)s, from the slot's buffer into the slot's signals,
-//                     the onset kernels and the fused detect as above
+//   engine's stream : whatever makes signals, conditioning, onsets -- as far as the stream's kind of input needs
+//                     them, see below -- then ONE fused-detect launch for the slot's K steps
+//                     (qm_engine_detect_batch); its combine kernel writes the results, packed as
+//                     [3][K x n_samples] float64, STRAIGHT into the slot's pinned host buffer (a few KB per
+//                     timestep; no D2H command)
 //   caller's thread : qm_stream_pop    waits for the launch's event, CPU copy of a step's three series
+//
+// What crosses the bus is one kind of input per stream (kFeedTable: a row per kind), and a slot's launch is the part
+// of ONE chain that kind still needs (launch_slot), every kernel writing straight into the slot's next buffer:
+//
+//   input over the bus  ->  signals made here  ->  conditioning  ->  onsets  ->  detect
+//   log-onsets   qm_stream_push            [n_rows][T]:  detect
+//   signals      qm_stream_push_signals    resampled component traces [n_traces][T]:  pre-processing in place (detrend,
+//                                          taper, zero-phase band-pass; qm_preproc.hpp), the two onset kernels over the
+//                                          slot's (step, trace)s and (step, row)s, detect
+//   raw traces   qm_stream_push_raw        packed raw samples, each trace at its own rate and length, int32 as miniSEED
+//                                          holds them or float64:  the resampling kernel (qm_resample.hpp) makes the
+//                                          signals, then as for signals
+//   gappy traces qm_stream_push_segments   traces with their layout, which changes from timestep to timestep and so
+//                                          travels with the push -- traces, records, taper weights in ONE pinned step
+//                                          (SegmentStage::pack; one move over the bus: bits):  the segment kernel
+//                                          (qm_preproc.hpp) over the slot's (step, record)s makes the signals,
+//                                          conditioned segment by segment, then onsets and detect
 //
 // Round 4 drove a pipeline like this from Python (three D2H copies, three events and NumPy staging per
 // launch): with the copies inside the clock the example-sized grids lost 30-40 % of their kernel
@@ -41,9 +43,10 @@
 // x1.00 of the resident step on those grids.  The caller's pointers are never handed to the HIP
 // runtime.
 //
-// The stages in front of the detect are the records of qm_engine.hpp (ResampleStage, PreprocStage, OnsetStage): the
-// stream builds its own, steps_per_launch times over, where the stage is set, launches them slot by slot and
-// releases them with its slots.  Nothing here checks a stage's arrays or fills a kernel's arguments.
+// The stages in front of the detect are the records of qm_engine.hpp (ResampleStage, SegmentStage, PreprocStage,
+// OnsetStage): the stream builds its own, steps_per_launch times over, where the stage is set, launches them slot by
+// slot and releases them with its slots.  Nothing here checks a stage's arrays, fills a kernel's arguments or lays out
+// a step of more than one array.
 //
 // Two records: a StreamLane is one engine's ring and does what it is told (fill, launch, pop, build or undo a stage,
 // release); a qm_stream, the C ABI's handle, owns one lane per engine and keeps what belongs to the whole stream --
@@ -53,20 +56,8 @@
 
 #include <deque>
 
-
-// what the pushes carry, one kind per stream: log-onsets [n_rows][T]; with an onset stage the component traces
-// [n_traces][T], from which the slot's log-onsets are made on the device; with a resampling stage as well the
-// packed raw samples, from which the slot's traces are made; or, with the segment feed on top of the onset stage,
-// gappy component traces with their segment records and taper weights, from which the slot's traces are made
+// what the pushes carry, one kind per stream (kFeedTable below says what each kind is called, needs and makes)
 enum Feed { kNothingYet = 0, kLogOnsets = 1, kSignals = 2, kRaw = 3, kSegments = 4, kFeeds = 5 };
-
-// what a step of the segment feed brings beside its signals (qm_stream_push_segments, checked there)
-struct SegmentStep {
-    const int64_t *records;
-    int32_t n_segments;
-    const double *weights;
-    int64_t n_weights;
-};
 
 struct StreamLane {
     qm_engine *e = nullptr;             // (nullptr: orphaned by qm_engine_destroy -- the lane holds nothing any more)
@@ -76,7 +67,8 @@ struct StreamLane {
     hipStream_t copy_stream = nullptr;
     struct Slot {
         struct In {
-            PinnedBuf<double> h;        // pinned [K][step_words[feed]] (the signals': given up at the first raw or segment step)
+            PinnedBuf<double> h;        // pinned [K][step_words[feed]] (the signals': given up at the first step of a
+                                        // feed that makes them on the device)
             DevBuf<double> d;           // device, the same (the signals': filtered in place)
         } in[kFeeds];                   // by Feed: log-onsets from create on, signals and raw samples from their stage on
         PinnedBuf<double> h_out;        // pinned [3][K * ns]: max_coa, max_norm_coa, indices (int64 bits) --
@@ -101,10 +93,31 @@ struct StreamLane {
     OnsetStage on;
     ResampleStage rs;
     SegmentStage seg;
-    // a step of the segment feed: [n_traces * T] signals, [seg_max][8] records, [seg_w_max] taper weights
-    size_t seg_sig = 0;
-    int32_t seg_max = 0;
-    int64_t seg_w_max = 0;
+};
+
+// One row per kind of input: its names in the refusals, what its stage stands on, what its stage is on a lane.  The
+// refusals (may_set, may_push), the pinned buffers (alloc_inputs, fill) and a stage's undoing read it; only the
+// launch chain (launch_slot) names kinds.
+struct FeedRow {
+    const char *push;                   // the entry point that pushes this kind
+    const char *set;                    // ... that sets its stage (nullptr: none -- log-onsets are taken from creation)
+    const char *takes;                  // "this stream takes <takes>"
+    const char *noun;                   // the stage in "has no <noun>", "has its <noun> already"
+    const char *word;                   // "the <word> is set before the first push"
+    int after;                          // the kind whose stage must be set first (kNothingYet: none)
+    bool makes_signals;                 // ... on the device: the signals' pinned buffers go at its first push, its own
+                                        // start zeroed (an int32 step's last bytes, weights a step does not bring)
+    void (*drop)(StreamLane *);         // the lane's stage records go back to empty
+};
+constexpr FeedRow kFeedTable[kFeeds] = {
+    {},
+    {"qm_stream_push", nullptr, "log-onsets", nullptr, nullptr, kNothingYet, false, nullptr},
+    {"qm_stream_push_signals", "qm_stream_set_onset_stage", "signals", "onset stage", "stage", kNothingYet, false,
+     [](StreamLane *l) { l->pre = PreprocStage{}; l->on = OnsetStage{}; }},
+    {"qm_stream_push_raw", "qm_stream_set_resample_stage", "raw traces", "resampling stage", "stage", kSignals, true,
+     [](StreamLane *l) { l->rs = ResampleStage{}; }},
+    {"qm_stream_push_segments", "qm_stream_set_segment_feed", "gappy traces", "segment feed", "feed", kSignals, true,
+     [](StreamLane *l) { l->seg = SegmentStage{}; }},
 };
 
 struct qm_stream {
@@ -116,8 +129,7 @@ struct qm_stream {
     std::deque<Launch> launched;        // every lane's launches in push order, oldest first
     int cur = 0;                        // the lane being filled
     int feed = kNothingYet;             // the kind of the steps pushed so far
-    bool staged = false, resampled = false;     // the onset stage, the resampling stage: on every lane or on none
-    bool segmented = false;                     // ... the segment feed
+    bool set[kFeeds] = {false, true};   // by Feed: its stage is set, on every lane or on none (log-onsets need none)
 };
 
 namespace {
@@ -145,17 +157,17 @@ __global__ void stamp_kernel(unsigned long long *slot) { *slot = wall_clock64();
 
 // ---- a lane: one engine's ring.  The engine's device is current in all of these. ------------------------------
 
-// every slot's buffers for one kind of input, K timesteps each (s->step_words[feed] is set)
-int alloc_inputs(StreamLane *s, int feed, const char *what) {
-    const size_t words = (size_t)s->K * s->step_words[feed];
+// every slot's buffers for one kind of input, K timesteps of `step_words` doubles each, `step_bytes` of them pushed
+int alloc_inputs(StreamLane *s, int feed, size_t step_words, size_t step_bytes, const char *what) {
+    s->step_words[feed] = step_words;
+    s->step_bytes[feed] = step_bytes;
+    const size_t words = (size_t)s->K * step_words;
     hipError_t r = hipSuccess;
     for (StreamLane::Slot &sl : s->slots) {
         StreamLane::Slot::In &in = sl.in[feed];
         if (r == hipSuccess) r = in.h.alloc(words, hipHostMallocDefault);
         if (r == hipSuccess) r = in.d.alloc(words);
-        if (r == hipSuccess && (feed == kRaw || feed == kSegments))    // (the bytes a step's int32s leave over; the
-                                                                        // weights a step does not bring)
-            std::memset(in.h.p, 0, words * sizeof(double));
+        if (r == hipSuccess && kFeedTable[feed].makes_signals) std::memset(in.h.p, 0, words * sizeof(double));
     }
     if (r != hipSuccess)
         return fail("%s: %s (%d steps of %zu bytes per slot, %d slots)", what, hipGetErrorString(r), s->K,
@@ -189,42 +201,28 @@ void release_lane(StreamLane *s) {
     {
         PoolReleaseScope one_wait;
         for (StreamLane::Slot &sl : s->slots) sl = StreamLane::Slot{};
-        s->rs = ResampleStage{};
-        s->pre = PreprocStage{};
-        s->seg = SegmentStage{};
-        s->on = OnsetStage{};
+        for (const FeedRow &row : kFeedTable)
+            if (row.drop) row.drop(s);
     }
     if (s->copy_stream) park_stream(s->e->device, s->copy_stream);
     s->copy_stream = nullptr;
     s->order.clear();
 }
 
-// A timestep of the stream's kind into the slot being filled, which has room (fill_n < K).  0, or 2: that slot is the
-// lane's oldest launch and holds results that have not been popped.
-int fill(StreamLane *s, const void *step, int feed, const char *what, const SegmentStep *seg) {
+// A timestep of the stream's kind into the slot being filled, which has room (fill_n < K): `write(dst)` puts the step
+// into its pinned words.  0, or 2: that slot is the lane's oldest launch and holds results that have not been popped.
+template <typename Write>
+int fill(StreamLane *s, int feed, const char *what, Write write) {
     StreamLane::Slot &sl = s->slots[s->fill_slot];
     if (s->fill_n == 0 && sl.in_flight) {
         (void)fail("%s: all %d slots hold results that have not been popped", what, s->depth);
         return 2;
     }
     // (the slot's previous H2D has finished: its launch's results were popped)
-    if ((feed == kRaw || feed == kSegments) && sl.in[kSignals].h.p)     // the first raw or segment step: the ring's
-        for (StreamLane::Slot &other : s->slots)        // pinned slots hold those from here on, the signals' pinned
-            other.in[kSignals].h.release();             // buffers are given up
-    double *dst = sl.in[feed].h.p + (size_t)s->fill_n * s->step_words[feed];
-    if (feed == kSegments) {
-        // the step's three parts; records it does not use are padding (n = 0), weights it does not bring are never read
-        host_copy(dst, step, s->seg_sig * sizeof(double));
-        int64_t *rec = reinterpret_cast<int64_t *>(dst + s->seg_sig);
-        const size_t used = (size_t)seg->n_segments * qm::kSegmentFields;
-        std::memcpy(rec, seg->records, used * sizeof(int64_t));
-        std::memset(rec + used, 0, ((size_t)s->seg_max * qm::kSegmentFields - used) * sizeof(int64_t));
-        if (seg->n_weights > 0)
-            std::memcpy(dst + s->seg_sig + (size_t)s->seg_max * qm::kSegmentFields, seg->weights,
-                        (size_t)seg->n_weights * sizeof(double));
-    } else {
-        host_copy(dst, step, s->step_bytes[feed]);
-    }
+    if (kFeedTable[feed].makes_signals && sl.in[kSignals].h.p)     // its first step: the ring's pinned slots hold this
+        for (StreamLane::Slot &other : s->slots)                    // kind from here on, the signals' pinned buffers
+            other.in[kSignals].h.release();                         // are given up
+    write(sl.in[feed].h.p + (size_t)s->fill_n * s->step_words[feed]);
     ++s->fill_n;
     return 0;
 }
@@ -269,23 +267,16 @@ int launch_slot(StreamLane *s, int feed) {
         QM_HIP(hipStreamWaitEvent(e->stream, sl.copied, 0));
     }
     s->pulled = pull;
+    // The chain, all on the engine's stream, every kernel straight into the slot's next buffer.  What makes the n
+    // steps' signals on the device: raw samples resampled to the scan rate, or every record's segment conditioned and
+    // the gaps filled ...
     double *d_sig = sl.in[kSignals].d.p, *d_on = sl.in[kLogOnsets].d.p;
-    // raw samples -> the n steps' traces at the scan rate, straight into the slot's signals
     if (feed == kRaw && s->rs.launch(e, d_in, d_sig, n)) return 1;
-    // waveforms -> log-onsets, all on the engine's stream: the n steps' traces filtered in place, then the onset
-    // kernels, straight into the slot's log-onsets
-    if (feed == kRaw || feed == kSignals)
-        if (s->pre.launch(e, d_sig, d_sig, n) || s->on.launch(e, d_sig, nullptr, d_on, n)) return 1;
-    // gappy waveforms -> log-onsets: every record's segment conditioned from the slot's buffer into the slot's signals,
-    // the gaps filled, then the onset kernels as above
-    if (feed == kSegments) {
-        const int64_t step = (int64_t)s->step_words[feed];
-        const double *d_w = d_in + s->seg_sig + (size_t)s->seg_max * qm::kSegmentFields;
-        if (s->seg.launch(e, d_in, step, reinterpret_cast<const int64_t *>(d_in + s->seg_sig), step, d_w, step, d_sig,
-                          (int64_t)s->seg_sig, n) ||
-            s->on.launch(e, d_sig, nullptr, d_on, n))
-            return 1;
-    }
+    if (feed == kSegments && s->seg.launch(e, d_in, d_sig, n)) return 1;
+    // ... signals that are not conditioned yet -- pushed, or resampled here -- are filtered in place ...
+    if ((feed == kSignals || feed == kRaw) && s->pre.launch(e, d_sig, d_sig, n)) return 1;
+    // ... and the onset kernels make the slot's log-onsets of them.
+    if (feed != kLogOnsets && s->on.launch(e, d_sig, nullptr, d_on, n)) return 1;
     // The results are a few KB per timestep: the combine kernel writes them STRAIGHT into the slot's
     // pinned host buffer (pinned memory is device-accessible under one address; the event behind the
     // launch makes them visible to the host) -- no D2H copy command, no third stream.  (With a copy on a
@@ -326,21 +317,12 @@ int pop_oldest(StreamLane *s, int take, double *max_coa, double *max_norm_coa, i
     return 0;
 }
 
-// A stage that did not come about, on this lane or on a later one -- the onset stage (feed = kSignals), the
-// resampling stage (kRaw) or the segment feed (kSegments): what it took goes back and the lane is what it was before
-// (the error text stays).
+// A stage that did not come about, on this lane or on a later one: what it took goes back and the lane is what it
+// was before (the error text stays).
 void stage_undo(StreamLane *s, int feed) {
     PoolReleaseScope one_wait;
     for (StreamLane::Slot &sl : s->slots) sl.in[feed] = {};
-    if (feed == kRaw) {
-        s->rs = ResampleStage{};
-    } else if (feed == kSegments) {
-        s->seg = SegmentStage{};
-        s->seg_sig = 0; s->seg_max = 0; s->seg_w_max = 0;
-    } else {
-        s->pre = PreprocStage{};
-        s->on = OnsetStage{};
-    }
+    kFeedTable[feed].drop(s);
 }
 
 // ---- the stream: one pipeline over its lanes ------------------------------------------------------------------
@@ -365,6 +347,41 @@ int64_t waiting(const qm_stream *s) {
 bool pushed_to(const qm_stream *s) {
     return std::any_of(s->lanes.begin(), s->lanes.end(),
                        [](const auto &lane) { return lane->fill_n > 0 || lane->launched_steps > 0; });
+}
+
+// ---- what a stream refuses by its kind of input: every text comes from kFeedTable ----------------------------------
+// "has no ... (...)": the kind's own stage is not set
+int has_stage(const qm_stream *s, int feed, const char *what) {
+    return s->set[feed] ? 0 : fail("%s: the stream has no %s (%s)", what, kFeedTable[feed].noun, kFeedTable[feed].set);
+}
+
+// "this stream takes ... (...)": `by` names the taker's set call in a set call, its push in a push
+int taken(const char *what, int taker, const char *by) {
+    return fail("%s: this stream takes %s (%s): one stream, one kind of input", what, kFeedTable[taker].takes, by);
+}
+
+// May the stage of `feed` be set now?  In this order: the stage it stands on is there, it is not set yet, no other
+// stage stands on the same one, nothing has been pushed, the engines live.
+int may_set(const qm_stream *s, int feed, const char *what) {
+    const FeedRow &row = kFeedTable[feed], &base = kFeedTable[row.after];
+    if (row.after != kNothingYet && !s->set[row.after])
+        return fail("%s: the stream has no %s (%s comes first)", what, base.noun, base.set);
+    if (s->set[feed]) return fail("%s: the stream has its %s already (it is set once)", what, row.noun);
+    for (int other = kLogOnsets; row.after != kNothingYet && other < kFeeds; ++other)
+        if (other != feed && s->set[other] && kFeedTable[other].after == row.after)
+            return taken(what, other, kFeedTable[other].set);
+    if (pushed_to(s)) return fail("%s: the %s is set before the first push", what, row.word);
+    return alive(s, what);
+}
+
+// May a step of `feed` be pushed now?  In this order: its stage is set, no stage stands on it (that one's kind is
+// what crosses the bus then), and the stream has not taken another kind already.
+int may_push(const qm_stream *s, int feed, const char *what) {
+    if (has_stage(s, feed, what)) return 1;
+    for (int above = kLogOnsets; above < kFeeds; ++above)
+        if (s->set[above] && kFeedTable[above].after == feed) return taken(what, above, kFeedTable[above].push);
+    if (s->feed != kNothingYet && s->feed != feed) return taken(what, s->feed, kFeedTable[s->feed].push);
+    return 0;
 }
 
 // the lane being filled sends what its slot holds (its device is current); the next lane is filled from here on
@@ -397,8 +414,31 @@ int stage_every_lane(qm_stream *s, int feed, Build build) {
         }
         return 1;
     }
-    (feed == kRaw ? s->resampled : feed == kSegments ? s->segmented : s->staged) = true;
+    s->set[feed] = true;
     return 0;
+}
+
+// A timestep of kind `feed` into the lane being filled; `write(lane, dst)` puts it into the slot's pinned words.
+template <typename Write>
+int push_step(qm_stream *s, int feed, Write write) {
+    const char *what = kFeedTable[feed].push;
+    if (alive(s, what) || may_push(s, feed, what)) return 1;
+    // A full slot whose launch FAILED (the table changed under the stream, no memory, a refused step) is still
+    // waiting to go out: it goes first, or this call fails as that one did -- never a copy past the slot's
+    // K timesteps (ADVICE r05: the next push used to write one timestep behind the pinned buffer and launch
+    // K + 1 of them).  This timestep then goes to the next lane, not behind it on the same one.
+    if (s->lanes[s->cur]->fill_n >= s->lanes[s->cur]->K && flush(s)) return 1;
+    StreamLane *lane = s->lanes[s->cur].get();
+    DeviceGuard guard(lane->e->device);
+    if (const int rc = fill(lane, feed, what, [&](double *dst) { write(lane, dst); })) return rc;
+    s->feed = feed;
+    return lane->fill_n < lane->K ? 0 : send(s);
+}
+
+// ... of the kinds whose step is one array: a plain copy of the bytes a step of that kind has
+int push_array(qm_stream *s, const void *step, int feed) {
+    if (!step || !s) return fail("%s: NULL argument", kFeedTable[feed].push);
+    return push_step(s, feed, [&](const StreamLane *lane, double *dst) { host_copy(dst, step, lane->step_bytes[feed]); });
 }
 
 // One lane per engine, on tables the caller has found equal; `what` is the entry point's name.
@@ -425,8 +465,6 @@ int create(qm_engine *const *engines, int n_engines, const char *what, int32_t t
         lane->n_nodes_total = n_nodes_total > 0 ? n_nodes_total : e->n_nodes;
         // (the copy stream is taken at the first launch that copies: slots that are pulled never need one)
         lane->slots.resize((size_t)depth);
-        lane->step_words[kLogOnsets] = (size_t)lane->n_rows * lane->T;
-        lane->step_bytes[kLogOnsets] = lane->step_words[kLogOnsets] * sizeof(double);
         const size_t out_bytes = 3 * (size_t)lane->K * ns * sizeof(double);
         for (StreamLane::Slot &sl : lane->slots) {
             hipError_t err = sl.h_out.alloc(out_bytes / sizeof(double), hipHostMallocDefault);
@@ -436,7 +474,8 @@ int create(qm_engine *const *engines, int n_engines, const char *what, int32_t t
                 return fail("%s: %s (%d steps of %zu bytes of results per slot, %d slots)", what,
                             hipGetErrorString(err), lane->K, out_bytes / lane->K, depth);
         }
-        if (alloc_inputs(lane, kLogOnsets, what)) return 1;
+        const size_t words = (size_t)lane->n_rows * lane->T;
+        if (alloc_inputs(lane, kLogOnsets, words, words * sizeof(double), what)) return 1;
         e->streams.push_back(lane);
     }
     *out = s.release();
@@ -508,63 +547,17 @@ void qm_stream_destroy(qm_stream *s) {
     delete s;
 }
 
-// a timestep into the lane being filled: log-onsets, (an onset stage) signals or (a resampling stage as well) raw
-// samples -- one kind per stream
-static int push_step(qm_stream *s, const void *step, int feed, const char *what, const SegmentStep *seg = nullptr) {
-    if (!step || !s) return fail("%s: NULL argument", what);
-    if (alive(s, what)) return 1;
-    if (feed == kSignals && !s->staged)
-        return fail("qm_stream_push_signals: the stream has no onset stage (qm_stream_set_onset_stage)");
-    if (feed == kRaw && !s->resampled)
-        return fail("qm_stream_push_raw: the stream has no resampling stage (qm_stream_set_resample_stage)");
-    if (feed == kSignals && s->resampled)
-        return fail("qm_stream_push_signals: this stream takes raw traces (qm_stream_push_raw): one stream, one kind of "
-                    "input");
-    if (feed == kSignals && s->segmented)
-        return fail("qm_stream_push_signals: this stream takes gappy traces (qm_stream_push_segments): one stream, one "
-                    "kind of input");
-    if (s->feed != kNothingYet && s->feed != feed)
-        return fail("%s: this stream takes %s: one stream, one kind of input", what,
-                    s->feed == kRaw        ? "raw traces (qm_stream_push_raw)"
-                    : s->feed == kSegments ? "gappy traces (qm_stream_push_segments)"
-                    : s->feed == kSignals  ? "signals (qm_stream_push_signals)"
-                                           : "log-onsets (qm_stream_push)");
-    // A full slot whose launch FAILED (the table changed under the stream, no memory, a refused step) is still
-    // waiting to go out: it goes first, or this call fails as that one did -- never a copy past the slot's
-    // K timesteps (ADVICE r05: the next push used to write one timestep behind the pinned buffer and launch
-    // K + 1 of them).  This timestep then goes to the next lane, not behind it on the same one.
-    if (s->lanes[s->cur]->fill_n >= s->lanes[s->cur]->K && flush(s)) return 1;
-    StreamLane *lane = s->lanes[s->cur].get();
-    DeviceGuard guard(lane->e->device);
-    if (const int rc = fill(lane, step, feed, what, seg)) return rc;
-    s->feed = feed;
-    return lane->fill_n < lane->K ? 0 : send(s);
-}
-
-int qm_stream_push(qm_stream *s, const double *log_onsets) {
-    return push_step(s, log_onsets, kLogOnsets, "qm_stream_push");
-}
-
-int qm_stream_push_signals(qm_stream *s, const double *signals) {
-    return push_step(s, signals, kSignals, "qm_stream_push_signals");
-}
-
-int qm_stream_push_raw(qm_stream *s, const void *raw) {
-    return push_step(s, raw, kRaw, "qm_stream_push_raw");
-}
+int qm_stream_push(qm_stream *s, const double *log_onsets) { return push_array(s, log_onsets, kLogOnsets); }
+int qm_stream_push_signals(qm_stream *s, const double *signals) { return push_array(s, signals, kSignals); }
+int qm_stream_push_raw(qm_stream *s, const void *raw) { return push_array(s, raw, kRaw); }
 
 int qm_stream_set_resample_stage(qm_stream *s, int32_t n_traces, const int64_t *records, const double *sos_lp,
                                  int32_t n_lowpass, int32_t n_sections_lp, int detrend, const int32_t *taper_table,
                                  int32_t n_tapers, const double *taper_weights, int64_t n_taper_weights,
                                  int32_t t_samples, int raw_dtype, int64_t total_raw_samples) {
-    const char *what = "qm_stream_set_resample_stage";
+    const char *what = kFeedTable[kRaw].set;
     if (!s) return fail("%s: NULL argument", what);
-    if (!s->staged) return fail("%s: the stream has no onset stage (qm_stream_set_onset_stage comes first)", what);
-    if (s->resampled) return fail("%s: the stream has its resampling stage already (it is set once)", what);
-    if (s->segmented)
-        return fail("%s: this stream takes gappy traces (qm_stream_set_segment_feed): one stream, one kind of input", what);
-    if (pushed_to(s)) return fail("%s: the stage is set before the first push", what);
-    if (alive(s, what)) return 1;
+    if (may_set(s, kRaw, what)) return 1;
     const StreamLane *lead = s->lanes[0].get();
     if (t_samples != lead->T || n_traces != lead->pre.n_traces)
         return fail("%s: %d traces of %d samples, the onset stage takes %d of %d", what, n_traces, t_samples,
@@ -573,13 +566,10 @@ int qm_stream_set_resample_stage(qm_stream *s, int32_t n_traces, const int64_t *
         (double)lead->K * (double)ResampleStage::step_doubles(raw_dtype, total_raw_samples) * 8.0 >= 0x1p40)
         return fail("%s: too many raw samples per launch", what);
     return stage_every_lane(s, kRaw, [&](StreamLane *lane) {
-        if (lane->rs.build(lane->e, what, lane->K, raw_dtype, total_raw_samples, n_traces, t_samples, records, sos_lp,
-                           n_lowpass, n_sections_lp, detrend, taper_table, n_tapers, taper_weights, n_taper_weights))
-            return 1;
         // (the signals' pinned buffers are given up at the first qm_stream_push_raw: until then nothing is lost)
-        lane->step_words[kRaw] = lane->rs.raw_step;
-        lane->step_bytes[kRaw] = lane->rs.raw_bytes;
-        return alloc_inputs(lane, kRaw, what);
+        return lane->rs.build(lane->e, what, lane->K, raw_dtype, total_raw_samples, n_traces, t_samples, records, sos_lp,
+                              n_lowpass, n_sections_lp, detrend, taper_table, n_tapers, taper_weights, n_taper_weights) ||
+               alloc_inputs(lane, kRaw, lane->rs.step_words(), lane->rs.step_bytes(), what);
     });
 }
 
@@ -588,73 +578,56 @@ int qm_stream_set_onset_stage(qm_stream *s, int32_t n_traces, const int32_t *tra
                               const double *taper_left, int32_t n_left, const double *taper_right, int32_t n_right,
                               const int32_t *nsta, const int32_t *nlta, int transform, int position,
                               int32_t taper_pad, double min_onset_value) {
-    const char *what = "qm_stream_set_onset_stage";
+    const char *what = kFeedTable[kSignals].set;
     if (!s) return fail("%s: NULL argument", what);
-    if (s->staged) return fail("%s: the stream has its onset stage already (it is set once)", what);
-    if (pushed_to(s)) return fail("%s: the stage is set before the first push", what);
-    if (alive(s, what)) return 1;
+    if (may_set(s, kSignals, what)) return 1;
     const StreamLane *lead = s->lanes[0].get();
     if ((int64_t)lead->K * n_traces * lead->T >= INT32_MAX || (int64_t)lead->K * lead->n_rows * lead->T >= INT32_MAX)
         return fail("%s: too many samples per launch", what);
     return stage_every_lane(s, kSignals, [&](StreamLane *lane) {
-        if (lane->pre.build(lane->e, what, lane->K, n_traces, lane->T, trace_filter, sos, n_filters, n_sections, detrend,
-                            taper_left, n_left, taper_right, n_right, /*zero_phase=*/1) ||
-            lane->on.build(lane->e, what, lane->K, n_traces, lane->T, trace_row, lane->n_rows, nsta, nlta, transform,
-                           position, taper_pad, min_onset_value))
-            return 1;
-        lane->step_words[kSignals] = (size_t)n_traces * lane->T;
-        lane->step_bytes[kSignals] = lane->step_words[kSignals] * sizeof(double);
-        return alloc_inputs(lane, kSignals, what);
+        const size_t words = (size_t)n_traces * lane->T;
+        return lane->pre.build(lane->e, what, lane->K, n_traces, lane->T, trace_filter, sos, n_filters, n_sections,
+                               detrend, taper_left, n_left, taper_right, n_right, /*zero_phase=*/1) ||
+               lane->on.build(lane->e, what, lane->K, n_traces, lane->T, trace_row, lane->n_rows, nsta, nlta, transform,
+                              position, taper_pad, min_onset_value) ||
+               alloc_inputs(lane, kSignals, words, words * sizeof(double), what);
     });
 }
 
 int qm_stream_set_segment_feed(qm_stream *s, int32_t max_segments, int64_t max_taper_weights, int second_taper,
                                double fill_value) {
-    const char *what = "qm_stream_set_segment_feed";
+    const char *what = kFeedTable[kSegments].set;
     if (!s) return fail("%s: NULL argument", what);
-    if (!s->staged) return fail("%s: the stream has no onset stage (qm_stream_set_onset_stage comes first)", what);
-    if (s->segmented) return fail("%s: the stream has its segment feed already (it is set once)", what);
-    if (s->resampled)
-        return fail("%s: this stream takes raw traces (qm_stream_set_resample_stage): one stream, one kind of input", what);
-    if (pushed_to(s)) return fail("%s: the feed is set before the first push", what);
-    if (alive(s, what)) return 1;
+    if (may_set(s, kSegments, what)) return 1;
     if (max_segments < 1) return fail("%s: max_segments must be at least 1 (got %d)", what, max_segments);
     if (max_taper_weights < 0)
         return fail("%s: max_taper_weights must be at least 0 (got %lld)", what, (long long)max_taper_weights);
     if (!std::isfinite(fill_value)) return fail("%s: fill_value %g is not finite", what, fill_value);
-    const StreamLane *lead = s->lanes[0].get();
-    const double words = (double)lead->pre.n_traces * lead->T + 8.0 * max_segments + (double)max_taper_weights;
-    if ((double)lead->K * words * 8.0 >= 0x1p40 || (int64_t)lead->K * max_segments >= INT32_MAX)
-        return fail("%s: too many segments or taper weights per launch", what);
     return stage_every_lane(s, kSegments, [&](StreamLane *lane) {
-        lane->seg.adopt(lane->pre, max_segments, second_taper, fill_value);
-        lane->seg_sig = (size_t)lane->pre.n_traces * lane->T;
-        lane->seg_max = max_segments;
-        lane->seg_w_max = max_taper_weights;
-        lane->step_words[kSegments] = lane->seg_sig + (size_t)max_segments * qm::kSegmentFields + (size_t)max_taper_weights;
-        lane->step_bytes[kSegments] = lane->step_words[kSegments] * sizeof(double);
-        return alloc_inputs(lane, kSegments, what);
+        return lane->seg.adopt(what, lane->K, lane->pre, max_segments, max_taper_weights, second_taper, fill_value) ||
+               alloc_inputs(lane, kSegments, lane->seg.step_words(), lane->seg.step_bytes(), what);
     });
 }
 
 int qm_stream_push_segments(qm_stream *s, const double *signals, const int64_t *records, int32_t n_segments,
                             const double *taper_weights, int64_t n_taper_weights) {
-    const char *what = "qm_stream_push_segments";
+    const char *what = kFeedTable[kSegments].push;
     if (!s || !signals || !records) return fail("%s: NULL argument", what);
-    if (!s->segmented) return fail("%s: the stream has no segment feed (qm_stream_set_segment_feed)", what);
-    if (alive(s, what)) return 1;
+    if (has_stage(s, kSegments, what) || alive(s, what)) return 1;
     // the records, on the caller's thread: the kernel takes them as they are
     const StreamLane *lead = s->lanes[0].get();
     if (n_taper_weights < 0 || (n_taper_weights > 0 && !taper_weights))
         return fail("%s: %lld taper weights without their array", what, (long long)n_taper_weights);
-    if (n_segments > lead->seg_max)
-        return fail("%s: %d segments, the feed was set for up to %d (max_segments)", what, n_segments, lead->seg_max);
-    if (n_taper_weights > lead->seg_w_max)
+    if (n_segments > lead->seg.max_segments)
+        return fail("%s: %d segments, the feed was set for up to %d (max_segments)", what, n_segments,
+                    lead->seg.max_segments);
+    if (n_taper_weights > lead->seg.max_weights)
         return fail("%s: %lld taper weights, the feed was set for up to %lld (max_taper_weights)", what,
-                    (long long)n_taper_weights, (long long)lead->seg_w_max);
+                    (long long)n_taper_weights, (long long)lead->seg.max_weights);
     if (check_segment_records(what, lead->pre.n_traces, lead->T, records, n_segments, n_taper_weights)) return 1;
-    const SegmentStep seg{records, n_segments, taper_weights, n_taper_weights};
-    return push_step(s, signals, kSegments, what, &seg);
+    return push_step(s, kSegments, [&](const StreamLane *lane, double *dst) {
+        lane->seg.pack(dst, signals, records, n_segments, taper_weights, n_taper_weights);
+    });
 }
 
 int qm_stream_flush(qm_stream *s) {

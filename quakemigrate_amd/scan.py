@@ -415,7 +415,7 @@ class MigrationScan:
                     signals, stage, onset_data = staged
                     onsets = None
                 else:
-                    stage = None
+                    stage = signals = None
                     onsets, onset_data = self.onset.calculate_onsets(data)
             except Exception as e:  # noqa: BLE001
                 if not _is_no_data(e):
@@ -468,11 +468,8 @@ class MigrationScan:
                                                                   and stage.fill_gaps else None))
                 state["key"] = key
             stream = state["stream"]
-            push, window = (stream.push, onsets) if stage is None else (stream.push_signals, signals)
-            if stage is not None and stage.fill_gaps:
-                gappy = (signals, segments)
-                push, window = (lambda pair: stream.push_segments(*pair)), gappy
-            while not push(window):
+            item = {"log_onsets": onsets, "signals": signals, "segments": (signals, segments)}[stream.feed]
+            while not stream.push_step(item):
                 emit(min(stream.k, stream.pending()[0]))
             pending.append((_shift(data.starttime, self.pre_pad), onset_data))
             rows.append(dict(onset_data.availability))

@@ -92,6 +92,7 @@ class StreamingDetector:
         import weakref
 
         self._finalizer = weakref.finalize(self, _qm.qm_stream_destroy, h)
+        self.feed = "log_onsets"            # the kind of timestep the stages call for: each set_* call names its own
         self.n_traces = None
         self.raw_dtype = self._raw_records = self.total_raw_samples = None
         self.max_segments = self.max_taper_weights = None
@@ -130,7 +131,7 @@ class StreamingDetector:
             self._h, len(trace_row), trace_row, trace_filter, sos.reshape(-1), int(sos.shape[0]), int(sos.shape[1]),
             int(a.get("detrend", 1)), left, len(left), right, len(right), nsta, nlta, int(a["transform"]),
             int(a["position"]), int(a["taper_pad"]), float(a["min_onset_value"])))
-        self.n_traces = len(trace_row)
+        self.n_traces, self.feed = len(trace_row), "signals"
         if "fill_value" in a or "second_taper" in a:
             from quakemigrate_amd.preprocess import GAP_FILL_VALUE
 
@@ -151,7 +152,7 @@ class StreamingDetector:
         _lib._check(_qm.qm_stream_set_segment_feed(
             self._h, int(max_segments), int(max_taper_weights), int(second_taper),
             GAP_FILL_VALUE if fill_value is None else float(fill_value)))
-        self.max_segments, self.max_taper_weights = int(max_segments), int(max_taper_weights)
+        self.max_segments, self.max_taper_weights, self.feed = int(max_segments), int(max_taper_weights), "segments"
 
     def set_resample_stage(self, resample_stage, raw_dtype=np.int32):
         """Once, after the onset stage and before the first push (``qm_stream_set_resample_stage``)."""
@@ -162,23 +163,34 @@ class StreamingDetector:
         _lib._check(_qm.qm_stream_set_resample_stage(
             self._h, len(records), records.reshape(-1), sos.reshape(-1), int(sos.shape[0]), int(sos.shape[1]), detrend,
             table.reshape(-1), len(table), weights, len(weights), t_samples, _lib.RAW_DTYPES[kind], total))
-        self.raw_dtype, self._raw_records, self.total_raw_samples = kind, records, total
+        self.raw_dtype, self._raw_records, self.total_raw_samples, self.feed = kind, records, total, "raw"
 
     def close(self):
         self._finalizer()
 
     # -- the three calls --------------------------------------------------------------
+    @staticmethod
+    def _pushed(rc):
+        """A push's return code: False for 2 (every slot holds un-popped results), the library's error otherwise."""
+        if rc == 2:
+            return False
+        _lib._check(rc)
+        return True
+
+    def push_step(self, item):
+        """One timestep of the kind the stream's stages call for (``feed``), as :meth:`run` documents it per kind;
+        returns like :meth:`push`."""
+        if self.feed == "segments":
+            return self.push_segments(*item)
+        return {"log_onsets": self.push, "signals": self.push_signals, "raw": self.push_raw}[self.feed](item)
+
     def push(self, window):
         """One timestep's log-onsets (n_rows, t_samples) into the pipeline.  False: every slot holds
         results that have not been popped (``pop`` first, then push again)."""
         w = np.ascontiguousarray(window, dtype=np.float64)
         if w.shape != (self.n_rows, self.t_samples):
             raise ValueError(f"window of shape {w.shape}, the stream takes {(self.n_rows, self.t_samples)}")
-        rc = _qm.qm_stream_push(self._h, w.ctypes.data_as(ctypes.c_void_p))
-        if rc == 2:
-            return False
-        _lib._check(rc)
-        return True
+        return self._pushed(_qm.qm_stream_push(self._h, w.ctypes.data_as(ctypes.c_void_p)))
 
     def push_signals(self, window):
         """One timestep's resampled component traces (n_traces, t_samples) into a pipeline with an onset stage;
@@ -186,11 +198,7 @@ class StreamingDetector:
         w = np.ascontiguousarray(window, dtype=np.float64)
         if self.n_traces is not None and w.shape != (self.n_traces, self.t_samples):
             raise ValueError(f"window of shape {w.shape}, the stage takes {(self.n_traces, self.t_samples)}")
-        rc = _qm.qm_stream_push_signals(self._h, w.ctypes.data_as(ctypes.c_void_p))
-        if rc == 2:
-            return False
-        _lib._check(rc)
-        return True
+        return self._pushed(_qm.qm_stream_push_signals(self._h, w.ctypes.data_as(ctypes.c_void_p)))
 
     def push_raw(self, raw):
         """One timestep's raw traces -- a list of 1-D arrays, one per trace, or the packed array, of the stage's
@@ -199,11 +207,7 @@ class StreamingDetector:
             raise _lib.QMHipError("qm_stream_push_raw: the stream has no resampling stage "
                                   "(qm_stream_set_resample_stage)")
         w = _lib.pack_raw(raw, self._raw_records, self.total_raw_samples, self.raw_dtype)
-        rc = _qm.qm_stream_push_raw(self._h, w.ctypes.data_as(ctypes.c_void_p))
-        if rc == 2:
-            return False
-        _lib._check(rc)
-        return True
+        return self._pushed(_qm.qm_stream_push_raw(self._h, w.ctypes.data_as(ctypes.c_void_p)))
 
     def push_segments(self, window, segments, taper_weights=None):
         """One timestep's gappy component traces (n_traces, t_samples) in window layout with their layout into a
@@ -218,12 +222,8 @@ class StreamingDetector:
 
             segments, taper_weights = plan_segments(self.t_samples, w.shape[0], segments, self.taper_percentage)
         records, weights = _lib.segment_arrays(segments, taper_weights)
-        rc = _qm.qm_stream_push_segments(self._h, w.ctypes.data_as(ctypes.c_void_p), records.reshape(-1), len(records),
-                                         weights, len(weights))
-        if rc == 2:
-            return False
-        _lib._check(rc)
-        return True
+        return self._pushed(_qm.qm_stream_push_segments(self._h, w.ctypes.data_as(ctypes.c_void_p), records.reshape(-1),
+                                                        len(records), weights, len(weights)))
 
     def flush(self):
         _lib._check(_qm.qm_stream_flush(self._h))
@@ -247,11 +247,16 @@ class StreamingDetector:
     # -- the loop -----------------------------------------------------------------------
     def run(self, windows, on_result=None):
         """
-        ``windows``: iterable of float64 arrays, one per timestep: (n_rows, t_samples), already logged --
-        or, on a stream with an onset stage, (n_traces, t_samples) resampled component traces -- or, with a
-        resampling stage as well, the timestep's raw traces as :meth:`push_raw` takes them -- or, on a stream with the
-        segment feed, ``(traces, segments)`` pairs as :meth:`push_segments` takes them.  Returns a list of ``(max_coa, max_norm_coa, max_coa_idx)`` NumPy triples (or
-        calls ``on_result(step, triple)`` and returns the number of steps).
+        ``windows``: iterable with one item per timestep, of the stream's kind (``feed``):
+
+        ``"log_onsets"``  a float64 array (n_rows, t_samples), already logged
+        ``"signals"``     (an onset stage) a float64 array (n_traces, t_samples) of resampled component traces
+        ``"raw"``         (a resampling stage as well) the timestep's raw traces as :meth:`push_raw` takes them
+        ``"segments"``    (the segment feed) a ``(traces, segments)`` pair -- or ``(traces, records, taper_weights)`` --
+                          as :meth:`push_segments` takes them
+
+        Returns a list of ``(max_coa, max_norm_coa, max_coa_idx)`` NumPy triples (or calls ``on_result(step, triple)``
+        and returns the number of steps).
         """
         results = []
         step = 0
@@ -267,13 +272,8 @@ class StreamingDetector:
                     on_result(step, triple)
                 step += 1
 
-        push = self.push if self.n_traces is None else self.push_signals
-        if self._raw_records is not None:
-            push = self.push_raw
-        if self.max_segments is not None:
-            push = lambda pair: self.push_segments(*pair)     # noqa: E731
         for w in windows:
-            while not push(w):
+            while not self.push_step(w):
                 take(min(self.k, self.pending()[0]))     # the oldest launch's timesteps
         self.flush()
         left = self.pending()[0]

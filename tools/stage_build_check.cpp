@@ -1,6 +1,7 @@
 // stage_build_check.cpp -- the three front-end stage records' build() on the CPU, under the sanitizers: their
 // refusals and the images they put on the "device" for repeat = 1 and 3; then the two checks the trace stages share
-// (check_sections, check_taper_table: qm_engine.hpp), every refusal with its whole message.  A stand-alone host program: the runtime's
+// (check_sections, check_taper_table: qm_engine.hpp), every refusal with its whole message; then the step a stream's
+// segment feed holds -- SegmentStage::adopt, step_words and pack into a malloc of exactly that size.  A stand-alone host program: the runtime's
 // pool and copies are replaced below by malloc and memcpy, so no device is needed and every image lands in an
 // allocation of exactly the size build() asked for (an overrun is an AddressSanitizer report).  No kernel is launched.
 // The records own their device arrays: once they and the engine are gone, no block of the pool is out.
@@ -46,6 +47,7 @@ hipError_t copy_back(void *dst, const void *src, size_t bytes, hipStream_t) {
     std::memcpy(dst, src, bytes);
     return hipSuccess;
 }
+void host_copy(void *dst, const void *src, size_t n) { std::memcpy(dst, src, n); }
 PoolReleaseScope::PoolReleaseScope() {}
 PoolReleaseScope::~PoolReleaseScope() {}
 
@@ -194,6 +196,43 @@ static void stages() {
     CHECK(refused_with(check_taper_table("rs", negative + 2, 1, 20), "rs: taper 0: 2 x -3 weights from 0 on, 20 weights given"));
     CHECK(check_taper_table("rs", nullptr, 0, 0) == 0);
     std::printf("shared checks: 7 refusals, whole messages\n");
+
+    // -- the segment feed's step: adopt() from the pre-processing stage built above, pack() into exactly step_words()
+    //    words pre-filled with a marker -- an overrun is a sanitizer report
+    const size_t sig = (size_t)n_traces * T;
+    std::vector<double> signals(sig), w_in(6);
+    for (size_t i = 0; i < sig; ++i) signals[i] = 1.0 + (double)i;
+    for (size_t i = 0; i < w_in.size(); ++i) w_in[i] = 0.125 * (double)(i + 1);
+    const int max_seg = 3;
+    int64_t seg_rec[max_seg * kSegmentFields];
+    for (int i = 0; i < max_seg * kSegmentFields; ++i) seg_rec[i] = 100 + i;
+    double marker;
+    std::memset(&marker, 0xA5, sizeof(marker));
+    auto same_bits = [](double a, double b) { return std::memcmp(&a, &b, sizeof(a)) == 0; };
+    SegmentStage seg;
+    REFUSED(seg.adopt("seg", 3, pre, max_seg, (int64_t)1 << 40, 1, 0.5), "too many segments or taper weights per launch");
+    REFUSED(seg.adopt("seg", 2, pre, INT32_MAX / 2 + 1, 0, 1, 0.5), "too many segments or taper weights per launch");
+    // (a) every record and every weight; (b) one segment, no weights; (c) as (b), a feed without room for weights
+    struct { int64_t max_w; int32_t n_seg; int64_t n_w; } const cases[3] = {{6, max_seg, 6}, {6, 1, 0}, {0, 1, 0}};
+    for (const auto &c : cases) {
+        CHECK(seg.adopt("seg", 3, pre, max_seg, c.max_w, 1, 0.5) == 0);
+        CHECK(seg.sig_words == sig && seg.max_segments == max_seg && seg.max_weights == c.max_w);
+        CHECK(seg.step_words() == sig + (size_t)max_seg * kSegmentFields + (size_t)c.max_w);
+        CHECK(seg.step_bytes() == seg.step_words() * 8 && seg.args.n_records == max_seg && seg.args.T == T);
+        CHECK(seg.args.trace_filter == pre.args.trace_filter && seg.args.sos == pre.args.sos && seg.n_traces == n_traces);
+        double *dst = static_cast<double *>(std::malloc(seg.step_words() * 8));
+        CHECK(dst != nullptr);
+        for (size_t i = 0; i < seg.step_words(); ++i) dst[i] = marker;
+        seg.pack(dst, signals.data(), seg_rec, c.n_seg, c.n_w > 0 ? w_in.data() : nullptr, c.n_w);
+        CHECK(std::equal(signals.begin(), signals.end(), dst));
+        int64_t got[max_seg * kSegmentFields];
+        std::memcpy(got, dst + sig, sizeof(got));
+        for (int i = 0; i < max_seg * kSegmentFields; ++i) CHECK(got[i] == (i < c.n_seg * kSegmentFields ? seg_rec[i] : 0));
+        const double *w_out = dst + sig + max_seg * kSegmentFields;
+        for (int64_t i = 0; i < c.max_w; ++i) CHECK(same_bits(w_out[i], i < c.n_w ? w_in[(size_t)i] : marker));
+        std::free(dst);
+    }
+    std::printf("segment feed: 2 refusals, adopt, step_words and pack for 3 + 6, 1 + 0 of 6, 1 + 0 of 0\n");
 
     CHECK(g_blocks_out > 0);
 }
