@@ -8,7 +8,8 @@ The STEIM2 packer of ``quakemigrate_amd/scanmseed.py`` restated on arrays, as th
   1x30 bits whose count is <= ``n - p`` (the end of the TRACE) and whose differences all fit.
 - The words of a trace are the chain ``p -> p + count(p)`` from 0, cut into records every 943 words.
 
-Also the series the codec's tests are run on (``designed_series``, ``switching_walk``).
+Also the series the codec's tests are run on (``designed_series``, ``switching_walk``, ``folded_switching_walk`` for
+lengths beyond a Python loop's).
 """
 
 import numpy as np
@@ -56,10 +57,10 @@ def counts(cls):
 
 def chain(count):
     """The word starts: p -> p + count(p) from 0."""
-    starts, p, n = [], 0, len(count)
+    step, starts, p, n = count.tolist(), [], 0, len(count)     # (a list: the loop below runs millions of times)
     while p < n:
         starts.append(p)
-        p += int(count[p])
+        p += step[p]
     assert p == n
     return np.array(starts, dtype=np.int64)
 
@@ -78,16 +79,22 @@ def pack_words(d, starts, count):
     return words.astype(np.uint32), codes.astype(np.uint32)
 
 
-def encode_trace(x):
+def trace_chain(x):
+    """``(d, count, starts)`` of one trace: its differences, count(p) of every position, the word starts."""
+    d = differences(np.asarray(x, dtype=np.int32))
+    count = counts(width_class(d))
+    return d, count, chain(count)
+
+
+def encode_trace(x, parts=None):
     """
     ``(records, rec_first, rec_count)`` of one trace: records uint8 (n_records, 4096) with the 64 header bytes zero and
-    the payload complete, every record's first sample index and sample count.
+    the payload complete, every record's first sample index and sample count.  ``parts``: ``trace_chain(x)``, where
+    the caller has walked the chain already.
     """
     x = np.asarray(x, dtype=np.int32)
     n = len(x)
-    d = differences(x)
-    count = counts(width_class(d))
-    starts = chain(count)
+    d, count, starts = trace_chain(x) if parts is None else parts
     words, codes = pack_words(d, starts, count)
     n_rec = -(-len(starts) // REC_WORDS)
     payload = np.zeros((n_rec, N_FRAMES * 16), dtype=np.uint32)
@@ -105,9 +112,9 @@ def encode_trace(x):
     return records, rec_first.astype(np.int32), rec_count.astype(np.int32)
 
 
-def encode_channels(series):
-    """Five channels (5, n) -> what ``Engine.scanmseed_encode`` returns."""
-    parts = [encode_trace(row) for row in series]
+def encode_channels(series, chains=None):
+    """Five channels (5, n) -> what ``Engine.scanmseed_encode`` returns.  ``chains``: the rows' ``trace_chain``."""
+    parts = [encode_trace(row, None if chains is None else chains[j]) for j, row in enumerate(series)]
     return {"n_records": np.array([len(p[0]) for p in parts], dtype=np.int64),
             "records": np.concatenate([p[0] for p in parts]),
             "rec_first": np.concatenate([p[1] for p in parts]),
@@ -166,6 +173,24 @@ def switching_walk(rng, n, classes=(0, 1, 2, 3, 4, 5), max_run=40):
             d[i] = step = -step - (1 if step < 0 else 0)
         x += step
     return from_differences(d)
+
+
+def folded_switching_walk(rng, n, classes=(0, 1, 2, 3, 4, 5), max_run=40, bound=1 << 30):
+    """
+    ``switching_walk`` for series of millions of samples, without its Python loop: differences drawn from ``[-hi, hi]``
+    of a width class that switches in runs of random length, their 64-bit running sum folded into ``[-bound, bound]``
+    by reflection at both ends (a triangle wave of period ``4 bound``).  Between two reflections the series' differences
+    are the drawn ones up to one sign, which keeps their class; the step across a reflection is shorter than the drawn
+    one.
+    """
+    n_runs = 4 * n // (max_run + 1) + 64
+    runs = rng.integers(1, max_run + 1, size=n_runs)
+    assert int(runs.sum()) >= n - 1
+    hi = np.array([b[1] for b in CLASS_BOUNDS], dtype=np.int64)[rng.choice(classes, size=n_runs)]
+    hi = np.repeat(hi, runs)[:n - 1]
+    walk = np.concatenate([[0], np.cumsum(rng.integers(-hi, hi + 1))])
+    m = np.mod(walk + bound, 4 * bound)
+    return np.where(m < 2 * bound, m - bound, 3 * bound - m).astype(np.int32)
 
 
 def designed_series():

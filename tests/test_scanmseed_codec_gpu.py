@@ -318,3 +318,238 @@ def test_trigger_on_the_device_resident_read_gives_the_same_events(engine, sm, t
     assert np.array_equal(bits(t.last["events_f"]), bits(host_last["events_f"]))
     recorded = trigger.read_triggered_events(GOLDEN / b["csv"])
     assert [e["EventID"] for e in resident] == [e["EventID"] for e in recorded]
+
+
+# -- 10: past one trip of the compose and quantise loops ----------------------------------------------------------------
+# sms_compose_kernel carries the chain's state (entry offset, word index) from one chunk of "scanmseed_compose_chunk"
+# tiles to the next; sms_quantise_kernel strides a grid of at most QUANT_GRID threads per channel over the samples.  The
+# series below are (chunk + 3) tiles + 11 samples long: two trips of the compose loop, three of the quantiser's.  Every
+# test asserts on the restatement alone, before the device is asked, what makes it able to fail.
+QUANT_GRID = 4096 * 256                                         # (qm_scanmseed.hip: the quantise launch's cap)
+MIXED = [300, -300, 20, -20, 100, -100, 16000, -16000, 5] * 2
+
+
+def long_shape(engine):
+    tile, chunk = engine.get("scanmseed_tile"), engine.get("scanmseed_compose_chunk")
+    return tile, chunk, (chunk + 3) * tile + 11
+
+
+def encode_equals(engine, stacked, want):
+    """One encode call (a NumPy array or a device tensor) against the restatement's dict; returns the engine's."""
+    got = engine.scanmseed_encode(stacked)
+    assert np.array_equal(got["n_records"], want["n_records"])
+    assert got["records"].shape == want["records"].shape
+    assert np.array_equal(got["records"], want["records"]), np.argwhere(got["records"] != want["records"])[:8]
+    assert np.array_equal(got["rec_first"], want["rec_first"]) and np.array_equal(got["rec_count"], want["rec_count"])
+    return got
+
+
+def decodes_back(engine, out, stacked):
+    counts = out["rec_count"].astype(np.int64)
+    offsets = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    ints, none = engine.scanmseed_decode(out["records"], out["rec_count"], offsets, int(counts.sum()))
+    assert none is None and np.array_equal(ints, stacked.ravel())
+
+
+def restated(rows, edge):
+    """The rows' chains walked once: (encode_channels' dict, per row (entry offset into the tile at `edge`, word index
+    there), the counts of the words from there on)."""
+    chains = [ref.trace_chain(x) for x in rows]
+    at = [int(np.searchsorted(starts, edge)) for _, _, starts in chains]
+    state = [(int(starts[k] - edge), k) for (_, _, starts), k in zip(chains, at)]
+    late = sum(np.bincount(count[starts[k:]], minlength=8) for (_, count, starts), k in zip(chains, at))
+    return ref.encode_channels(rows, chains), state, late
+
+
+@pytest.fixture(scope="module")
+def long_chains(engine):
+    """
+    C1's two calls, built and restated once: [(stacked (5, n) int32, encode_channels' dict, [(entry, word)] * 5)].
+    Words of seven 4-bit differences behind `lead` one-difference words, as in the tile-edge test above: the chain
+    enters tile `chunk` at offset lead % 7 (6 for no lead).  A run of other widths takes at most three differences a
+    word and gathers every chain that reaches it into three alignments, so where it lies ACROSS position chunk x tile
+    the tile is entered at 0, 1 or 2 whatever the lead.  Hence: the run lies across (chunk + 1) x tile in every channel,
+    across chunk x tile in the second call's last two (leads 8 and 9, whose offsets 1 and 2 the first call has), and
+    eight positions behind chunk x tile in the others, whose seven-difference words straddle that position.
+    """
+    tile, chunk, n = long_shape(engine)
+    wide = (1 << 29) - 1
+    calls = []
+    for shifts in (range(0, 5), range(5, 10)):
+        rows = []
+        for lead in shifts:
+            d = np.where(np.arange(n - 1) % 2 == 0, 7, -8)
+            d[:lead] = np.where(np.arange(lead) % 2 == 0, wide, -wide)
+            at = chunk * tile - 9 if lead >= 8 else chunk * tile + 8
+            d[at:at + len(MIXED)] = MIXED
+            d[(chunk + 1) * tile - 9:(chunk + 1) * tile + 9] = MIXED
+            rows.append(ref.from_differences(d))
+        if shifts[0] == 5:                                      # one word per sample: 943 samples per record
+            rows[2] = ref.from_differences(np.where(np.arange(n - 1) % 2 == 0, wide, -wide), first=-(1 << 28))
+        stacked = np.ascontiguousarray(np.stack(rows))
+        want, state, _ = restated(stacked, chunk * tile)
+        calls.append((stacked, want, state))
+    return calls
+
+
+def test_long_chain_carries_entry_offset_and_word_index_across_a_compose_chunk(engine, long_chains):
+    tile, chunk, n = long_shape(engine)
+    assert n > chunk * tile + 2 * tile                          # tiles chunk .. chunk + 3 belong to the second trip
+    state = [s for _, _, states in long_chains for s in states]
+    print("entry offsets, word indices at tile", chunk, ":", state)
+    assert {e for e, _ in state} == set(range(7))               # a dropped `e` (0 again) shows in six of them
+    assert min(w for _, w in state) > 65_535                    # ... a dropped or 16-bit `w` in every channel
+    assert sum(e != 0 for e, _ in state) >= 4                   # words that straddle position chunk x tile
+    wide_records = long_chains[1][1]["n_records"]
+    print("records per channel:", [c[1]["n_records"].tolist() for c in long_chains])
+    assert wide_records[2] == -(-n // ref.REC_WORDS) and wide_records[2] > 2000
+    for stacked, want, _ in long_chains:
+        decodes_back(engine, encode_equals(engine, stacked, want), stacked)
+
+
+CLASS_SETS = [(0, 1, 2), (0, 1, 2, 3, 4), (2, 3, 4, 5), (0, 1, 2, 3, 4, 5, 6), (0, 6)]
+
+
+@pytest.fixture(scope="module")
+def long_walks(engine):
+    """C2's series, built and restated once: (stacked (5, n) int32, encode_channels' dict, word histogram late)."""
+    tile, chunk, n = long_shape(engine)
+    rng = np.random.default_rng(2014)
+    rows = [ref.folded_switching_walk(rng, n, classes=cl, max_run=int(rng.integers(2, 60))) for cl in CLASS_SETS]
+    stacked = np.ascontiguousarray(np.stack(rows))
+    want, _, late = restated(stacked, chunk * tile)
+    return stacked, want, late
+
+
+def test_long_random_widths(engine, long_walks):
+    stacked, want, late = long_walks
+    print("words of 1..7 differences in tiles at or beyond the compose chunk:", late[1:].tolist())
+    assert late[0] == 0 and late[1:].min() > 0                  # all seven layouts behind the carried state
+    decodes_back(engine, encode_equals(engine, stacked, want), stacked)
+    import torch
+
+    encode_equals(engine, torch.from_numpy(stacked).to(f"cuda:{engine.device}"), want)
+
+
+def test_long_float_input_quantises_past_the_grid(engine, sm):
+    """test_float_flavour_quantises_like_numpy's 5000 samples, repeated over the whole length: the same ties, clips,
+    zeros and negative coordinates in the quantiser's second and third trip."""
+    _, _, n = long_shape(engine)
+    assert n > 2 * QUANT_GRID + 5000
+    ucf, m = 1000.0, 5000
+    rng = np.random.default_rng(8)
+    k = np.arange(m)
+    coa = (2 * (k % 400) + 1) / 64.0
+    coa[:2] = [0.0, -0.0]
+    coa_n = 1.0 + rng.uniform(0, 0.5, m)
+    coa[940:1000] = np.linspace(coa[939], 21473.9, 60)
+    coa[1000:1400] = np.linspace(21473.9, 21474.1, 400)
+    coa[1400:1408] = [21474.0, 21474.00001, 21474.5, 3e4, 1e9, np.inf, 21473.999995, 21473.99999]
+    coa[1408:1468] = np.linspace(21473.9, coa[1468], 60)
+    coa_n[1900:2000] = np.linspace(coa_n[1899], 21473.0, 100)
+    coa_n[2000:2003] = [21474.0, 5e4, 21473.999999]
+    coa_n[2003:2103] = np.linspace(21473.0, coa_n[2103], 100)
+    block = np.stack([coa, coa_n, ((2 * (k % 300) + 1) / 128.0) * np.where(k % 2, -1, 1),
+                      -64.5 + np.cumsum(rng.uniform(-1e-5, 1e-5, m)), (2 * (k % 50) + 1) / 128.0 - 0.25])
+    stacked = np.ascontiguousarray(np.tile(block, (1, -(-n // m)))[:, :n])
+    stacked[3] += np.repeat(np.arange(-(-n // m)) % 7, m)[:n] * 1e-3           # (the repeats differ on Y)
+    want = sm.quantise(stacked[0], stacked[1], stacked[2:].T, ucf)
+    at = np.arange(n)
+    scaled = np.minimum(stacked[0], sm.COA_CLIP) * 1e5
+    tie = scaled - np.floor(scaled) == 0.5
+    for trip in (1, 2):                                         # ties whose lower neighbour is odd, and is even
+        late = tie & (at >= trip * QUANT_GRID) & (at < (trip + 1) * QUANT_GRID)
+        up, down = int((late & (want["COA"] > scaled)).sum()), int((late & (want["COA"] < scaled)).sum())
+        print("COA ties in trip", trip, "of the quantiser's grid, rounded up / down:", up, down)
+        assert up > 100 and down > 100
+    scaled = stacked[2] * 1e6
+    tie = (scaled - np.floor(scaled) == 0.5) & (at >= QUANT_GRID)
+    below, above = int((tie & (scaled < 0)).sum()), int((tie & (scaled > 0)).sum())
+    print("X ties beyond the grid, negative / positive:", below, above)
+    assert below > 100 and above > 100
+    clipped = np.flatnonzero((stacked[0] > sm.COA_CLIP) & (want["COA"] == 2147400000))
+    print("clipped COA samples beyond", 2 * QUANT_GRID, ":", int((clipped > 2 * QUANT_GRID).sum()))
+    assert clipped.max() > 2 * QUANT_GRID and want["X"][2 * QUANT_GRID:].min() < 0 and want["Y"].min() < 0
+    expect = ref.encode_channels(np.stack([want[ch] for ch in sm.CHANNELS]))
+    factors = [sm.scale_factors(ucf)[ch] for ch in sm.CHANNELS]
+    clips = [sm.COA_CLIP, sm.COA_CLIP, None, None, None]
+    import torch
+
+    for series in (stacked, torch.from_numpy(stacked).to(f"cuda:{engine.device}")):
+        got = engine.scanmseed_encode(series, factors, clips)
+        assert np.array_equal(got["n_records"], expect["n_records"])
+        assert np.array_equal(got["records"], expect["records"])
+        assert np.array_equal(got["rec_first"], expect["rec_first"])
+        assert np.array_equal(got["rec_count"], expect["rec_count"])
+
+
+def test_long_refusals_name_late_positions(engine, lib, sm, long_chains):
+    tile, chunk, n = long_shape(engine)
+    edge = chunk * tile
+    assert edge > 2_000_000 > QUANT_GRID + 1                    # every position below lies in a second trip
+    x = np.zeros((5, n), dtype=np.int32)
+    x[3, edge + 5:] = 1 << 29
+    with pytest.raises(lib.QMHipError, match=rf"channel Y, sample {edge + 5}: difference does not fit 30 bits"):
+        engine.scanmseed_encode(x)
+    # one step on each side of the compose chunk's edge: X's lies further into its channel and still comes first
+    x = np.zeros((5, n), dtype=np.int32)
+    x[2, edge + 7:] = 1 << 29
+    x[4, edge - 7:] = 1 << 29
+    assert 2 * n + edge + 7 < 4 * n + edge - 7
+    with pytest.raises(lib.QMHipError, match=rf"channel X, sample {edge + 7}: difference does not fit 30 bits"):
+        engine.scanmseed_encode(x)
+    x = np.zeros((5, n), dtype=np.int32)
+    x[1, edge + 7:] = 1 << 29
+    x[0, edge - 7:] = 1 << 29
+    with pytest.raises(lib.QMHipError, match=rf"channel COA, sample {edge - 7}: difference does not fit 30 bits"):
+        engine.scanmseed_encode(x)
+    del x
+    f = np.array(list(sm.scale_factors(1000.0).values()))
+    clips = [sm.COA_CLIP, sm.COA_CLIP, None, None, None]
+    y = np.ones((5, n))
+    y[4, 2_000_000] = np.nan
+    with pytest.raises(lib.QMHipError, match=r"channel Z, sample 2000000 is NaN"):
+        engine.scanmseed_encode(y, f, clips)
+    y[4, 2_000_000] = 1.0
+    y[1, QUANT_GRID + 1] = -3e4                                 # x 1e5: below int32 (the clip bounds the other side)
+    with pytest.raises(lib.QMHipError,
+                       match=rf"channel COA_N, sample {QUANT_GRID + 1}: the scaled value is outside int32"):
+        engine.scanmseed_encode(y, f, clips)
+    del y
+    # the engine goes on working after the refusals
+    stacked, want, _ = long_chains[0]
+    encode_equals(engine, stacked, want)
+
+
+def test_long_file_to_device_to_trigger(engine, sm, tmp_path, long_walks):
+    import trigger_ref as tr
+
+    stacked, _, _ = long_walks
+    ucf, period = 1000.0, 20_000_000
+    stride = engine.get("trigger_merge_stride")
+    series = {ch: stacked[j] for j, ch in enumerate(sm.CHANNELS)}
+    path = tmp_path / "2014_180.scanmseed"
+    sm.write_scanmseed(path, dt.datetime(2014, 6, 29), 50.0, series, engine=engine)
+    f = sm.scale_factors(ucf)
+    coa, coa_n = series["COA"] / f["COA"], series["COA_N"] / f["COA_N"]
+    # COA is a random walk: it crosses its median some hundreds of times, and with a marginal window of one sample most
+    # of those runs are events of their own
+    threshold, mw_ns, mei_ns = float(np.median(coa)), period, 2 * period
+    par = dict(trigger_on=0, method="static", value=threshold)
+    want = tr.trigger_series(coa, coa_n, 0, None, tr.STATIC, threshold, 1, period, mw_ns, mei_ns)
+    print("threshold", threshold, "candidates", want["n_candidates"], "events", want["n_events"])
+    assert want["n_events"] > stride and want["n_candidates"] > want["n_events"]
+    _, rate, host = sm.read_scanmseed(path, ucf, engine=engine)
+    _, _, dev = sm.read_scanmseed(path, ucf, engine=engine, device=True)
+    assert rate == 50.0 and hasattr(dev["COA"], "data_ptr") and not hasattr(host["COA"], "data_ptr")
+    assert np.array_equal(bits(host["COA"]), bits(coa)) and np.array_equal(bits(host["COA_N"]), bits(coa_n))
+    for ch in sm.CHANNELS:
+        assert np.array_equal(host["int"][ch], series[ch])
+    answers = [engine.trigger_series(c["COA"], c["COA_N"], period, mw_ns, mei_ns, want_candidates=True, **par)
+               for c in (dev, host)]
+    for got in answers:
+        assert (got["n_candidates"], got["n_events"]) == (want["n_candidates"], want["n_events"])
+        assert np.array_equal(got["candidates"], want["candidates"])
+        assert np.array_equal(got["events_i"], want["events_i"])
+        assert np.array_equal(bits(got["events_f"]), bits(want["events_f"]))
+        assert np.array_equal(bits(got["thresholds"]), bits(want["thresholds"]))

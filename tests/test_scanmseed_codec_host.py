@@ -72,6 +72,25 @@ def test_restatement_equals_the_python_on_switching_walks(seed):
     assert restated_trace(sm, x) == sm.write_trace(sm.Trace("COA", "NW", T0, 50.0, x))
 
 
+def test_folded_walk_keeps_its_classes_and_equals_the_python():
+    """The vectorised builder of the long GPU cases: a quarter of 30 011 steps of up to 2^29 would leave int32 many
+    times over, the folded series stays inside +-2^30 and comes near it; no difference outside 30 bits, every class
+    asked for present, the same series for the same seed; the restatement on it equals the Python encoder."""
+    from quakemigrate_amd import scanmseed as sm
+
+    n = 30_011
+    x = ref.folded_switching_walk(np.random.default_rng(5), n, classes=(0, 2, 4, 6), max_run=30)
+    assert x.dtype == np.int32 and len(x) == n
+    assert (1 << 29) < np.abs(x.astype(np.int64)).max() <= (1 << 30)
+    assert np.array_equal(x, ref.folded_switching_walk(np.random.default_rng(5), n, classes=(0, 2, 4, 6), max_run=30))
+    cls = ref.width_class(ref.differences(x))
+    assert cls.max() == 6 and set(np.unique(cls)) >= {0, 2, 4, 6}
+    # runs of one class: words of 7, 5, 3 and 1 differences all occur on the chain
+    count = ref.counts(cls)
+    assert np.bincount(count[ref.chain(count)], minlength=8)[[1, 3, 5, 7]].min() > 0
+    assert restated_trace(sm, x) == sm.write_trace(sm.Trace("COA", "NW", T0, 50.0, x))
+
+
 def test_restatement_refuses_what_the_python_refuses():
     from quakemigrate_amd import scanmseed as sm
 

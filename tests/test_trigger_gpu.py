@@ -44,15 +44,23 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
+def restate(coa, coa_n=None, period_ns=PERIOD, mw_ns=1_000_000_000, mei_ns=2_000_000_000, trigger_on=0,
+            method="static", value=1.0, chunk_samples=1, weights=None):
+    """trigger_ref's answer to check()'s arguments."""
+    return tr.trigger_series(coa, coa if coa_n is None else coa_n, trigger_on, weights, METHODS[method], value,
+                             chunk_samples, period_ns, mw_ns, mei_ns)
+
+
 def check(eng, coa, coa_n=None, period_ns=PERIOD, mw_ns=1_000_000_000, mei_ns=2_000_000_000, trigger_on=0,
-          method="static", value=1.0, chunk_samples=1, weights=None):
-    """One call on the engine and on the restatement; everything equal.  Returns the engine's answer."""
+          method="static", value=1.0, chunk_samples=1, weights=None, want=None):
+    """One call on the engine and on the restatement (`want`: its answer to these arguments, where the caller has it
+    already); everything equal.  Returns the engine's answer."""
     coa = np.ascontiguousarray(coa, dtype=np.float64)
     coa_n = coa.copy() if coa_n is None else np.ascontiguousarray(coa_n, dtype=np.float64)
     got = eng.trigger_series(coa, coa_n, period_ns, mw_ns, mei_ns, trigger_on=trigger_on, method=method, value=value,
                              chunk_samples=chunk_samples, weights=weights, max_events=len(coa), want_candidates=True)
-    want = tr.trigger_series(coa, coa_n, trigger_on, weights, METHODS[method], value, chunk_samples, period_ns, mw_ns,
-                             mei_ns)
+    if want is None:
+        want = restate(coa, coa_n, period_ns, mw_ns, mei_ns, trigger_on, method, value, chunk_samples, weights)
     assert (got["n_candidates"], got["n_events"]) == (want["n_candidates"], want["n_events"])
     assert np.array_equal(got["candidates"], want["candidates"])
     assert np.array_equal(got["events_i"], want["events_i"])
@@ -327,8 +335,9 @@ def test_seeded_parameter_sets_equal_the_restatement(engine, seed):
 
 
 # -- refusals -----------------------------------------------------------------------------------------------------------
-def raw_call(lib, eng, coa, coa_n, n=None, max_events=8, nulls=(), **par):
-    """The C call itself, every output pre-filled with 7: (rc, message, untouched)."""
+def raw_call(lib, eng, coa, coa_n, n=None, max_events=8, max_candidates=64, nulls=(), **par):
+    """The C call itself, every output pre-filled with 7: (rc, message, untouched).  The tables hold `max_events`
+    events and `max_candidates` candidates, the series may be of any length."""
     vp = ctypes.c_void_p
     fields = dict(trigger_on=0, threshold_method=0, threshold_value=1.0, chunk_samples=1, smooth_radius=0, reserved=0,
                   smooth_weights=vp(None), period_ns=PERIOD, mw_ns=10 ** 9, mei_ns=2 * 10 ** 9)
@@ -337,9 +346,9 @@ def raw_call(lib, eng, coa, coa_n, n=None, max_events=8, nulls=(), **par):
     if weights is not None:
         fields["smooth_weights"] = weights.ctypes.data_as(vp)
     p = lib.TriggerParams(**fields)
-    out = {"events_i": np.full((8, 4), 7, dtype=np.int64), "events_f": np.full((8, 3), 7.0),
+    out = {"events_i": np.full((max_events, 4), 7, dtype=np.int64), "events_f": np.full((max_events, 3), 7.0),
            "thresholds": np.full(64, 7.0), "smoothed": np.full((2, len(coa)), 7.0),
-           "candidates": np.full((64, 5), 7, dtype=np.int64)}
+           "candidates": np.full((max_candidates, 5), 7, dtype=np.int64)}
     nc, ne = ctypes.c_int64(7), ctypes.c_int64(7)
     args = {"e": eng._h, "coa": coa.ctypes.data_as(vp), "coa_n": coa_n.ctypes.data_as(vp), "p": ctypes.byref(p),
             "nc": ctypes.byref(nc), "ne": ctypes.byref(ne), "events_i": out["events_i"].ctypes.data_as(vp),
@@ -349,7 +358,7 @@ def raw_call(lib, eng, coa, coa_n, n=None, max_events=8, nulls=(), **par):
     rc = lib.qmlib.qm_engine_trigger(args["e"], args["coa"], args["coa_n"], len(coa) if n is None else n, args["p"],
                                      max_events, args["nc"], args["ne"], args["events_i"], args["events_f"],
                                      out["thresholds"].ctypes.data_as(vp), out["smoothed"].ctypes.data_as(vp),
-                                     out["candidates"].ctypes.data_as(vp), 64)
+                                     out["candidates"].ctypes.data_as(vp), max_candidates)
     untouched = nc.value == 7 and ne.value == 7 and all(np.all(a == 7) for a in out.values())
     return rc, lib.qmlib.qm_last_error().decode(), untouched
 
@@ -390,6 +399,169 @@ def test_refusals_leave_the_outputs_untouched(lib, engine):
         engine.trigger_series(np.zeros(8000)[::2], x, PERIOD, 10 ** 9, 2 * 10 ** 9)
     with pytest.raises(ValueError, match="coa_n of shape"):
         engine.trigger_series(x, x[:-1].copy(), PERIOD, 10 ** 9, 2 * 10 ** 9)
+
+
+# -- past one trip of the scan and merge loops --------------------------------------------------------------------------
+# trig_scan_kernel carries the run starts, the run ends and the non-finite count from one tile of run blocks to the next;
+# trig_merge_kernel carries a segment from one pass of "trigger_merge_stride" candidates to the next.  The tile has no
+# read-out: 600 run blocks are more than two of any tile up to 299 blocks (it is 256).  Every test asserts on the
+# restatement alone, before the device is asked, what makes it able to fail.
+LONG_BLOCKS = 600
+SHORT = dict(mw_ns=PERIOD, mei_ns=2 * PERIOD)                                  # most candidates are events of their own
+
+
+@pytest.fixture(scope="module")
+def boundary_series(engine):
+    """T1's series, built and restated once: (x, [(f, l, p)] in order, trigger_ref's answer under SHORT)."""
+    block = engine.get("trigger_run_block")
+    n = LONG_BLOCKS * block + 17
+    x, runs = np.zeros(n), []
+
+    def run(f, l, p, peak):
+        x[f:l + 1] = 2.0
+        x[p] = peak
+        runs.append((f, l, p))
+
+    for b in range(LONG_BLOCKS):
+        e = b * block
+        if b and b % 3 == 0:
+            run(e - 40, e - 1, e - 1, 5.0)                                      # ends at e - 1, the next starts at e + 5
+            run(e + 5, e + 44, e + 5, 4.0)
+        elif b % 3 == 1:
+            run(e - 41, e - 2, e - 2, 5.0)                                      # ends at e - 2, the next starts at e
+            run(e, e + 39, e + 20, 4.0)
+        elif b % 3 == 2:
+            run(e - 70, e + 69, e + (b // 3) % 3 - 1, 3.0)                      # across e, peak at e - 1, e, e + 1
+        for j in range(1 + b % 5):                                              # single samples inside the block
+            run(e + 500 + 100 * j, e + 500 + 100 * j, e + 500 + 100 * j, 2.0 + 0.25 * j)
+    run(n - 3, n - 1, n - 2, 6.0)                                               # ... and a run up to the last sample
+    return x, sorted(runs), restate(x, **SHORT)
+
+
+def test_long_series_runs_at_every_block_boundary(engine, boundary_series):
+    block, stride = engine.get("trigger_run_block"), engine.get("trigger_merge_stride")
+    x, runs, want = boundary_series
+    assert len(x) == LONG_BLOCKS * block + 17
+    cand = want["candidates"]
+    starts, ends = np.bincount(cand[:, 0] // block), np.bincount(cand[:, 1] // block)
+    print("blocks with starts / ends:", np.count_nonzero(starts), np.count_nonzero(ends), "start counts per block:",
+          sorted(set(starts.tolist())), "end counts:", sorted(set(ends.tolist())), "candidates:", len(cand), "events:", want["n_events"])
+    assert np.count_nonzero(starts) > 512 and np.count_nonzero(ends) > 512    # prefixes carried over two tiles
+    assert len(set(starts)) > 3 and np.count_nonzero(starts != ends) > 100     # ... and no two alike to cancel out
+    assert len(cand) > 4 * stride and want["n_events"] > len(cand) // 2
+    assert [tuple(c) for c in cand[:, :3]] == runs                              # (the restatement against the list)
+    got = check(engine, x, want=want, **SHORT)
+    assert [tuple(c) for c in got["candidates"][:, :3]] == runs
+
+
+def test_long_series_non_finite_samples_are_counted_across_tiles(lib, engine, boundary_series):
+    block = engine.get("trigger_run_block")
+    x, _, want = boundary_series
+    coa, coa_n = x.copy(), x.copy()
+    coa[[7, 300 * block + 1000, 599 * block + 2047]] = np.nan, np.inf, -np.inf
+    coa_n[[257 * block, 511 * block + 2047]] = np.nan, -np.inf
+    assert sorted(np.flatnonzero(~np.isfinite(coa)) // block) == [0, 300, 599]
+    assert sorted(np.flatnonzero(~np.isfinite(coa_n)) // block) == [257, 511]
+    room = dict(max_events=want["n_events"], max_candidates=want["n_candidates"], **SHORT)
+    for a, b, count in ((coa, coa_n, 5), (x, coa_n, 2), (coa, x, 3)):
+        with pytest.raises(tr.Refused, match=f"^{count} non-finite samples"):
+            restate(a, b, **SHORT)
+        rc, message, untouched = raw_call(lib, engine, a, b, **room)
+        assert rc != 0 and f" {count} non-finite samples" in message and untouched, message
+    check(engine, x, want=want, **SHORT)                                        # the same engine, the clean series
+
+
+def long_event_layout(stride, chain, tail):
+    """Sample positions: stride - 56 separate single samples, a chain of `chain` 1 s apart, `tail` separate ones."""
+    at = list(200 * np.arange(1, stride - 55))
+    first = len(at)
+    at += [at[-1] + 200 + 50 * k for k in range(chain)]
+    at += [at[-1] + 200 * (k + 1) for k in range(tail)]
+    return np.array(at), first
+
+
+def test_event_longer_than_a_pass_of_the_merge_loop(engine):
+    stride = engine.get("trigger_merge_stride")
+    members = 2 * stride + 188
+    at, first = long_event_layout(stride, members, stride)
+    last = first + members - 1
+    passes = list(range(first // stride, last // stride + 1))
+    filled = [q for q in passes if first <= q * stride and (q + 1) * stride - 1 <= last]
+    print("chain of", members, "from candidate", first, "to", last, ": passes", passes, "filled", filled)
+    assert len(passes) >= 3 and filled and first % stride and (last + 1) % stride
+    two_s = 2 * 10 ** 9
+    peaks = {"first pass": [first + 30], "filled pass": [filled[0] * stride + stride // 2],
+             "last pass": [last - 40], "equal, two passes": [filled[0] * stride + 44, last - 3]}
+    for name, where in peaks.items():
+        values = 2.0 + (np.arange(len(at)) % 7) * 0.25
+        values[where] = 9.0
+        x = spikes(at[-1] + 10, at, values)
+        want = restate(x)
+        cand_of = {int(p): k for k, p in enumerate(want["candidates"][:, 2])}
+        event = want["events_i"][first]
+        peak_pass = cand_of[int(event[0])] // stride
+        print(name, ": peak at candidate", cand_of[int(event[0])], "pass", peak_pass, "members", event[3])
+        assert want["n_candidates"] == len(at) and want["n_events"] == len(at) - members + 1
+        assert event[3] == members and cand_of[int(event[0])] == where[0]
+        assert peak_pass == {"first pass": passes[0], "filled pass": filled[0], "last pass": passes[-1],
+                             "equal, two passes": filled[0]}[name]
+        if len(where) == 2:
+            assert where[1] // stride != where[0] // stride
+        got = check(engine, x, want=want)
+        assert tuple(got["events_i"][first]) == (at[where[0]], at[first] * PERIOD - two_s, at[last] * PERIOD + two_s,
+                                                 members)
+        assert tuple(got["events_f"][first]) == (9.0, 9.0, 9.0)
+        for row, k in ((first - 1, first - 1), (first + 1, last + 1)):         # its neighbours: untouched single events
+            assert tuple(got["events_i"][row]) == (at[k], at[k] * PERIOD - two_s, at[k] * PERIOD + two_s, 1)
+            assert got["events_f"][row, 0] == values[k]
+    # a chain that ends in the last slot of a pass, a separate event in slot 0 of the next
+    at, first = long_event_layout(stride, 2 * stride - (stride - 56), stride)
+    last = 2 * stride - 1
+    values = 2.0 + (np.arange(len(at)) % 7) * 0.25
+    x = spikes(at[-1] + 10, at, values)
+    want = restate(x)
+    sizes = want["events_i"][:, 3]
+    assert list(sizes[first - 1:first + 3]) == [1, last - first + 1, 1, 1] and first + sizes[first] - 1 == last
+    assert want["events_i"][first + 1, 0] == at[2 * stride]                      # slot 0 of pass 2 opens an event
+    got = check(engine, x, want=want)
+    assert tuple(got["events_i"][first + 1]) == (at[last + 1], at[last + 1] * PERIOD - two_s,
+                                                 at[last + 1] * PERIOD + two_s, 1)
+    assert got["events_i"][first, 2] == at[last] * PERIOD + two_s
+
+
+def test_long_seeded_series_equals_the_restatement_from_host_and_device(engine):
+    import torch
+
+    block = engine.get("trigger_run_block")
+    n = LONG_BLOCKS * block + 17
+    rng = np.random.default_rng(2014)
+    noise = rng.gamma(2.0, 0.5, (2, n))
+    for at in rng.integers(0, n, 400):                                          # bursts of random width and height
+        width = int(rng.integers(1, 200))
+        shape = rng.uniform(4.0, 12.0) * np.hanning(width + 2)[1:-1]
+        stop = min(n, at + width)
+        noise[:, at:stop] += shape[:stop - at] * rng.uniform(0.5, 1.5, (2, 1))
+    x = np.round(noise, 5)
+    par = dict(trigger_on=1, method="mad", value=3.0, chunk_samples=180_000,
+               weights=tr.gaussian_weights(2.5, 4.0)[1])
+    want = restate(x[0], x[1], **par)
+    blocks = np.count_nonzero(np.bincount(want["candidates"][:, 0] // block, minlength=LONG_BLOCKS + 1))
+    print("candidates:", want["n_candidates"], "events:", want["n_events"], "blocks with starts:", blocks,
+          "chunks:", len(want["thresholds"]))
+    assert want["n_events"] > 100 and len(want["thresholds"]) == -(-n // 180_000)
+    assert want["candidates"][:, 0].min() < 256 * block and want["candidates"][:, 0].max() > 512 * block
+    got = check(engine, x[0], x[1], want=want, **par)
+    where = f"cuda:{engine.device}"
+    coa, coa_n = torch.from_numpy(x[0]).to(where), torch.from_numpy(x[1]).to(where)
+    torch.cuda.synchronize(where)
+    resident = engine.trigger_series(coa, coa_n, PERIOD, 10 ** 9, 2 * 10 ** 9, max_events=n, want_candidates=True,
+                                     **par)
+    assert sorted(resident) == sorted(got)
+    for key, value in got.items():
+        if isinstance(value, np.ndarray) and value.dtype == np.float64:
+            assert np.array_equal(bits(resident[key]), bits(value)), key
+        else:
+            assert np.array_equal(resident[key], value), key
 
 
 def test_long_lived_engine_equals_fresh_engines(lib, engine):
